@@ -9,9 +9,16 @@ all-reduce (RCCL, overlapped) -> fused Adam.  Inputs are resident in HBM before 
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
       bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel (by summed time) among the GEMM instantiations,
-timed with HIP events on the launch stream during the timed steps; `cpu_baseline` times the CPU oracle (a port of
-the reference algorithm, oracle/kalle_oracle.py) on the host cores for a bounded sample (rank 0, N=1 only).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the --steps steps, writes --dump-outputs if asked
+and prints the line (headline figure, ms_per_step, loss, algorithmic TFLOP/s).  --full adds the measurements that cost
+time of their own: `comm` (HIP events around the all-reduce waits of the timed steps), `roofline` for the dominant kernel
+(by summed time) among the GEMM instantiations, timed with HIP events on the launch stream during the timed steps, plus
+one extra step with events around every GEMM launch, and `cpu_baseline`, which times the CPU oracle (a port of the
+reference algorithm, oracle/kalle_oracle.py) on the host cores for a bounded sample (rank 0, N=1 only).
+
+--dump-outputs DIR (rank 0) writes what the last timed step computed, as float32 .npy files: loss.npy, and the updated
+fp32 weights and the step's gradients at a fixed, seeded sample of 2^22 positions of the parameters (model order),
+params_sample.npy / grads_sample.npy (32 MiB in all).
 """
 import argparse
 import json
@@ -114,22 +121,51 @@ def cpu_baseline(sample_clips=2, depth=None):
                       + ("" if depth is None else f" scaled x{scale:g} to 24 blocks") + f", {dt:.1f} s on {cores} threads"}
 
 
+DUMP_SAMPLE, DUMP_SEED = 1 << 22, 20240607
+
+
+def dump_outputs(d, trainer, loss):
+    """DIR/loss.npy + the updated weights and the gradients of the last step at DUMP_SAMPLE positions drawn with a fixed seed
+    over the trainable parameters laid end to end in model order (independent of the flat buffer's padding and bucket order)"""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    flat = trainer.flat
+    sizes = torch.tensor([flat.slices[n][1] for n in flat.names], dtype=torch.int64)
+    starts = torch.tensor([flat.slices[n][0] for n in flat.names], dtype=torch.int64)
+    ends = torch.cumsum(sizes, 0)
+    g = torch.Generator().manual_seed(DUMP_SEED)
+    logical = torch.randint(0, int(ends[-1]), (DUMP_SAMPLE,), generator=g, dtype=torch.int64).sort().values
+    which = torch.searchsorted(ends, logical, right=True)
+    phys = (starts[which] + logical - (ends[which] - sizes[which])).to(flat.param.device)
+    np.save(os.path.join(d, "loss.npy"), loss.detach().float().reshape(1).cpu().numpy())
+    np.save(os.path.join(d, "params_sample.npy"), flat.param[phys].float().cpu().numpy())
+    np.save(os.path.join(d, "grads_sample.npy"), flat.grad[phys].float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=256, help="clips per GPU per step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timer", action="store_true")
-    ap.add_argument("--time-all-launches", action="store_true", help="events around EVERY GEMM launch of the timed region (the bench "
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss and a seeded sample of its weights / gradients as .npy")
+    ap.add_argument("--full", action="store_true", help="also the exposed-communication events, the GEMM kernel timer and "
+                    "roofline (one extra step) and the CPU baseline; a plain run measures the headline figure only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-kernel-timer", action="store_true", help="(--full) skip the GEMM kernel timer and roofline")
+    ap.add_argument("--time-all-launches", action="store_true", help="(--full) events around EVERY GEMM launch of the timed region (the bench "
                     "of rounds 1-3; kept to measure what those events cost)")
-    ap.add_argument("--cpu-depth", type=int, default=None, help="time a shallower oracle and scale (debug)")
+    ap.add_argument("--cpu-depth", type=int, default=None, help="(--full) time a shallower oracle and scale (debug)")
     # sweep axes of SURVEY.md 8(d) - the defaults are the headline configuration
     ap.add_argument("--io-channels", type=int, default=CFG["io_channels"], help="latent channels: 64 | 512 | 1024")
     ap.add_argument("--global-cond-type", default=CFG["global_cond_type"], choices=["prepend", "adaLN"])
     ap.add_argument("--objective", default="v", choices=["v", "rectified_flow"])
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if not args.full:
+        args.no_cpu_baseline = args.no_kernel_timer = True
     CFG["io_channels"], CFG["global_cond_type"] = args.io_channels, args.global_cond_type
 
     import torch.distributed as dist
@@ -164,7 +200,7 @@ def main():
     DOMINANT = "gemm3_wgrad_group_kernel"
     timer = None if (args.no_kernel_timer or rank != 0) else []
     ops.KERNEL_TIMER, ops.KERNEL_TIMER_ONLY = timer, (None if args.time_all_launches else DOMINANT)
-    trainer.comm_timing = []          # events around the all-reduce waits of the timed steps (exposed communication)
+    trainer.comm_timing = [] if args.full else None   # events around the all-reduce waits of the timed steps (exposed comm)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         loss = step()
@@ -176,7 +212,9 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = tt.item()
     loss_v = loss.item()
-    comm = trainer.comm_summary()     # RCCL rank count, buckets per step, exposed (non-overlapped) all-reduce time
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer, loss)
+    comm = trainer.comm_summary() if args.full else None   # RCCL rank count, buckets per step, exposed all-reduce time
     trainer.comm_timing = None
     full = None
     if not args.no_kernel_timer:      # the extra step: every rank runs it (collectives), rank 0 brackets every GEMM launch
@@ -203,8 +241,9 @@ def main():
                        "global_cond_type": CFG["global_cond_type"], "loss": loss_v},
             "algorithmic_tflops_per_gpu": 3 * fwd * args.batch * args.steps / dt / 1e12,
             "mfma_roofline_frac_step": 3 * fwd * args.batch * args.steps / dt / 1e12 / PEAK_BF16_TFLOPS,
-            "comm": comm,
         }
+        if comm is not None:
+            out["comm"] = comm
         if full:
             agg = {}
             shapes = {}

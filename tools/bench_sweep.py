@@ -9,7 +9,7 @@ rows = []
 for r in runs:
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--batch", str(r["batch"]),
            "--io-channels", str(r["io"]), "--global-cond-type", r.get("gct", "prepend"), "--objective", r.get("obj", "v"),
-           "--no-cpu-baseline"]
+           "--no-cpu-baseline", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     line = [l for l in out.stdout.splitlines() if l.startswith("{")]
     if not line:

@@ -10,7 +10,7 @@ for i in 1 2; do
   for v in "$@"; do
     L=$R/kalle_audio_amd/libkalle_hip.so; [ "$v" != product ] && L=$R/kalle_audio_amd/libkalle_hip_$v.so
     echo "== $v"
-    KALLE_LIB_PATH=$L KALLE_BENCH_SHAPES=1 timeout -k 10 300 python bench.py --no-cpu-baseline ${BENCH_ARGS} 2> $O/err.txt | tail -n 1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('ms_per_step', round(d['ms_per_step'], 2))" || exit 1
+    KALLE_LIB_PATH=$L KALLE_BENCH_SHAPES=1 timeout -k 10 300 python bench.py --full --no-cpu-baseline ${BENCH_ARGS} 2> $O/err.txt | tail -n 1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('ms_per_step', round(d['ms_per_step'], 2))" || exit 1
     grep -E "$PAT" $O/err.txt | head -n 6
   done
 done 2>&1 | tee $O/log.txt

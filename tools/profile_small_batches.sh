@@ -9,5 +9,5 @@ for B in 16 64; do
   rm -rf $O/prof$B
 done
 cd $R
-KALLE_BENCH_SHAPES=1 timeout -k 10 300 python bench.py --no-cpu-baseline --batch 16 --steps 10 --warmup 3 > $O/shapes16.json 2> $O/shapes16.err
+KALLE_BENCH_SHAPES=1 timeout -k 10 300 python bench.py --full --no-cpu-baseline --batch 16 --steps 10 --warmup 3 > $O/shapes16.json 2> $O/shapes16.err
 echo done

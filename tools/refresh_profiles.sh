@@ -8,7 +8,7 @@ rm -rf $O; mkdir -p $O
 cd $R
 python -c "from kalle_audio_amd.build import source_stamp; print(source_stamp())" > $O/source_stamp.txt
 timeout -k 10 900 python -m pytest tests -q -m gpu > $O/tests.log 2>&1; echo "tests rc=$?" >> $O/tests.log
-timeout -k 10 600 python bench.py 2> $O/default.err | tail -n 1 > $O/default.json || exit 1
+timeout -k 10 600 python bench.py --full 2> $O/default.err | tail -n 1 > $O/default.json || exit 1
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 $R/bench.py --no-cpu-baseline 2> $O/prof.err | tail -n 1 > $O/under_rocprof.json || exit 1
 cd $R
