@@ -160,7 +160,8 @@ int kalle_rmsnorm_bwd_acc(const void* dy, int dy_dtype, const void* x, int x_dty
                           void* dx_bf16, int rows, int D, void* stream);
 
 /* Attention(qk_norm=...) (transformer.py:303-307, 422-428): every 64-wide head of q / k is normalised before the rotary
- * embedding.  mode 1 "l2": F.normalize = x / max(||x||_2, 1e-12);  mode 2 "ln": LayerNorm(64, eps 1e-6), gamma / beta fp32 [64].
+ * embedding (any head width dh in {32, 64, 128}: the _hd forms below).
+ * mode 1 "l2": F.normalize = x / max(||x||_2, 1e-12);  mode 2 "ln": LayerNorm(64, eps 1e-6), gamma / beta fp32 [64].
  * x, y: bf16 row-major with leading dimensions ldx / ldy and element offsets (the q or k slice of a projection output, as in
  * kalle_attention_fwd; all multiples of 8); `heads` consecutive heads per row.  stat: fp32 [rows][heads][2], written by the
  * forward (mean | clamp flag, reciprocal std | reciprocal norm) and read by the backward.
@@ -171,6 +172,15 @@ int kalle_head_norm_fwd(const void* x, int64_t ldx, int64_t x_off, void* y, int6
 int kalle_head_norm_bwd(const void* x, int64_t ldx, int64_t x_off, const float* stat, const void* g, int64_t ldg,
                         int64_t g_off, void* dx, int64_t lddx, int64_t dx_off, const float* gamma, float* dgamma,
                         float* dbeta, int mode, int64_t rows, int heads, void* stream);
+/* the same for heads of width head_dim in {32, 64, 128} (Attention(dim_heads = head_dim, qk_norm=...), transformer.py:303-307:
+ * LayerNorm(dim_heads)): head h of a row at column h * head_dim, "ln" statistics over head_dim values, gamma / beta / dgamma /
+ * dbeta fp32 [head_dim]; ld* >= heads * head_dim.  Any other head_dim: KALLE_ERR_ARG.  head_dim 64 is exactly
+ * kalle_head_norm_fwd / _bwd (which forward here). */
+int kalle_head_norm_fwd_hd(const void* x, int64_t ldx, int64_t x_off, void* y, int64_t ldy, int64_t y_off, float* stat,
+                           const float* gamma, const float* beta, int mode, int64_t rows, int heads, int head_dim, void* stream);
+int kalle_head_norm_bwd_hd(const void* x, int64_t ldx, int64_t x_off, const float* stat, const void* g, int64_t ldg,
+                           int64_t g_off, void* dx, int64_t lddx, int64_t dx_off, const float* gamma, float* dgamma,
+                           float* dbeta, int mode, int64_t rows, int heads, int head_dim, void* stream);
 
 /* column sums: out[c] (+)= sum_r in[r][c]; in fp32 or bf16 [rows][ld]. Used for bias grads and partial reduces. */
 int kalle_colsum(const void* in, int in_dtype, int64_t ld, float* out, int rows, int cols, int accumulate,
@@ -285,7 +295,8 @@ int kalle_fourier_features_bwd(const float* dout, const float* t, const float* w
  * causal != 0: query i attends keys j <= i + (Nk - Nq) only (the Llama decoder called at model_sigmaVAE.py:78-81); the
  *   queries are then the LAST Nq positions (rotary position of query row i = i + Nk - Nq), which is what decoding against
  *   a KV cache needs (model_sigmaVAE.py:122-146 re-runs the prefix instead).
- * key_mask: uint8 [B][Nk] (1 = attend) or NULL.  lse: [B][H][Nq] fp32 saved for backward.  head dim fixed at 64.
+ * key_mask: uint8 [B][Nk] (1 = attend) or NULL.  lse: [B][H][Nq] fp32 saved for backward.  Head dim 64 here; the _hd
+ * forms below take 32 and 128 too.
  */
 int kalle_attention_fwd(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off,
                         const void* v, int64_t ldv, int v_off, void* out, int64_t ldo, float* lse,
@@ -298,6 +309,24 @@ int kalle_attention_bwd(const void* q, int64_t ldq, int q_off, const void* k, in
                         const float* lse, float* delta, void* dq, void* dk, void* dv,
                         const float* rope_cos, const float* rope_sin, int rot, const uint8_t* key_mask, int causal,
                         int B, int H, int Hkv, int Nq, int Nk, void* stream);
+/* The same two at head dim dh = head_dim in {32, 64, 128} (DiffusionTransformer(embed_dim, num_heads) -> dim_heads =
+ * embed_dim // num_heads, dit.py:118; Attention(dim, dim_heads), transformer.py:290-300):
+ *   out[b, i, h*dh+d] = softmax_j(q_i . k_j / sqrt(dh) + maskbias_j) v_j      (scale 1/sqrt(dh) in fp32: 0.17678 / 0.125 / 0.088388)
+ *   q head h at column q_off + h*dh, k / v head (h / (H/Hkv)) at k_off / v_off + (h / (H/Hkv))*dh; out / dout / dq / dk / dv
+ *   likewise with dh-wide heads; lse / delta [B][H][Nq] as above.
+ * rot in {0, 32, 64} and rot <= dh: rotary on the first rot dims of every head (RotaryEmbedding(max(dh // 2, 32)),
+ * transformer.py:730: the DiT's rot is 32 at dh 32 - the whole head - and 64 at dh 128).
+ * Anything else (head_dim not in {32, 64, 128}, rot > head_dim) returns KALLE_ERR_ARG.  head_dim 64 is exactly
+ * kalle_attention_fwd / _bwd (which forward here); at 32 and 128 the backward is the two-pass kernel pair at every shape. */
+int kalle_attention_fwd_hd(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off,
+                           const void* v, int64_t ldv, int v_off, void* out, int64_t ldo, float* lse,
+                           const float* rope_cos, const float* rope_sin, int rot, const uint8_t* key_mask, int causal,
+                           int B, int H, int Hkv, int Nq, int Nk, int head_dim, void* stream);
+int kalle_attention_bwd_hd(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off,
+                           const void* v, int64_t ldv, int v_off, const void* out, const void* dout, int64_t ldo,
+                           const float* lse, float* delta, void* dq, void* dk, void* dv,
+                           const float* rope_cos, const float* rope_sin, int rot, const uint8_t* key_mask, int causal,
+                           int B, int H, int Hkv, int Nq, int Nk, int head_dim, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Optimizer: fused Adam / AdamW over a flat fp32 master buffer, also emitting the bf16 compute copy.

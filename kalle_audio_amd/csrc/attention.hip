@@ -1,13 +1,15 @@
-// Fused attention for the DiT block and the Llama decoder layers (gfx950), forward and backward, head dim 64,
-// optional causal mask (keys j <= i + Nk - Nq), optional key-padding mask, rotary on the first 32 or on all 64 dims.
+// Fused attention for the DiT block and the Llama decoder layers (gfx950), forward and backward, head dim DH = 32, 64 or
+// 128, optional causal mask (keys j <= i + Nk - Nq), optional key-padding mask, rotary on the first 32 or 64 dims.
 // Reference: stable_audio_tools/models/transformer.py:396-547 (Attention.forward: rotary 430-444, key mask 446-462,
 // softmax(QK^T/sqrt(d))V 502-530 / SDPA 382-387, GQA repeat_interleave 337-340, 505-508) and
 // transformer.py:146-170 (rotate_half / apply_rotary_pos_emb, partial rotary on the first 32 dims).
 //
 // Design (sequences of ~126 latent frames at 12.5 Hz, S~130 context tokens): one workgroup of 4 waves owns a
 // 128-row block of one (batch, head); the whole 128-key K/V block is LDS-resident (one image per tensor,
-// [128][64] bf16 with a 160-B row stride that is conflict-free for BOTH ds_read_b128 row fragments and
-// ds_read_b64_tr_b16 transposed fragments), longer sequences loop over blocks with an online softmax.
+// [128][DH] bf16 with a (2 DH + 32)-B row stride - 96, 160, 288 B - that is conflict-free for BOTH ds_read_b128 row fragments
+// and ds_read_b64_tr_b16 transposed fragments at each DH), longer sequences loop over blocks with an online softmax.
+// The kernels are templates on DH; the fused single-block backward kernels exist for DH = 64 only (the two-pass backward
+// covers 32 and 128).
 // Q/K/V are read in place from the projection outputs ([B][N][ld] with a column offset per head): no head
 // transposes ever touch HBM. RoPE is applied while staging Q/K into LDS (fp32 math, as the reference does) and
 // un-applied on dQ/dK in registers.
@@ -19,53 +21,87 @@
 
 namespace {
 
-constexpr int AT_STRIDE = 160;             // bytes per LDS row: 64 bf16 + 32 B pad
-constexpr int AT_TILE = 128 * AT_STRIDE;   // 20480 B
-constexpr float SM_SCALE = 0.125f;         // 1/sqrt(64)
+// Per-head-dim constants.  STRIDE: bytes per LDS row, DH bf16 + 32 B pad - the pad keeps both the ds_read_b128 row fragments
+// (16 lanes on 16 rows of one 16-B column) and the ds_read_b64_tr_b16 transposed fragments (4 rows x 4 columns of 8 B per
+// 16 lanes) on distinct banks at every DH: 96 / 160 / 288 B are 24 / 40 / 72 dwords, and 16 consecutive rows land on
+// 16 distinct 4-bank slots of the 64-bank row for each (what a power-of-two stride like 64 / 128 / 256 B does not).
+// SCALE = 1/sqrt(DH) in fp32 (F.scaled_dot_product_attention's default, transformer.py:382-387).
+template <int DH>
+struct Hd {
+    static_assert(DH == 32 || DH == 64 || DH == 128, "head dim 32, 64 or 128");
+    static constexpr int STRIDE = 2 * DH + 32;
+    static constexpr int TILE = 128 * STRIDE;
+    static constexpr float SCALE = DH == 32 ? 0.17677669529663687f : DH == 64 ? 0.125f : 0.08838834764831845f;
+    static constexpr float SCALE_LOG2E = SCALE * 1.4426950408889634f;   // exponent of 2 per unit of raw score
+    static constexpr int PAIRS = DH / 16;            // 2-chunk staging slots per tile row
+    static constexpr int PAIRS_LOG2 = DH == 32 ? 1 : DH == 64 ? 2 : 3;
+    static constexpr int NP = DH == 128 ? 2 : 1;     // staging slots per thread of a 512-thread workgroup
+};
+constexpr int AT_STRIDE = Hd<64>::STRIDE;  // 160: the DH = 64 kernels (fused backward, decode)
+constexpr int AT_TILE = Hd<64>::TILE;      // 20480 B
+constexpr float SM_SCALE = Hd<64>::SCALE;  // 1/sqrt(64)
 constexpr float NEG_BIG = -1.0e30f;
-constexpr float SM_SCALE_LOG2E = SM_SCALE * 1.4426950408889634f;   // exponent of 2 per unit of raw score
+constexpr float SM_SCALE_LOG2E = Hd<64>::SCALE_LOG2E;
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr float M_INIT = -2.0e30f;         // running max before the first block: below a fully masked row's NEG_BIG
 
-// stage a [128][64] bf16 tile (rows row0.., `nvalid` valid) into LDS, optionally applying rotary on the first `rot`
-// (32: DiT partial rotary; 64: Llama) dims: out = x cos + rotate_half(x) sin, tables [pos][rot/2].
+// stage a [128][DH] bf16 tile (rows row0.., `nvalid` valid) into LDS, optionally applying rotary on the first `rot`
+// (32: DiT partial rotary at DH 32 / 64; 64: Llama, and the DiT at DH 128) dims: out = x cos + rotate_half(x) sin, tables
+// [pos][rot/2].
 // Split in two so that a kernel can put the global loads of several tiles in flight together (one HBM latency instead
 // of one per tile) and do the rotary + LDS writes afterwards.
-// A thread owns ONE row and TWO 8-element chunks of it: the two partners of a rotary pair (chunk j and j + rot/16), so the
+// A staging slot is ONE row and TWO 8-element chunks of it: the two partners of a rotary pair (chunk j and j + rot/16), so the
 // rotation needs no second load of the partner and one fetch of the cos / sin row per pair (a quarter of the table traffic
 // and half the data traffic of one-chunk-per-thread staging); chunks outside the rotary dims are plain adjacent pairs.
-template <int NT>
+// Slot s = tid + 512 i (i < NP) is row s / PAIRS, pair s % PAIRS: one slot per thread at DH 64, two at DH 128, and at DH 32
+// threads 256.. have none (their row is >= 128).
+template <int NT, int DH = 64>
 struct TileRegs {
-    static_assert(NT == 512, "128 rows x 4 chunk pairs");
-    i32x4 v[2];
+    static_assert(NT == 512, "512 threads stage a tile");
+    i32x4 v[Hd<DH>::NP][2];
 };
 __device__ __forceinline__ void tile_chunks(int rot, int j, int& ca, int& cb) {
     const int hc = rot >> 4;                            // 8-element chunks per rotary half: 0, 2 (DiT) or 4 (Llama)
     if (j < hc) { ca = j; cb = j + hc; }                // a rotary pair
-    else if (hc == 2) { ca = 2 * j; cb = 2 * j + 1; }   // rot 32: j = 2, 3 -> chunks (4, 5), (6, 7) pass through
-    else { ca = 2 * j; cb = 2 * j + 1; }                // rot 0
+    else if (hc == 2) { ca = 2 * j; cb = 2 * j + 1; }   // rot 32: j = 2, 3, .. -> chunks (4, 5), (6, 7), .. pass through
+    else { ca = 2 * j; cb = 2 * j + 1; }                // rot 0 (and rot 64: j = 4.. -> chunks 8.. at DH 128)
 }
-template <int NT>
-__device__ __forceinline__ void tile_load(TileRegs<NT>& t, const bf16_t* src, int64_t ld, int row0, int nvalid, int rot,
-                                          int tid) {
-    const int row = tid >> 2;
+template <int DH>
+__device__ __forceinline__ int slot_row(int tid, int i) { return (tid + 512 * i) >> Hd<DH>::PAIRS_LOG2; }
+template <int DH>
+__device__ __forceinline__ int slot_pair(int tid) { return tid & (Hd<DH>::PAIRS - 1); }   // (512 i keeps the pair)
+// (the per-slot bodies are called once per slot without a loop: at DH = 64 the kernels then compile to what they were before
+// the head dim became a parameter)
+template <int DH>
+__device__ __forceinline__ void tile_load_slot(i32x4 (&v)[2], const bf16_t* src, int64_t ld, int row0, int nvalid, int rot,
+                                               int tid, int i) {
+    const int row = slot_row<DH>(tid, i);
     int ca, cb;
-    tile_chunks(rot, tid & 3, ca, cb);
-    t.v[0] = i32x4{0, 0, 0, 0};
-    t.v[1] = i32x4{0, 0, 0, 0};
+    tile_chunks(rot, slot_pair<DH>(tid), ca, cb);
+    v[0] = i32x4{0, 0, 0, 0};
+    v[1] = i32x4{0, 0, 0, 0};
     if (row < nvalid) {
         const bf16_t* rp = src + (int64_t)(row0 + row) * ld;
-        t.v[0] = *reinterpret_cast<const i32x4*>(rp + 8 * ca);
-        t.v[1] = *reinterpret_cast<const i32x4*>(rp + 8 * cb);
+        v[0] = *reinterpret_cast<const i32x4*>(rp + 8 * ca);
+        v[1] = *reinterpret_cast<const i32x4*>(rp + 8 * cb);
     }
+}
+template <int NT, int DH = 64>
+__device__ __forceinline__ void tile_load(TileRegs<NT, DH>& t, const bf16_t* src, int64_t ld, int row0, int nvalid, int rot,
+                                          int tid) {
+    tile_load_slot<DH>(t.v[0], src, ld, row0, nvalid, rot, tid, 0);
+    if constexpr (Hd<DH>::NP == 2) tile_load_slot<DH>(t.v[1], src, ld, row0, nvalid, rot, tid, 1);
 }
 // The rotary factors of a thread's pair, fetched WITH the tile (rope_load next to tile_load) instead of inside tile_store: there
 // the table loads start only once the tile data has arrived - a second, dependent memory latency in front of the first barrier
 // (the round-3 stamps: 4.9 us of load + stage per self-attention workgroup against 2.8 us for the rotary-free cross-attention).
 struct RopeRegs { f32x4 c0, c1, s0, s1; };
-__device__ __forceinline__ RopeRegs rope_load(const float* __restrict__ cosT, const float* __restrict__ sinT, int row0,
-                                              int nvalid, int rot, int tid, int pos_off = 0) {
-    const int row = tid >> 2, j = tid & 3;
+template <int DH = 64>
+struct RopeSet { RopeRegs r[Hd<DH>::NP]; };
+template <int DH>
+__device__ __forceinline__ RopeRegs rope_load_slot(const float* __restrict__ cosT, const float* __restrict__ sinT, int row0,
+                                                   int nvalid, int rot, int tid, int pos_off, int i) {
+    const int row = slot_row<DH>(tid, i), j = slot_pair<DH>(tid);
     f32x4 c0 = f32x4{0.f, 0.f, 0.f, 0.f}, c1 = c0, s0 = c0, s1 = c0;
     if (row < nvalid && j < (rot >> 4)) {
         const float* cp = cosT + (int64_t)(row0 + row + pos_off) * (rot >> 1) + j * 8;
@@ -75,15 +111,26 @@ __device__ __forceinline__ RopeRegs rope_load(const float* __restrict__ cosT, co
     }
     return RopeRegs{c0, c1, s0, s1};
 }
+template <int DH = 64>
+__device__ __forceinline__ RopeSet<DH> rope_load(const float* __restrict__ cosT, const float* __restrict__ sinT, int row0,
+                                                 int nvalid, int rot, int tid, int pos_off = 0) {
+    RopeSet<DH> rs;
+    rs.r[0] = rope_load_slot<DH>(cosT, sinT, row0, nvalid, rot, tid, pos_off, 0);
+    if constexpr (Hd<DH>::NP == 2) rs.r[1] = rope_load_slot<DH>(cosT, sinT, row0, nvalid, rot, tid, pos_off, 1);
+    return rs;
+}
 
-template <int NT>
-__device__ __forceinline__ void tile_store(char* lds, const TileRegs<NT>& t, int row0, int nvalid,
-                                           const float* __restrict__ cosT, const float* __restrict__ sinT, int rot,
-                                           int tid, int pos_off, bool use_pre, const RopeRegs pre) {
-    const int row = tid >> 2, j = tid & 3;
+template <int DH>
+__device__ __forceinline__ void tile_store_slot(char* lds, const i32x4 (&v)[2], int row0, int nvalid,
+                                                const float* __restrict__ cosT, const float* __restrict__ sinT, int rot,
+                                                int tid, int pos_off, bool use_pre, const RopeRegs pre, int i) {
+    const int row = slot_row<DH>(tid, i), j = slot_pair<DH>(tid);
+    if constexpr (DH == 32) {
+        if (row >= 128) return;                         // (threads without a slot)
+    }
     int ca, cb;
     tile_chunks(rot, j, ca, cb);
-    i32x4 va = t.v[0], vb = t.v[1];
+    i32x4 va = v[0], vb = v[1];
     if (row < nvalid && j < (rot >> 4)) {               // out_a = a cos - b sin, out_b = b cos + a sin (rotate_half)
         f32x4 c0, c1, s0, s1;
         if (use_pre) {
@@ -104,39 +151,51 @@ __device__ __forceinline__ void tile_store(char* lds, const TileRegs<NT>& t, int
             vb[e] = (int)pack_bf16x2(b0 * cc0 + a0 * ss0, b1 * cc1 + a1 * ss1);
         }
     }
-    *reinterpret_cast<i32x4*>(lds + row * AT_STRIDE + 16 * ca) = va;
-    *reinterpret_cast<i32x4*>(lds + row * AT_STRIDE + 16 * cb) = vb;
+    *reinterpret_cast<i32x4*>(lds + row * Hd<DH>::STRIDE + 16 * ca) = va;
+    *reinterpret_cast<i32x4*>(lds + row * Hd<DH>::STRIDE + 16 * cb) = vb;
 }
-template <int NT>
-__device__ __forceinline__ void tile_store(char* lds, const TileRegs<NT>& t, int row0, int nvalid,
+template <int NT, int DH = 64>
+__device__ __forceinline__ void tile_store(char* lds, const TileRegs<NT, DH>& t, int row0, int nvalid,
+                                           const float* __restrict__ cosT, const float* __restrict__ sinT, int rot,
+                                           int tid, int pos_off, bool use_pre, const RopeSet<DH> pre) {
+    tile_store_slot<DH>(lds, t.v[0], row0, nvalid, cosT, sinT, rot, tid, pos_off, use_pre, pre.r[0], 0);
+    if constexpr (Hd<DH>::NP == 2)
+        tile_store_slot<DH>(lds, t.v[1], row0, nvalid, cosT, sinT, rot, tid, pos_off, use_pre, pre.r[1], 1);
+}
+template <int NT, int DH = 64>
+__device__ __forceinline__ void tile_store(char* lds, const TileRegs<NT, DH>& t, int row0, int nvalid,
                                            const float* __restrict__ cosT, const float* __restrict__ sinT, int rot,
                                            int tid, int pos_off = 0) {
     const f32x4 z = f32x4{0.f, 0.f, 0.f, 0.f};
-    tile_store<NT>(lds, t, row0, nvalid, cosT, sinT, rot, tid, pos_off, false, RopeRegs{z, z, z, z});
+    tile_store_slot<DH>(lds, t.v[0], row0, nvalid, cosT, sinT, rot, tid, pos_off, false, RopeRegs{z, z, z, z}, 0);
+    if constexpr (Hd<DH>::NP == 2)
+        tile_store_slot<DH>(lds, t.v[1], row0, nvalid, cosT, sinT, rot, tid, pos_off, false, RopeRegs{z, z, z, z}, 1);
 }
-template <int NT>
+template <int NT, int DH = 64>
 __device__ __forceinline__ void stage_tile(char* lds, const bf16_t* src, int64_t ld, int row0, int nvalid,
                                            const float* __restrict__ cosT, const float* __restrict__ sinT, int rot,
                                            int tid, int pos_off = 0) {
-    TileRegs<NT> t;
-    tile_load<NT>(t, src, ld, row0, nvalid, rot, tid);
-    tile_store<NT>(lds, t, row0, nvalid, cosT, sinT, rot, tid, pos_off);
+    TileRegs<NT, DH> t;
+    tile_load<NT, DH>(t, src, ld, row0, nvalid, rot, tid);
+    tile_store<NT, DH>(lds, t, row0, nvalid, cosT, sinT, rot, tid, pos_off);
 }
 
 // fragment of 16 tile rows (rbase..) x 32 d (k-step s): MFMA operand whose k index is the head dim
+template <int DH = 64>
 __device__ __forceinline__ bf16x8 rowfrag(const char* lds, int rbase, int s, int lane) {
     const int row = rbase + (lane & 15);
     const int c = 4 * s + (lane >> 4);
-    return *reinterpret_cast<const bf16x8*>(lds + row * AT_STRIDE + 16 * c);
+    return *reinterpret_cast<const bf16x8*>(lds + row * Hd<DH>::STRIDE + 16 * c);
 }
 // transposed fragment: MFMA operand whose k index is the TILE ROW and whose lane index is d (dbase + lane&15).
 // element j<4 -> row ra + 4g + j ; j>=4 -> row rb + 4g + (j-4): the k order of a packed accumulator pair.
+template <int DH = 64>
 __device__ __forceinline__ bf16x8 trfrag(const char* lds, int ra, int rb, int dbase, int lane) {
     const int g = lane >> 4, i = lane & 15;
     const int qq = i >> 2, pp = i & 3;
     const int cb = (dbase + 4 * pp) * 2;
-    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, lds + (ra + 4 * g + qq) * AT_STRIDE + cb));
-    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, lds + (rb + 4 * g + qq) * AT_STRIDE + cb));
+    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, lds + (ra + 4 * g + qq) * Hd<DH>::STRIDE + cb));
+    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, lds + (rb + 4 * g + qq) * Hd<DH>::STRIDE + cb));
     s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
     return __builtin_bit_cast(bf16x8, v);
 }
@@ -230,6 +289,25 @@ __device__ __forceinline__ void attn_stamp(const AttnParams& p, int tid, int idx
 #ifndef KALLE_ATTN_ST16
 #define KALLE_ATTN_ST16 1
 #endif
+// store_row<DH>: the same for DH / 16 blocks (pairs of blocks traded as above)
+template <int DH>
+__device__ __forceinline__ void store_row(bf16_t* row, const f32x4 (&v)[DH / 16], int g) {
+    constexpr int NB = DH / 16;
+    uint32_t w[NB][2];
+#pragma unroll
+    for (int dt = 0; dt < NB; ++dt) { w[dt][0] = pack_bf16x2(v[dt][0], v[dt][1]); w[dt][1] = pack_bf16x2(v[dt][2], v[dt][3]); }
+#if KALLE_ATTN_ST16
+#pragma unroll
+    for (int pr = 0; pr < NB / 2; ++pr) {
+        const auto a = __builtin_amdgcn_permlane16_swap(w[2 * pr][0], w[2 * pr + 1][0], false, false);
+        const auto c = __builtin_amdgcn_permlane16_swap(w[2 * pr][1], w[2 * pr + 1][1], false, false);
+        *reinterpret_cast<i32x4*>(row + 16 * (2 * pr + (g & 1)) + 4 * (g & ~1)) = i32x4{(int)a[0], (int)c[0], (int)a[1], (int)c[1]};
+    }
+#else
+#pragma unroll
+    for (int dt = 0; dt < NB; ++dt) *reinterpret_cast<i32x2*>(row + 16 * dt + 4 * g) = i32x2{(int)w[dt][0], (int)w[dt][1]};
+#endif
+}
 __device__ __forceinline__ void store_row64(bf16_t* row, const f32x4& v0, const f32x4& v1, const f32x4& v2, const f32x4& v3, int g) {
     const f32x4 v[4] = {v0, v1, v2, v3};
     uint32_t w[4][2];
@@ -250,16 +328,19 @@ __device__ __forceinline__ void store_row64(bf16_t* row, const f32x4& v0, const 
 }
 
 
-template <int QT>
-__global__ __launch_bounds__(128 / (16 * QT) * 64, QT == 1 ? 4 : 2) void attn_fwd_kernel(AttnParams p) {
+// DH = 128: the Q | K | V tiles (3 x 36 KiB) leave room for one workgroup per CU, so its 8 waves may take 256 VGPRs each.
+template <int QT, int DH = 64>
+__global__ __launch_bounds__(128 / (16 * QT) * 64, DH == 128 ? 2 : QT == 1 ? 4 : 2) void attn_fwd_kernel(AttnParams p) {
     constexpr int NT = 128 / (16 * QT) * 64;
+    constexpr int STRIDE = Hd<DH>::STRIDE, TILE = Hd<DH>::TILE, KS = DH / 32, DT = DH / 16;
+    constexpr float SCALE = Hd<DH>::SCALE, SCALE_LOG2E = Hd<DH>::SCALE_LOG2E;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Qs = smem;
-    char* Ks = smem + AT_TILE;
-    char* Vs = smem + 2 * AT_TILE;
-    float* kbias = reinterpret_cast<float*>(smem + 3 * AT_TILE);  // [128] + [32] for the folded tail
-    char* Kt = smem + 3 * AT_TILE + 640;                          // tail keys (fold_tail): two 16-row tiles of K and of V
-    char* Vt = Kt + 32 * AT_STRIDE;
+    char* Ks = smem + TILE;
+    char* Vs = smem + 2 * TILE;
+    float* kbias = reinterpret_cast<float*>(smem + 3 * TILE);  // [128] + [32] for the folded tail
+    char* Kt = smem + 3 * TILE + 640;                          // tail keys (fold_tail): two 16-row tiles of K and of V
+    char* Vt = Kt + 32 * STRIDE;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 4, li = lane & 15;
@@ -273,33 +354,49 @@ __global__ __launch_bounds__(128 / (16 * QT) * 64, QT == 1 ? 4 : 2) void attn_fw
     attn_stamp(p, tid, 0);
     const int hk = h / (p.H / p.Hkv);
 
-    const bf16_t* qsrc = p.q + (int64_t)b * p.Nq * p.ldq + p.q_off + h * 64;
-    const bf16_t* ksrc = p.k + (int64_t)b * p.Nk * p.ldk + p.k_off + hk * 64;
-    const bf16_t* vsrc = p.v + (int64_t)b * p.Nk * p.ldv + p.v_off + hk * 64;
+    const bf16_t* qsrc = p.q + (int64_t)b * p.Nq * p.ldq + p.q_off + h * DH;
+    const bf16_t* ksrc = p.k + (int64_t)b * p.Nk * p.ldk + p.k_off + hk * DH;
+    const bf16_t* vsrc = p.v + (int64_t)b * p.Nk * p.ldv + p.v_off + hk * DH;
 
     {   // Q and the first K / V block: all global loads in flight together, then rotary + LDS writes
-        TileRegs<NT> tq, tk, tv;
+        TileRegs<NT, DH> tq, tk, tv;
         const int kv0 = min(128, p.Nk);
-        tile_load<NT>(tq, qsrc, p.ldq, q0, min(128, p.Nq - q0), p.rot, tid);
-        tile_load<NT>(tk, ksrc, p.ldk, 0, kv0, p.rot, tid);
-        tile_load<NT>(tv, vsrc, p.ldv, 0, kv0, 0, tid);
-        const RopeRegs rq = rope_load(p.cosT, p.sinT, q0, min(128, p.Nq - q0), p.rot, tid, p.qpos);   // (rot == 0: no loads)
-        const RopeRegs rk = rope_load(p.cosT, p.sinT, 0, kv0, p.rot, tid);
-        i32x4 tt = i32x4{0, 0, 0, 0};                   // one 16-byte chunk of the tail per thread: K rows then V rows (zero beyond Nk)
+        tile_load<NT, DH>(tq, qsrc, p.ldq, q0, min(128, p.Nq - q0), p.rot, tid);
+        tile_load<NT, DH>(tk, ksrc, p.ldk, 0, kv0, p.rot, tid);
+        tile_load<NT, DH>(tv, vsrc, p.ldv, 0, kv0, 0, tid);
+        const RopeSet<DH> rq = rope_load<DH>(p.cosT, p.sinT, q0, min(128, p.Nq - q0), p.rot, tid, p.qpos);   // (rot == 0: no loads)
+        const RopeSet<DH> rk = rope_load<DH>(p.cosT, p.sinT, 0, kv0, p.rot, tid);
+        // the tail: 16-byte chunks c = tid + 512 i over [K | V][32 rows][DH / 8 chunks] (zero beyond Nk): one per thread at DH 64
+        constexpr int TCH = DH / 8, TCH_LOG2 = DH == 32 ? 2 : DH == 64 ? 3 : 4, TN = (64 * TCH + NT - 1) / NT;
+        constexpr bool TEXACT = TN * NT == 64 * TCH;     // (DH 32: threads 256.. carry no chunk)
+        i32x4 tt[TN];
+        tt[0] = i32x4{0, 0, 0, 0};
+        if constexpr (TN == 2) tt[1] = i32x4{0, 0, 0, 0};
         if constexpr (QT == 1) {
             if (fold_tail) {
-                const int row = (tid >> 3) & 31, key = 128 + row;
-                if (key < p.Nk)
-                    tt = *reinterpret_cast<const i32x4*>((tid < 256 ? ksrc + (int64_t)key * p.ldk : vsrc + (int64_t)key * p.ldv) +
-                                                         8 * (tid & 7));
+                auto tail_load = [&](int i) {
+                    const int c = tid + NT * i;
+                    const int row = (c >> TCH_LOG2) & 31, key = 128 + row;
+                    if ((TEXACT || c < 64 * TCH) && key < p.Nk)
+                        tt[i] = *reinterpret_cast<const i32x4*>((c < 32 * TCH ? ksrc + (int64_t)key * p.ldk : vsrc + (int64_t)key * p.ldv) +
+                                                                8 * (c & (TCH - 1)));
+                };
+                tail_load(0);
+                if constexpr (TN == 2) tail_load(1);
             }
         }
-        tile_store<NT>(Qs, tq, q0, min(128, p.Nq - q0), p.cosT, p.sinT, p.rot, tid, p.qpos, p.rot != 0, rq);
-        tile_store<NT>(Ks, tk, 0, kv0, p.cosT, p.sinT, p.rot, tid, 0, p.rot != 0, rk);
-        tile_store<NT>(Vs, tv, 0, kv0, nullptr, nullptr, 0, tid);
+        tile_store<NT, DH>(Qs, tq, q0, min(128, p.Nq - q0), p.cosT, p.sinT, p.rot, tid, p.qpos, p.rot != 0, rq);
+        tile_store<NT, DH>(Ks, tk, 0, kv0, p.cosT, p.sinT, p.rot, tid, 0, p.rot != 0, rk);
+        tile_store<NT, DH>(Vs, tv, 0, kv0, nullptr, nullptr, 0, tid);
         if constexpr (QT == 1) {
             if (fold_tail) {
-                *reinterpret_cast<i32x4*>((tid < 256 ? Kt : Vt) + ((tid >> 3) & 31) * AT_STRIDE + 16 * (tid & 7)) = tt;
+                auto tail_store = [&](int i) {
+                    const int c = tid + NT * i;
+                    if (TEXACT || c < 64 * TCH)
+                        *reinterpret_cast<i32x4*>((c < 32 * TCH ? Kt : Vt) + ((c >> TCH_LOG2) & 31) * STRIDE + 16 * (c & (TCH - 1))) = tt[i];
+                };
+                tail_store(0);
+                if constexpr (TN == 2) tail_store(1);
                 if (tid < 32) {
                     float bias = 0.f;
                     if (128 + tid >= p.Nk) bias = -INFINITY;
@@ -311,18 +408,18 @@ __global__ __launch_bounds__(128 / (16 * QT) * 64, QT == 1 ? 4 : 2) void attn_fw
     }
     __syncthreads();
     attn_stamp(p, tid, 1);
-    bf16x8 qf[QT][2];
+    bf16x8 qf[QT][KS];
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt)
 #pragma unroll
-        for (int s = 0; s < 2; ++s) qf[qt][s] = rowfrag(Qs, wave * (16 * QT) + 16 * qt, s, lane);
+        for (int s = 0; s < KS; ++s) qf[qt][s] = rowfrag<DH>(Qs, wave * (16 * QT) + 16 * qt, s, lane);
 
     float m[QT], l[QT];
-    f32x4 o[4][QT];
+    f32x4 o[DT][QT];
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) { m[qt] = M_INIT; l[qt] = 0.f; }   // m: running max of the RAW scores
 #pragma unroll
-    for (int dt = 0; dt < 4; ++dt)
+    for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) o[dt][qt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
@@ -332,8 +429,8 @@ __global__ __launch_bounds__(128 / (16 * QT) * 64, QT == 1 ? 4 : 2) void attn_fw
         const int kval = min(128, p.Nk - k0);
         if (k0 > 0) {         // (block 0 was staged with Q)
             __syncthreads();  // previous block's K/V reads are done
-            stage_tile<NT>(Ks, ksrc, p.ldk, k0, kval, p.cosT, p.sinT, p.rot, tid);
-            stage_tile<NT>(Vs, vsrc, p.ldv, k0, kval, nullptr, nullptr, 0, tid);
+            stage_tile<NT, DH>(Ks, ksrc, p.ldk, k0, kval, p.cosT, p.sinT, p.rot, tid);
+            stage_tile<NT, DH>(Vs, vsrc, p.ldv, k0, kval, nullptr, nullptr, 0, tid);
         }
         if (tid < 128) {
             float bias = 0.f;
@@ -356,8 +453,8 @@ __global__ __launch_bounds__(128 / (16 * QT) * 64, QT == 1 ? 4 : 2) void attn_fw
 #pragma unroll
                 for (int qt = 0; qt < QT; ++qt) acc[kt][qt] = kb;
 #pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    const bf16x8 kf = rowfrag(Kb, 16 * kt, s, lane);
+                for (int s = 0; s < KS; ++s) {
+                    const bf16x8 kf = rowfrag<DH>(Kb, 16 * kt, s, lane);
 #pragma unroll
                     for (int qt = 0; qt < QT; ++qt)
                         acc[kt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[qt][s], acc[kt][qt], 0, 0, 0);
@@ -389,9 +486,9 @@ __global__ __launch_bounds__(128 / (16 * QT) * 64, QT == 1 ? 4 : 2) void attn_fw
                     mx = max3_raw(mx, acc[kt][qt][2], acc[kt][qt][3]);
                 }
                 const float mn = xor16_32_max(mx);
-                alpha[qt] = __builtin_amdgcn_exp2f((m[qt] - mn) * SM_SCALE_LOG2E);
+                alpha[qt] = __builtin_amdgcn_exp2f((m[qt] - mn) * SCALE_LOG2E);
                 m[qt] = mn;
-                const f32x2 nm2 = f32x2{-mn, -mn}, c2 = f32x2{SM_SCALE_LOG2E, SM_SCALE_LOG2E};
+                const f32x2 nm2 = f32x2{-mn, -mn}, c2 = f32x2{SCALE_LOG2E, SCALE_LOG2E};
                 f32x4 ps4 = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int kt = 0; kt < NKT; ++kt) {
@@ -404,7 +501,7 @@ __global__ __launch_bounds__(128 / (16 * QT) * 64, QT == 1 ? 4 : 2) void attn_fw
                 }
                 l[qt] = l[qt] * alpha[qt] + ((ps4[0] + ps4[1]) + (ps4[2] + ps4[3]));
 #pragma unroll
-                for (int dt = 0; dt < 4; ++dt) o[dt][qt] *= alpha[qt];      // (feeds the P.V MFMAs as SrcC: no inline asm)
+                for (int dt = 0; dt < DT; ++dt) o[dt][qt] *= alpha[qt];      // (feeds the P.V MFMAs as SrcC: no inline asm)
             }
             // O^T += V^T P^T
 #pragma unroll
@@ -413,8 +510,8 @@ __global__ __launch_bounds__(128 / (16 * QT) * 64, QT == 1 ? 4 : 2) void attn_fw
 #pragma unroll
                 for (int qt = 0; qt < QT; ++qt) pb[qt] = pack_pair(acc[2 * ks][qt], acc[2 * ks + 1][qt]);
 #pragma unroll
-                for (int dt = 0; dt < 4; ++dt) {
-                    const bf16x8 vf = trfrag(Vb, 32 * ks, 32 * ks + 16, 16 * dt, lane);
+                for (int dt = 0; dt < DT; ++dt) {
+                    const bf16x8 vf = trfrag<DH>(Vb, 32 * ks, 32 * ks + 16, 16 * dt, lane);
 #pragma unroll
                     for (int qt = 0; qt < QT; ++qt)
                         o[dt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pb[qt], o[dt][qt], 0, 0, 0);
@@ -435,9 +532,11 @@ __global__ __launch_bounds__(128 / (16 * QT) * 64, QT == 1 ? 4 : 2) void attn_fw
         const float inv = lt > 0.f ? 1.f / lt : 0.f;
         const int qi = q0 + wave * (16 * QT) + 16 * qt + li;
         if (qi < p.Nq) {
-            store_row64(p.out + ((int64_t)b * p.Nq + qi) * p.ldo + h * 64, o[0][qt] * inv, o[1][qt] * inv, o[2][qt] * inv,
-                        o[3][qt] * inv, g);
-            if (g == 0 && p.lse) p.lse[((int64_t)b * p.H + h) * p.Nq + qi] = m[qt] * SM_SCALE + __logf(lt);
+            f32x4 ov[DT];
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt) ov[dt] = o[dt][qt] * inv;
+            store_row<DH>(p.out + ((int64_t)b * p.Nq + qi) * p.ldo + h * DH, ov, g);
+            if (g == 0 && p.lse) p.lse[((int64_t)b * p.H + h) * p.Nq + qi] = m[qt] * SCALE + __logf(lt);
         }
     }
     if (p.stamps) {
@@ -454,13 +553,16 @@ __global__ __launch_bounds__(128 / (16 * QT) * 64, QT == 1 ? 4 : 2) void attn_fw
 //           S^T[key,q] = K Q^T ; dQ^T += K^T dS^T
 // In both, the owner's fragments sit in registers (B operand, "column" index on the lane) and the streamed tensors
 // are LDS images read as row fragments (A operand) and as transposed fragments.
-template <bool KV, int OT>
-__global__ __launch_bounds__(128 / (16 * OT) * 64, OT == 1 ? 4 : 2) void attn_bwd_kernel(AttnParams p) {
+// DH = 128: twice the owner fragments and accumulators of DH = 64 - up to 256 VGPRs (one workgroup per CU) instead of spilling.
+template <bool KV, int OT, int DH = 64>
+__global__ __launch_bounds__(128 / (16 * OT) * 64, DH == 128 ? 2 : OT == 1 ? 4 : 2) void attn_bwd_kernel(AttnParams p) {
     constexpr int NT = 128 / (16 * OT) * 64;
+    constexpr int STRIDE = Hd<DH>::STRIDE, TILE = Hd<DH>::TILE, KS = DH / 32, DT = DH / 16;
+    constexpr float SM_SCALE = Hd<DH>::SCALE, SM_SCALE_LOG2E = Hd<DH>::SCALE_LOG2E;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* R1 = smem;
-    char* R2 = smem + AT_TILE;
-    float* rowa = reinterpret_cast<float*>(smem + 2 * AT_TILE);  // [128] per streamed row: lse (KV) / key bias (!KV)
+    char* R2 = smem + TILE;
+    float* rowa = reinterpret_cast<float*>(smem + 2 * TILE);  // [128] per streamed row: lse (KV) / key bias (!KV)
     float* rowb = rowa + 128;                                    // [128] per streamed row: delta (KV)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -472,8 +574,8 @@ __global__ __launch_bounds__(128 / (16 * OT) * 64, OT == 1 ? 4 : 2) void attn_bw
     const int hown = blockIdx.y;      // kv head (KV) or q head (!KV)
     const int hk = KV ? hown : hown / group;
 
-    const bf16_t* kbase = p.k + (int64_t)b * p.Nk * p.ldk + p.k_off + hk * 64;
-    const bf16_t* vbase = p.v + (int64_t)b * p.Nk * p.ldv + p.v_off + hk * 64;
+    const bf16_t* kbase = p.k + (int64_t)b * p.Nk * p.ldk + p.k_off + hk * DH;
+    const bf16_t* vbase = p.v + (int64_t)b * p.Nk * p.ldv + p.v_off + hk * DH;
 
     // The first streamed block (first query block of the group's first head / first key block) is fetched together with the
     // owner tiles - one global-load latency per workgroup instead of two.  With causal masking the dK/dV kernel starts at the
@@ -484,52 +586,66 @@ __global__ __launch_bounds__(128 / (16 * OT) * 64, OT == 1 ? 4 : 2) void attn_bw
     if (KV && p.causal) sfirst = ((max(o0 - coff - 127, 0) + 127) / 128) * 128;
     const bool has_first = sfirst < nstream;
     const int sval0 = min(128, nstream - sfirst);
-    TileRegs<NT> f1, f2;
+    TileRegs<NT, DH> f1, f2;
     // ---- owner fragments -> registers ----
     if constexpr (KV) {
         const int val = min(128, p.Nk - o0);
-        TileRegs<NT> t1, t2;
-        tile_load<NT>(t1, kbase, p.ldk, o0, val, p.rot, tid);
-        tile_load<NT>(t2, vbase, p.ldv, o0, val, 0, tid);
+        TileRegs<NT, DH> t1, t2;
+        tile_load<NT, DH>(t1, kbase, p.ldk, o0, val, p.rot, tid);
+        tile_load<NT, DH>(t2, vbase, p.ldv, o0, val, 0, tid);
         if (has_first) {
             const int hq0 = hk * group;
-            tile_load<NT>(f1, p.q + (int64_t)b * p.Nq * p.ldq + p.q_off + hq0 * 64, p.ldq, sfirst, sval0, p.rot, tid);
-            tile_load<NT>(f2, p.dout + (int64_t)b * p.Nq * p.ldo + hq0 * 64, p.ldo, sfirst, sval0, 0, tid);
+            tile_load<NT, DH>(f1, p.q + (int64_t)b * p.Nq * p.ldq + p.q_off + hq0 * DH, p.ldq, sfirst, sval0, p.rot, tid);
+            tile_load<NT, DH>(f2, p.dout + (int64_t)b * p.Nq * p.ldo + hq0 * DH, p.ldo, sfirst, sval0, 0, tid);
         }
-        tile_store<NT>(R1, t1, o0, val, p.cosT, p.sinT, p.rot, tid);
-        tile_store<NT>(R2, t2, o0, val, nullptr, nullptr, 0, tid);
+        tile_store<NT, DH>(R1, t1, o0, val, p.cosT, p.sinT, p.rot, tid);
+        tile_store<NT, DH>(R2, t2, o0, val, nullptr, nullptr, 0, tid);
     } else {
         const int val = min(128, p.Nq - o0);
-        const bf16_t* qb = p.q + (int64_t)b * p.Nq * p.ldq + p.q_off + hown * 64;
-        const bf16_t* dob = p.dout + (int64_t)b * p.Nq * p.ldo + hown * 64;
+        const bf16_t* qb = p.q + (int64_t)b * p.Nq * p.ldq + p.q_off + hown * DH;
+        const bf16_t* dob = p.dout + (int64_t)b * p.Nq * p.ldo + hown * DH;
         // delta[q] = sum_d dO[q][d] O[q][d] of the owner rows is computed here (4 threads per row: O from global, in flight
         // with the tile loads; dO from its LDS tile) and stored for the dK/dV kernel, which runs after this one - a
         // separate pass over dO and O (attn_delta_kernel, 34 us per layer at the bench shape) is gone
+        // (a thread reads DH / 4 elements of its row: NE 16-byte chunks)
+        constexpr int NE = DH / 32;
         const int drow = tid >> 2, dq4 = tid & 3;
-        i32x4 o0v = i32x4{0, 0, 0, 0}, o1v = i32x4{0, 0, 0, 0};
+        i32x4 o0v = i32x4{0, 0, 0, 0}, o1v = i32x4{0, 0, 0, 0}, o2v = i32x4{0, 0, 0, 0}, o3v = i32x4{0, 0, 0, 0};
         if (NT == 512 && drow < val) {
-            const bf16_t* op = p.out + ((int64_t)b * p.Nq + o0 + drow) * p.ldo + hown * 64 + 16 * dq4;
+            const bf16_t* op = p.out + ((int64_t)b * p.Nq + o0 + drow) * p.ldo + hown * DH + (DH / 4) * dq4;
             o0v = *reinterpret_cast<const i32x4*>(op);
-            o1v = *reinterpret_cast<const i32x4*>(op + 8);
+            if constexpr (NE >= 2) o1v = *reinterpret_cast<const i32x4*>(op + 8);
+            if constexpr (NE == 4) {
+                o2v = *reinterpret_cast<const i32x4*>(op + 16);
+                o3v = *reinterpret_cast<const i32x4*>(op + 24);
+            }
         }
-        TileRegs<NT> t1, t2;
-        tile_load<NT>(t1, qb, p.ldq, o0, val, p.rot, tid);
-        tile_load<NT>(t2, dob, p.ldo, o0, val, 0, tid);
+        TileRegs<NT, DH> t1, t2;
+        tile_load<NT, DH>(t1, qb, p.ldq, o0, val, p.rot, tid);
+        tile_load<NT, DH>(t2, dob, p.ldo, o0, val, 0, tid);
         if (has_first) {
-            tile_load<NT>(f1, kbase, p.ldk, sfirst, sval0, p.rot, tid);
-            tile_load<NT>(f2, vbase, p.ldv, sfirst, sval0, 0, tid);
+            tile_load<NT, DH>(f1, kbase, p.ldk, sfirst, sval0, p.rot, tid);
+            tile_load<NT, DH>(f2, vbase, p.ldv, sfirst, sval0, 0, tid);
         }
-        tile_store<NT>(R1, t1, o0, val, p.cosT, p.sinT, p.rot, tid, p.qpos);
-        tile_store<NT>(R2, t2, o0, val, nullptr, nullptr, 0, tid);
+        tile_store<NT, DH>(R1, t1, o0, val, p.cosT, p.sinT, p.rot, tid, p.qpos);
+        tile_store<NT, DH>(R2, t2, o0, val, nullptr, nullptr, 0, tid);
         __syncthreads();
         if (NT == 512) {
-            const i32x4 d0v = *reinterpret_cast<const i32x4*>(R2 + drow * AT_STRIDE + 32 * dq4);
-            const i32x4 d1v = *reinterpret_cast<const i32x4*>(R2 + drow * AT_STRIDE + 32 * dq4 + 16);
+            const char* dp_ = R2 + drow * STRIDE + (DH / 2) * dq4;
+            const i32x4 d0v = *reinterpret_cast<const i32x4*>(dp_);
+            const i32x4 d1v = NE >= 2 ? *reinterpret_cast<const i32x4*>(dp_ + 16) : i32x4{0, 0, 0, 0};
+            const i32x4 d2v = NE == 4 ? *reinterpret_cast<const i32x4*>(dp_ + 32) : i32x4{0, 0, 0, 0};
+            const i32x4 d3v = NE == 4 ? *reinterpret_cast<const i32x4*>(dp_ + 48) : i32x4{0, 0, 0, 0};
             float dl = 0.f;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 dl += bf16lo((uint32_t)o0v[e]) * bf16lo((uint32_t)d0v[e]) + bf16hi((uint32_t)o0v[e]) * bf16hi((uint32_t)d0v[e]);
-                dl += bf16lo((uint32_t)o1v[e]) * bf16lo((uint32_t)d1v[e]) + bf16hi((uint32_t)o1v[e]) * bf16hi((uint32_t)d1v[e]);
+                if constexpr (NE >= 2)
+                    dl += bf16lo((uint32_t)o1v[e]) * bf16lo((uint32_t)d1v[e]) + bf16hi((uint32_t)o1v[e]) * bf16hi((uint32_t)d1v[e]);
+                if constexpr (NE == 4) {
+                    dl += bf16lo((uint32_t)o2v[e]) * bf16lo((uint32_t)d2v[e]) + bf16hi((uint32_t)o2v[e]) * bf16hi((uint32_t)d2v[e]);
+                    dl += bf16lo((uint32_t)o3v[e]) * bf16lo((uint32_t)d3v[e]) + bf16hi((uint32_t)o3v[e]) * bf16hi((uint32_t)d3v[e]);
+                }
             }
             dl += __shfl_xor(dl, 1, 64);
             dl += __shfl_xor(dl, 2, 64);
@@ -540,13 +656,13 @@ __global__ __launch_bounds__(128 / (16 * OT) * 64, OT == 1 ? 4 : 2) void attn_bw
         }
     }
     __syncthreads();
-    bf16x8 y1[OT][2], y2[OT][2];
+    bf16x8 y1[OT][KS], y2[OT][KS];
 #pragma unroll
     for (int ot = 0; ot < OT; ++ot)
 #pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            y1[ot][s] = rowfrag(R1, wave * (16 * OT) + 16 * ot, s, lane);
-            y2[ot][s] = rowfrag(R2, wave * (16 * OT) + 16 * ot, s, lane);
+        for (int s = 0; s < KS; ++s) {
+            y1[ot][s] = rowfrag<DH>(R1, wave * (16 * OT) + 16 * ot, s, lane);
+            y2[ot][s] = rowfrag<DH>(R2, wave * (16 * OT) + 16 * ot, s, lane);
         }
     // per-owner-column scalars
     // KV: ca = score bias of the owner key (0 valid / -inf masked or past the end).  !KV: ca = -lse[q] * log2 e (-inf for
@@ -567,9 +683,9 @@ __global__ __launch_bounds__(128 / (16 * OT) * 64, OT == 1 ? 4 : 2) void attn_bw
         }
     }
 
-    f32x4 g1[4][OT], g2[4][OT];  // g2: dK^T / dQ^T accumulators [d tile][owner tile]; g1: dV^T (KV only)
+    f32x4 g1[DT][OT], g2[DT][OT];  // g2: dK^T / dQ^T accumulators [d tile][owner tile]; g1: dV^T (KV only)
 #pragma unroll
-    for (int dt = 0; dt < 4; ++dt)
+    for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
         for (int ot = 0; ot < OT; ++ot) {
             g1[dt][ot] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -581,8 +697,8 @@ __global__ __launch_bounds__(128 / (16 * OT) * 64, OT == 1 ? 4 : 2) void attn_bw
     // before the loop (kept alive by a flag inside the loop they would cost 16 VGPRs in every iteration)
     if (has_first) {
         __syncthreads();
-        tile_store<NT>(R1, f1, sfirst, sval0, p.cosT, p.sinT, p.rot, tid, KV ? p.qpos : 0);
-        tile_store<NT>(R2, f2, sfirst, sval0, nullptr, nullptr, 0, tid);
+        tile_store<NT, DH>(R1, f1, sfirst, sval0, p.cosT, p.sinT, p.rot, tid, KV ? p.qpos : 0);
+        tile_store<NT, DH>(R2, f2, sfirst, sval0, nullptr, nullptr, 0, tid);
     }
     bool first = has_first;                 // (the first block the loop reaches is block `sfirst` of head 0)
     for (int hh = 0; hh < nheads; ++hh) {
@@ -594,11 +710,11 @@ __global__ __launch_bounds__(128 / (16 * OT) * 64, OT == 1 ? 4 : 2) void attn_bw
             if (!first) __syncthreads();  // previous tile fully consumed
             const int sval = min(128, nstream - s0);
             if constexpr (KV) {
-                const bf16_t* qb = p.q + (int64_t)b * p.Nq * p.ldq + p.q_off + hq * 64;
-                const bf16_t* dob = p.dout + (int64_t)b * p.Nq * p.ldo + hq * 64;
+                const bf16_t* qb = p.q + (int64_t)b * p.Nq * p.ldq + p.q_off + hq * DH;
+                const bf16_t* dob = p.dout + (int64_t)b * p.Nq * p.ldo + hq * DH;
                 if (!first) {
-                    stage_tile<NT>(R1, qb, p.ldq, s0, sval, p.cosT, p.sinT, p.rot, tid, p.qpos);
-                    stage_tile<NT>(R2, dob, p.ldo, s0, sval, nullptr, nullptr, 0, tid);
+                    stage_tile<NT, DH>(R1, qb, p.ldq, s0, sval, p.cosT, p.sinT, p.rot, tid, p.qpos);
+                    stage_tile<NT, DH>(R2, dob, p.ldo, s0, sval, nullptr, nullptr, 0, tid);
                 }
                 if (tid < 128) {
                     const bool ok = tid < sval;
@@ -608,8 +724,8 @@ __global__ __launch_bounds__(128 / (16 * OT) * 64, OT == 1 ? 4 : 2) void attn_bw
                 }
             } else {
                 if (!first) {
-                    stage_tile<NT>(R1, kbase, p.ldk, s0, sval, p.cosT, p.sinT, p.rot, tid);
-                    stage_tile<NT>(R2, vbase, p.ldv, s0, sval, nullptr, nullptr, 0, tid);
+                    stage_tile<NT, DH>(R1, kbase, p.ldk, s0, sval, p.cosT, p.sinT, p.rot, tid);
+                    stage_tile<NT, DH>(R2, vbase, p.ldv, s0, sval, nullptr, nullptr, 0, tid);
                 }
                 if (tid < 128) {
                     bool ok = tid < sval;
@@ -643,9 +759,9 @@ __global__ __launch_bounds__(128 / (16 * OT) * 64, OT == 1 ? 4 : 2) void attn_bw
                         dp[t][ot] = f32x4{0.f, 0.f, 0.f, 0.f};
                     }
 #pragma unroll
-                    for (int s = 0; s < 2; ++s) {
-                        const bf16x8 x1 = rowfrag(R1, rb, s, lane);
-                        const bf16x8 x2 = rowfrag(R2, rb, s, lane);
+                    for (int s = 0; s < KS; ++s) {
+                        const bf16x8 x1 = rowfrag<DH>(R1, rb, s, lane);
+                        const bf16x8 x2 = rowfrag<DH>(R2, rb, s, lane);
 #pragma unroll
                         for (int ot = 0; ot < OT; ++ot) {
                             sa[t][ot] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x1, y1[ot][s], sa[t][ot], 0, 0, 0);
@@ -687,13 +803,13 @@ __global__ __launch_bounds__(128 / (16 * OT) * 64, OT == 1 ? 4 : 2) void attn_bw
                     dsb[ot] = pack_pair(dp[0][ot], dp[1][ot]);
                 }
 #pragma unroll
-                for (int dt = 0; dt < 4; ++dt) {
-                    const bf16x8 a1 = trfrag(R1, 32 * pr, 32 * pr + 16, 16 * dt, lane);
+                for (int dt = 0; dt < DT; ++dt) {
+                    const bf16x8 a1 = trfrag<DH>(R1, 32 * pr, 32 * pr + 16, 16 * dt, lane);
 #pragma unroll
                     for (int ot = 0; ot < OT; ++ot)
                         g2[dt][ot] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, dsb[ot], g2[dt][ot], 0, 0, 0);
                     if constexpr (KV) {
-                        const bf16x8 a2 = trfrag(R2, 32 * pr, 32 * pr + 16, 16 * dt, lane);
+                        const bf16x8 a2 = trfrag<DH>(R2, 32 * pr, 32 * pr + 16, 16 * dt, lane);
 #pragma unroll
                         for (int ot = 0; ot < OT; ++ot)
                             g1[dt][ot] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, pb[ot], g1[dt][ot], 0, 0, 0);
@@ -710,15 +826,15 @@ __global__ __launch_bounds__(128 / (16 * OT) * 64, OT == 1 ? 4 : 2) void attn_bw
         const int oi = o0 + wave * (16 * OT) + 16 * ot + li;
         if (oi >= nown) continue;
         if (p.rot) {
-            const int hts = p.rot >> 5;                 // 16-dim tiles per rotary half (1 or 2)
+            const int hts = p.rot >> 5;                 // 16-dim tiles per rotary half (1 or 2; 1 at DH 32)
 #pragma unroll
-            for (int ht = 0; ht < 2; ++ht) {
+            for (int ht = 0; ht < (DH == 32 ? 1 : 2); ++ht) {
                 if (ht >= hts) break;
                 const int64_t pos = oi + (KV ? 0 : p.qpos);
                 const f32x4 c4 = *reinterpret_cast<const f32x4*>(p.cosT + pos * (p.rot >> 1) + 16 * ht + 4 * g);
                 const f32x4 s4 = *reinterpret_cast<const f32x4*>(p.sinT + pos * (p.rot >> 1) + 16 * ht + 4 * g);
                 f32x4& lo = hts == 1 ? g2[0][ot] : g2[ht][ot];
-                f32x4& hi = hts == 1 ? g2[1][ot] : g2[ht + 2][ot];
+                f32x4& hi = hts == 1 ? g2[1][ot] : g2[DH == 32 ? 1 : ht + 2][ot];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const float a = lo[r], bb = hi[r];
@@ -728,10 +844,10 @@ __global__ __launch_bounds__(128 / (16 * OT) * 64, OT == 1 ? 4 : 2) void attn_bw
             }
         }
         if constexpr (KV) {
-            bf16_t* dkp = p.dk + ((int64_t)b * p.Nk + oi) * p.ldk + p.k_off + hk * 64 + 4 * g;
-            bf16_t* dvp = p.dv + ((int64_t)b * p.Nk + oi) * p.ldv + p.v_off + hk * 64 + 4 * g;
+            bf16_t* dkp = p.dk + ((int64_t)b * p.Nk + oi) * p.ldk + p.k_off + hk * DH + 4 * g;
+            bf16_t* dvp = p.dv + ((int64_t)b * p.Nk + oi) * p.ldv + p.v_off + hk * DH + 4 * g;
 #pragma unroll
-            for (int dt = 0; dt < 4; ++dt) {
+            for (int dt = 0; dt < DT; ++dt) {
                 i32x2 w;
                 w[0] = (int)pack_bf16x2(g2[dt][ot][0], g2[dt][ot][1]);
                 w[1] = (int)pack_bf16x2(g2[dt][ot][2], g2[dt][ot][3]);
@@ -741,9 +857,9 @@ __global__ __launch_bounds__(128 / (16 * OT) * 64, OT == 1 ? 4 : 2) void attn_bw
                 *reinterpret_cast<i32x2*>(dvp + 16 * dt) = w;
             }
         } else {
-            bf16_t* dqp = p.dq + ((int64_t)b * p.Nq + oi) * p.ldq + p.q_off + hown * 64 + 4 * g;
+            bf16_t* dqp = p.dq + ((int64_t)b * p.Nq + oi) * p.ldq + p.q_off + hown * DH + 4 * g;
 #pragma unroll
-            for (int dt = 0; dt < 4; ++dt) {
+            for (int dt = 0; dt < DT; ++dt) {
                 i32x2 w;
                 w[0] = (int)pack_bf16x2(g2[dt][ot][0], g2[dt][ot][1]);
                 w[1] = (int)pack_bf16x2(g2[dt][ot][2], g2[dt][ot][3]);
@@ -788,8 +904,8 @@ __global__ __launch_bounds__(512, 4) __attribute__((amdgpu_waves_per_eu(4, 4))) 
         tile_load<NT>(td, dob, p.ldo, 0, N, 0, tid);
         tile_load<NT>(tk, kb, p.ldk, 0, Nk, p.rot, tid);
         tile_load<NT>(tv, vb, p.ldv, 0, Nk, 0, tid);
-        const RopeRegs rq = rope_load(p.cosT, p.sinT, 0, N, p.rot, tid, p.qpos);
-        const RopeRegs rk = rope_load(p.cosT, p.sinT, 0, Nk, p.rot, tid);
+        const RopeSet<> rq = rope_load(p.cosT, p.sinT, 0, N, p.rot, tid, p.qpos);
+        const RopeSet<> rk = rope_load(p.cosT, p.sinT, 0, Nk, p.rot, tid);
         // delta[q] = sum_d dO[q][d] O[q][d]: 4 threads per row, O straight from global (in flight with the tiles)
         const int drow = tid >> 2, dq4 = tid & 3;
         i32x4 o0v = i32x4{0, 0, 0, 0}, o1v = i32x4{0, 0, 0, 0};
@@ -1359,11 +1475,35 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(AttnParams p) {
 static unsigned long long* g_attn_stamps = nullptr;      // diagnostics only
 extern "C" int kalle_attn_debug_stamps(void* buf) { g_attn_stamps = static_cast<unsigned long long*>(buf); return KALLE_OK; }
 
-extern "C" int kalle_attention_fwd(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off,
-                                   const void* v, int64_t ldv, int v_off, void* out, int64_t ldo, float* lse,
-                                   const float* rope_cos, const float* rope_sin, int rot, const uint8_t* key_mask,
-                                   int causal, int B, int H, int Hkv, int Nq, int Nk, void* stream) {
-    if (!out || !check_common(q, ldq, q_off, k, ldk, k_off, v, ldv, v_off, ldo, rot, B, H, Hkv, Nq, Nk))
+// head dims other than 64 (DH 32 / 128): the tiled kernels, Nq == 1 included (the decode kernel is DH = 64 only)
+template <int DH>
+static int attention_fwd_dh(const AttnParams& p, hipStream_t st) {
+    constexpr int lds = 3 * Hd<DH>::TILE + 160 * 4 + 2 * 32 * Hd<DH>::STRIDE;   // Q | K | V, key bias [128 + 32], tail tiles
+    static std::atomic<uint64_t> lds_ok{0};
+    kalle_allow_lds(reinterpret_cast<const void*>(attn_fwd_kernel<1, DH>), lds, lds_ok);
+    KALLE_LAUNCH((attn_fwd_kernel<1, DH>), dim3((p.Nq + 127) / 128, p.H, p.B), dim3(512), lds, st, p);
+    return kalle_check_launch();
+}
+template <int DH>
+static int attention_bwd_dh(const AttnParams& p, hipStream_t st) {
+    constexpr int lds = 2 * Hd<DH>::TILE + 256 * 4;
+    static std::atomic<uint64_t> lds_ok_kv{0}, lds_ok_q{0};
+    kalle_allow_lds(reinterpret_cast<const void*>(attn_bwd_kernel<true, 1, DH>), lds, lds_ok_kv);
+    kalle_allow_lds(reinterpret_cast<const void*>(attn_bwd_kernel<false, 1, DH>), lds, lds_ok_q);
+    KALLE_LAUNCH((attn_bwd_kernel<false, 1, DH>), dim3((p.Nq + 127) / 128, p.H, p.B), dim3(512), lds, st, p);   // dQ + delta first
+    KALLE_LAUNCH((attn_bwd_kernel<true, 1, DH>), dim3((p.Nk + 127) / 128, p.Hkv, p.B), dim3(512), lds, st, p);
+    return kalle_check_launch();
+}
+static bool check_head_dim(int head_dim, int rot) {
+    return (head_dim == 32 || head_dim == 64 || head_dim == 128) && rot <= head_dim;
+}
+
+extern "C" int kalle_attention_fwd_hd(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off,
+                                      const void* v, int64_t ldv, int v_off, void* out, int64_t ldo, float* lse,
+                                      const float* rope_cos, const float* rope_sin, int rot, const uint8_t* key_mask,
+                                      int causal, int B, int H, int Hkv, int Nq, int Nk, int head_dim, void* stream) {
+    if (!out || !check_common(q, ldq, q_off, k, ldk, k_off, v, ldv, v_off, ldo, rot, B, H, Hkv, Nq, Nk) ||
+        !check_head_dim(head_dim, rot))
         return KALLE_ERR_ARG;
     if (rot && (!rope_cos || !rope_sin)) return KALLE_ERR_ARG;
     AttnParams p{};
@@ -1376,6 +1516,8 @@ extern "C" int kalle_attention_fwd(const void* q, int64_t ldq, int q_off, const 
     p.stamps = g_attn_stamps;
     if (causal && Nk < Nq) return KALLE_ERR_ARG;
     p.qpos = causal ? Nk - Nq : 0;
+    if (head_dim == 32) return attention_fwd_dh<32>(p, static_cast<hipStream_t>(stream));
+    if (head_dim == 128) return attention_fwd_dh<128>(p, static_cast<hipStream_t>(stream));
     if (Nq == 1 && Nk <= 15360) {   // decoding against a KV cache: scores of all keys fit in LDS (60 KB)
         const dim3 grid(H, B), block(256);
         hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1392,13 +1534,14 @@ extern "C" int kalle_attention_fwd(const void* q, int64_t ldq, int q_off, const 
     return kalle_check_launch();
 }
 
-extern "C" int kalle_attention_bwd(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off,
-                                   const void* v, int64_t ldv, int v_off, const void* out, const void* dout,
-                                   int64_t ldo, const float* lse, float* delta, void* dq, void* dk, void* dv,
-                                   const float* rope_cos, const float* rope_sin, int rot, const uint8_t* key_mask,
-                                   int causal, int B, int H, int Hkv, int Nq, int Nk, void* stream) {
+extern "C" int kalle_attention_bwd_hd(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off,
+                                      const void* v, int64_t ldv, int v_off, const void* out, const void* dout,
+                                      int64_t ldo, const float* lse, float* delta, void* dq, void* dk, void* dv,
+                                      const float* rope_cos, const float* rope_sin, int rot, const uint8_t* key_mask,
+                                      int causal, int B, int H, int Hkv, int Nq, int Nk, int head_dim, void* stream) {
     if (!out || !dout || !lse || !delta || !dq || !dk || !dv ||
-        !check_common(q, ldq, q_off, k, ldk, k_off, v, ldv, v_off, ldo, rot, B, H, Hkv, Nq, Nk))
+        !check_common(q, ldq, q_off, k, ldk, k_off, v, ldv, v_off, ldo, rot, B, H, Hkv, Nq, Nk) ||
+        !check_head_dim(head_dim, rot))
         return KALLE_ERR_ARG;
     if (rot && (!rope_cos || !rope_sin)) return KALLE_ERR_ARG;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1414,6 +1557,8 @@ extern "C" int kalle_attention_bwd(const void* q, int64_t ldq, int q_off, const 
     p.dout = static_cast<const bf16_t*>(dout); p.delta = delta;
     p.dq = static_cast<bf16_t*>(dq); p.dk = static_cast<bf16_t*>(dk); p.dv = static_cast<bf16_t*>(dv);
     p.stamps = g_attn_stamps;
+    if (head_dim == 32) return attention_bwd_dh<32>(p, st);
+    if (head_dim == 128) return attention_bwd_dh<128>(p, st);
 
     // one block of queries and keys, one kv head per query head (the DiT's self-attention): everything in one kernel
     static const bool fused_env = !(getenv("KALLE_ATTN_FUSED_BWD") && atoi(getenv("KALLE_ATTN_FUSED_BWD")) == 0);
@@ -1442,4 +1587,21 @@ extern "C" int kalle_attention_bwd(const void* q, int64_t ldq, int q_off, const 
     KALLE_LAUNCH((attn_bwd_kernel<false, 1>), dim3((Nq + 127) / 128, H, B), dim3(512), lds, st, p);
     KALLE_LAUNCH((attn_bwd_kernel<true, 1>), dim3((Nk + 127) / 128, Hkv, B), dim3(512), lds, st, p);
     return kalle_check_launch();
+}
+
+// the head-dim-64 entry points of the C ABI (bound by signature from ctypes): unchanged, forwarders
+extern "C" int kalle_attention_fwd(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off,
+                                   const void* v, int64_t ldv, int v_off, void* out, int64_t ldo, float* lse,
+                                   const float* rope_cos, const float* rope_sin, int rot, const uint8_t* key_mask,
+                                   int causal, int B, int H, int Hkv, int Nq, int Nk, void* stream) {
+    return kalle_attention_fwd_hd(q, ldq, q_off, k, ldk, k_off, v, ldv, v_off, out, ldo, lse, rope_cos, rope_sin, rot, key_mask,
+                                  causal, B, H, Hkv, Nq, Nk, 64, stream);
+}
+extern "C" int kalle_attention_bwd(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off,
+                                   const void* v, int64_t ldv, int v_off, const void* out, const void* dout,
+                                   int64_t ldo, const float* lse, float* delta, void* dq, void* dk, void* dv,
+                                   const float* rope_cos, const float* rope_sin, int rot, const uint8_t* key_mask,
+                                   int causal, int B, int H, int Hkv, int Nq, int Nk, void* stream) {
+    return kalle_attention_bwd_hd(q, ldq, q_off, k, ldk, k_off, v, ldv, v_off, out, dout, ldo, lse, delta, dq, dk, dv, rope_cos,
+                                  rope_sin, rot, key_mask, causal, B, H, Hkv, Nq, Nk, 64, stream);
 }

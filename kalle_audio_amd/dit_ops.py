@@ -197,7 +197,7 @@ def dgrad(dy, w, **kw):
 # ------------------------------------------------------------------------------------------------ attention
 def qk_norm_params(attn):
     """Attention(qk_norm=...) (transformer.py:303-307): None, or (mode, q gamma, q beta, k gamma, k beta) - mode 1 "l2" (no
-    parameters), 2 "ln" (two LayerNorm(64))"""
+    parameters), 2 "ln" (two LayerNorm(dim_heads))"""
     kind = getattr(attn, "qk_norm", "none")
     if kind == "none":
         return None
@@ -206,41 +206,42 @@ def qk_norm_params(attn):
     return (2, f32_of(attn.q_norm.weight), f32_of(attn.q_norm.bias), f32_of(attn.k_norm.weight), f32_of(attn.k_norm.bias))
 
 
-def _qk_norm_bwd(go, pre, qkn, which, x, ldx, x_off, stat, g, dx, lddx, dx_off, rows, heads):
+def _qk_norm_bwd(go, pre, qkn, which, x, ldx, x_off, stat, g, dx, lddx, dx_off, rows, heads, dh=64):
     """head-norm backward of q (`which` = "q_norm") or k; LayerNorm scale / bias gradients go to the sinks (added atomically)"""
     mode = qkn[0]
     gamma = dga = dbe = None
     if mode == 2:
         gamma = qkn[1] if which == "q_norm" else qkn[3]
-        dga = go.bias_acc(pre + which + ".weight", 64, x.device)
-        dbe = go.bias_acc(pre + which + ".bias", 64, x.device)
-    ops.head_norm_bwd(x, ldx, x_off, stat, g, dx, lddx, dx_off, rows, heads, mode, gamma, dga, dbe)
+        dga = go.bias_acc(pre + which + ".weight", dh, x.device)
+        dbe = go.bias_acc(pre + which + ".bias", dh, x.device)
+    ops.head_norm_bwd(x, ldx, x_off, stat, g, dx, lddx, dx_off, rows, heads, mode, gamma, dga, dbe, dh=dh)
 
 
-def self_attn_fwd(h, wqkv, wo, B, N, H, rope, mask8, residual=None, gate=None, out_dtype=F32, qkn=None, causal=False):
-    """transformer.py:419-420, 430-444, 500/514-530, 541-545.  h: bf16 [B*N, D].  qkn: qk_norm_params()"""
-    D = H * 64
+def self_attn_fwd(h, wqkv, wo, B, N, H, rope, mask8, residual=None, gate=None, out_dtype=F32, qkn=None, causal=False,
+                  dh=64):
+    """transformer.py:419-420, 430-444, 500/514-530, 541-545.  h: bf16 [B*N, D].  qkn: qk_norm_params().  dh: head dim"""
+    D = H * dh
     causal = bool(causal) and N > 1                      # :468-469
     qkv = ops.gemm(h, wqkv)
     nrm = None
     if qkn is not None:     # :422-428, before the rotary embedding (which the attention kernel applies)
-        qn, qs = ops.head_norm_fwd(qkv, 3 * D, 0, B * N, H, qkn[0], qkn[1], qkn[2])
-        kn, ks = ops.head_norm_fwd(qkv, 3 * D, D, B * N, H, qkn[0], qkn[3], qkn[4])
+        qn, qs = ops.head_norm_fwd(qkv, 3 * D, 0, B * N, H, qkn[0], qkn[1], qkn[2], dh=dh)
+        kn, ks = ops.head_norm_fwd(qkv, 3 * D, D, B * N, H, qkn[0], qkn[3], qkn[4], dh=dh)
         nrm = (qn, qs, kn, ks)
         ao, lse = ops.attention_fwd(qn, kn, qkv, ldq=D, q_off=0, ldk=D, k_off=0, ldv=3 * D, v_off=2 * D,
-                                    B=B, H=H, Hkv=H, Nq=N, Nk=N, rope=rope, key_mask=mask8, causal=causal)
+                                    B=B, H=H, Hkv=H, Nq=N, Nk=N, rope=rope, key_mask=mask8, causal=causal, dh=dh)
     else:
         ao, lse = ops.attention_fwd(qkv, qkv, qkv, ldq=3 * D, q_off=0, ldk=3 * D, k_off=D, ldv=3 * D, v_off=2 * D,
-                                    B=B, H=H, Hkv=H, Nq=N, Nk=N, rope=rope, key_mask=mask8, causal=causal)
+                                    B=B, H=H, Hkv=H, Nq=N, Nk=N, rope=rope, key_mask=mask8, causal=causal, dh=dh)
     out = ops.gemm(ao.view(B * N, D), wo, out_dtype=out_dtype, residual=residual, gate=gate, rows_per_batch=N,
                    row_mask=mask8)
     return out, (qkv, ao, lse, nrm)
 
 
-def self_attn_bwd(go, gb, h, saved, wqkv, wo, B, N, H, rope, mask8, pre="self_attn.", qkn=None, causal=False):
+def self_attn_bwd(go, gb, h, saved, wqkv, wo, B, N, H, rope, mask8, pre="self_attn.", qkn=None, causal=False, dh=64):
     """gb: bf16 [B*N, D] gradient w.r.t. the to_out GEMM result. Returns dh (bf16)."""
     qkv, ao, lse, nrm = saved
-    D = H * 64
+    D = H * dh
     causal = bool(causal) and N > 1
     go.wgrad(pre + "to_out.weight", gb, ao.view(B * N, D))
     dao = dgrad(gb, wo)
@@ -249,12 +250,14 @@ def self_attn_bwd(go, gb, h, saved, wqkv, wo, B, N, H, rope, mask8, pre="self_at
         qn, qs, kn, ks = nrm
         dqn, dkn = torch.empty_like(qn), torch.empty_like(kn)
         ops.attention_bwd(qn, kn, qkv, ao, dao, lse, dqn, dkn, dqkv, ldq=D, q_off=0, ldk=D, k_off=0,
-                          ldv=3 * D, v_off=2 * D, B=B, H=H, Hkv=H, Nq=N, Nk=N, rope=rope, key_mask=mask8, causal=causal)
-        _qk_norm_bwd(go, pre, qkn, "q_norm", qkv, 3 * D, 0, qs, dqn, dqkv, 3 * D, 0, B * N, H)
-        _qk_norm_bwd(go, pre, qkn, "k_norm", qkv, 3 * D, D, ks, dkn, dqkv, 3 * D, D, B * N, H)
+                          ldv=3 * D, v_off=2 * D, B=B, H=H, Hkv=H, Nq=N, Nk=N, rope=rope, key_mask=mask8, causal=causal,
+                          dh=dh)
+        _qk_norm_bwd(go, pre, qkn, "q_norm", qkv, 3 * D, 0, qs, dqn, dqkv, 3 * D, 0, B * N, H, dh)
+        _qk_norm_bwd(go, pre, qkn, "k_norm", qkv, 3 * D, D, ks, dkn, dqkv, 3 * D, D, B * N, H, dh)
     else:
         ops.attention_bwd(qkv, qkv, qkv, ao, dao, lse, dqkv, dqkv, dqkv, ldq=3 * D, q_off=0, ldk=3 * D, k_off=D,
-                          ldv=3 * D, v_off=2 * D, B=B, H=H, Hkv=H, Nq=N, Nk=N, rope=rope, key_mask=mask8, causal=causal)
+                          ldv=3 * D, v_off=2 * D, B=B, H=H, Hkv=H, Nq=N, Nk=N, rope=rope, key_mask=mask8, causal=causal,
+                          dh=dh)
     go.wgrad(pre + "to_qkv.weight", dqkv, h)
     return dgrad(dqkv, wqkv)
 
@@ -300,42 +303,42 @@ class ContextKV:
 
 
 def cross_attn_fwd(h, ctx, wq, wkv, wo, B, N, S, H, cmask8, residual=None, out_dtype=F32, row_mask=None, qkn=None,
-                   ckv=None, layer_ix=0, causal=False):
+                   ckv=None, layer_ix=0, causal=False, dh=64):
     """transformer.py:411-416, 505-508 (GQA), 541.  h: bf16 [B*N, D]; ctx: bf16 [B*S, Dc].  ckv: ContextKV of the enclosing
     ContinuousTransformer (then this layer's k | v are columns of ckv.kv and no projection runs here)."""
-    D = H * 64
+    D = H * dh
     Dc = ctx.shape[-1]
-    Hkv = Dc // 64
+    Hkv = Dc // dh
     causal = bool(causal) and N > 1                      # :468-469; query r sees keys c <= r + S - N (create_causal_mask, :32)
     q = ops.gemm(h, wq)
     if ckv is not None and qkn is None:
         off = layer_ix * 2 * Dc
         co, lse = ops.attention_fwd(q, ckv.kv, ckv.kv, ldq=D, q_off=0, ldk=ckv.ld, k_off=off, ldv=ckv.ld, v_off=off + Dc,
-                                    B=B, H=H, Hkv=Hkv, Nq=N, Nk=S, key_mask=cmask8, causal=causal)
+                                    B=B, H=H, Hkv=Hkv, Nq=N, Nk=S, key_mask=cmask8, causal=causal, dh=dh)
         out = ops.gemm(co.view(B * N, D), wo, out_dtype=out_dtype, residual=residual, row_mask=row_mask)
         return out, (q, (ckv, off), co, lse, None)
     kv = ops.gemm(ctx, wkv)
     nrm = None
     if qkn is not None:
-        qn, qs = ops.head_norm_fwd(q, D, 0, B * N, H, qkn[0], qkn[1], qkn[2])
-        kn, ks = ops.head_norm_fwd(kv, 2 * Dc, 0, B * S, Hkv, qkn[0], qkn[3], qkn[4])
+        qn, qs = ops.head_norm_fwd(q, D, 0, B * N, H, qkn[0], qkn[1], qkn[2], dh=dh)
+        kn, ks = ops.head_norm_fwd(kv, 2 * Dc, 0, B * S, Hkv, qkn[0], qkn[3], qkn[4], dh=dh)
         nrm = (qn, qs, kn, ks)
         co, lse = ops.attention_fwd(qn, kn, kv, ldq=D, q_off=0, ldk=Dc, k_off=0, ldv=2 * Dc, v_off=Dc, B=B, H=H,
-                                    Hkv=Hkv, Nq=N, Nk=S, key_mask=cmask8, causal=causal)
+                                    Hkv=Hkv, Nq=N, Nk=S, key_mask=cmask8, causal=causal, dh=dh)
     else:
         co, lse = ops.attention_fwd(q, kv, kv, ldq=D, q_off=0, ldk=2 * Dc, k_off=0, ldv=2 * Dc, v_off=Dc, B=B, H=H,
-                                    Hkv=Hkv, Nq=N, Nk=S, key_mask=cmask8, causal=causal)
+                                    Hkv=Hkv, Nq=N, Nk=S, key_mask=cmask8, causal=causal, dh=dh)
     out = ops.gemm(co.view(B * N, D), wo, out_dtype=out_dtype, residual=residual, row_mask=row_mask)
     return out, (q, kv, co, lse, nrm)
 
 
 def cross_attn_bwd(go, gb, h, ctx, saved, wq, wkv, wo, B, N, S, H, cmask8, dctx_acc=None, want_dctx=True,
-                   pre="cross_attn.", qkn=None, causal=False):
+                   pre="cross_attn.", qkn=None, causal=False, dh=64):
     """Returns dh (bf16), dctx (fp32 [B*S, Dc]; accumulated into dctx_acc when given; None if not wanted)."""
     q, kv, co, lse, nrm = saved
-    D = H * 64
+    D = H * dh
     Dc = ctx.shape[-1]
-    Hkv = Dc // 64
+    Hkv = Dc // dh
     causal = bool(causal) and N > 1
     go.wgrad(pre + "to_out.weight", gb, co.view(B * N, D))
     dco = dgrad(gb, wo)
@@ -344,7 +347,8 @@ def cross_attn_bwd(go, gb, h, ctx, saved, wq, wkv, wo, B, N, S, H, cmask8, dctx_
         ckv, off = kv
         dkv_all = ckv.grad_buffer()
         ops.attention_bwd(q, ckv.kv, ckv.kv, co, dco, lse, dq, dkv_all, dkv_all, ldq=D, q_off=0, ldk=ckv.ld, k_off=off,
-                          ldv=ckv.ld, v_off=off + Dc, B=B, H=H, Hkv=Hkv, Nq=N, Nk=S, key_mask=cmask8, causal=causal)
+                          ldv=ckv.ld, v_off=off + Dc, B=B, H=H, Hkv=Hkv, Nq=N, Nk=S, key_mask=cmask8, causal=causal,
+                          dh=dh)
         go.wgrad(pre + "to_q.weight", dq, h)
         dh = dgrad(dq, wq)
         go.wgrad(pre + "to_kv.weight", dkv_all[:, off:off + 2 * Dc], ctx)
@@ -354,12 +358,12 @@ def cross_attn_bwd(go, gb, h, ctx, saved, wq, wkv, wo, B, N, S, H, cmask8, dctx_
         qn, qs, kn, ks = nrm
         dkn = torch.empty_like(kn)
         ops.attention_bwd(qn, kn, kv, co, dco, lse, dq, dkn, dkv, ldq=D, q_off=0, ldk=Dc, k_off=0, ldv=2 * Dc,
-                          v_off=Dc, B=B, H=H, Hkv=Hkv, Nq=N, Nk=S, key_mask=cmask8, causal=causal)
-        _qk_norm_bwd(go, pre, qkn, "q_norm", q, D, 0, qs, dq, dq, D, 0, B * N, H)          # in place over dq
-        _qk_norm_bwd(go, pre, qkn, "k_norm", kv, 2 * Dc, 0, ks, dkn, dkv, 2 * Dc, 0, B * S, Hkv)
+                          v_off=Dc, B=B, H=H, Hkv=Hkv, Nq=N, Nk=S, key_mask=cmask8, causal=causal, dh=dh)
+        _qk_norm_bwd(go, pre, qkn, "q_norm", q, D, 0, qs, dq, dq, D, 0, B * N, H, dh)      # in place over dq
+        _qk_norm_bwd(go, pre, qkn, "k_norm", kv, 2 * Dc, 0, ks, dkn, dkv, 2 * Dc, 0, B * S, Hkv, dh)
     else:
         ops.attention_bwd(q, kv, kv, co, dco, lse, dq, dkv, dkv, ldq=D, q_off=0, ldk=2 * Dc, k_off=0, ldv=2 * Dc,
-                          v_off=Dc, B=B, H=H, Hkv=Hkv, Nq=N, Nk=S, key_mask=cmask8, causal=causal)
+                          v_off=Dc, B=B, H=H, Hkv=Hkv, Nq=N, Nk=S, key_mask=cmask8, causal=causal, dh=dh)
     go.wgrad(pre + "to_q.weight", dq, h)
     dh = dgrad(dq, wq)
     go.wgrad(pre + "to_kv.weight", dkv, ctx)
@@ -497,6 +501,7 @@ def block_params(blk):
     if p.ada:
         p.wmod = bf16_of(blk.to_scale_shift_gate[1].weight)
     p.H = blk.dim // blk.dim_heads
+    p.dh = blk.dim_heads
     p.layer_ix = getattr(blk, "layer_ix", 0)
     p.qkn_s = qk_norm_params(blk.self_attn)
     p.qkn_c = qk_norm_params(blk.cross_attn) if p.cross else None
@@ -533,14 +538,14 @@ def block_fwd(p, x, ctx, global_cond, mask8, cmask8, rope, B, N, S, ckv=None):
     # self-attention
     sv.h1, sv.mean1, sv.rstd1 = ops.layernorm_fwd(x, p.g1, p.beta1, sc_s, sh_s, rows_per_batch=N)
     sv.x1, sv.sa = self_attn_fwd(sv.h1, p.wqkv, p.wo, B, N, p.H, rope, mask8, residual=x, gate=g_s, qkn=p.qkn_s,
-                                 causal=p.causal)
+                                 causal=p.causal, dh=p.dh)
     xcur = sv.x1
     # cross-attention (never modulated, 670-671)
     sv.has_cross = p.cross and ctx is not None
     if sv.has_cross:
         sv.h2, sv.mean2, sv.rstd2 = ops.layernorm_fwd(xcur, p.g2, p.beta2)
         sv.x2, sv.ca = cross_attn_fwd(sv.h2, ctx, p.wq, p.wkv, p.wo2, B, N, S, p.H, cmask8, residual=xcur, qkn=p.qkn_c,
-                                      ckv=ckv, layer_ix=p.layer_ix, causal=p.causal)
+                                      ckv=ckv, layer_ix=p.layer_ix, causal=p.causal, dh=p.dh)
         xcur = sv.x2
     # conformer module (673-674 / 691-692: x = x + conformer(x), never modulated)
     sv.cf = None
@@ -590,7 +595,7 @@ def block_bwd(p, sv, g, ctx, mask8, cmask8, rope, B, N, S, go=None, dctx_acc=Non
     dctx = None
     if sv.has_cross:
         dh2, dctx = cross_attn_bwd(go, g2b, sv.h2, ctx, sv.ca, p.wq, p.wkv, p.wo2, B, N, S, p.H, cmask8, dctx_acc,
-                                   want_dctx, qkn=p.qkn_c, causal=p.causal)
+                                   want_dctx, qkn=p.qkn_c, causal=p.causal, dh=p.dh)
         g1, g1bf = go.ln("cross_attend_norm.gamma", dh2, sv.x1, p.g2, sv.mean2, sv.rstd2, dres=g2,
                          want_bf16=not ada and mask8 is None)
     else:
@@ -603,7 +608,8 @@ def block_bwd(p, sv, g, ctx, mask8, cmask8, rope, B, N, S, go=None, dctx_acc=Non
         g1b, _ = ops.grad_cast(g1, B, N, row_mask=mask8)
     else:
         g1b = g1bf if g1bf is not None else ops.cast(g1, BF16)
-    dh1 = self_attn_bwd(go, g1b, sv.h1, sv.sa, p.wqkv, p.wo, B, N, p.H, rope, mask8, qkn=p.qkn_s, causal=p.causal)
+    dh1 = self_attn_bwd(go, g1b, sv.h1, sv.sa, p.wqkv, p.wo, B, N, p.H, rope, mask8, qkn=p.qkn_s, causal=p.causal,
+                        dh=p.dh)
     if ada:
         dsc, dsh = ops.adaln_mod_bwd(dh1, sv.x, p.g1, p.beta1, sv.mean1, sv.rstd1, B, N)
         dsl(0).copy_(dsc)

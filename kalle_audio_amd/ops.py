@@ -395,45 +395,64 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, param_bf16, *, lr, beta1=0.9, be
 
 # ------------------------------------------------------------------------------------------------ attention
 def attention_fwd(q, k, v, *, ldq, q_off, ldk, k_off, ldv, v_off, B, H, Hkv, Nq, Nk, rope=None, key_mask=None,
-                  causal=False):
-    """q/k/v: base tensors (bf16) of the projection outputs; see kalle_attention_fwd. Returns (out [B,Nq,H*64], lse)."""
+                  causal=False, dh=64):
+    """q/k/v: base tensors (bf16) of the projection outputs; see kalle_attention_fwd (_hd for head dims dh = 32, 128).
+    Returns (out [B,Nq,H*dh], lse)."""
     lib = _lib.load()
-    out = torch.empty((B, Nq, H * 64), device=q.device, dtype=torch.bfloat16)
+    out = torch.empty((B, Nq, H * dh), device=q.device, dtype=torch.bfloat16)
     lse = torch.empty((B, H, Nq), device=q.device, dtype=torch.float32)
     cos, sin, rot = (rope[0], rope[1], rope[0].shape[-1] * 2) if rope is not None else (None, None, 0)
     m8 = key_mask.to(torch.uint8).contiguous() if key_mask is not None else None
-    check(lib.kalle_attention_fwd(_p(q), ldq, q_off, _p(k), ldk, k_off, _p(v), ldv, v_off, _p(out), H * 64, _p(lse),
-                                  _p(cos), _p(sin), rot, _p(m8), int(causal), B, H, Hkv, Nq, Nk, _stream()),
-          "kalle_attention_fwd")
+    if dh == 64:
+        check(lib.kalle_attention_fwd(_p(q), ldq, q_off, _p(k), ldk, k_off, _p(v), ldv, v_off, _p(out), H * 64, _p(lse),
+                                      _p(cos), _p(sin), rot, _p(m8), int(causal), B, H, Hkv, Nq, Nk, _stream()),
+              "kalle_attention_fwd")
+    else:
+        check(lib.kalle_attention_fwd_hd(_p(q), ldq, q_off, _p(k), ldk, k_off, _p(v), ldv, v_off, _p(out), H * dh, _p(lse),
+                                         _p(cos), _p(sin), rot, _p(m8), int(causal), B, H, Hkv, Nq, Nk, dh, _stream()),
+              "kalle_attention_fwd_hd")
     return out, lse
 
 
 def attention_bwd(q, k, v, out, dout, lse, dq, dk, dv, *, ldq, q_off, ldk, k_off, ldv, v_off, B, H, Hkv, Nq, Nk,
-                  rope=None, key_mask=None, causal=False):
+                  rope=None, key_mask=None, causal=False, dh=64):
     lib = _lib.load()
     delta = torch.empty((B, H, Nq), device=q.device, dtype=torch.float32)
     cos, sin, rot = (rope[0], rope[1], rope[0].shape[-1] * 2) if rope is not None else (None, None, 0)
     m8 = key_mask.to(torch.uint8).contiguous() if key_mask is not None else None
-    check(lib.kalle_attention_bwd(_p(q), ldq, q_off, _p(k), ldk, k_off, _p(v), ldv, v_off, _p(out), _p(dout), H * 64,
-                                  _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), _p(cos), _p(sin), rot, _p(m8),
-                                  int(causal), B, H, Hkv, Nq, Nk, _stream()), "kalle_attention_bwd")
+    if dh == 64:
+        check(lib.kalle_attention_bwd(_p(q), ldq, q_off, _p(k), ldk, k_off, _p(v), ldv, v_off, _p(out), _p(dout), H * 64,
+                                      _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), _p(cos), _p(sin), rot, _p(m8),
+                                      int(causal), B, H, Hkv, Nq, Nk, _stream()), "kalle_attention_bwd")
+    else:
+        check(lib.kalle_attention_bwd_hd(_p(q), ldq, q_off, _p(k), ldk, k_off, _p(v), ldv, v_off, _p(out), _p(dout), H * dh,
+                                         _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), _p(cos), _p(sin), rot, _p(m8),
+                                         int(causal), B, H, Hkv, Nq, Nk, dh, _stream()), "kalle_attention_bwd_hd")
 
 
-def head_norm_fwd(x, ldx, x_off, rows, heads, mode, gamma=None, beta=None):
-    """qk_norm (transformer.py:422-428) on the q or k slice of a projection output: returns (y bf16 [rows, heads*64], stat)"""
+def head_norm_fwd(x, ldx, x_off, rows, heads, mode, gamma=None, beta=None, dh=64):
+    """qk_norm (transformer.py:422-428) on the q or k slice of a projection output: returns (y bf16 [rows, heads*dh], stat)"""
     lib = _lib.load()
-    y = torch.empty((rows, heads * 64), device=x.device, dtype=torch.bfloat16)
+    y = torch.empty((rows, heads * dh), device=x.device, dtype=torch.bfloat16)
     stat = torch.empty((rows, heads, 2), device=x.device, dtype=torch.float32)
-    check(lib.kalle_head_norm_fwd(_p(x), ldx, x_off, _p(y), heads * 64, 0, _p(stat), _p(gamma), _p(beta), mode, rows, heads,
-                                  _stream()), "kalle_head_norm_fwd")
+    if dh == 64:
+        check(lib.kalle_head_norm_fwd(_p(x), ldx, x_off, _p(y), heads * 64, 0, _p(stat), _p(gamma), _p(beta), mode, rows, heads,
+                                      _stream()), "kalle_head_norm_fwd")
+    else:
+        check(lib.kalle_head_norm_fwd_hd(_p(x), ldx, x_off, _p(y), heads * dh, 0, _p(stat), _p(gamma), _p(beta), mode, rows,
+                                         heads, dh, _stream()), "kalle_head_norm_fwd_hd")
     return y, stat
 
 
-def head_norm_bwd(x, ldx, x_off, stat, g, dx, lddx, dx_off, rows, heads, mode, gamma=None, dgamma=None, dbeta=None):
-    """g: bf16 [rows, heads*64] gradient w.r.t. the normalised values; writes the gradient w.r.t. x into dx (ld / offset)"""
+def head_norm_bwd(x, ldx, x_off, stat, g, dx, lddx, dx_off, rows, heads, mode, gamma=None, dgamma=None, dbeta=None, dh=64):
+    """g: bf16 [rows, heads*dh] gradient w.r.t. the normalised values; writes the gradient w.r.t. x into dx (ld / offset)"""
     lib = _lib.load()
-    check(lib.kalle_head_norm_bwd(_p(x), ldx, x_off, _p(stat), _p(g), heads * 64, 0, _p(dx), lddx, dx_off, _p(gamma),
-                                  _p(dgamma), _p(dbeta), mode, rows, heads, _stream()), "kalle_head_norm_bwd")
+    if dh == 64:
+        check(lib.kalle_head_norm_bwd(_p(x), ldx, x_off, _p(stat), _p(g), heads * 64, 0, _p(dx), lddx, dx_off, _p(gamma),
+                                      _p(dgamma), _p(dbeta), mode, rows, heads, _stream()), "kalle_head_norm_bwd")
+    else:
+        check(lib.kalle_head_norm_bwd_hd(_p(x), ldx, x_off, _p(stat), _p(g), heads * dh, 0, _p(dx), lddx, dx_off, _p(gamma),
+                                         _p(dgamma), _p(dbeta), mode, rows, heads, dh, _stream()), "kalle_head_norm_bwd_hd")
 
 
 # ------------------------------------------------------------------------------------------------ Llasa head / tail

@@ -148,6 +148,9 @@ class FeedForward(nn.Module):
         return KF.FeedForwardFn.apply(self, x, l1.weight, l1.bias, l2.weight, l2.bias)
 
 
+SUPPORTED_HEAD_DIMS = (32, 64, 128)     # dim_heads the attention and qk_norm kernels are built for
+
+
 class Attention(nn.Module):
     """transformer.py:271-547.
 
@@ -164,12 +167,19 @@ class Attention(nn.Module):
             raise NotImplementedError("Attention(natten): not on the DiT path (dit.py:252)")
         if qk_norm not in ("none", "l2", "ln"):
             raise ValueError(f"unknown qk_norm {qk_norm!r}")
-        if dim_heads != 64:
-            raise NotImplementedError("the fused attention kernel is specialised for head dim 64")
+        if dim_heads not in SUPPORTED_HEAD_DIMS:
+            raise NotImplementedError(f"Attention(dim_heads={dim_heads}): the fused attention kernels support head dims "
+                                      f"{SUPPORTED_HEAD_DIMS}")
+        dim_kv = dim_context if dim_context is not None else dim
+        # shapes the kernels cannot run are refused here rather than as a kernel error at the first call
+        if dim % dim_heads or dim_kv % dim_heads:
+            raise ValueError(f"Attention: dim {dim} and dim_context {dim_kv} must be multiples of dim_heads {dim_heads}")
+        if (dim // dim_heads) % (dim_kv // dim_heads):
+            raise ValueError(f"Attention: {dim // dim_heads} query heads are not a multiple of {dim_kv // dim_heads} kv heads "
+                             f"(dim {dim}, dim_context {dim_kv}, dim_heads {dim_heads})")
         self.dim = dim
         self.dim_heads = dim_heads
         self.causal = causal
-        dim_kv = dim_context if dim_context is not None else dim
         self.num_heads = dim // dim_heads
         self.kv_heads = dim_kv // dim_heads
         if dim_context is not None:
