@@ -63,7 +63,10 @@ typedef struct kalle_gemm_epilogue {
      *   glu_mode 1 (forward,  a_kmajor=0,b_kmajor=0, N = 2*glu_inner): C = h = x W^T + b  [M][2*inner]  AND
      *              glu_aux = act [M][inner] bf16 = h[:, j] * silu(h[:, inner + j])
      *   glu_mode 2 (backward, a_kmajor=0,b_kmajor=1, N = glu_inner):   acc = d(act); glu_aux = h [M][2*inner] bf16;
-     *              C = dh [M][2*inner] bf16; glu_dbias (fp32 [2*inner], optional) += column sums of dh */
+     *              C = dh [M][2*inner] bf16; glu_dbias (fp32 [2*inner], optional) += column sums of dh
+     * The fused epilogues take no other field: glu_mode 1 with alpha != 1, a gate, residual, row_mask, output-row remap or
+     * accumulate, and glu_mode 2 with a bias or any of those (alpha is applied to d(act) first), return KALLE_ERR_UNSUPPORTED
+     * before any kernel runs. */
     int32_t glu_mode;
     int32_t glu_inner;
     void* glu_aux;

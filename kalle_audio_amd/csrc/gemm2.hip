@@ -1757,7 +1757,14 @@ extern "C" int kalle_gemm_bf16(const void* A, int64_t lda, int a_kmajor, const v
         p.row_mask = ep->row_mask;
         p.c_rpb = ep->c_rows_per_batch; p.c_brows = ep->c_batch_rows; p.c_roff = ep->c_row_offset;
         p.glu_mode = ep->glu_mode; p.glu_inner = ep->glu_inner; p.glu_aux = ep->glu_aux; p.glu_dbias = ep->glu_dbias;
-        if (p.glu_mode && (!p.glu_aux || p.glu_inner <= 0)) return KALLE_ERR_ARG;
+        if (p.glu_mode && (p.glu_mode > 2 || p.glu_mode < 0 || !p.glu_aux || p.glu_inner <= 0)) return KALLE_ERR_ARG;
+        // the fused SwiGLU epilogues apply the bias (forward) or alpha (backward) and no other field: a call that asks for more
+        // is refused before any kernel runs, so that the caller un-fuses instead of losing a field (the few-rows finishing pass
+        // took a forward call with a gate, residual, row mask or row remap and dropped them; every forward path dropped alpha)
+        if (p.glu_mode && (p.gate || p.residual || p.row_mask || p.c_rpb || p.accumulate || c_dtype != KALLE_BF16 || a_kmajor ||
+                           (p.glu_mode == 1 && (p.alpha != 1.f || b_kmajor || N != 2 * p.glu_inner)) ||
+                           (p.glu_mode == 2 && (p.bias || !b_kmajor || N != p.glu_inner))))
+            return KALLE_ERR_UNSUPPORTED;
         if (p.accumulate && c_dtype != KALLE_F32) return KALLE_ERR_ARG;
         if ((p.bias && !al16(p.bias)) || (p.gate && (!al16(p.gate) || (p.ldg & 3))) ||
             (p.residual && (!al16(p.residual) || (p.ldr & 3))))

@@ -52,12 +52,18 @@ def _same(got, ref, tol=2e-5):
 def _check(fx, prefix, sd, **arrs):
     for k, v in arrs.items():
         _same(v, fx[f"{prefix}/{k}"])
-    n = 0
-    for k in fx.files:
-        if k.startswith(prefix + "/digest/"):
-            _same(sd[k[len(prefix) + 8:]].grad, fx[k])
-            n += 1
-    assert n > 0
+    keys = [k for k in fx.files if k.startswith(prefix + "/digest/")]
+    assert keys
+    # a gradient that is zero in exact arithmetic (the cross-attention k_norm.bias: softmax ignores a shift shared by a row's
+    # logits) is fp32 rounding noise on both sides, ~1e-7 of the case's typical gradient norm, and that noise changes with
+    # the thread count: such a gradient must be as small on this side too, its samples are not compared
+    zero = 1e-6 * float(np.median([fx[k][0] for k in keys]))
+    for k in keys:
+        g = sd[k[len(prefix) + 8:]].grad
+        if fx[k][0] < zero:
+            assert gu.digest(g.detach().numpy())[0] < zero, (k, gu.digest(g.detach().numpy())[0], zero)
+        else:
+            _same(g, fx[k])
 
 
 @pytest.mark.parametrize("dh", [32, 128])
