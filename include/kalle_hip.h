@@ -11,7 +11,7 @@
  * is asynchronous on that stream, allocates nothing, and returns 0 on success or a negative KALLE_ERR_* code (never
  * throws).  Process state the library does keep: per-thread caches of GEMM split plans (pure functions of the shape), the
  * calling thread's last plan / last HIP error name (kalle_gemm_last_plan, kalle_last_error), a per-kernel per-device flag for
- * the dynamic-LDS attribute, and experiment switches read once from KALLE_* environment variables.  bf16 tensors are raw uint16 storage.
+ * the dynamic-LDS attribute.  The library reads no environment variables.  bf16 tensors are raw uint16 storage.
  */
 #ifndef KALLE_HIP_H
 #define KALLE_HIP_H
@@ -88,8 +88,9 @@ int kalle_gemm_bf16(const void* A, int64_t lda, int a_kmajor, const void* B, int
 
 /* which kernel the calling thread's most recent kalle_gemm_bf16 used: low byte 1 = gemm_bf16_kernel (128x128,
  * register-staged, any shape), 2 = gemm2_kernel (256x128, LDS-DMA 3-stage ring, K % 8 == 0), 3 = gemm3_kernel (256x256, 2 stages),
- * 4 = few-rows K slices (slabs + finishing pass), 5 = small tiles with two wave groups (gemm2_ks2_kernel); for 1-4 bits 8.. =
- * split-K factor, for 5 bits 8-11 / 12-15 = tile rows / columns in units of 64, bits 16.. = K slices */
+ * 4 = few-rows K slices (slabs + finishing pass), 5 = small tiles with two wave groups (gemm2_ks2_kernel); for 1-4 bits 8-23 =
+ * split-K factor and bit 24 = mixed split-K (3 only: some tiles are cut into one K slice fewer than bits 8-23 say), for 5
+ * bits 8-11 / 12-15 = tile rows / columns in units of 64, bits 16.. = K slices */
 int kalle_gemm_last_plan(void);
 
 /* diagnostics (tools/gemm_stamps.py), never set by the product path: with a non-NULL device buffer of

@@ -286,9 +286,6 @@ __device__ __forceinline__ void attn_stamp(const AttnParams& p, int tid, int idx
 // owns 8 consecutive features of two blocks: 16-byte stores, 64 contiguous bytes per row and instruction, half the store
 // instructions (the GEMM epilogues' lesson: the store side is bound by the number of store instructions, not by bytes).
 // `row`: the row's first feature (no lane offset).  Partners share li, i.e. the row and its validity: safe under a row guard.
-#ifndef KALLE_ATTN_ST16
-#define KALLE_ATTN_ST16 1
-#endif
 // store_row<DH>: the same for DH / 16 blocks (pairs of blocks traded as above)
 template <int DH>
 __device__ __forceinline__ void store_row(bf16_t* row, const f32x4 (&v)[DH / 16], int g) {
@@ -296,24 +293,18 @@ __device__ __forceinline__ void store_row(bf16_t* row, const f32x4 (&v)[DH / 16]
     uint32_t w[NB][2];
 #pragma unroll
     for (int dt = 0; dt < NB; ++dt) { w[dt][0] = pack_bf16x2(v[dt][0], v[dt][1]); w[dt][1] = pack_bf16x2(v[dt][2], v[dt][3]); }
-#if KALLE_ATTN_ST16
 #pragma unroll
     for (int pr = 0; pr < NB / 2; ++pr) {
         const auto a = __builtin_amdgcn_permlane16_swap(w[2 * pr][0], w[2 * pr + 1][0], false, false);
         const auto c = __builtin_amdgcn_permlane16_swap(w[2 * pr][1], w[2 * pr + 1][1], false, false);
         *reinterpret_cast<i32x4*>(row + 16 * (2 * pr + (g & 1)) + 4 * (g & ~1)) = i32x4{(int)a[0], (int)c[0], (int)a[1], (int)c[1]};
     }
-#else
-#pragma unroll
-    for (int dt = 0; dt < NB; ++dt) *reinterpret_cast<i32x2*>(row + 16 * dt + 4 * g) = i32x2{(int)w[dt][0], (int)w[dt][1]};
-#endif
 }
 __device__ __forceinline__ void store_row64(bf16_t* row, const f32x4& v0, const f32x4& v1, const f32x4& v2, const f32x4& v3, int g) {
     const f32x4 v[4] = {v0, v1, v2, v3};
     uint32_t w[4][2];
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) { w[dt][0] = pack_bf16x2(v[dt][0], v[dt][1]); w[dt][1] = pack_bf16x2(v[dt][2], v[dt][3]); }
-#if KALLE_ATTN_ST16
 #pragma unroll
     for (int pr = 0; pr < 2; ++pr) {
         // even g keeps block 2 pr and receives the partner's; odd g keeps block 2 pr + 1 and receives the partner's (lower features)
@@ -321,10 +312,6 @@ __device__ __forceinline__ void store_row64(bf16_t* row, const f32x4& v0, const 
         const auto c = __builtin_amdgcn_permlane16_swap(w[2 * pr][1], w[2 * pr + 1][1], false, false);
         *reinterpret_cast<i32x4*>(row + 16 * (2 * pr + (g & 1)) + 4 * (g & ~1)) = i32x4{(int)a[0], (int)c[0], (int)a[1], (int)c[1]};
     }
-#else
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) *reinterpret_cast<i32x2*>(row + 16 * dt + 4 * g) = i32x2{(int)w[dt][0], (int)w[dt][1]};
-#endif
 }
 
 
@@ -1561,8 +1548,7 @@ extern "C" int kalle_attention_bwd_hd(const void* q, int64_t ldq, int q_off, con
     if (head_dim == 128) return attention_bwd_dh<128>(p, st);
 
     // one block of queries and keys, one kv head per query head (the DiT's self-attention): everything in one kernel
-    static const bool fused_env = !(getenv("KALLE_ATTN_FUSED_BWD") && atoi(getenv("KALLE_ATTN_FUSED_BWD")) == 0);
-    if (fused_env && !causal && Nq <= 128 && Nk <= 128 && H == Hkv) {
+    if (!causal && Nq <= 128 && Nk <= 128 && H == Hkv) {
         constexpr int flds = 4 * AT_TILE;
         static std::atomic<uint64_t> lds_ok_f{0};
         kalle_allow_lds(reinterpret_cast<const void*>(attn_bwd_fused_kernel), flds, lds_ok_f);
@@ -1570,9 +1556,8 @@ extern "C" int kalle_attention_bwd_hd(const void* q, int64_t ldq, int q_off, con
         return kalle_check_launch();
     }
     // cross-attention of the DiT: several query heads per kv head and / or a few keys beyond one block, no rotary
-    static const bool gqa_env = !(getenv("KALLE_ATTN_FUSED_GQA") && atoi(getenv("KALLE_ATTN_FUSED_GQA")) == 0);
     const int tail = Nk > 128 ? Nk - 128 : 0;
-    if (fused_env && gqa_env && !causal && rot == 0 && Nq <= 128 && tail <= 16 && tail <= 128 - Nq) {
+    if (!causal && rot == 0 && Nq <= 128 && tail <= 16 && tail <= 128 - Nq) {
         constexpr int flds = 4 * AT_TILE;
         static std::atomic<uint64_t> lds_ok_g{0};
         kalle_allow_lds(reinterpret_cast<const void*>(attn_bwd_fused_gqa_kernel), flds, lds_ok_g);

@@ -1025,8 +1025,7 @@ extern "C" int kalle_conv1d_fwd(const void* x, int x_dtype, const float* w_packe
     // weights small enough to stay in one XCD's L2: run the channel tiles of a position tile back to back (x re-read hits L2)
     p.co_fast = (int64_t)Cin * ksize * p.CoutP * 4 <= (2 << 20);
     const bool v2_stride = stride == 1 || (dilation == 1 && (stride == 2 || stride == 4 || stride == 8) && ksize <= 32);
-    static const bool v1_env = getenv("KALLE_CONV_V1") != nullptr;       // experiment switch, read once per process
-    if (v2_stride && p.act != 4 && xf == yf && !v1_env) {
+    if (v2_stride && p.act != 4 && xf == yf) {
 #define KALLE_CONV_V2N(COW, LPT, WCO, CI, SPAN, NW)                                                                    \
     do {                                                                                                                \
         p.ntile = (Lout + 64 * LPT * (NW / WCO) - 1) / (64 * LPT * (NW / WCO));                                        \
@@ -1050,10 +1049,7 @@ extern "C" int kalle_conv1d_fwd(const void* x, int x_dtype, const float* w_packe
                 // pointwise convs: 256 positions x 128 channels per workgroup (64 accumulator registers per wave, 66 KiB of LDS) so
                 // that TWO workgroups share a CU - one's residual loads / stores run under the other's FMAs; with 512 positions
                 // (128 accumulator registers, 133 KiB) a CU runs one workgroup whose memory phases nothing overlaps
-                // (KALLE_CONV_K1_WIDE=1: the 512-position tile of rounds 1-2)
-                static const bool k1_wide = getenv("KALLE_CONV_K1_WIDE") && atoi(getenv("KALLE_CONV_K1_WIDE")) == 1;
-                if (ksize == 1 && Cout > 64 && !k1_wide) KALLE_CONV_V2N(16, 4, 8, 32, 256, 8);
-                if (ksize == 1 && Cout > 64) KALLE_CONV_V2N(16, 8, 8, 32, 512, 8);
+                if (ksize == 1 && Cout > 64) KALLE_CONV_V2N(16, 4, 8, 32, 256, 8);
                 // (the same halving for the wide k = 7 convs - 7 x the FMAs per byte - is worth 0.4 % of a decode: not taken)
                 if (ksize != 1 && Cout >= 256 && halo + 512 <= 640) KALLE_CONV_V2N(16, 8, 8, 8, 640, 8);
                 if (ksize == 1) KALLE_CONV_V2(16, 8, 4, 16, 512);   // pointwise conv: longer chunks cover the HBM latency
@@ -1204,8 +1200,7 @@ extern "C" int kalle_conv_transpose1d_fwd(const void* x, int x_dtype, const floa
     hipStream_t st = static_cast<hipStream_t>(stream);
     const bool xf = x_dtype == KALLE_F32, yf = y_dtype == KALLE_F32;
     const int mmax = (ksize + stride - 1) / stride;
-    static const bool v1_env = getenv("KALLE_CONV_V1") != nullptr;
-    if (xf == yf && mmax <= 64 && !v1_env) {
+    if (xf == yf && mmax <= 64) {
         const int nq = (Lout - 1 + padding) / stride + 1;      // input positions that reach an output
 #define KALLE_CONVT_V2(COW, LPT, WCO)                                                                                  \
     do {                                                                                                                \

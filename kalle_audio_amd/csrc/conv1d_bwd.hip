@@ -343,8 +343,7 @@ extern "C" int kalle_conv_wgrad(const float* U, const float* V, float* dW, int B
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
     // LDS-staged kernel: the activation (if any) sits on V, V has at least a quarter of a wave's worth of channels
-    static const bool lds_off = getenv("KALLE_CONV_WGRAD_V1") != nullptr;       // experiment switch: the per-lane-load kernel
-    if (!lds_off && (act_on == 0 || code == 0) && CV >= 16) {
+    if ((act_on == 0 || code == 0) && CV >= 16) {
         int P = 64;
         auto rows_of = [&](int p) { return (p - 1) * stride + (ksize - 1) * dilation + 1; };
         while (P > 4 && rows_of(P) * 65 * 4 > 48 * 1024) P >>= 1;

@@ -79,30 +79,6 @@ struct Loader {
             src[i] += kstep;
         }
     }
-    // one piece (the software-pipelined 256 x 256 loop spreads a K-tile's pieces over its MFMA rows); `tail`: this is the ragged
-    // last K-tile (see issue_tail)
-    template <int I>
-    __device__ __forceinline__ void issue_one(char* region, int wave, int lane, bool tail, int kvalid) {
-        static_assert(I < PER_WAVE, "piece index");
-        const bf16_t* sp = src[I];
-        if (tail) {
-            const int q = wave * PER_WAVE + I;
-            bool ok;
-            if constexpr (!KM) {
-                const int row = 8 * q + (lane >> 3);
-                const int c = (lane & 7) ^ ((row >> 1) & 7);
-                ok = 8 * c < kvalid;
-            } else {
-                constexpr int RB = 2 * R, ROWS = 1024 / RB;
-                const int pos = q * ROWS + (lane * 16) / RB;
-                const int krow = (pos & ~7) | ((pos & 7) ^ (((pos >> 3) & 1) << 2));
-                ok = krow < kvalid;
-            }
-            if (!ok) sp = reinterpret_cast<const bf16_t*>(kalle_zero_block);
-        }
-        __builtin_amdgcn_global_load_lds(GPTR(sp), LDS_PTR(void, region + (wave * PER_WAVE + I) * 1024), 16, 0, 0);
-        src[I] += kstep;
-    }
     // the ragged last K-tile (K % 64 != 0): only the first `kvalid` (a multiple of 8) of its 64 k exist; every piece that lies
     // beyond them is fetched from the zero block instead, so both operands contribute exact zeros there
     __device__ __forceinline__ void issue_tail(char* region, int wave, int lane, int kvalid) {
@@ -173,18 +149,6 @@ struct Reader {
                 b0[s] = region_off + pos1 * RB + ((cl ^ (2 * (pos1 & 7))) << 4) + hb;
                 b1[s] = region_off + pos2 * RB + ((cl ^ (2 * (pos2 & 7))) << 4) + hb;
             }
-        }
-    }
-    static constexpr int NI = KM ? 2 : 1;    // LDS instructions per fragment
-    // ONE fragment: tile T (16 operand rows from rbase + 16 T) of k-step S, stage byte offset `so`
-    template <int S, int T>
-    __device__ __forceinline__ void read1(unsigned so, i32x4& f) const {
-        if constexpr (!KM) {
-            f = lds_b128<2048 * T>(b0[S] + so);
-        } else {
-            const i32x2 lo = lds_tr((b0[S] + so) ^ (T << 5));
-            const i32x2 hi = lds_tr((b1[S] + so) ^ (T << 5));
-            f = i32x4{lo[0], lo[1], hi[0], hi[1]};
         }
     }
     // fragments of the 4 tiles (16 operand rows each) of k-step S, stage byte offset `so`
@@ -268,7 +232,7 @@ __device__ __forceinline__ void wave_epilogue(const GemmParams& p, f32x4 (&acc)[
             const int gm = row0 + 16 * mt + (lane >> 3) + 8 * half;
             hv[half][0] = i32x4{0, 0, 0, 0};
             hv[half][1] = i32x4{0, 0, 0, 0};
-            if (gm < p.M && j0 < p.glu_inner && !(p.dbg & 1)) {
+            if (gm < p.M && j0 < p.glu_inner) {
                 const bf16_t* hp = static_cast<const bf16_t*>(p.glu_aux) + (int64_t)gm * 2 * p.glu_inner;
                 hv[half][0] = *reinterpret_cast<const i32x4*>(hp + j0);
                 hv[half][1] = *reinterpret_cast<const i32x4*>(hp + p.glu_inner + j0);
@@ -393,11 +357,9 @@ __device__ __forceinline__ void wave_epilogue(const GemmParams& p, f32x4 (&acc)[
                         sx[2 * e] += bf16lo((uint32_t)ox[e]); sx[2 * e + 1] += bf16hi((uint32_t)ox[e]);
                         sg[2 * e] += bf16lo((uint32_t)og[e]); sg[2 * e + 1] += bf16hi((uint32_t)og[e]);
                     }
-                    if (!(p.dbg & 2)) {
-                        bf16_t* dp = reinterpret_cast<bf16_t*>(p.C) + (int64_t)gm * p.ldc;
-                        *reinterpret_cast<i32x4*>(dp + j0) = ox;
-                        *reinterpret_cast<i32x4*>(dp + p.glu_inner + j0) = og;
-                    }
+                    bf16_t* dp = reinterpret_cast<bf16_t*>(p.C) + (int64_t)gm * p.ldc;
+                    *reinterpret_cast<i32x4*>(dp + j0) = ox;
+                    *reinterpret_cast<i32x4*>(dp + p.glu_inner + j0) = og;
                 }
             }
         } else if (p.atomic) {
@@ -810,24 +772,8 @@ int launch2(const GemmParams& p, hipStream_t st) {
 // a wave reads the 12 fragments of a 32-deep k-step, waits, issues its 32 MFMAs; latency is covered by its SIMD
 // partner, which runs half a phase apart (second half of the workgroup defers the last MFMA block of a K-tile past
 // the barrier).  Per MFMA this tile needs 25 % fewer LDS reads, 33 % fewer DMA pieces and L2->LDS bytes than 256x128.
-// build switches: KALLE_GEMM_PIPE = 1 software-pipelined main loop (fragments refilled row by row; measured 3-4 % SLOWER over the
-// train step, 226.9 -> 235.4 ms same box: the loop is not waiting for LDS latency - on all-zero operands, i.e. at full clock, every
-// shape runs in the time of its LDS-DMA stream alone, on random operands the chip holds ~2.0 GHz - and spreading the DMA issue
-// over the second k-step halves the time the pieces have to land), 0 = the round-1 loop (default: whole k-step read in a burst,
-// SIMD partners half a phase apart, all DMA of K-tile kt + 2 issued right behind the hand-over); KALLE_GEMM_KNOCKOUT (variant builds for knock-out timing of the main
-// loop, tools/gemm_stamps.py): 1 no LDS-DMA after the prologue, 2 no fragment reads, 3 no MFMAs, 4 neither reads nor MFMAs
-#ifndef KALLE_GEMM_PIPE
-#define KALLE_GEMM_PIPE 0
-#endif
-#ifndef KALLE_GEMM_KNOCKOUT
-#define KALLE_GEMM_KNOCKOUT 0
-#endif
-#define KO_READ(...) do { if (KALLE_GEMM_KNOCKOUT != 2 && KALLE_GEMM_KNOCKOUT != 4) { __VA_ARGS__; } } while (0)
-#define KO_MFMA(...) do { if (KALLE_GEMM_KNOCKOUT != 3 && KALLE_GEMM_KNOCKOUT != 4) { __VA_ARGS__; } } while (0)
-template <int... I, typename F>
-__device__ __forceinline__ void static_for_impl(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) { static_for_impl(std::make_integer_sequence<int, N>{}, f); }
+// (a software-pipelined main loop that refilled the fragments row by row measured 3-4 % slower over the train step: the loop is
+// not waiting for LDS latency, and spreading the DMA issue over the second k-step halves the time the pieces have to land)
 
 constexpr int GEMM3_LDS = 2 * (256 + 256) * 128 + 8 * 16 * 64 * 4;      // two 64-KiB stages + the epilogue patches = 160 KiB
 
@@ -917,32 +863,20 @@ __device__ __forceinline__ void gemm3_tiles(const GemmParams& p, int tile0, int 
     ra.init(lds0, arow, lane);
     rb.init(lds0 + A_BYTES, bcol, lane);
     const bool late = wave >= NW / 2;     // the staggered half
-#if !KALLE_GEMM_PIPE
     if (late) __builtin_amdgcn_s_setprio(1);   // the second-dispatched half loses every issue arbitration by age otherwise
-#endif
 
     auto coords = [&](int tile, int& tm, int& tn) {
         if constexpr (XCD_RASTER) gemm_tile_coords(tile, ntiles_raster, p.tiles_m, p.tiles_n, p.group_m, tm, tn);
         else gemm_tile_coords_plain(tile, p.tiles_m, p.tiles_n, p.group_m, tm, tn);
     };
     auto init_loaders = [&](int tm, int tn, int kt_first) {      // source pointers of K-tile `kt_first` of this workgroup's range
-        // (KALLE_GEMM_DBG bit 2, timing experiment only - results are wrong: every workgroup fetches the operand panels of tile
-        // (tm & 1, tn & 1), i.e. all of an XCD's workgroups share four panels and the L2 -> LDS stream runs at ~100 % L2 hits)
-        if (p.dbg & 4) { tm &= 1; tn &= 1; }
         la.init(p.A, p.lda, p.M, tm * BM, (kt0 + kt_first) * BK2, wave, lane);
         lb.init(p.B, p.ldb, p.N, tn * BN, (kt0 + kt_first) * BK2, wave, lane, GLU == 1 ? p.glu_inner : 0, tn);
     };
-    if constexpr (PERSIST) {
-        if (p.dephase_ticks > 0 && ((blockIdx.x >> 3) & 1)) {
-            const unsigned long long t_end = __builtin_amdgcn_s_memrealtime() + (unsigned long long)p.dephase_ticks;
-            while (__builtin_amdgcn_s_memrealtime() < t_end) __builtin_amdgcn_s_sleep(32);
-        }
-    }
     bool prefetched = false;              // K-tiles 0 (and 1) of `tile` were requested by the previous tile's tail
     unsigned s0 = 0;                      // stage (byte offset) that holds K-tile 0 of `tile`
 
-    // (the software-pipelined build variant keeps the static walk)
-    int* const sched = PERSIST && !KALLE_GEMM_PIPE && p.sched_set > 0 ? &kalle_gemm_sched[p.sched_set - 1][0] : nullptr;
+    int* const sched = PERSIST && p.sched_set > 0 ? &kalle_gemm_sched[p.sched_set - 1][0] : nullptr;
     int next_tile = tile_end;
     int drawn = 0;                        // lane 0 of wave 0: the counter value drawn last (two tiles ahead of the one being computed)
     if constexpr (PERSIST) {
@@ -994,78 +928,6 @@ __device__ __forceinline__ void gemm3_tiles(const GemmParams& p, int tile0, int 
         }
         gemm_stamp(p, wave, lane, 1, tile);
 
-#if KALLE_GEMM_PIPE
-        // ---- software-pipelined main loop (round 3): every wave keeps its own MFMA stream fed.  A k-step is 8 rows of 4 MFMAs
-        // (acc[r][0..3] += A_r x B_0..3); right behind row r the register of A_r is refilled with the NEXT k-step's A_r, and rows
-        // 0-3 also fetch the next k-step's B_r into the second B set - one or two LDS reads per 4 MFMAs instead of 12-24 reads in
-        // a burst that only the SIMD partner could cover; the 8 DMA pieces of K-tile kt + 2 go out one per row of the second
-        // k-step.  LDS reads return in order, so the waits are counted: before row 0 everything but the four youngest A
-        // fragments, before row r >= 1 everything up to A_r (= all but 7 A + 4 B fragments' worth of instructions; the counter
-        // has 4 bits).  One barrier per K-tile, at the k-step boundary: behind it the stage just read is free for the DMA of
-        // K-tile kt + 2 and the other stage (K-tile kt + 1, requested a K-tile ago) may be read.
-        i32x4 fa[8], fb[2][4];
-        constexpr int NIA = Reader<A_KM, BM>::NI, NIB = Reader<B_KM, BN>::NI;
-        constexpr int W0 = 4 * NIA < 15 ? 4 * NIA : 15;
-        constexpr int WR = 7 * NIA + 4 * NIB < 15 ? 7 * NIA + 4 * NIB : 15;
-        unsigned so_cur = s0;
-        int kt = 0;
-        // CUR: B set multiplied; RS: k-step whose fragments are fetched behind the rows (from stage so_rd); READ / WAIT / ISSUE:
-        // fetch at all / counted waits in front of the rows / DMA pieces of K-tile `kt_dma` into stage so_dma
-        auto kstep = [&](auto cur_c, auto rs_c, auto read_c, auto wait_c, auto issue_c, unsigned so_rd, unsigned so_dma, bool dma_tail) {
-            constexpr int CUR = decltype(cur_c)::value, RS = decltype(rs_c)::value;
-            constexpr bool READ = decltype(read_c)::value, WAIT = decltype(wait_c)::value;
-            constexpr bool ISSUE = decltype(issue_c)::value && KALLE_GEMM_KNOCKOUT != 1;
-            static_for<8>([&](auto rc) {
-                constexpr int r = decltype(rc)::value;
-                if constexpr (WAIT) {
-                    asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(r == 0 ? W0 : WR) : "memory");
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-#pragma unroll
-                for (int nt = 0; nt < 4; ++nt)
-                    KO_MFMA(acc[r][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fa[r]),
-                                                                                __builtin_bit_cast(bf16x8, fb[CUR][nt]), acc[r][nt], 0, 0, 0));
-                __builtin_amdgcn_sched_barrier(0);
-                if constexpr (ISSUE) {
-                    if constexpr (r < 4) la.template issue_one<r>(smem + so_dma, wave, lane, dma_tail, kvalid);
-                    else lb.template issue_one<r - 4>(smem + so_dma + A_BYTES, wave, lane, dma_tail, kvalid);
-                }
-                if constexpr (READ) {
-                    KO_READ(ra.template read1<RS, r>(so_rd, fa[r]));
-                    if constexpr (r < 4) KO_READ(rb.template read1<RS, r>(so_rd, fb[1 - CUR][r]));
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            });
-        };
-        using T_ = std::true_type;
-        using F_ = std::false_type;
-        using I0 = std::integral_constant<int, 0>;
-        using I1 = std::integral_constant<int, 1>;
-        // prologue: k-step 0 of K-tile 0, in the issue order the counted waits assume
-        static_for<8>([&](auto rc) {
-            constexpr int r = decltype(rc)::value;
-            ra.template read1<0, r>(so_cur, fa[r]);
-            if constexpr (r < 4) rb.template read1<0, r>(so_cur, fb[0][r]);
-        });
-        __builtin_amdgcn_sched_barrier(0);
-        auto iteration = [&](auto issue_c) {
-            kstep(I0{}, I1{}, T_{}, T_{}, F_{}, so_cur, 0u, false);
-            // hand-over: my reads of this stage have returned, my DMA pieces of K-tile kt + 1 have landed - and everybody's
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-            kstep(I1{}, I0{}, T_{}, F_{}, issue_c, so_cur ^ STAGE, so_cur, kt + 2 == tail_t);
-            so_cur ^= STAGE;
-        };
-#pragma unroll 1
-        for (; kt + 2 < nk; ++kt) iteration(T_{});
-        if (kt + 1 < nk) { iteration(F_{}); ++kt; }
-        // the last K-tile: nothing to hand over (the epilogue's barrier follows)
-        kstep(I0{}, I1{}, T_{}, T_{}, F_{}, so_cur, 0u, false);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        kstep(I1{}, I0{}, F_{}, F_{}, F_{}, 0u, 0u, false);
-#else
         i32x4 fa[8], fb[4];
         unsigned so_cur = s0;
         int kt = 0;
@@ -1073,20 +935,19 @@ __device__ __forceinline__ void gemm3_tiles(const GemmParams& p, int tile0, int 
         ra.template read<0, 8>(so_cur, fa);
         rb.template read<0, 4>(so_cur, fb);
 
-        // (variant builds for knock-out timing of the main loop, tools/gemm_stamps.py: -DKALLE_GEMM_KNOCKOUT=1 no LDS-DMA after
-        // the prologue, =2 no fragment reads, =3 no MFMAs, =4 neither reads nor MFMAs; the product build has none of it)
         auto iteration = [&](auto issue_c, auto next_c) {
-            constexpr bool ISSUE = decltype(issue_c)::value && KALLE_GEMM_KNOCKOUT != 1, NEXT = decltype(next_c)::value;
+            constexpr bool ISSUE = decltype(issue_c)::value, NEXT = decltype(next_c)::value;
             // k-step 0 of this tile is in flight / landed
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_sched_barrier(0);
-            KO_MFMA(MFMA32(fa, fb));
+            MFMA32(fa, fb);
             __builtin_amdgcn_sched_barrier(0);
-            KO_READ(ra.template read<1, 8>(so_cur, fa); rb.template read<1, 4>(so_cur, fb));
+            ra.template read<1, 8>(so_cur, fa);
+            rb.template read<1, 4>(so_cur, fb);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // my last reads of this stage are done
             __builtin_amdgcn_sched_barrier(0);
             if (!late) {
-                KO_MFMA(MFMA32(fa, fb));
+                MFMA32(fa, fb);
                 __builtin_amdgcn_sched_barrier(0);
             }
             // hand-over: everybody's DMA of tile kt+1 has landed, everybody is done reading this stage
@@ -1094,7 +955,7 @@ __device__ __forceinline__ void gemm3_tiles(const GemmParams& p, int tile0, int 
             __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_sched_barrier(0);
             if (late) {
-                KO_MFMA(MFMA32(fa, fb));
+                MFMA32(fa, fb);
                 __builtin_amdgcn_sched_barrier(0);
             }
             if constexpr (ISSUE) {      // this stage is free: start the DMA of tile kt+2 into it
@@ -1103,7 +964,8 @@ __device__ __forceinline__ void gemm3_tiles(const GemmParams& p, int tile0, int 
             }
             so_cur ^= STAGE;
             if constexpr (NEXT) {
-                KO_READ(ra.template read<0, 8>(so_cur, fa); rb.template read<0, 4>(so_cur, fb));
+                ra.template read<0, 8>(so_cur, fa);
+                rb.template read<0, 4>(so_cur, fb);
             }
             __builtin_amdgcn_sched_barrier(0);
         };
@@ -1129,7 +991,6 @@ __device__ __forceinline__ void gemm3_tiles(const GemmParams& p, int tile0, int 
         // under the last MFMAs - 27 more VGPRs in the one-tile kernels, 33 spilled in the fused SwiGLU backward)
         if constexpr (!PERSIST || GLU == 2) iteration(F_{}, F_{});
         else last_iteration();
-#endif
         gemm_stamp(p, wave, lane, 2, tile);
 
         // Behind the epilogue's barrier both stages are free: request the next tile's K-tiles 0 and 1 there.  The loaders are
@@ -1187,7 +1048,7 @@ __global__ __launch_bounds__(512, 2) void gemm3_kernel(GemmParams p) {
         // whole-K tiles: gridDim.x <= tiles workgroups (one per CU) walk tiles b, b + grid, ...; a multiple-of-8 grid keeps a
         // workgroup's tiles on the XCD-contiguous run of the raster its XCD owns
         gemm3_tiles<A_KM, B_KM, C_F32, GLU, true, true>(p, blockIdx.x, gridDim.x, ntiles, ntiles, 0, nk_all);
-        if (!KALLE_GEMM_PIPE && p.sched_set > 0 && threadIdx.x == 0) sched_leave(&kalle_gemm_sched[p.sched_set - 1][0], gridDim.x);
+        if (p.sched_set > 0 && threadIdx.x == 0) sched_leave(&kalle_gemm_sched[p.sched_set - 1][0], gridDim.x);
     }
 }
 
@@ -1282,30 +1143,20 @@ int launch3(const GemmParams& p, hipStream_t st) {
         const int ntiles = p.tiles_m * p.tiles_n;
         grid = dim3(p.mix_na * p.mix_sa + (ntiles - p.mix_na) * (p.mix_sa + 1), 1);
     } else if (!A_KM) {
-        // persistent: one workgroup per CU (160 KiB of LDS each) walks its tiles; KALLE_GEMM_PERSIST=0: one workgroup per tile
-        // (the same code with a grid of `tiles` workgroups: every workgroup finds no next tile)
+        // persistent: one workgroup per CU (160 KiB of LDS each) walks its tiles; a grid that fits the CUs runs one workgroup per
+        // tile (the same code: every workgroup finds no next tile)
         if (p.splits != 1) return KALLE_ERR_UNSUPPORTED;
-        static const bool persist = !(getenv("KALLE_GEMM_PERSIST") && atoi(getenv("KALLE_GEMM_PERSIST")) == 0);
-        // KALLE_GEMM_GRID: workgroups of the persistent launch (experiment: fewer than one per CU)
-        static const int grid_env = getenv("KALLE_GEMM_GRID") ? atoi(getenv("KALLE_GEMM_GRID")) & ~7 : 0;
-        const int cus = grid_env >= 8 ? std::min(grid_env, kalle_cu_count()) : kalle_cu_count();
-        if (persist && (int)grid.x > cus) {
-            // experiment switch: "us" for every shape, or "glu2:us" for the fused SwiGLU backward only
-            static const char* de = getenv("KALLE_GEMM_DEPHASE_US");
+        const int cus = kalle_cu_count();
+        if ((int)grid.x > cus) {
             GemmParams q = p;
-            if (de && (int)grid.x >= 4 * cus) {
-                const bool only_glu2 = !strncmp(de, "glu2:", 5);
-                if (!only_glu2 || GLU == 2) q.dephase_ticks = (int)(atof(only_glu2 ? de + 5 : de) * 100.0);
-            }
             grid.x = cus;
-            // dynamic tile hand-out (KALLE_GEMM_DYNAMIC=0: static walk); a set is reused after SCHED_SETS persistent launches
-            static const bool dynamic = !(getenv("KALLE_GEMM_DYNAMIC") && atoi(getenv("KALLE_GEMM_DYNAMIC")) == 0);
+            // dynamic tile hand-out; a set is reused after SCHED_SETS persistent launches
             static std::atomic<unsigned> next_set{0};
             // (a launch that is being captured into a HIP graph keeps the static walk: a replayed node would come back with the
             // same counter set while an eager launch on another stream may hold it)
             hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
             const bool capturing = hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
-            q.sched_set = dynamic && !capturing ? 1 + (int)(next_set.fetch_add(1, std::memory_order_relaxed) % SCHED_SETS) : 0;
+            q.sched_set = !capturing ? 1 + (int)(next_set.fetch_add(1, std::memory_order_relaxed) % SCHED_SETS) : 0;
             KALLE_LAUNCH((gemm3_kernel<A_KM, B_KM, C_F32, GLU>), grid, block, lds, st, q);
             return kalle_check_launch();
         }
@@ -1329,14 +1180,32 @@ int launch2_layout(const GemmParams& p, bool a_km, bool b_km, bool f32, hipStrea
     return KALLE_ERR_UNSUPPORTED;
 }
 
-int g_force = -1;  // KALLE_GEMM=v1 | v2 (A/B testing); default: v2 where eligible
-int force_mode() {
-    if (g_force < 0) {
-        const char* e = getenv("KALLE_GEMM");
-        g_force = !e ? 0 : (!strcmp(e, "v1") ? 1 : (!strcmp(e, "v2") ? 2 : 0));
+// Makespan model of a split-K weight-gradient dispatch on 256 CUs, shared by the two planners (mixed split-K in
+// kalle_gemm_v2_launch, kalle_gemm_wgrad_group): workgroups go out in grid order, each to the CU that falls free first, and one
+// over k K-tiles takes 10 us + 1.6 us per K-tile (fitted to measured weight-gradient GEMMs).  Each planner adds its own atomic traffic.
+struct CuReplay {
+    double cu[256] = {};                        // min-heap of the times at which the CUs fall free
+    // `tiles` output tiles of `nk` K-tiles, each cut into `slices` K slices (the last one may be shorter), slice by slice
+    void run(int tiles, int nk, int slices) {
+        if (tiles <= 0 || slices <= 0) return;
+        const int per = (nk + slices - 1) / slices;
+        for (int sl = 0; sl < slices; ++sl) {
+            const int k = nk - sl * per < per ? nk - sl * per : per;
+            if (k <= 0) break;
+            const double d = 10.0 + 1.6 * k;
+            for (int t = 0; t < tiles; ++t) {
+                std::pop_heap(cu, cu + 256, std::greater<double>());
+                cu[255] += d;
+                std::push_heap(cu, cu + 256, std::greater<double>());
+            }
+        }
     }
-    return g_force;
-}
+    double makespan() const {
+        double mk = 0.0;
+        for (int c = 0; c < 256; ++c) mk = cu[c] > mk ? cu[c] : mk;
+        return mk;
+    }
+};
 
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
@@ -1348,8 +1217,7 @@ int kalle_gemm_v2_launch(GemmParams& p, bool a_km, bool b_km, bool f32, hipStrea
     if (p.K & 7) return KALLE_ERR_UNSUPPORTED;        // (a ragged last K-tile is fine: K % 64 in multiples of 8)
     if (a_km && !b_km) return KALLE_ERR_UNSUPPORTED;
     if (a_km && !f32) return KALLE_ERR_UNSUPPORTED;
-    static const int min_m = getenv("KALLE_V2_MIN_M") ? atoi(getenv("KALLE_V2_MIN_M")) : 256;
-    if (p.M < min_m || p.N < 128) return KALLE_ERR_UNSUPPORTED;
+    if (p.M < 256 || p.N < 128) return KALLE_ERR_UNSUPPORTED;
     if (a_km && (p.M & 7)) return KALLE_ERR_UNSUPPORTED;
     const int nk = (p.K + BK2 - 1) / BK2;
     if (p.glu_mode) {
@@ -1370,17 +1238,11 @@ int kalle_gemm_v2_launch(GemmParams& p, bool a_km, bool b_km, bool f32, hipStrea
     }
     const bool plain = !p.bias && !p.gate && !p.residual && !p.row_mask && p.c_rpb == 0;
     const bool can_split = f32 && plain && a_km && nk >= 16;
-    static int tile_env = -1;
-    if (tile_env < 0) {
-        const char* e = getenv("KALLE_GEMM_TILE");
-        tile_env = e ? atoi(e) : 0;
-    }
     // modelled time of a configuration: MFMA work / (tile rate x wave-quantisation efficiency) + split-K atomic bytes
     const double flops = 2.0 * p.M * p.N * p.K;
     double best = 1e30;
     int best_bn = 128, best_s = 1;
     for (int bn = 128; bn <= 256; bn += 128) {
-        if (tile_env && bn != tile_env) continue;
         if (bn == 256 && p.N < 256) continue;
         const double rate = bn == 256 ? 1150e12 : 1000e12;
         const int tiles = ((p.M + 255) / 256) * ((p.N + bn - 1) / bn);
@@ -1394,10 +1256,8 @@ int kalle_gemm_v2_launch(GemmParams& p, bool a_km, bool b_km, bool f32, hipStrea
     // Weight gradients on the 256 x 256 kernel: mixed split-K.  `na` tiles get `sa` K slices, the others sa + 1, the longer
     // slices are dispatched first: the last round of workgroups then consists of short slices instead of leaving most CUs idle
     // (288 tiles x 3 slices = 3.4 rounds -> 4 with uniform splitting).  The plan comes from replaying the dispatch on 256 CUs
-    // (time of a slice = 10 us + 1.6 us per K-tile, atomics at 2 TB/s - fitted to tools/wgrad_sweep.py) and is cached per shape.
-    static const bool nomix_env = getenv("KALLE_GEMM_NOMIX") != nullptr, debug_env = getenv("KALLE_GEMM_DEBUG") != nullptr;
-    static const char* const mix_env = getenv("KALLE_GEMM_MIX");          // experiment switches: read once per process
-    if (can_split && best_bn == 256 && !tile_env && !nomix_env) {
+    // (CuReplay, atomics at 2 TB/s) and is cached per shape.
+    if (can_split && best_bn == 256) {
         struct Plan { int M, N, kb, sa, na; };          // kb: K-tiles / 16 (a plan is valid for any K; nearby K share it)
         static thread_local Plan cache[32];
         static thread_local int ncache = 0, victim = 0;
@@ -1407,29 +1267,12 @@ int kalle_gemm_v2_launch(GemmParams& p, bool a_km, bool b_km, bool f32, hipStrea
             if (cache[i].M == p.M && cache[i].N == p.N && cache[i].kb == nk / 16) hit = &cache[i];
         if (!hit) {
             const int ntiles = ((p.M + 255) / 256) * ((p.N + 255) / 256);
-            auto replay = [&](int sa, int na) {        // makespan (us) of the dispatch order on 256 CUs + atomic traffic
-                double cu[256];                         // min-heap of the times at which the CUs fall free
-                for (int c = 0; c < 256; ++c) cu[c] = 0.0;
-                auto run = [&](int tiles, int slices) {
-                    if (tiles <= 0 || slices <= 0) return;
-                    const int per = (nk + slices - 1) / slices;
-                    for (int sl = 0; sl < slices; ++sl) {
-                        const int k = nk - sl * per < per ? nk - sl * per : per;
-                        if (k <= 0) break;
-                        const double d = 10.0 + 1.6 * k;
-                        for (int t = 0; t < tiles; ++t) {
-                            std::pop_heap(cu, cu + 256, std::greater<double>());
-                            cu[255] += d;
-                            std::push_heap(cu, cu + 256, std::greater<double>());
-                        }
-                    }
-                };
-                run(na, sa);
-                run(ntiles - na, sa + 1);
-                double mk = 0.0;
-                for (int c = 0; c < 256; ++c) mk = cu[c] > mk ? cu[c] : mk;
+            auto replay = [&](int sa, int na) {        // makespan (us) + atomic traffic
+                CuReplay r;
+                r.run(na, nk, sa);
+                r.run(ntiles - na, nk, sa + 1);
                 const double savg = ((double)na * sa + (double)(ntiles - na) * (sa + 1)) / ntiles;
-                return mk + (savg > 1.0 ? savg * p.M * p.N * 4.0 / 2.0e12 * 1e6 : 0.0);
+                return r.makespan() + (savg > 1.0 ? savg * p.M * p.N * 4.0 / 2.0e12 * 1e6 : 0.0);
             };
             Plan best_plan{p.M, p.N, nk / 16, 0, -1};
             double t_uniform = 1e30, t_best = 1e30;
@@ -1456,27 +1299,12 @@ int kalle_gemm_v2_launch(GemmParams& p, bool a_km, bool b_km, bool f32, hipStrea
             na_sel = hit->na;
         }
         if (na_sel > 0 && nk / (sa_sel + 1) < 8) na_sel = -1;    // (a cached plan of a longer K)
-        if (debug_env) fprintf(stderr, "[kalle gemm] %d x %d x %d: mixed split sa=%d na=%d (hit=%d)\n", p.M, p.N, p.K, sa_sel, na_sel, hit != nullptr);
         if (na_sel > 0) { p.mix_na = na_sel; p.mix_sa = sa_sel; best_s = sa_sel + 1; }
     }
-    if (const char* e = mix_env) {      // "sa,na": experiment override
-        int sa = 0, na = 0;
-        if (can_split && sscanf(e, "%d,%d", &sa, &na) == 2 && sa >= 1 && best_bn == 256 && nk / (sa + 1) >= 8) {
-            const int ntiles = ((p.M + 255) / 256) * ((p.N + 255) / 256);
-            p.mix_sa = sa;
-            p.mix_na = na < ntiles ? na : ntiles;
-            best_s = sa + 1;                             // (>1: atomic epilogue + cleared C below)
-        }
-    }
-    static const int s_env = getenv("KALLE_GEMM_SPLITS") ? atoi(getenv("KALLE_GEMM_SPLITS")) : 0;
-    if (s_env > 0 && can_split && nk / s_env >= 8) best_s = s_env;
     p.tiles_m = (p.M + 255) / 256;
     p.tiles_n = (p.N + best_bn - 1) / best_bn;
     p.tile_n = best_bn;
-    static int gm_env = -1;
-    if (gm_env < 0) { const char* e = getenv("KALLE_GEMM_GM"); gm_env = e ? atoi(e) : 0; }
-    const int gm_want = gm_env > 0 ? gm_env : 4;
-    p.group_m = p.tiles_m < gm_want ? p.tiles_m : gm_want;
+    p.group_m = p.tiles_m < 4 ? p.tiles_m : 4;
     p.splits = best_s;
     p.atomic = best_s > 1;
     if (p.atomic && !p.accumulate) {
@@ -1565,30 +1393,22 @@ __global__ __launch_bounds__(256) void gemm_finish_kernel(GemmParams p, const fl
 // into slices (slabs + finishing pass).  `cfg` packs the choice for kalle_gemm_last_plan: 5 | WM << 8 | WN << 12 | splits << 16.
 template <bool C_F32, int GLU>
 int launch_skinny_tile(int wm, int wn, const GemmParams& q, hipStream_t st, bool b_km = false) {
-    static const bool one_group = getenv("KALLE_SKINNY_KS") && atoi(getenv("KALLE_SKINNY_KS")) == 1;    // experiment switch
     if (b_km) {             // k-major weights (data gradients): 128-column tiles only
         if constexpr (GLU == 0) {
             if (wm == 2 && wn == 2) return launch2_ks2<true, C_F32, 2, 2, 0, 4>(q, st);
         }
         return KALLE_ERR_UNSUPPORTED;
     }
-    if (!one_group) {       // two wave groups per tile (one per 32-deep k-step): two waves per SIMD cover each other
-        if (wm == 1 && wn == 1) return launch2_ks2<false, C_F32, 1, 1, GLU, 5>(q, st);         // 80 KiB
-        if (wm == 2 && wn == 1) return launch2_ks2<false, C_F32, 2, 1, GLU, 5>(q, st);         // 120 KiB
-        if (wm == 2 && wn == 2) return launch2_ks2<false, C_F32, 2, 2, GLU, 4>(q, st);         // 128 KiB
-    }
-    if (wm == 1 && wn == 1) return launch2<false, false, C_F32, 1, 1, 4, GLU, 5>(q, st);
-    if (wm == 2 && wn == 1) return launch2<false, false, C_F32, 2, 1, 4, GLU, 5>(q, st);
-    if (wm == 2 && wn == 2) return launch2<false, false, C_F32, 2, 2, 4, GLU, 4>(q, st);
+    // two wave groups per tile (one per 32-deep k-step): two waves per SIMD cover each other
+    if (wm == 1 && wn == 1) return launch2_ks2<false, C_F32, 1, 1, GLU, 5>(q, st);         // 80 KiB
+    if (wm == 2 && wn == 1) return launch2_ks2<false, C_F32, 2, 1, GLU, 5>(q, st);         // 120 KiB
+    if (wm == 2 && wn == 2) return launch2_ks2<false, C_F32, 2, 2, GLU, 4>(q, st);         // 128 KiB
     return KALLE_ERR_UNSUPPORTED;
 }
 
 int kalle_gemm_skinny_launch(const GemmParams& pin, bool a_km, bool b_km, bool f32, void* ws, int64_t ws_bytes, hipStream_t st,
                              int* cfg) {
-    static const char* env = getenv("KALLE_SKINNY");           // "0": off; "wm,wn,splits": forced configuration (experiments)
-    if (env && env[0] == '0' && !env[1]) return KALLE_ERR_UNSUPPORTED;
-    static const int max_m = getenv("KALLE_SKINNY_MAX_M") ? atoi(getenv("KALLE_SKINNY_MAX_M")) : 2048;
-    if (a_km || pin.M > max_m || (pin.K & 7) || (pin.N & 63) || pin.atomic) return KALLE_ERR_UNSUPPORTED;
+    if (a_km || pin.M > 2048 || (pin.K & 7) || (pin.N & 63) || pin.atomic) return KALLE_ERR_UNSUPPORTED;
     if (b_km && ((pin.N & 127) || pin.glu_mode)) return KALLE_ERR_UNSUPPORTED;
     if (pin.glu_mode == 2 || (pin.glu_mode == 1 && (f32 || pin.N != 2 * pin.glu_inner || (pin.glu_inner & 31) || pin.gate ||
                                                     pin.residual || pin.row_mask || pin.c_rpb || pin.accumulate)))
@@ -1601,8 +1421,6 @@ int kalle_gemm_skinny_launch(const GemmParams& pin, bool a_km, bool b_km, bool f
     static const int cand[3][2] = {{1, 1}, {2, 1}, {2, 2}};
     int wm = 0, wn = 0, splits = 1;
     double best = 1e30;
-    int fwm = 0, fwn = 0, fs = 0;
-    const bool forced = env && sscanf(env, "%d,%d,%d", &fwm, &fwn, &fs) == 3;
     for (int c = 0; c < 3; ++c) {
         const int bm = cand[c][0] * 64, bn = cand[c][1] * 64;
         if (pin.glu_mode == 1 && (pin.glu_inner % (bn / 2))) continue;
@@ -1626,8 +1444,7 @@ int kalle_gemm_skinny_launch(const GemmParams& pin, bool a_km, bool b_km, bool f
             // slabs: second launch + write + read back.  (The slabs of these shapes are a few MB that the finishing pass finds in L2 /
             // Infinity Cache: 3 TB/s fits M = 252 ... 1008 x 1536 x 6144, where 1.7 TB/s kept M = 504 on whole-K 64 x 64 tiles at 37 us)
             if (sp > 1) t += 4.0 + 2.0 * sp * pin.M * (double)pin.N * 4.0 / 3.0e6;
-            const bool pick = forced ? (cand[c][0] == fwm && cand[c][1] == fwn && sp == fs) : t < best;
-            if (pick) { best = t; wm = cand[c][0]; wn = cand[c][1]; splits = sp; }
+            if (t < best) { best = t; wm = cand[c][0]; wn = cand[c][1]; splits = sp; }
         }
     }
     if (!wm) return KALLE_ERR_UNSUPPORTED;
@@ -1678,8 +1495,7 @@ int kalle_gemm_few_rows_launch(const GemmParams& pin, bool a_km, bool b_km, bool
     constexpr int bn = 128;
     const int tiles = ((pin.M + 255) / 256) * ((pin.N + bn - 1) / bn);
     if (tiles >= 192) return KALLE_ERR_UNSUPPORTED;                 // enough output tiles on their own
-    static const int target = getenv("KALLE_FEW_ROWS_TARGET") ? atoi(getenv("KALLE_FEW_ROWS_TARGET")) : 320;
-    int splits = (target + tiles - 1) / tiles;                       // ~1.25 workgroups per CU
+    int splits = (320 + tiles - 1) / tiles;                       // ~1.25 workgroups per CU
     // at least two K-tiles per slice; with more than a couple of tile rows (training at small batch) a slice must be long
     // enough (16 K-tiles) to pay for its slab: M x N x 4 bytes written and read back per slice
     const int min_per = pin.M > 512 ? 16 : 2;
@@ -1771,34 +1587,26 @@ extern "C" int kalle_gemm_bf16(const void* A, int64_t lda, int a_kmajor, const v
             return KALLE_ERR_ARG;
     }
     p.stamps = g_stamps;
-    static const int dbg_env = getenv("KALLE_GEMM_DBG") ? atoi(getenv("KALLE_GEMM_DBG")) : 0;   // knock-out timing (diagnostics)
-    p.dbg = dbg_env;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const bool f32 = c_dtype == KALLE_F32;
-    if (force_mode() != 1) {
-        int cfg = 0;
-        const int rc = kalle_gemm_skinny_launch(p, a_kmajor != 0, b_kmajor != 0, f32, ep ? ep->workspace : nullptr,
-                                                ep ? ep->workspace_bytes : 0, st, &cfg);
-        if (rc != KALLE_ERR_UNSUPPORTED) {
-            g_last_plan = cfg;
-            return rc;
-        }
+    int cfg = 0;
+    int rc = kalle_gemm_skinny_launch(p, a_kmajor != 0, b_kmajor != 0, f32, ep ? ep->workspace : nullptr,
+                                      ep ? ep->workspace_bytes : 0, st, &cfg);
+    if (rc != KALLE_ERR_UNSUPPORTED) {
+        g_last_plan = cfg;
+        return rc;
     }
-    if (ep && ep->workspace && force_mode() != 1) {
-        const int rc = kalle_gemm_few_rows_launch(p, a_kmajor != 0, b_kmajor != 0, f32, ep->workspace, ep->workspace_bytes, st);
+    if (ep && ep->workspace) {
+        rc = kalle_gemm_few_rows_launch(p, a_kmajor != 0, b_kmajor != 0, f32, ep->workspace, ep->workspace_bytes, st);
         if (rc != KALLE_ERR_UNSUPPORTED) {
             g_last_plan = 4 | (1 << 8);
             return rc;
         }
     }
-    if (force_mode() != 1) {
-        const int rc = kalle_gemm_v2_launch(p, a_kmajor != 0, b_kmajor != 0, f32, st);
-        if (rc != KALLE_ERR_UNSUPPORTED) {
-            g_last_plan = (p.tile_n == 256 ? 3 : 2) | (p.splits << 8);
-            return rc;
-        }
-        static const bool strict_env = getenv("KALLE_GEMM_STRICT") != nullptr;
-        if (force_mode() == 2 && strict_env) return rc;
+    rc = kalle_gemm_v2_launch(p, a_kmajor != 0, b_kmajor != 0, f32, st);
+    if (rc != KALLE_ERR_UNSUPPORTED) {
+        g_last_plan = (p.tile_n == 256 ? 3 : 2) | (p.splits << 8) | (p.mix_na >= 0 ? 1 << 24 : 0);
+        return rc;
     }
     if (p.glu_mode) return KALLE_ERR_UNSUPPORTED;   // fused SwiGLU exists only in the 256x256 kernel: caller un-fuses
     p.tiles_n = (N + 127) / 128;
@@ -1810,16 +1618,9 @@ extern "C" int kalle_gemm_bf16(const void* A, int64_t lda, int a_kmajor, const v
 namespace {
 struct GroupPlan { uint64_t key; int ntot; int unsplit_total, splits; };
 
-// makespan (us) of a plan on 256 CUs: whole tiles first, then the slices; a slice costs 10 us + 1.6 us per K-tile (fitted to
-// tools/wgrad_sweep.py), atomics at 2 TB/s for the sliced tiles only
+// makespan (us) of a plan: whole tiles first, then the slices (CuReplay), atomics at 2 TB/s for the sliced tiles only
 double replay_group(const GroupProblem* pr, int n, int unsplit_total, int splits) {
-    double cu[256];
-    for (int c = 0; c < 256; ++c) cu[c] = 0.0;
-    auto put = [&](double d) {
-        std::pop_heap(cu, cu + 256, std::greater<double>());
-        cu[255] += d;
-        std::push_heap(cu, cu + 256, std::greater<double>());
-    };
+    CuReplay r;
     int left = unsplit_total;
     double atomic_bytes = 0.0;
     int rest[KALLE_MAX_GROUP];
@@ -1827,22 +1628,14 @@ double replay_group(const GroupProblem* pr, int n, int unsplit_total, int splits
         const int t = pr[i].tiles_m * pr[i].tiles_n, u = left < t ? left : t;
         left -= u;
         rest[i] = t - u;
-        const double d = 10.0 + 1.6 * ((pr[i].K + BK2 - 1) / BK2);
-        for (int k = 0; k < u; ++k) put(d);
+        r.run(u, (pr[i].K + BK2 - 1) / BK2, 1);
     }
     for (int i = 0; i < n; ++i) {
         if (!rest[i]) continue;
-        const int nk = (pr[i].K + BK2 - 1) / BK2, per = (nk + splits - 1) / splits;
-        for (int sl = 0; sl < splits; ++sl) {
-            const int k = nk - sl * per < per ? nk - sl * per : per;
-            if (k <= 0) break;
-            for (int t = 0; t < rest[i]; ++t) put(10.0 + 1.6 * k);
-        }
+        r.run(rest[i], (pr[i].K + BK2 - 1) / BK2, splits);
         if (splits > 1) atomic_bytes += (double)rest[i] * splits * 256.0 * 256.0 * 4.0;
     }
-    double mk = 0.0;
-    for (int c = 0; c < 256; ++c) mk = cu[c] > mk ? cu[c] : mk;
-    return mk + atomic_bytes / 2.0e12 * 1e6;
+    return r.makespan() + atomic_bytes / 2.0e12 * 1e6;
 }
 }  // namespace
 
@@ -1876,11 +1669,7 @@ extern "C" int kalle_gemm_wgrad_group(const kalle_wgrad_problem* problems, int n
     for (int i = 0; i < ncache; ++i)
         if (cache[i].key == key && cache[i].ntot == ntot) hit = &cache[i];
     GroupPlan plan{key, ntot, ntot, 1};
-    static const char* env_plan = getenv("KALLE_WGRAD_GROUP_PLAN");      // "unsplit,splits": experiment override
-    if (env_plan && sscanf(env_plan, "%d,%d", &plan.unsplit_total, &plan.splits) == 2) {
-        plan.unsplit_total = plan.unsplit_total < ntot ? (plan.unsplit_total < 0 ? 0 : plan.unsplit_total) : ntot;
-        plan.splits = plan.splits < 1 ? 1 : plan.splits;
-    } else if (hit) {
+    if (hit) {
         plan = *hit;
     } else {
         double best = 1e30;
@@ -1915,9 +1704,6 @@ extern "C" int kalle_gemm_wgrad_group(const kalle_wgrad_problem* problems, int n
         q.r2_start = b2;
         b2 += (q.tiles_m * q.tiles_n - q.unsplit) * q.splits;
     }
-    static const bool dbg = getenv("KALLE_GEMM_DEBUG") != nullptr;
-    if (dbg) fprintf(stderr, "[kalle wgrad group] %d problems, %d tiles: %d whole + %d x %d slices = %d workgroups\n", nprob, ntot,
-                     b1, ntot - b1, plan.splits, b2);
     if (gp.overwrite && ntot - b1 > 0 && plan.splits >= 1) {
         // (N % 4 == 0 is implied by N % 8 == 0: the clears are 16-byte stores)
         KALLE_LAUNCH(gemm3_group_zero_kernel, dim3(4 * (ntot - b1)), dim3(256), 0, static_cast<hipStream_t>(stream), gp);

@@ -504,29 +504,31 @@ def test_conv1d_causal_leaky_gate_scale_accumulate(ops, dev):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("force_v1", [False, True])
-def test_conv_post_activation_and_fallback_kernels(ops, dev, force_v1, monkeypatch):
+@pytest.mark.parametrize("fallback", [False, True])
+def test_conv_post_activation_and_fallback_kernels(ops, dev, fallback):
     """output-side activation (the consumer's input activation applied at the producer's store) for conv and transposed
-    conv, on the main kernels and on the fallback kernels (KALLE_CONV_V1=1)"""
+    conv, on the main kernels and on the fallback kernels (stride 3: no position-per-lane v2 kernel and no channels-per-lane
+    kernel takes it, so kalle_conv1d_fwd runs conv1d_kernel)"""
     from kalle_audio_amd import conv_ops
-    if force_v1:
-        monkeypatch.setenv("KALLE_CONV_V1", "1")
+    s = 3 if fallback else 1
     torch.manual_seed(11)
     Bn, Cin, Cout, K, L = 2, 40, 24, 7, 900
+    Lout = (L - 1) // s + 1                     # both convs below pad to 'same' length before the stride
     x = torch.randn(Bn, Cin, L, device=dev)
     w = torch.randn(Cout, Cin, K, device=dev) / (Cin * K) ** 0.5
     bias = torch.randn(Cout, device=dev)
     a, b = 0.3 * torch.randn(Cout, device=dev), 0.3 * torch.randn(Cout, device=dev)
-    res = torch.randn(Bn, Cout, L, device=dev)
+    res = torch.randn(Bn, Cout, Lout, device=dev)
     snake = lambda t: t + torch.sin(t * a.exp()[None, :, None]) ** 2 / (b.exp()[None, :, None] + 1e-9)
     wp = conv_ops.weight_norm_fold(w, None)
-    ref = snake(F.conv1d(x, w, bias, padding=9, dilation=3) + res)
-    got = conv_ops.conv1d(x, wp, bias, Cout=Cout, K=K, padding=9, dilation=3, residual=res, post_act=(1, a, b, True, 0.0))
+    ref = snake(F.conv1d(x, w, bias, stride=s, padding=9, dilation=3) + res)
+    got = conv_ops.conv1d(x, wp, bias, Cout=Cout, K=K, stride=s, padding=9, dilation=3, residual=res,
+                          post_act=(1, a, b, True, 0.0))
     assert rel_l2(got, ref) < 2e-5
-    ref = F.elu(F.conv1d(x, w, bias, padding=3))
-    got = conv_ops.conv1d(x, wp, bias, Cout=Cout, K=K, padding=3, post_act=(2, None, None, False, 0.0))
+    ref = F.elu(F.conv1d(x, w, bias, stride=s, padding=3))
+    got = conv_ops.conv1d(x, wp, bias, Cout=Cout, K=K, stride=s, padding=3, post_act=(2, None, None, False, 0.0))
     assert rel_l2(got, ref) < 2e-5
-    if not force_v1:
+    if not fallback:
         wt = torch.randn(Cin, Cout, 8, device=dev) / (Cin * 2) ** 0.5
         wtp = conv_ops.weight_norm_fold(wt, None, transposed=True)
         ref = snake(F.conv_transpose1d(x, wt, bias, stride=4, padding=2))
@@ -611,20 +613,27 @@ def test_gemv_single_row(ops, dev, N, K):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("mix", [None, "1,3", "2,5", "3,12", "2,0"])
-def test_wgrad_mixed_split_k(ops, dev, mix, monkeypatch):
-    """weight-gradient GEMM (TN, fp32, atomics) with some tiles cut into sa and the others into sa + 1 K slices (1-D grid,
-    long slices first): same result as fp32 matmul for forced plans and for the planner's own choice"""
-    if mix:
-        monkeypatch.setenv("KALLE_GEMM_MIX", mix)
-    M, N, K = 768, 1024, 8192                                            # 12 tiles of 256 x 256, 128 K-tiles
+@pytest.mark.parametrize("M,N,K,plan", [
+    (768, 11008, 6144, 3 | 3 << 8 | 1 << 24),      # mixed: 120 tiles in 2 K slices, the other 48 in 3
+    (2816, 3328, 8192, 3 | 4 << 8 | 1 << 24),      # mixed: 84 tiles in 3 K slices, the other 59 in 4
+    (1280, 3328, 4096, 3 | 3 << 8),                # uniform: every 256 x 256 tile in 3 K slices
+    (768, 1024, 8192, 2 | 8 << 8),                 # uniform on the 256 x 128 kernel: 8 K slices
+], ids=["mixed-sa2", "mixed-sa3", "uniform3", "uniform8-256x128"])
+def test_wgrad_mixed_split_k(ops, dev, M, N, K, plan):
+    """weight-gradient GEMM (TN, fp32, atomics) under the planner's split-K choice: mixed plans (some tiles cut into sa, the
+    others into sa + 1 K slices, 1-D grid, long slices first) for two different sa, and uniform plans; the plan word says which
+    ran.  Same result as fp64-accumulated matmul into a fresh output and with accumulate=True"""
+    from kalle_audio_amd import _lib
+    lib = _lib.load()
     dy = (_mk((K, M), dev, seed=150) * 0.5).bfloat16()
     x = (_mk((K, N), dev, seed=151) * 0.5).bfloat16()
-    ref = dy.float().T @ x.float()
+    ref = (dy.double().T @ x.double()).float()
     got = ops.gemm(dy, x, a_kmajor=True, b_kmajor=True, out_dtype=torch.float32)
+    assert lib.kalle_gemm_last_plan() == plan, hex(lib.kalle_gemm_last_plan())
     assert rel_l2(got, ref) < 2e-6, rel_l2(got, ref)
     acc = torch.ones(M, N, device=dev)
     ops.gemm(dy, x, a_kmajor=True, b_kmajor=True, out=acc, accumulate=True)
+    assert lib.kalle_gemm_last_plan() == plan, hex(lib.kalle_gemm_last_plan())
     assert rel_l2(acc, ref + 1.0) < 2e-6
 
 

@@ -1,5 +1,5 @@
 """the seven weight gradients of one bench-width TransformerBlock through kalle_gemm_wgrad_group at a given token count:
-python tools/wgrad_group_bench.py TOKENS [overwrite]   (KALLE_WGRAD_GROUP_PLAN="whole,slices" forces a plan, KALLE_GEMM_DEBUG=1 prints it)"""
+python tools/wgrad_group_bench.py TOKENS [overwrite]"""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from kalle_audio_amd import ops
@@ -21,4 +21,4 @@ for _ in range(10):
     ops.gemm_wgrad_group(probs, overwrite=over)
 e1.record(); torch.cuda.synchronize()
 ms = e0.elapsed_time(e1) / 10
-print(f"tokens {T} overwrite {int(over)} plan {os.environ.get('KALLE_WGRAD_GROUP_PLAN', 'auto')}: {ms*1e3:.0f} us {flops/ms/1e9:.0f} TFLOP/s", flush=True)
+print(f"tokens {T} overwrite {int(over)}: {ms*1e3:.0f} us {flops/ms/1e9:.0f} TFLOP/s", flush=True)
