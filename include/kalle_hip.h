@@ -170,7 +170,9 @@ int kalle_rmsnorm_bwd_acc(const void* dy, int dy_dtype, const void* x, int x_dty
  * kalle_attention_fwd; all multiples of 8); `heads` consecutive heads per row.  stat: fp32 [rows][heads][2], written by the
  * forward (mean | clamp flag, reciprocal std | reciprocal norm) and read by the backward.
  * Backward: g = gradient w.r.t. the normalised values (bf16, as kalle_attention_bwd leaves it), dx may alias g; mode 2 ADDS the
- * column sums into dgamma / dbeta (fp32 [64], atomics; either may be NULL). */
+ * column sums into dgamma / dbeta (fp32 [64], atomics; either may be NULL, independently of the other).  mode 1 with
+ * ||x|| <= 1e-12 (an all-zero head of a padded token): the clamp is active, y = x * 1e12 (= 0) and dx = g * 1e12, which is what
+ * autograd gives for F.normalize. */
 int kalle_head_norm_fwd(const void* x, int64_t ldx, int64_t x_off, void* y, int64_t ldy, int64_t y_off, float* stat,
                         const float* gamma, const float* beta, int mode, int64_t rows, int heads, void* stream);
 int kalle_head_norm_bwd(const void* x, int64_t ldx, int64_t x_off, const float* stat, const void* g, int64_t ldg,
@@ -453,7 +455,10 @@ int kalle_llama_decode_step(const kalle_llama_layer* layers, int n_layers, const
  * peak: one fp32 of device scratch that receives max|x|; x fp32 or bf16 */
 int kalle_peak_normalize_int16(const void* x, int dtype, float* peak, int16_t* out, int64_t n, void* stream);
 /* out[r, :] = audio[r, :] * audio_mask[r] + table[ids[r], :] * ids_mask[r]   (embed_tokens + masked mix, :66-73);
- * table fp32 [vocab][D], audio fp32 or bf16 [rows][D], masks fp32 [rows], out fp32 */
+ * table fp32 [vocab][D], audio fp32 or bf16 [rows][D], masks fp32 [rows], out fp32.  A row whose ids_mask is 0 contributes
+ * exactly 0 from the table and its id is NOT read as an index (padding ids such as -100 lie outside the table); a row whose
+ * audio_mask is 0 does not read its audio row (which may hold anything, NaN included).  Ids of rows that are read are clamped
+ * to [0, vocab).  D % 4 == 0. */
 int kalle_embed_mix_fwd(const int64_t* ids, const float* table, const void* audio, int audio_dtype, const float* ids_mask,
                         const float* audio_mask, float* out, int64_t rows, int D, int64_t vocab, void* stream);
 /* daudio = dout * audio_mask (if daudio); dtable[ids[r], :] += dout[r, :] * ids_mask[r] (if dtable; fp32 atomics) */

@@ -168,12 +168,23 @@ __global__ __launch_bounds__(256) void absmax_kernel(const void* __restrict__ x,
     if (threadIdx.x == 0)   // non-negative floats order like their bit patterns
         atomicMax(peak_bits, __float_as_uint(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]))));
 }
+// float quotient with one residual correction.  The library is built with -ffast-math, under which a / b (__fdiv_rn included, and a
+// double quotient narrowed back to float too) compiles to a * rcp(b) with a 1-ulp reciprocal: peak / peak can then be 1 - 2^-24 and the
+// loudest sample lands on 32766 instead of 32767.  q + (a - q b) / b with the residual in one fma is exact for a == b and within
+// half an ulp (+ 2^-46 relative) of a / b otherwise.
+__device__ __forceinline__ float div_refined(float a, float b) {
+    const float r = __builtin_amdgcn_rcpf(b);
+    const float q = a * r;
+    return __builtin_fmaf(__builtin_fmaf(-q, b, a), r, q);
+}
+
 template <bool F32>
 __global__ __launch_bounds__(256) void to_int16_kernel(const void* __restrict__ x, const unsigned* __restrict__ peak_bits,
                                                        int16_t* __restrict__ out, int64_t n) {
     const float peak = __uint_as_float(peak_bits[0]);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        float v = __fdiv_rn(F32 ? static_cast<const float*>(x)[i] : bf16_to_f32(static_cast<const bf16_t*>(x)[i]), peak);
+        const float v0 = div_refined(F32 ? static_cast<const float*>(x)[i] : bf16_to_f32(static_cast<const bf16_t*>(x)[i]), peak);
+        float v = v0;
         v = fminf(fmaxf(v, -1.f), 1.f) * 32767.f;
         out[i] = (int16_t)(int)v;
     }

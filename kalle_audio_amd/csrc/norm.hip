@@ -492,7 +492,7 @@ __global__ __launch_bounds__(256) void head_norm_bwd_kernel(const bf16_t* __rest
         }
         store8<false>(dx, row * lddx + h * DH + sub * 8, o);
     }
-    if (mode != 2 || !dgamma) return;
+    if (mode != 2 || (!dgamma && !dbeta)) return;      // (uniform over the workgroup: the barrier below is safe)
     // column sums of this workgroup: across the 64 / L groups of a wave by shuffles, across the 4 waves through LDS, one atomic
     // per column
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;

@@ -248,7 +248,7 @@ def test_hd64_entry_points_bit_identical(ops, dev, Nq, Nk, H, Hkv, rot, causal):
 
 
 # ------------------------------------------------------------------------------------------------ head norm
-@pytest.mark.parametrize("dh", [32, 128])
+@pytest.mark.parametrize("dh", [32, 64, 128])
 @pytest.mark.parametrize("mode", [1, 2])
 def test_head_norm_hd(ops, dev, dh, mode):
     rows, heads = 257, 3
