@@ -10,7 +10,7 @@
  * Conventions: plain device pointers + sizes, `stream` is a hipStream_t passed as void*, every call
  * is asynchronous on that stream, allocates nothing, and returns 0 on success or a negative KALLE_ERR_* code (never
  * throws).  Process state the library does keep: per-thread caches of GEMM split plans (pure functions of the shape), the
- * calling thread's last plan / last HIP error name (kalle_gemm_last_plan, kalle_last_error), a per-kernel per-device flag for
+ * calling thread's last plan / last HIP error name (kalle_gemm_last_plan, kalle_conv_last_plan, kalle_last_error), a per-kernel per-device flag for
  * the dynamic-LDS attribute.  The library reads no environment variables.  bf16 tensors are raw uint16 storage.
  */
 #ifndef KALLE_HIP_H
@@ -419,6 +419,19 @@ int kalle_conv_transpose1d_cfirst_fwd(const float* x_padded, const float* w_pack
 int kalle_conv_transpose1d_fwd(const void* x, int x_dtype, const float* w_packed, const float* bias, void* y,
                                int y_dtype, int B, int Cin, int Lin, int Cout, int Lout, int ksize, int stride,
                                int padding, const kalle_act* in_act, const kalle_conv_epilogue* epi, void* stream);
+/* which kernel the calling thread's most recent kalle_conv1d_fwd / kalle_conv_transpose1d_fwd / kalle_conv1d_cfirst_fwd /
+ * kalle_conv_transpose1d_cfirst_fwd / kalle_conv_wgrad launched; 0 when that call returned before launching anything.
+ *   bits 0-3 family: 1 conv1d_kernel (fallback), 2 conv1d_v2_kernel, 3 convT1d_kernel (fallback), 4 convT1d_v2_kernel,
+ *                    5 conv1d_cfirst_kernel stride 1, 6 the same strided (phase rows), 7 the same transposed,
+ *                    8 conv_wgrad_lds_kernel, 9 conv_wgrad_kernel (per-lane loads)
+ *   bit 4 / bit 5:   x / y is fp32 (both set for the fp32-only families 5-9)
+ *   families 2, 4:   bits 8-12 COW (output channels per wave), 13-16 LPT (positions per lane), 17-20 WCO (waves along the
+ *                    channels), 21-24 NW (waves per workgroup), 25-27 log2(CI / 8) (input-channel chunk 8 / 16 / 32),
+ *                    28-30 log2(stride) (the de-interleaved stride 2 / 4 / 8 forms of family 2)
+ *   families 5-7:    bits 8-11 split (waves that share a position tile's input channels: 1 / 2 / 4), bits 12-16 ks (workgroup-level
+ *                    input-channel split; > 1 means cfirst_finish_kernel ran too)
+ *   family 8:        bits 8-12 TU, 13-17 KT;    family 9: bits 8-12 TU, 13-17 TV, 18-22 KM */
+int kalle_conv_last_plan(void);
 /* ------------------------------------------------------------------------------------------------
  * Llasa task model head / tail (model_sigmaVAE.py:53-104); the Llama decoder layers in between run on kalle_gemm_bf16,
  * kalle_rmsnorm_*, kalle_attention_* (causal, rot = 64, GQA).

@@ -1003,12 +1003,24 @@ TileChoice pick_tile(int64_t npos, int Cout, int B, int halo, int span, int lpt_
     return best;
 }
 constexpr int V2_SPAN = 640;
+// kalle_conv_last_plan (encoding: include/kalle_hip.h)
+thread_local int g_conv_plan = 0;
+constexpr int ilog2(int v) { return v <= 1 ? 0 : 1 + ilog2(v >> 1); }
+constexpr int plan_dtypes(bool xf, bool yf) { return (xf ? 1 << 4 : 0) | (yf ? 1 << 5 : 0); }
+constexpr int plan_v2(int family, int cow, int lpt, int wco, int nw, int ci) {
+    return family | cow << 8 | lpt << 13 | wco << 17 | nw << 21 | ilog2(ci / 8) << 25;
+}
 }  // namespace
+
+extern "C" int kalle_conv_last_plan(void) { return g_conv_plan; }
+// library-internal (conv1d_bwd.hip records its launches through it): not part of the ABI, not exported
+extern "C" __attribute__((visibility("hidden"))) void kalle_set_conv_plan(int plan) { g_conv_plan = plan; }
 
 extern "C" int kalle_conv1d_fwd(const void* x, int x_dtype, const float* w_packed, const float* bias, void* y,
                                 int y_dtype, int B, int Cin, int Lin, int Cout, int Lout, int ksize, int stride,
                                 int padding, int dilation, const kalle_act* in_act, const kalle_conv_epilogue* epi,
                                 void* stream) {
+    g_conv_plan = 0;
     if (!x || !w_packed || !y || B <= 0 || Cin <= 0 || Cout <= 0 || Lin <= 0 || Lout <= 0) return KALLE_ERR_ARG;
     if (ksize <= 0 || ksize > MAX_K || stride <= 0 || dilation <= 0 || padding < 0) return KALLE_ERR_ARG;
     // `padding` is the LEFT pad; the right pad is implied by Lout (symmetric, 'same' or causal alike): taps beyond Lin read 0
@@ -1032,6 +1044,7 @@ extern "C" int kalle_conv1d_fwd(const void* x, int x_dtype, const float* w_packe
         p.nco = (Cout + COW * WCO - 1) / (COW * WCO);                                                                   \
         if ((int64_t)p.ntile * p.nco > 0x7fffffff) return KALLE_ERR_ARG;                                                \
         dim3 g(p.ntile * p.nco, 1, B);                                                                                  \
+        g_conv_plan = plan_v2(2, COW, LPT, WCO, NW, CI) | plan_dtypes(xf, yf) | ilog2(stride) << 28;                    \
         if (xf)                                                                                                         \
             KALLE_LAUNCH((conv1d_v2_kernel<COW, LPT, WCO, CI, SPAN, true, true, NW>), g, dim3(64 * NW), 0, st, p);      \
         else                                                                                                            \
@@ -1073,6 +1086,7 @@ extern "C" int kalle_conv1d_fwd(const void* x, int x_dtype, const float* w_packe
     }
     if ((L_T - 1) * stride + halo + 1 > MAX_SPAN) return KALLE_ERR_UNSUPPORTED;
     dim3 grid((Lout + L_T - 1) / L_T, (Cout + CO_T - 1) / CO_T, B), block(256);
+    g_conv_plan = 1 | plan_dtypes(xf, yf);
     if (xf && yf) KALLE_LAUNCH((conv1d_kernel<true, true>), grid, block, 0, st, p);
     else if (xf) KALLE_LAUNCH((conv1d_kernel<true, false>), grid, block, 0, st, p);
     else if (yf) KALLE_LAUNCH((conv1d_kernel<false, true>), grid, block, 0, st, p);
@@ -1119,6 +1133,7 @@ extern "C" int kalle_conv_cfirst_ws_floats(int B, int Cin, int Cout, int Lout, i
 extern "C" int kalle_conv1d_cfirst_fwd(const float* x_padded, const float* w_packed, const float* bias, float* y, int B,
                                        int Cin, int Lp, int Cout, int Lout, int ksize, int stride, int padding,
                                        int dilation, const kalle_conv_epilogue* epi, float* workspace, void* stream) {
+    g_conv_plan = 0;
     if (!x_padded || !w_packed || !y || B <= 0 || Cin <= 0 || Cout <= 0 || Lout <= 0 || ksize <= 0 || dilation <= 0 ||
         stride <= 0 || padding < 0)
         return KALLE_ERR_ARG;
@@ -1142,6 +1157,7 @@ extern "C" int kalle_conv1d_cfirst_fwd(const float* x_padded, const float* w_pac
     const int tiles_per_wg = 4 / split;
     if ((int64_t)B * ks > 65535) return KALLE_ERR_ARG;
     dim3 grid(((Lout + 15) / 16 + tiles_per_wg - 1) / tiles_per_wg, (Cout + 255) / 256, B * ks);
+    g_conv_plan = (stride > 1 ? 6 : 5) | plan_dtypes(true, true) | split << 8 | ks << 12;
     KALLE_LAUNCH(conv1d_cfirst_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), p);
     if (ks > 1) {
         const int64_t n = (int64_t)B * Cout * Lout;
@@ -1159,6 +1175,7 @@ extern "C" int kalle_convT_pad_len(int Lout, int ksize, int stride, int padding)
 extern "C" int kalle_conv_transpose1d_cfirst_fwd(const float* x_padded, const float* w_packed, const float* bias, float* y,
                                                  int B, int Cin, int Lp, int Cout, int Lout, int ksize, int stride,
                                                  int padding, const kalle_conv_epilogue* epi, void* stream) {
+    g_conv_plan = 0;
     if (!x_padded || !w_packed || !y || B <= 0 || Cin <= 0 || Cout <= 0 || Lout <= 0 || ksize <= 0 || stride <= 0 ||
         padding < 0)
         return KALLE_ERR_ARG;
@@ -1177,6 +1194,7 @@ extern "C" int kalle_conv_transpose1d_cfirst_fwd(const float* x_padded, const fl
     const int64_t gx = (int64_t)(((nq + 15) / 16 + tiles_per_wg - 1) / tiles_per_wg) * stride;
     if (gx > 0x7fffffff) return KALLE_ERR_ARG;
     dim3 grid((unsigned)gx, (Cout + 255) / 256, B);
+    g_conv_plan = 7 | plan_dtypes(true, true) | split << 8 | 1 << 12;
     KALLE_LAUNCH(conv1d_cfirst_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), p);
     return kalle_check_launch();
 }
@@ -1185,6 +1203,7 @@ extern "C" int kalle_conv_transpose1d_fwd(const void* x, int x_dtype, const floa
                                           int y_dtype, int B, int Cin, int Lin, int Cout, int Lout, int ksize,
                                           int stride, int padding, const kalle_act* in_act,
                                           const kalle_conv_epilogue* epi, void* stream) {
+    g_conv_plan = 0;
     if (!x || !w_packed || !y || B <= 0 || Cin <= 0 || Cout <= 0 || Lin <= 0 || Lout <= 0) return KALLE_ERR_ARG;
     if (ksize <= 0 || stride <= 0 || padding < 0) return KALLE_ERR_ARG;
     // shorter than (Lin-1)*stride - 2*padding + K = causal trim of the tail; up to `padding` longer = the outputs the symmetric
@@ -1209,6 +1228,7 @@ extern "C" int kalle_conv_transpose1d_fwd(const void* x, int x_dtype, const floa
         const int64_t nwg = (((int64_t)p.ntile * p.nco + 7) / 8) * 8 * stride;                                          \
         if (nwg > 0x7fffffff) return KALLE_ERR_ARG;                                                                     \
         dim3 g((unsigned)nwg, 1, B);                                                                                    \
+        g_conv_plan = plan_v2(4, COW, LPT, WCO, 4, 8) | plan_dtypes(xf, yf);                                            \
         if (xf) KALLE_LAUNCH((convT1d_v2_kernel<COW, LPT, WCO, 8, 640, true, true>), g, dim3(256), 0, st, p);           \
         else KALLE_LAUNCH((convT1d_v2_kernel<COW, LPT, WCO, 8, 640, false, false>), g, dim3(256), 0, st, p);            \
         return kalle_check_launch();                                                                                    \
@@ -1231,6 +1251,7 @@ extern "C" int kalle_conv_transpose1d_fwd(const void* x, int x_dtype, const floa
     if (ksize > MAX_K + 2 || ksize > 2 * stride + 1 || p.res || p.post || p.pact || p.y_raw || p.out_scale != 1.f)
         return KALLE_ERR_UNSUPPORTED;
     dim3 grid((Lout + L_T - 1) / L_T, (Cout + CO_T - 1) / CO_T, B), block(256);
+    g_conv_plan = 3 | plan_dtypes(xf, yf);
     if (xf && yf) KALLE_LAUNCH((convT1d_kernel<true, true>), grid, block, 0, st, p);
     else if (xf) KALLE_LAUNCH((convT1d_kernel<true, false>), grid, block, 0, st, p);
     else if (yf) KALLE_LAUNCH((convT1d_kernel<false, true>), grid, block, 0, st, p);

@@ -331,8 +331,11 @@ __global__ __launch_bounds__(256) void wn_bwd_kernel(const float* __restrict__ d
 
 }  // namespace
 
+extern "C" __attribute__((visibility("hidden"))) void kalle_set_conv_plan(int plan);   // conv1d.hip: the thread's kalle_conv_last_plan word
+
 extern "C" int kalle_conv_wgrad(const float* U, const float* V, float* dW, int B, int CU, int CV, int MU, int LV, int ksize,
                                 int stride, int padding, int dilation, int act_on, const kalle_act* act, void* stream) {
+    kalle_set_conv_plan(0);
     if (!U || !V || !dW || B <= 0 || CU <= 0 || CV <= 0 || MU <= 0 || LV <= 0) return KALLE_ERR_ARG;
     if (ksize <= 0 || ksize > 16 || stride <= 0 || dilation <= 0 || padding < 0 || (act_on != 0 && act_on != 1)) return KALLE_ERR_ARG;
     int code = 0, logscale = 0;
@@ -360,6 +363,7 @@ extern "C" int kalle_conv_wgrad(const float* U, const float* V, float* dW, int B
             const int chunks = (MU + per_wg - 1) / per_wg;
             if ((int64_t)chunks * B > 0x7fffffff) return KALLE_ERR_ARG;
             const int lds = std::max(rows * 65 * 4, 4 * 64 * KT * 4);
+            kalle_set_conv_plan(8 | 3 << 4 | TU << 8 | KT << 13);
             KALLE_LAUNCH((conv_wgrad_lds_kernel<TU, KT>), dim3(chunks * B, ty, tz), dim3(256), lds, st, U, V, dW, CU, CV, MU, LV,
                          stride, padding, dilation, code, al, be, logscale, chunks, per_wg, P, rows);
             return kalle_check_launch();
@@ -387,6 +391,7 @@ extern "C" int kalle_conv_wgrad(const float* U, const float* V, float* dW, int B
         chunks = chunks < 1 ? 1 : (chunks > max_chunks ? max_chunks : chunks);
         const int64_t per_wg = ((total + chunks - 1) / chunks + 255) / 256 * 256;
         const int gx = (int)((total + per_wg - 1) / per_wg);
+        kalle_set_conv_plan(9 | 3 << 4 | TU << 8 | TV << 13 | KM << 18);
         KALLE_LAUNCH((conv_wgrad_kernel<TU, TV, KM>), dim3(gx, ty, tz), dim3(256), 0, st, U, V, dW, B, CU, CV, MU, LV, ksize,
                      stride, padding, dilation, act_on, code, al, be, logscale, per_wg);
         return kalle_check_launch();

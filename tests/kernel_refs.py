@@ -337,3 +337,231 @@ def peak_normalize(x):
     """clamp(x / max|x|, -1, 1) * 32767 BEFORE the truncation to int16; returns (that, max|x|)"""
     peak = x.abs().max()
     return (x / peak).clamp(-1, 1) * 32767, peak
+
+
+# ------------------------------------------------------------------------------------------------ VAE conv stack
+# Written from the header text of the conv section of include/kalle_hip.h as explicit sums over taps on shifted slices (one
+# einsum per tap), never by calling F.conv1d: tests/test_conv_refs_cpu.py checks them against torch.nn.functional, torch's
+# weight_norm parametrisation and float64 autograd.  Activations are (B, C, L); `w` is the packed [Cin][K][CoutP] weight.
+def weight_norm_fold(v, g, transposed):
+    """flags bit 0: v is [Cin][Cout][K] (ConvTranspose1d) instead of [Cout][Cin][K]; bit 1: tap k is stored at K-1-k.
+    w[ci][k][co] = g[o] v[o][.][k] / ||v[o]||, o = the index of dim 0 (g None: repack only); CoutP = Cout rounded up to 8,
+    pad columns 0"""
+    d0, d1, K = v.shape
+    w = v if g is None else v * (g / v.reshape(d0, -1).pow(2).sum(1).sqrt())[:, None, None]
+    if transposed & 2:
+        w = w.flip(2)
+    w = w.permute(0, 2, 1) if transposed & 1 else w.permute(1, 2, 0)          # -> [Cin][K][Cout]
+    cout = w.shape[2]
+    out = torch.zeros((w.shape[0], K, (cout + 7) // 8 * 8), dtype=torch.float64, device=v.device)
+    out[:, :, :cout] = w
+    return out
+
+
+def _act_ab(alpha, beta, logscale):
+    a, b = alpha.double(), beta.double()
+    return (a.exp(), b.exp()) if logscale else (a, b)
+
+
+def act(x, code, alpha=None, beta=None, logscale=0, param=0.0):
+    """kalle_act on (B, C, L): 0 none, 1 x + sin^2(a x) / (b + 1e-9) per channel (a, b = exp(alpha), exp(beta) when logscale),
+    2 ELU, 3 LeakyReLU(param), 4 WaveNet gate tanh(x[:, :C/2]) * sigmoid(x[:, C/2:])"""
+    if code == 0:
+        return x
+    if code == 1:
+        a, b = _act_ab(alpha, beta, logscale)
+        return x + torch.sin(x * a[None, :, None]).pow(2) / (b[None, :, None] + 1e-9)
+    if code == 2:
+        return torch.where(x > 0, x, torch.expm1(x.clamp_max(0)))
+    if code == 3:
+        return torch.where(x > 0, x, x * param)
+    if code == 4:
+        h = x.shape[1] // 2
+        return torch.tanh(x[:, :h]) * sigmoid(x[:, h:])
+    raise ValueError(code)
+
+
+def snake_beta(x, alpha, beta, logscale):
+    """kalle_snake_beta_fwd"""
+    return act(x, 1, alpha, beta, logscale)
+
+
+def _epilogue(conv, asum, w_cout, bias, ep):
+    """(conv + bias + residual) * out_scale; += y (accumulate); y_raw = that; post_act; tanh.  ep: dict with the optional keys
+    residual, out_scale, accumulate (the previous contents of y), post (code, alpha, beta, logscale, param), tanh.
+    Returns (y, y_raw, abs_sum = the sum of the magnitudes of all terms that were added)"""
+    ep = ep or {}
+    v, a = conv, asum
+    if bias is not None:
+        v, a = v + bias[None, :, None], a + bias.abs()[None, :, None]
+    if ep.get("residual") is not None:
+        v, a = v + ep["residual"], a + ep["residual"].abs()
+    s = ep.get("out_scale", 1.0)
+    v, a = v * s, a * abs(s)
+    if ep.get("accumulate") is not None:
+        v, a = v + ep["accumulate"], a + ep["accumulate"].abs()
+    raw = v
+    if ep.get("post"):
+        v = act(v, *ep["post"])
+    if ep.get("tanh"):
+        v = torch.tanh(v)
+    return v, raw, a
+
+
+def conv1d(x, w, Cout, bias=None, stride=1, padding=0, dilation=1, Lout=None, in_act=None, epilogue=None, tap_shift=None):
+    """y[b][co][l] = sum_{ci, k} w[ci][k][co] act(x)[b][ci][l stride - padding + k dilation] (0 outside 0 <= . < Lin): `padding`
+    is the LEFT pad, the right pad is whatever Lout implies.  in_act: (code, alpha, beta, logscale, param).
+    tap_shift (k, s, lmax): the WRONG conv whose tap k reads one position + s for outputs l < lmax (tests that must fail).
+    Returns (y, y_raw, abs_sum)"""
+    xa = act(x, *in_act) if in_act else x
+    B, Cin, Lin = xa.shape
+    K = w.shape[1]
+    conv = torch.zeros((B, Cout, Lout), dtype=torch.float64, device=x.device)
+    asum = torch.zeros_like(conv)
+    for k in range(K):
+        segs = [(0, Lout, 0)]
+        if tap_shift is not None and tap_shift[0] == k:
+            segs = [(0, min(tap_shift[2], Lout), tap_shift[1]), (min(tap_shift[2], Lout), Lout, 0)]
+        for s0, s1, sh in segs:
+            # outputs l in [s0, s1) whose input position i = l stride + o lies in [0, Lin)
+            o = k * dilation - padding + sh
+            lo = max(s0, -(o // stride) if o < 0 else 0)
+            hi = min(s1, (Lin - 1 - o) // stride + 1 if Lin - 1 - o >= 0 else 0)
+            if hi <= lo:
+                continue
+            xs = xa[:, :, lo * stride + o:(hi - 1) * stride + o + 1:stride]
+            conv[:, :, lo:hi] += torch.einsum("bil,io->bol", xs, w[:, k, :Cout])
+            asum[:, :, lo:hi] += torch.einsum("bil,io->bol", xs.abs(), w[:, k, :Cout].abs())
+    return _epilogue(conv, asum, Cout, bias, epilogue)
+
+
+def conv_transpose1d(x, w, Cout, bias=None, stride=1, padding=0, Lout=None, in_act=None, epilogue=None, drop_last_tap_from=None):
+    """y[b][co][lo] = sum_{ci, k, li : li stride - padding + k = lo} w[ci][k][co] act(x)[b][ci][li], for any
+    0 < Lout <= (Lin - 1) stride - padding + K (the full length minus the LEFT trim only).
+    drop_last_tap_from: the WRONG conv without tap K-1 for outputs lo >= that (tests that must fail).
+    Returns (y, y_raw, abs_sum)"""
+    xa = act(x, *in_act) if in_act else x
+    B, Cin, Lin = xa.shape
+    K = w.shape[1]
+    full = (Lin - 1) * stride + K
+    conv = torch.zeros((B, Cout, full), dtype=torch.float64, device=x.device)
+    asum = torch.zeros_like(conv)
+    for k in range(K):
+        t = torch.einsum("bil,io->bol", xa, w[:, k, :Cout])
+        ta = torch.einsum("bil,io->bol", xa.abs(), w[:, k, :Cout].abs())
+        if drop_last_tap_from is not None and k == K - 1:
+            pos = torch.arange(Lin, device=x.device) * stride + k - padding
+            t, ta = t * (pos < drop_last_tap_from), ta * (pos < drop_last_tap_from)
+        conv[:, :, k:k + (Lin - 1) * stride + 1:stride] += t
+        asum[:, :, k:k + (Lin - 1) * stride + 1:stride] += ta
+    assert 0 < Lout <= full - padding
+    return _epilogue(conv[:, :, padding:padding + Lout], asum[:, :, padding:padding + Lout], Cout, bias, epilogue)
+
+
+def conv_pad_act(x, Lp, padding, act_args=None, phases=1):
+    """x_padded [B][C][Lp]: padded index j holds act(x)[j - padding] (0 outside 0 <= . < Lin); with phases > 1 padded index j
+    is stored at slot (j % phases) * (Lp / phases) + j / phases (phase rows)"""
+    xa = act(x, *act_args) if act_args else x
+    B, C, Lin = xa.shape
+    xp = torch.zeros((B, C, Lp), dtype=torch.float64, device=x.device)
+    n = min(Lin, Lp - padding)
+    if n > 0:
+        xp[:, :, padding:padding + n] = xa[:, :, :n]
+    if phases > 1:
+        xp = xp.view(B, C, Lp // phases, phases).transpose(2, 3).reshape(B, C, Lp)
+    return xp
+
+
+def conv_wgrad(U, V, K, stride, padding, dilation, act_on=0, act_args=None):
+    """dW[cu][cv][k] = sum_{b, m} U[b][cu][m] V[b][cv][m stride - padding + k dilation] (0 outside V), the activation applied
+    to V (act_on 0) or U (act_on 1) first.  Returns (dW, abs_sum)"""
+    if act_args:
+        U, V = (U, act(V, *act_args)) if act_on == 0 else (act(U, *act_args), V)
+    B, CU, MU = U.shape
+    LV = V.shape[2]
+    dW = torch.zeros((CU, V.shape[1], K), dtype=torch.float64, device=U.device)
+    asum = torch.zeros_like(dW)
+    for k in range(K):
+        o = k * dilation - padding
+        lo = -(o // stride) if o < 0 else 0
+        hi = min(MU, (LV - 1 - o) // stride + 1 if LV - 1 - o >= 0 else 0)
+        if hi <= lo:
+            continue
+        vs = V[:, :, lo * stride + o:(hi - 1) * stride + o + 1:stride]
+        dW[:, :, k] = torch.einsum("bum,bvm->uv", U[:, :, lo:hi], vs)
+        asum[:, :, k] = torch.einsum("bum,bvm->uv", U[:, :, lo:hi].abs(), vs.abs())
+    return dW, asum
+
+
+def act_bwd(x, g, code, alpha=None, beta=None, logscale=0):
+    """closed form of dx = g act'(x) for codes 0 / 1 / 2; the snake also returns d alpha, d beta [C] (through the exp when
+    logscale): d/da = x sin(2 a x) / (b + 1e-9), d/db = -sin^2(a x) / (b + 1e-9)^2.  Returns (dx, dalpha, dbeta, abs terms of the
+    two channel sums)"""
+    if code == 0:
+        return g, None, None, None
+    if code == 2:
+        return g * torch.where(x > 0, torch.ones_like(x), torch.exp(x.clamp_max(0))), None, None, None
+    a, b = _act_ab(alpha, beta, logscale)
+    a3, b3 = a[None, :, None], b[None, :, None] + 1e-9
+    s2 = torch.sin(2 * a3 * x)
+    dx = g * (1 + a3 * s2 / b3)
+    ta = g * x * s2 / b3
+    tb = -g * torch.sin(a3 * x).pow(2) / b3.pow(2)
+    if logscale:
+        ta, tb = ta * a3, tb * b[None, :, None]
+    return dx, ta.sum((0, 2)), tb.sum((0, 2)), (ta.abs().sum((0, 2)), tb.abs().sum((0, 2)))
+
+
+def tanh_bwd(dy, y):
+    return dy * (1 - y * y)
+
+
+def upsample_nearest(x, scale, backward=False):
+    """[rows][L] -> [rows][L scale], y[r][l] = x[r][l // scale]; backward: dx[r][m] = sum_{j < scale} dy[r][m scale + j]"""
+    if backward:
+        return x.view(x.shape[0], -1, scale).sum(-1)
+    return x[:, :, None].expand(-1, -1, scale).reshape(x.shape[0], -1)
+
+
+def channel_sum(x):
+    return x.sum((0, 2))
+
+
+def weight_norm_bwd(dw, v, g):
+    """closed form for w = g v / ||v|| per slice of dim 0: dg = <dw, v> / ||v||, dv = g / ||v|| (dw - v <dw, v> / ||v||^2)"""
+    d0 = v.shape[0]
+    v2, dw2 = v.reshape(d0, -1), dw.reshape(d0, -1)
+    nn = v2.pow(2).sum(1)
+    dot = (dw2 * v2).sum(1)
+    dv = (g / nn.sqrt())[:, None] * (dw2 - v2 * (dot / nn)[:, None])
+    return dv.view_as(v), dot / nn.sqrt()
+
+
+def act1d_up(x, filt):
+    """2x up-sampling of Activation1d: replicate pad 5, zero-stuffed 12-tap FIR, gain 2, crop 15 each side -> [B][C][2 L]"""
+    B, C, L = x.shape
+    xp = torch.cat([x[:, :, :1].expand(-1, -1, 5), x, x[:, :, -1:].expand(-1, -1, 5)], 2)
+    full = torch.zeros((B, C, 2 * (L + 10 - 1) + 12), dtype=torch.float64, device=x.device)
+    for k in range(12):
+        full[:, :, k:k + 2 * (L + 9) + 1:2] += 2 * filt[k] * xp
+    up = full[:, :, 15:full.shape[2] - 15]
+    assert up.shape[2] == 2 * L
+    return up
+
+
+def act1d_down(h, filt):
+    """2x down-sampling of Activation1d: replicate pad (5, 6), 12-tap FIR, stride 2 -> [B][C][L]"""
+    B, C, L2 = h.shape
+    L = L2 // 2
+    hp = torch.cat([h[:, :, :1].expand(-1, -1, 5), h, h[:, :, -1:].expand(-1, -1, 6)], 2)
+    y = torch.zeros((B, C, L), dtype=torch.float64, device=h.device)
+    for k in range(12):
+        y += filt[k] * hp[:, :, k:k + 2 * (L - 1) + 1:2]
+    return y
+
+
+def act1d(x, filt, alpha=None, beta=None, logscale=0):
+    """Activation1d: act1d_up -> snake (ELU when alpha is None) -> act1d_down"""
+    up = act1d_up(x, filt)
+    h = act(up, 2) if alpha is None else act(up, 1, alpha, beta, logscale)
+    return act1d_down(h, filt)

@@ -38,6 +38,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import kernel_refs as kr  # noqa: E402
+from gpu_checks import Guard, _bits, _exact, check  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
@@ -76,63 +77,7 @@ def _randn(shape, g, scale=1.0):
 
 
 def _check(out, ref, tol, what, key=None, unit=None):
-    """every element of `out` within `tol` of `ref` (NaN never passes); reports the count and the first offender"""
-    out = out.double()
-    if not torch.is_tensor(tol):
-        tol = torch.tensor(float(tol), dtype=torch.float64, device=ref.device)
-    tol = torch.broadcast_to(tol.double(), ref.shape)
-    if key is not None:
-        unit = torch.broadcast_to(torch.as_tensor(unit, dtype=torch.float64, device=ref.device), ref.shape)
-    assert out.shape == ref.shape, (what, out.shape, ref.shape)
-    w = ref.shape[-1] if ref.dim() >= 1 and ref.numel() else 1
-    out, ref, tol = out.reshape(-1, w), ref.reshape(-1, w), tol.reshape(-1, w)
-    err = (out - ref).abs()
-    if key is not None:
-        un = unit.reshape(-1, w)
-        ok = (un > 0) & ~torch.isnan(err)
-        if ok.any():
-            MEASURED[key] = max(MEASURED.get(key, 0.0), float((err[ok] / (U * un[ok])).max()))
-    bad = (err > tol) | torch.isnan(out)
-    if bad.any():
-        r, c = bad.nonzero()[0].tolist()
-        raise AssertionError(f"{what}: {int(bad.sum())} elements out of bound; first at (row {r}, col {c}): "
-                             f"out {out[r, c].item():.9g} ref {ref[r, c].item():.9g} tol {tol[r, c].item():.3g}")
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int16 if t.element_size() == 2 else torch.int32)
-
-
-def _exact(out, ref, what):
-    """bit for bit (NaN patterns compare equal to any NaN)"""
-    assert out.dtype == ref.dtype and out.shape == ref.shape, (what, out.dtype, ref.dtype, out.shape, ref.shape)
-    bad = (_bits(out) != _bits(ref)) & ~(torch.isnan(out) & torch.isnan(ref))
-    if bad.any():
-        i = bad.reshape(-1).nonzero()[0].item()
-        raise AssertionError(f"{what}: {int(bad.sum())} elements differ; first at flat index {i}: "
-                             f"out {out.reshape(-1)[i].item()!r} ref {ref.reshape(-1)[i].item()!r}")
-
-
-class Guard:
-    """a [rows + 2][ld] buffer of NaN (or of random contents inside the window when `init`) whose [:rows, :cols] window a call
-    may write: `.v` is the window, `.clean()` asserts that everything else is still NaN"""
-
-    def __init__(self, rows, cols, ld=None, dtype=torch.float32, init=None, extra=2):
-        ld = ld or cols
-        self.buf = torch.full((rows + extra, ld), NAN, device="cuda", dtype=dtype)
-        self.rows, self.cols = rows, cols
-        if init is not None:
-            self.buf[:rows, :cols] = init.to(dtype)
-        self.v = self.buf[:rows, :cols]
-
-    def clean(self, what):
-        m = torch.ones_like(self.buf, dtype=torch.bool)
-        m[:self.rows, :self.cols] = False
-        stray = ~torch.isnan(self.buf[m])
-        assert not stray.any(), (what, "stray writes", int(stray.sum()))
-
-    def untouched(self, what):
-        assert torch.isnan(self.buf).all(), (what, "output written by a rejected call")
+    return check(out, ref, tol, what, key, unit, MEASURED)
 
 
 def _nan_tail(t, extra=2):

@@ -1103,16 +1103,38 @@ def test_gemm_random_shapes_every_dispatch_path(dev):
 def test_conv_random_shapes_against_torch(dev):
     """seeded sweep over the conv kernels' dispatch (position-per-lane tiles of 2 / 8 / 16 channels, 8-wave tiles, channels-per-lane
     kernel with and without the input-channel split, strided and transposed forms): channel counts that are no multiple of the
-    tile widths, kernel sizes 1-16, dilations, strides, asymmetric padding, odd lengths - against torch's fp32 conv (1e-4)"""
+    tile widths, kernel sizes 1-16, dilations, strides, asymmetric padding, odd lengths - against torch's fp32 conv (1e-4).
+    kalle_conv_last_plan of every iteration is collected and the families named above must all have been seen: the 40 seeded
+    shapes stay below the ~6 M outputs at which pick_tile's cost model takes the 16-channel and 8-wave tiles, so three explicit
+    shapes follow them."""
     import torch.nn.functional as F
-    from kalle_audio_amd import conv_ops
+    from kalle_audio_amd import _lib, conv_ops
+    lib = _lib.load()
     rng = np.random.RandomState(77)
-    for it in range(40):
-        B = int(rng.choice([1, 2, 3]))
-        Cin = int(rng.choice([1, 2, 3, 8, 17, 32, 64, 130, 256, 520]))
-        Cout = int(rng.choice([1, 2, 6, 16, 17, 24, 64, 100, 256, 512]))
+    # (B, Cin, Cout, K, L): 16 x 8 x 4 tiles; 8-wave pointwise; 8-wave wide
+    explicit = [(3, 8, 64, 3, 32910), (1, 8, 272, 1, 21943), (2, 8, 272, 7, 21943)]
+    seen = set()
+    for it in range(40 + len(explicit)):
+        if it >= 40:
+            B, Cin, Cout = explicit[it - 40][:3]
+        else:
+            B = int(rng.choice([1, 2, 3]))
+            Cin = int(rng.choice([1, 2, 3, 8, 17, 32, 64, 130, 256, 520]))
+            Cout = int(rng.choice([1, 2, 6, 16, 17, 24, 64, 100, 256, 512]))
         g = torch.Generator().manual_seed(1000 + it)
-        if it % 4 == 3:                                   # transposed conv (decoder up-sampling): K = 2 s + s % 2, pad = ceil(s / 2)
+        if it >= 40:
+            stride, dil, (K, L) = 1, 1, explicit[it - 40][3:]
+            pad = pr = (K - 1) // 2
+            L += K - 1
+            x = torch.randn(B, Cin, L, generator=g).to(dev)
+            v = (torch.randn(Cout, Cin, K, generator=g) * 0.2).to(dev)
+            gg = (1 + 0.1 * torch.randn(Cout, generator=g)).to(dev)
+            bias = torch.randn(Cout, generator=g).to(dev)
+            w = gg.view(-1, 1, 1) * v / v.flatten(1).norm(dim=1).view(-1, 1, 1)
+            ref = F.conv1d(F.pad(F.elu(x), (pad, pr)), w, bias)
+            y = conv_ops.conv1d(x, conv_ops.weight_norm_fold(v, gg), bias, Cout=Cout, K=K, stride=1, padding=pad, dilation=1, act=2,
+                                pad_right=pr)
+        elif it % 4 == 3:                                   # transposed conv (decoder up-sampling): K = 2 s + s % 2, pad = ceil(s / 2)
             stride = int(rng.choice([2, 4, 5, 8]))
             K, pad = 2 * stride + stride % 2, (stride + 1) // 2
             L = int(rng.choice([5, 27, 130, 431]))
@@ -1142,6 +1164,16 @@ def test_conv_random_shapes_against_torch(dev):
                                 dilation=dil, act=2, pad_right=pr)
         assert y.shape == ref.shape, (it, y.shape, ref.shape)
         assert rel(y, ref) < 1e-4, (it, B, Cin, Cout, K, stride, rel(y, ref))
+        seen.add(lib.kalle_conv_last_plan())
+    fam = lambda p: p & 15                                                      # noqa: E731  (encoding: include/kalle_hip.h)
+    v2 = {p for p in seen if fam(p) in (2, 4)}
+    assert {2, 8, 16} <= {p >> 8 & 31 for p in v2}, sorted(map(hex, seen))      # tiles of 2 / 8 / 16 channels per wave
+    assert any(p >> 21 & 15 == 8 for p in v2), sorted(map(hex, seen))           # 8-wave tiles
+    cfirst = {p for p in seen if fam(p) in (5, 6, 7)}
+    assert {False, True} <= {(p >> 12 & 31) > 1 for p in cfirst}, sorted(map(hex, seen))    # with and without the input-channel split
+    assert any(fam(p) == 6 or (fam(p) == 2 and p >> 28 & 7) for p in seen)      # strided forms
+    assert {4, 7} <= {fam(p) for p in seen}, sorted(map(hex, seen))             # transposed: position-per-lane and channels-per-lane
+    assert 1 in {fam(p) for p in seen}                                          # the fallback kernel
 
 
 def test_attention_random_lengths_and_groups(dev):
