@@ -303,6 +303,14 @@ int kalle_fourier_features_bwd(const float* dout, const float* t, const float* w
  *   a KV cache needs (model_sigmaVAE.py:122-146 re-runs the prefix instead).
  * key_mask: uint8 [B][Nk] (1 = attend) or NULL.  lse: [B][H][Nq] fp32 saved for backward.  Head dim 64 here; the _hd
  * forms below take 32 and 128 too.
+ * A masked key has probability exactly 0 wherever its batch row has a live key (masked_fill(-finfo.max), transformer.py:446-462;
+ * the kernels fill with -1e30 in raw score units).  A batch row whose mask is all zero: the forward gives every key the same
+ * weight, out = mean_j v_j (what the fill gives the reference too; with causal != 0 as well such a row is not defined: -1e30 is
+ * also what a causally excluded key gets), and lse =
+ * -1e30 / sqrt(dh) from the tiled kernels, -1e30 from the single-query kernel (finite, otherwise meaningless).  The backward
+ * treats a masked key as absent: on every path dk and dv of a masked key are written as exact zeros, and in a fully masked
+ * batch row dq, dk and dv are all exact zeros (NOT the uniform-weight gradient dv = mean_i dout_i that autograd through the
+ * fill would give: such a row carries no signal); delta is written as rowsum(dout * out) there as everywhere.
  */
 int kalle_attention_fwd(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off,
                         const void* v, int64_t ldv, int v_off, void* out, int64_t ldo, float* lse,
@@ -333,6 +341,17 @@ int kalle_attention_bwd_hd(const void* q, int64_t ldq, int q_off, const void* k,
                            const float* lse, float* delta, void* dq, void* dk, void* dv,
                            const float* rope_cos, const float* rope_sin, int rot, const uint8_t* key_mask, int causal,
                            int B, int H, int Hkv, int Nq, int Nk, int head_dim, void* stream);
+/* which kernel family the calling thread's most recent kalle_attention_fwd / _bwd (_hd) launched; 0 when that call returned
+ * before launching anything.
+ *   bits 0-3   family: 1 fwd_tiled (attn_fwd_kernel), 2 fwd_decode (attn_decode_kernel: head dim 64, Nq == 1, Nk <= 15360),
+ *              3 bwd_two_pass (attn_bwd_kernel, dQ + delta then dK / dV), 4 bwd_fused (attn_bwd_fused_kernel: head dim 64, not
+ *              causal, H == Hkv, Nq, Nk <= 128), 5 bwd_fused_gqa (attn_bwd_fused_gqa_kernel: head dim 64, not causal, rot 0,
+ *              Nq <= 128, Nk - 128 <= min(16, 128 - Nq))
+ *   bit 4      direction: 0 forward, 1 backward
+ *   bits 8-15  head dim (32 / 64 / 128)
+ *   bit 16     family 1: the keys 128 .. Nk - 1 were folded into the first block (Nk in (128, 160], rot 0, not causal)
+ *   bits 17-23 family 2: the ROT instantiation (0 / 32 / 64) */
+int kalle_attn_last_plan(void);
 
 /* ------------------------------------------------------------------------------------------------
  * Optimizer: fused Adam / AdamW over a flat fp32 master buffer, also emitting the bf16 compute copy.

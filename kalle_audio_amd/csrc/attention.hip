@@ -271,6 +271,11 @@ struct AttnParams {
     bf16_t* dq; bf16_t* dk; bf16_t* dv;
     unsigned long long* stamps;   // diagnostics (kalle_attn_debug_stamps): [workgroup][8] s_memrealtime stamps of wave 0, or NULL
 };
+// the forward's folded tail (attn_fwd_kernel<1>; the host launches no other QT): the one rule, for the kernel and for the plan
+// word the host reports
+__host__ __device__ __forceinline__ bool attn_fold_tail(const AttnParams& p) {
+    return !p.causal && p.rot == 0 && p.Nk > 128 && p.Nk <= 160;
+}
 __device__ __forceinline__ void attn_stamp(const AttnParams& p, int tid, int idx) {
     if (p.stamps && tid == 0)
         p.stamps[((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * 8 + idx] = __builtin_amdgcn_s_memrealtime();
@@ -337,7 +342,7 @@ __global__ __launch_bounds__(128 / (16 * QT) * 64, DH == 128 ? 2 : QT == 1 ? 4 :
     // the staging code - barrier, global loads with nothing to hide their latency, barrier - 16 us of a 111-us call.  A tail of
     // up to 32 keys (no rotary, no causal mask) is fetched WITH the first block into its own small tiles instead and multiplied
     // right behind it: no further barrier, no exposed load.
-    const bool fold_tail = QT == 1 && !p.causal && p.rot == 0 && p.Nk > 128 && p.Nk <= 160;
+    const bool fold_tail = QT == 1 && attn_fold_tail(p);
     attn_stamp(p, tid, 0);
     const int hk = h / (p.H / p.Hkv);
 
@@ -1457,7 +1462,17 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(AttnParams p) {
     }
 }
 
+// kalle_attn_last_plan (encoding: include/kalle_hip.h)
+thread_local int g_attn_plan = 0;
+enum { PLAN_FWD_TILED = 1, PLAN_FWD_DECODE = 2, PLAN_BWD_TWO_PASS = 3, PLAN_BWD_FUSED = 4, PLAN_BWD_FUSED_GQA = 5 };
+constexpr int attn_plan(int family, int head_dim, bool fold_tail = false, int decode_rot = 0) {
+    return family | (family >= PLAN_BWD_TWO_PASS ? 1 << 4 : 0) | head_dim << 8 | (fold_tail ? 1 << 16 : 0) | decode_rot << 17;
+}
 }  // namespace
+
+extern "C" int kalle_attn_last_plan(void) { return g_attn_plan; }
+// library-internal, as kalle_set_conv_plan: not part of the ABI, not exported
+extern "C" __attribute__((visibility("hidden"))) void kalle_set_attn_plan(int plan) { g_attn_plan = plan; }
 
 static unsigned long long* g_attn_stamps = nullptr;      // diagnostics only
 extern "C" int kalle_attn_debug_stamps(void* buf) { g_attn_stamps = static_cast<unsigned long long*>(buf); return KALLE_OK; }
@@ -1469,6 +1484,7 @@ static int attention_fwd_dh(const AttnParams& p, hipStream_t st) {
     static std::atomic<uint64_t> lds_ok{0};
     kalle_allow_lds(reinterpret_cast<const void*>(attn_fwd_kernel<1, DH>), lds, lds_ok);
     KALLE_LAUNCH((attn_fwd_kernel<1, DH>), dim3((p.Nq + 127) / 128, p.H, p.B), dim3(512), lds, st, p);
+    kalle_set_attn_plan(attn_plan(PLAN_FWD_TILED, DH, attn_fold_tail(p)));
     return kalle_check_launch();
 }
 template <int DH>
@@ -1479,6 +1495,7 @@ static int attention_bwd_dh(const AttnParams& p, hipStream_t st) {
     kalle_allow_lds(reinterpret_cast<const void*>(attn_bwd_kernel<false, 1, DH>), lds, lds_ok_q);
     KALLE_LAUNCH((attn_bwd_kernel<false, 1, DH>), dim3((p.Nq + 127) / 128, p.H, p.B), dim3(512), lds, st, p);   // dQ + delta first
     KALLE_LAUNCH((attn_bwd_kernel<true, 1, DH>), dim3((p.Nk + 127) / 128, p.Hkv, p.B), dim3(512), lds, st, p);
+    kalle_set_attn_plan(attn_plan(PLAN_BWD_TWO_PASS, DH));
     return kalle_check_launch();
 }
 static bool check_head_dim(int head_dim, int rot) {
@@ -1489,6 +1506,7 @@ extern "C" int kalle_attention_fwd_hd(const void* q, int64_t ldq, int q_off, con
                                       const void* v, int64_t ldv, int v_off, void* out, int64_t ldo, float* lse,
                                       const float* rope_cos, const float* rope_sin, int rot, const uint8_t* key_mask,
                                       int causal, int B, int H, int Hkv, int Nq, int Nk, int head_dim, void* stream) {
+    kalle_set_attn_plan(0);
     if (!out || !check_common(q, ldq, q_off, k, ldk, k_off, v, ldv, v_off, ldo, rot, B, H, Hkv, Nq, Nk) ||
         !check_head_dim(head_dim, rot))
         return KALLE_ERR_ARG;
@@ -1511,6 +1529,7 @@ extern "C" int kalle_attention_fwd_hd(const void* q, int64_t ldq, int q_off, con
         if (rot == 64) KALLE_LAUNCH(attn_decode_kernel<64>, grid, block, (size_t)Nk * 4, st, p);
         else if (rot == 32) KALLE_LAUNCH(attn_decode_kernel<32>, grid, block, (size_t)Nk * 4, st, p);
         else KALLE_LAUNCH(attn_decode_kernel<0>, grid, block, (size_t)Nk * 4, st, p);
+        kalle_set_attn_plan(attn_plan(PLAN_FWD_DECODE, 64, false, rot));
         return kalle_check_launch();
     }
     constexpr int lds = 3 * AT_TILE + 160 * 4 + 2 * 32 * AT_STRIDE;     // Q | K | V tiles, key bias [128 + 32], folded tail tiles
@@ -1518,6 +1537,7 @@ extern "C" int kalle_attention_fwd_hd(const void* q, int64_t ldq, int q_off, con
     kalle_allow_lds(reinterpret_cast<const void*>(attn_fwd_kernel<1>), lds, lds_ok);
     dim3 grid((Nq + 127) / 128, H, B), block(512);
     KALLE_LAUNCH(attn_fwd_kernel<1>, grid, block, lds, static_cast<hipStream_t>(stream), p);
+    kalle_set_attn_plan(attn_plan(PLAN_FWD_TILED, 64, attn_fold_tail(p)));
     return kalle_check_launch();
 }
 
@@ -1526,6 +1546,7 @@ extern "C" int kalle_attention_bwd_hd(const void* q, int64_t ldq, int q_off, con
                                       int64_t ldo, const float* lse, float* delta, void* dq, void* dk, void* dv,
                                       const float* rope_cos, const float* rope_sin, int rot, const uint8_t* key_mask,
                                       int causal, int B, int H, int Hkv, int Nq, int Nk, int head_dim, void* stream) {
+    kalle_set_attn_plan(0);
     if (!out || !dout || !lse || !delta || !dq || !dk || !dv ||
         !check_common(q, ldq, q_off, k, ldk, k_off, v, ldv, v_off, ldo, rot, B, H, Hkv, Nq, Nk) ||
         !check_head_dim(head_dim, rot))
@@ -1553,6 +1574,7 @@ extern "C" int kalle_attention_bwd_hd(const void* q, int64_t ldq, int q_off, con
         static std::atomic<uint64_t> lds_ok_f{0};
         kalle_allow_lds(reinterpret_cast<const void*>(attn_bwd_fused_kernel), flds, lds_ok_f);
         KALLE_LAUNCH(attn_bwd_fused_kernel, dim3(1, H, B), dim3(512), flds, st, p);
+        kalle_set_attn_plan(attn_plan(PLAN_BWD_FUSED, 64));
         return kalle_check_launch();
     }
     // cross-attention of the DiT: several query heads per kv head and / or a few keys beyond one block, no rotary
@@ -1562,6 +1584,7 @@ extern "C" int kalle_attention_bwd_hd(const void* q, int64_t ldq, int q_off, con
         static std::atomic<uint64_t> lds_ok_g{0};
         kalle_allow_lds(reinterpret_cast<const void*>(attn_bwd_fused_gqa_kernel), flds, lds_ok_g);
         KALLE_LAUNCH(attn_bwd_fused_gqa_kernel, dim3(1, Hkv, B), dim3(512), flds, st, p);
+        kalle_set_attn_plan(attn_plan(PLAN_BWD_FUSED_GQA, 64));
         return kalle_check_launch();
     }
     constexpr int lds = 2 * AT_TILE + 256 * 4;
@@ -1571,6 +1594,7 @@ extern "C" int kalle_attention_bwd_hd(const void* q, int64_t ldq, int q_off, con
     // dQ first: it also produces delta, which the dK/dV kernel streams
     KALLE_LAUNCH((attn_bwd_kernel<false, 1>), dim3((Nq + 127) / 128, H, B), dim3(512), lds, st, p);
     KALLE_LAUNCH((attn_bwd_kernel<true, 1>), dim3((Nk + 127) / 128, Hkv, B), dim3(512), lds, st, p);
+    kalle_set_attn_plan(attn_plan(PLAN_BWD_TWO_PASS, 64));
     return kalle_check_launch();
 }
 

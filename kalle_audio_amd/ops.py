@@ -414,6 +414,11 @@ def attention_fwd(q, k, v, *, ldq, q_off, ldk, k_off, ldv, v_off, B, H, Hkv, Nq,
     return out, lse
 
 
+def attn_last_plan():
+    """the calling thread's kalle_attn_last_plan word (encoding: include/kalle_hip.h)"""
+    return _lib.load().kalle_attn_last_plan()
+
+
 def attention_bwd(q, k, v, out, dout, lse, dq, dk, dv, *, ldq, q_off, ldk, k_off, ldv, v_off, B, H, Hkv, Nq, Nk,
                   rope=None, key_mask=None, causal=False, dh=64):
     lib = _lib.load()

@@ -46,20 +46,20 @@ def _exact(out, ref, what):
 
 
 class Guard:
-    """a [rows + 2][ld] buffer of NaN (or of random contents inside the window when `init`) whose [:rows, :cols] window a call
-    may write: `.v` is the window, `.clean()` asserts that everything else is still NaN"""
+    """a [rows + 2][ld] buffer of NaN (or of random contents inside the window when `init`) whose [:rows, col0:col0 + cols]
+    window a call may write: `.v` is the window, `.clean()` asserts that everything else is still NaN"""
 
-    def __init__(self, rows, cols, ld=None, dtype=torch.float32, init=None, extra=2):
-        ld = ld or cols
+    def __init__(self, rows, cols, ld=None, dtype=torch.float32, init=None, extra=2, col0=0):
+        ld = ld or col0 + cols
         self.buf = torch.full((rows + extra, ld), NAN, device="cuda", dtype=dtype)
-        self.rows, self.cols = rows, cols
+        self.rows, self.cols, self.col0 = rows, cols, col0
         if init is not None:
-            self.buf[:rows, :cols] = init.to(dtype)
-        self.v = self.buf[:rows, :cols]
+            self.buf[:rows, col0:col0 + cols] = init.to(dtype)
+        self.v = self.buf[:rows, col0:col0 + cols]
 
     def clean(self, what):
         m = torch.ones_like(self.buf, dtype=torch.bool)
-        m[:self.rows, :self.cols] = False
+        m[:self.rows, self.col0:self.col0 + self.cols] = False
         stray = ~torch.isnan(self.buf[m])
         assert not stray.any(), (what, "stray writes", int(stray.sum()))
 

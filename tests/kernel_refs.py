@@ -1,4 +1,4 @@
-"""fp64 references of the norm / elementwise / Llasa-tail / conformer entry points of include/kalle_hip.h.
+"""fp64 references of the norm / elementwise / Llasa-tail / conformer / VAE-conv / attention entry points of include/kalle_hip.h.
 
 Plain torch functions on float64 tensors (any device), one per operation, written from the header comment of the entry
 point and the reference call sites it cites - not from the kernels.  Callers round whatever the kernel reads as bf16 with
@@ -565,3 +565,137 @@ def act1d(x, filt, alpha=None, beta=None, logscale=0):
     up = act1d_up(x, filt)
     h = act(up, 2) if alpha is None else act(up, 1, alpha, beta, logscale)
     return act1d_down(h, filt)
+
+
+# ------------------------------------------------------------------------------------------------ attention
+# kalle_attention_fwd / _bwd (_hd).  Operands are the head windows, already float64: q [B][Nq][H dh], k / v [B][Nk][Hkv dh],
+# cos / sin [positions][rot / 2], key_mask bool / uint8 [B][Nk] or None.  `round_points`: round to bf16 (nearest even) where the
+# kernels are documented to (the rotated q and k; in the backward also the P and dS operands of the gradient products, and
+# delta from the bf16 `out` the caller stored).  The forward's probabilities are never rounded here.  `wrong`: a deliberately wrong
+# variant, for the tests that show each would be caught.
+def _rotate(x, cos, sin, rot, pos, sign=1.0):
+    """rotate-half on the first `rot` dims of x [..][n][dh], row r at position pos[r]: x cos + cat(-x2, x1) sin"""
+    if not rot:
+        return x
+    h = rot // 2
+    c, s = cos[pos][:, :h], sign * sin[pos][:, :h]
+    x1, x2 = x[..., :h], x[..., h:rot]
+    return torch.cat([x1 * c - x2 * s, x2 * c + x1 * s, x[..., rot:]], -1)
+
+
+def _unrotate(g, cos, sin, rot, pos):
+    """the transpose of _rotate: what the gradient of the rotated tensor becomes for the tensor before rotation"""
+    if not rot:
+        return g
+    h = rot // 2
+    c, s = cos[pos][:, :h], sin[pos][:, :h]
+    g1, g2 = g[..., :h], g[..., h:rot]
+    return torch.cat([g1 * c + g2 * s, g2 * c - g1 * s, g[..., rot:]], -1)
+
+
+def _unrotate_abs(u, rot):
+    """a bound through _unrotate: |cos|, |sin| <= 1, so each rotated dim is bounded by the sum of the two partners' bounds"""
+    if not rot:
+        return u
+    h = rot // 2
+    t = u[..., :h] + u[..., h:rot]
+    return torch.cat([t, t, u[..., rot:]], -1)
+
+
+def _attn_core(q, k, v, H, Hkv, dh, rot, cos, sin, key_mask, causal, round_points, mask_fill, wrong):
+    B, Nq, Nk = q.shape[0], q.shape[1], k.shape[1]
+    group = H // Hkv
+    dev = q.device
+    hmap = torch.arange(H, device=dev) // group
+    if wrong == "gqa_modulo":
+        hmap = torch.arange(H, device=dev) % Hkv
+    off = Nk - Nq if causal else 0
+    qpos = torch.arange(Nq, device=dev) + off + (1 if wrong == "query_position" else 0)
+    kpos = torch.arange(Nk, device=dev)
+    sign = -1.0 if wrong == "rotate_half_sign" else 1.0
+    qh = _rotate(q.reshape(B, Nq, H, dh).transpose(1, 2), cos, sin, rot, qpos, sign)
+    kh = _rotate(k.reshape(B, Nk, Hkv, dh).transpose(1, 2), cos, sin, rot, kpos, sign)
+    vh = v.reshape(B, Nk, Hkv, dh).transpose(1, 2)
+    if round_points:
+        qh, kh = bf16r(qh), bf16r(kh)
+    scale = 0.125 if wrong == "scale_eighth" else dh ** -0.5
+    s = (qh @ kh[:, hmap].transpose(-1, -2)) * scale
+    if key_mask is not None:
+        m = key_mask.bool()
+        if wrong == "mask_other_batch":
+            m = m.flip(0)
+        fill = -torch.finfo(torch.float64).max if mask_fill is None else mask_fill
+        s = s.masked_fill(~m[:, None, None, :], fill)
+    if causal:
+        lim = torch.arange(Nq, device=dev)[:, None] + off - (1 if wrong == "causal_boundary" else 0)
+        s = s.masked_fill(kpos[None, :] > lim, -math.inf)
+    if isinstance(wrong, tuple) and wrong[0] == "drop_key":
+        s = s.clone()
+        s[..., wrong[1]] = -math.inf
+    lse = torch.logsumexp(s, -1)
+    p = torch.softmax(s, -1)          # (not exp(s - lse): the fill of a fully masked row absorbs log n)
+    return qh, kh, vh, hmap, scale, s, lse, p
+
+
+def attention_ref(q, k, v, H, Hkv, dh, rot=0, cos=None, sin=None, key_mask=None, causal=False, round_points=False,
+                  mask_fill=None, wrong=None):
+    """out [B][Nq][H dh], lse [B][H][Nq], p [B][H][Nq][Nk], rotated q [B][H][Nq][dh], rotated k [B][Hkv][Nk][dh]:
+    p = softmax_j(q~_i . k~_j dh^-0.5), head h reads kv head h // (H // Hkv), a query's rotary position is i + (Nk - Nq) when
+    causal and i otherwise, masked keys masked_fill(-finfo.max) (or `mask_fill`), causally excluded keys -inf"""
+    qh, kh, vh, hmap, scale, s, lse, p = _attn_core(q, k, v, H, Hkv, dh, rot, cos, sin, key_mask, causal, round_points, mask_fill, wrong)
+    out = (p @ vh[:, hmap]).transpose(1, 2).reshape(q.shape[0], q.shape[1], H * dh)
+    return out, lse, p, qh, kh
+
+
+def attention_fwd_units(p, qh, kh, v, out, lse, H, Hkv, dh):
+    """the magnitudes the forward's errors scale with: out sum_j p_ij |v_jd| + |out_id|; lse 1 + |lse| + sum_d |q~_id| max_j |k~_jd| dh^-0.5"""
+    B, Nq = out.shape[0], out.shape[1]
+    hmap = torch.arange(H, device=out.device) // (H // Hkv)
+    vh = v.reshape(B, -1, Hkv, dh).transpose(1, 2)
+    u_out = (p @ vh[:, hmap].abs()).transpose(1, 2).reshape(B, Nq, H * dh) + out.abs()
+    kmax = kh.abs().amax(-2)[:, hmap]                                      # [B][H][dh]
+    u_lse = 1 + lse.abs() + (qh.abs() * kmax[:, :, None, :]).sum(-1) * dh ** -0.5
+    return u_out, u_lse
+
+
+def attention_bwd_ref(q, k, v, dout, H, Hkv, dh, rot=0, cos=None, sin=None, key_mask=None, causal=False, round_points=False,
+                      out=None, masked_rows_zero=False, wrong=None):
+    """dq [B][Nq][H dh], dk, dv [B][Nk][Hkv dh], delta [B][H][Nq] and the per-element magnitudes {"dq", "dk", "dv"} their
+    errors scale with, as explicit sums (no autograd):
+      delta_i = sum_d dout_id out_id  (`out`: the stored output when given, else the exact one)
+      dv_jd = sum_{h in group} sum_i p_ij dout_id;  dP_ij = sum_d dout_id v_jd;  dS_ij = p_ij (dP_ij - delta_i) dh^-0.5
+      dq~_id = sum_j dS_ij k~_jd;  dk~_jd = sum_{h in group} sum_i dS_ij q~_id;  dq, dk = un-rotated dq~, dk~
+    `masked_rows_zero`: a masked key is absent (p = 0) even where every key of its batch row is masked - the header's
+    contract for the backward, where the fill of the forward would give uniform weights"""
+    B, Nq, Nk = q.shape[0], q.shape[1], k.shape[1]
+    group = H // Hkv
+    fwd_wrong = wrong if wrong in ("gqa_modulo", "query_position", "rotate_half_sign", "mask_other_batch", "scale_eighth",
+                                   "causal_boundary") or isinstance(wrong, tuple) else None
+    qh, kh, vh, hmap, scale, s, lse, p = _attn_core(q, k, v, H, Hkv, dh, rot, cos, sin, key_mask, causal, round_points, None, fwd_wrong)
+    if masked_rows_zero and key_mask is not None:
+        p = p * key_mask.bool()[:, None, None, :]
+    doh = dout.reshape(B, Nq, H, dh).transpose(1, 2)
+    oh = (p @ vh[:, hmap]) if out is None else out.reshape(B, Nq, H, dh).transpose(1, 2)
+    delta = (doh * (doh if wrong == "delta_dout_squared" else oh)).sum(-1)
+    dP = doh @ vh[:, hmap].transpose(-1, -2)
+    dS = p * (dP - delta[..., None]) * scale
+    pv = bf16r(p) if round_points else p
+    dSr = bf16r(dS) if round_points else dS
+    aS = p * (dP.abs() + (p * dP.abs()).sum(-1, keepdim=True)) * scale       # |dS| bounded term by term
+    heads = lambda t: t.reshape(B, Hkv, group, *t.shape[2:])  # noqa: E731
+    dvh = heads(pv.transpose(-1, -2) @ doh).sum(2)
+    a_dv = heads(p.transpose(-1, -2) @ doh.abs()).sum(2)
+    dkh = heads(dSr.transpose(-1, -2) @ qh)
+    a_dk = heads(aS.transpose(-1, -2) @ qh.abs()).sum(2)
+    dkh = dkh[:, :, 1:].sum(2) if wrong == "dk_missing_head" else dkh.sum(2)
+    dqh = dSr @ kh[:, hmap]
+    a_dq = aS @ kh[:, hmap].abs()
+    off = Nk - Nq if causal else 0
+    qpos, kpos = torch.arange(Nq, device=q.device) + off, torch.arange(Nk, device=q.device)
+    dq = dqh if wrong == "dq_not_unrotated" else _unrotate(dqh, cos, sin, rot, qpos)
+    dk = _unrotate(dkh, cos, sin, rot, kpos)
+    flat = lambda t, n, h: t.transpose(1, 2).reshape(B, n, h * dh)  # noqa: E731
+    dq, dk, dv = flat(dq, Nq, H), flat(dk, Nk, Hkv), flat(dvh, Nk, Hkv)
+    mags = {"dq": flat(_unrotate_abs(a_dq, rot), Nq, H) + dq.abs(), "dk": flat(_unrotate_abs(a_dk, rot), Nk, Hkv) + dk.abs(),
+            "dv": flat(a_dv, Nk, Hkv) + dv.abs()}
+    return dq, dk, dv, delta, mags

@@ -689,13 +689,17 @@ def test_single_query_attention_matches_tiled_kernel(ops, dev, Nk, rot, H, Hkv, 
         mask[:, -1] = True
     kw = dict(ldk=ld, k_off=Dq, ldv=ld, v_off=Dq + Dk, B=B, H=H, Hkv=Hkv, Nk=Nk, rope=rope, key_mask=mask, causal=True)
     full, lse_full = ops.attention_fwd(qkv, qkv, qkv, ldq=ld, q_off=0, Nq=Nk, **kw)
+    decode_plan = 2 | 64 << 8 | rot << 17          # kalle_attn_last_plan: the single-query kernel and its ROT instantiation
+    assert ops.attn_last_plan() == (decode_plan if Nk == 1 else 1 | 64 << 8), hex(ops.attn_last_plan())
     if Nk == 1:   # the tiled reference itself would take the single-query path: check against the value row instead
         want = qkv[:, :, Dq + Dk:].reshape(B, 1, Hkv, 64).repeat_interleave(H // Hkv, 2).reshape(B, 1, Dq)
         got, _ = ops.attention_fwd(qkv, qkv, qkv, ldq=ld, q_off=0, Nq=1, **kw)
+        assert ops.attn_last_plan() == decode_plan, hex(ops.attn_last_plan())
         assert rel_l2(got, want) < 1e-6
         return
     qlast = qkv[:, -1:, :Dq].contiguous()                               # [B, 1, Dq], ldq = Dq
     got, lse = ops.attention_fwd(qlast, qkv, qkv, ldq=Dq, q_off=0, Nq=1, **kw)
+    assert ops.attn_last_plan() == decode_plan, hex(ops.attn_last_plan())
     assert rel_l2(got, full[:, -1:]) < 4e-3, rel_l2(got, full[:, -1:])
     assert (lse[..., 0] - lse_full[..., -1]).abs().max() < 2e-3
 

@@ -388,6 +388,8 @@ def test_attention_forward_with_folded_tail_keys(dev, Nq, Nk, grp, masked_tail):
     ref = _attn_ref(q.float(), k, v, mask, None, H, Hkv)
     out, lse = ops.attention_fwd(q, kv, kv, ldq=D, q_off=0, ldk=2 * Dc, k_off=0, ldv=2 * Dc, v_off=Dc, B=B, H=H, Hkv=Hkv,
                                  Nq=Nq, Nk=Nk, key_mask=mask)
+    # kalle_attn_last_plan: the tiled forward at head dim 64, bit 16 = the tail was folded (161 keys: it was not)
+    assert ops.attn_last_plan() == (1 | 64 << 8 | (1 << 16 if Nk <= 160 else 0)), hex(ops.attn_last_plan())
     assert rel(out, ref) < 1e-2, rel(out, ref)
     qh = q.float().view(B, Nq, H, 64).transpose(1, 2)
     kh = k.reshape(B, Nk, Hkv, 64).transpose(1, 2).repeat_interleave(grp, dim=1)
