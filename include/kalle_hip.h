@@ -10,7 +10,7 @@
  * Conventions: plain device pointers + sizes, `stream` is a hipStream_t passed as void*, every call
  * is asynchronous on that stream, allocates nothing, and returns 0 on success or a negative KALLE_ERR_* code (never
  * throws).  Process state the library does keep: per-thread caches of GEMM split plans (pure functions of the shape), the
- * calling thread's last plan / last HIP error name (kalle_gemm_last_plan, kalle_conv_last_plan, kalle_last_error), a per-kernel per-device flag for
+ * calling thread's last plan / last HIP error name (kalle_gemm_last_plan, kalle_gemm_wgrad_group_last_plan, kalle_conv_last_plan, kalle_attn_last_plan, kalle_last_error), a per-kernel per-device flag for
  * the dynamic-LDS attribute.  The library reads no environment variables.  bf16 tensors are raw uint16 storage.
  */
 #ifndef KALLE_HIP_H
@@ -255,6 +255,22 @@ typedef struct kalle_wgrad_problem {
 /* overwrite != 0: dw_i = dy_i^T x_i instead (no clear needed: tiles that run whole store their result, the regions of the
  * tiles that are cut into token slices are cleared by a small launch first) */
 int kalle_gemm_wgrad_group(const kalle_wgrad_problem* problems, int nprob, int overwrite, void* stream);
+/* What the calling thread's most recent kalle_gemm_wgrad_group launched, as five ints (all 0 when that call returned before
+ * launching anything):
+ *   plan[0] tiles    256 x 256 output tiles of all problems: sum of ceil(N / 256) * ceil(K / 256)
+ *   plan[1] whole    tiles that ran over all tokens in one workgroup (read-add-store, or a plain store under `overwrite`): the
+ *                    first `whole` tiles in problem order; either all of them or a multiple of 256
+ *   plan[2] slices   token slices (atomic adds) per remaining tile, 2 .. 12; 0 when no tile is sliced.  A slice is
+ *                    ceil(ktiles / slices) 64-token K-tiles long, so the last one may be short and trailing ones empty
+ *   plan[3] cleared  1 when the clearing launch ran first (`overwrite` with sliced tiles)
+ *   plan[4] cached   1 when whole / slices were replayed from the thread's plan cache, which is keyed on every problem's
+ *                    (N, K, tokens / 1024): a plan found at one token count serves the others of its 1024-token bucket, with
+ *                    slices falling back to 0 (all tiles whole) where the shortest problem has fewer K-tiles than slices
+ * kalle_gemm_wgrad_group_plan is the same planner as a pure host query: same arguments (the pointers are only checked, never
+ * read), same return codes, `plan` filled as above for the launch that kalle_gemm_wgrad_group would make now on this thread;
+ * it launches nothing, needs no device and leaves the plan cache as it found it. */
+int kalle_gemm_wgrad_group_last_plan(int* plan);
+int kalle_gemm_wgrad_group_plan(const kalle_wgrad_problem* problems, int nprob, int overwrite, int* plan);
 
 /* Chunked VAE encode / decode (AudioAutoencoder.encode_audio / decode_audio, autoencoders.py:429-560) as a batched pipeline:
  * every chunk rides on the batch axis of ONE encoder / decoder pass; this call is the gather in front of it and the paste
@@ -469,7 +485,23 @@ int kalle_gemv_bf16(const void* x, const void* W, int64_t ldw, void* y, int y_dt
  *   layers: HOST array of n_layers descriptors; weights bf16 row-major ([out][in]; wqkv = [q;k;v], wug = [up;gate]),
  *           norm weights fp32 [D], kv_cache bf16 [cache_rows][2*Hkv*64] holding un-rotated k | v of positions < t0
  *   x: fp32 [D] input embedding of position t0; out: fp32 [D] residual stream after the last layer (final norm not applied)
- *   rope_cos / rope_sin: fp32 [>= t0+1][32]; workspace: kalle_llama_decode_ws_bytes(H, Hkv, inner) bytes, 64-byte aligned */
+ *   rope_cos / rope_sin: fp32 [>= t0+1][32]; workspace: kalle_llama_decode_ws_bytes(H, Hkv, inner) bytes, 64-byte aligned
+ *   H % Hkv == 0, inner % 8 == 0, 0 <= t0 < cache_rows, D = 64 H <= 32768, inner <= 32768 (a GEMV keeps its K-long bf16 operand in
+ *   LDS: 64 KiB at the bound); anything else, or a NULL field in a descriptor, returns KALLE_ERR_ARG.  Every launch is checked
+ *   where it is made: a refused launch returns KALLE_ERR_LAUNCH at once.
+ * Only row t0 of each cache is written (all 2*Hkv*64 of it); rows above t0 and rope rows above t0 are never read.
+ * The workspace is caller-owned and its layout is part of this contract (D = 64 H), in this order:
+ *   x2  fp32 [D]                         residual stream after the attention branch: x_in + Wo . ao
+ *   x3  fp32 [D]                         output of the layer before the last one = input of the last layer (n_layers >= 2;
+ *                                        a one-layer call does not touch it)
+ *   lse fp32 [H], padded to a multiple of 64 bytes (the padding is never written)
+ *   q   bf16 [D]                         bf16(Wq . bf16(rmsnorm(x_in)))            (un-rotated; k | v of the same GEMV are in cache row t0)
+ *   ao  bf16 [D]                         attention output
+ *   hf  bf16 [2*inner]                   up | gate = bf16(Wug . bf16(rmsnorm(x2)))
+ * After a call every region holds the LAST layer's values (x_in = x for one layer, x3 otherwise), so that each stage of a layer
+ * can be checked from that stage's own inputs; out = x2 + Wdown . bf16(up * silu(gate)).  bf16 rounding points of a layer: the
+ * two normalised activations, q | k | v, the rotated q and k and the probabilities inside the attention, ao, up | gate, and
+ * up * silu(gate); x2, x3 and out stay fp32. */
 typedef struct kalle_llama_layer {
     const float* input_norm;
     const void* wqkv;

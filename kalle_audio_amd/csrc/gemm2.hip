@@ -1637,11 +1637,18 @@ double replay_group(const GroupProblem* pr, int n, int unsplit_total, int splits
     }
     return r.makespan() + atomic_bytes / 2.0e12 * 1e6;
 }
-}  // namespace
 
-extern "C" int kalle_gemm_wgrad_group(const kalle_wgrad_problem* problems, int nprob, int overwrite, void* stream) {
+// what kalle_gemm_wgrad_group_last_plan / kalle_gemm_wgrad_group_plan report (the order of their `plan` array)
+struct GroupReport { int tiles, whole, slices, cleared, cached; };
+thread_local GroupReport g_group_report = {0, 0, 0, 0, 0};
+
+// Argument checks + plan of one kalle_gemm_wgrad_group call: fills `gp` (the launch parameters), `blocks` (the grid of
+// gemm3_wgrad_group_kernel) and `rep`.  The plan comes from the calling thread's cache when the key is there; a fresh one is
+// entered into it only with `remember` (the entry point; the host query leaves the cache as it found it).
+int plan_group(const kalle_wgrad_problem* problems, int nprob, int overwrite, bool remember, GroupParams& gp, int& blocks,
+               GroupReport& rep) {
     if (!problems || nprob <= 0 || nprob > KALLE_MAX_GROUP) return KALLE_ERR_ARG;
-    GroupParams gp{};
+    gp = GroupParams{};
     gp.nprob = nprob;
     gp.overwrite = overwrite ? 1 : 0;
     int ntot = 0, min_nk = 1 << 30;
@@ -1682,8 +1689,10 @@ extern "C" int kalle_gemm_wgrad_group(const kalle_wgrad_problem* problems, int n
             }
             if (ut == ntot) break;
         }
-        if (ncache < 16) cache[ncache++] = plan;
-        else { cache[victim] = plan; victim = (victim + 1) & 15; }
+        if (remember) {
+            if (ncache < 16) cache[ncache++] = plan;
+            else { cache[victim] = plan; victim = (victim + 1) & 15; }
+        }
     }
     if (min_nk / plan.splits < 1) plan.splits = 1;
     if (plan.splits == 1) plan.unsplit_total = ntot;
@@ -1704,14 +1713,48 @@ extern "C" int kalle_gemm_wgrad_group(const kalle_wgrad_problem* problems, int n
         q.r2_start = b2;
         b2 += (q.tiles_m * q.tiles_n - q.unsplit) * q.splits;
     }
-    if (gp.overwrite && ntot - b1 > 0 && plan.splits >= 1) {
+    blocks = b2;
+    rep = GroupReport{ntot, b1, ntot - b1 > 0 ? plan.splits : 0, gp.overwrite && ntot - b1 > 0 ? 1 : 0, hit ? 1 : 0};
+    return KALLE_OK;
+}
+
+void report_out(const GroupReport& r, int* plan) {
+    plan[0] = r.tiles; plan[1] = r.whole; plan[2] = r.slices; plan[3] = r.cleared; plan[4] = r.cached;
+}
+}  // namespace
+
+extern "C" int kalle_gemm_wgrad_group_last_plan(int* plan) {
+    if (!plan) return KALLE_ERR_ARG;
+    report_out(g_group_report, plan);
+    return KALLE_OK;
+}
+
+extern "C" int kalle_gemm_wgrad_group_plan(const kalle_wgrad_problem* problems, int nprob, int overwrite, int* plan) {
+    if (!plan) return KALLE_ERR_ARG;
+    GroupParams gp;
+    GroupReport rep;
+    int blocks = 0;
+    const int rc = plan_group(problems, nprob, overwrite, false, gp, blocks, rep);
+    if (rc == KALLE_OK) report_out(rep, plan);
+    return rc;
+}
+
+extern "C" int kalle_gemm_wgrad_group(const kalle_wgrad_problem* problems, int nprob, int overwrite, void* stream) {
+    g_group_report = GroupReport{0, 0, 0, 0, 0};
+    GroupParams gp;
+    GroupReport rep;
+    int blocks = 0;
+    const int rc = plan_group(problems, nprob, overwrite, true, gp, blocks, rep);
+    if (rc != KALLE_OK) return rc;
+    if (rep.cleared) {
         // (N % 4 == 0 is implied by N % 8 == 0: the clears are 16-byte stores)
-        KALLE_LAUNCH(gemm3_group_zero_kernel, dim3(4 * (ntot - b1)), dim3(256), 0, static_cast<hipStream_t>(stream), gp);
+        KALLE_LAUNCH(gemm3_group_zero_kernel, dim3(4 * (rep.tiles - rep.whole)), dim3(256), 0, static_cast<hipStream_t>(stream), gp);
         if (kalle_check_launch() != KALLE_OK) return KALLE_ERR_LAUNCH;
     }
+    g_group_report = rep;
     constexpr int lds = GEMM3_LDS;
     static std::atomic<uint64_t> lds_ok{0};
     kalle_allow_lds(reinterpret_cast<const void*>(gemm3_wgrad_group_kernel), lds, lds_ok);
-    KALLE_LAUNCH(gemm3_wgrad_group_kernel, dim3(b2), dim3(512), lds, static_cast<hipStream_t>(stream), gp);
+    KALLE_LAUNCH(gemm3_wgrad_group_kernel, dim3(blocks), dim3(512), lds, static_cast<hipStream_t>(stream), gp);
     return kalle_check_launch();
 }

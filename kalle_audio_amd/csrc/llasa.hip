@@ -429,17 +429,24 @@ extern "C" int kalle_llama_decode_step(const kalle_llama_layer* layers, int n_la
         if (!L.input_norm || !L.wqkv || !L.wo || !L.post_norm || !L.wug || !L.wdown || !L.kv_cache) return KALLE_ERR_ARG;
         bf16_t* kv_row = static_cast<bf16_t*>(L.kv_cache) + (int64_t)t0 * kvw;
         // q -> scratch, k | v -> cache row t0 (un-rotated: the attention kernel rotates by row index)
+        // (every launch is checked where it is made: KALLE_LAUNCH clears the error state, so a refused launch would otherwise be
+        // forgotten by the next one and the step would report success over an unwritten buffer)
         gemv_launch<false, PRO_RMS>(xin, L.input_norm, eps, L.wqkv, D, q, kv_row, D, nullptr, D + kvw, D, st);
-        int rc = kalle_attention_fwd(q, D, 0, L.kv_cache, kvw, 0, L.kv_cache, kvw, Hkv * 64, ao, D, lse, rope_cos, rope_sin,
+        int rc = kalle_check_launch();
+        if (rc != KALLE_OK) return rc;
+        rc = kalle_attention_fwd(q, D, 0, L.kv_cache, kvw, 0, L.kv_cache, kvw, Hkv * 64, ao, D, lse, rope_cos, rope_sin,
                                      64, nullptr, 1, 1, H, Hkv, 1, t0 + 1, stream);
         if (rc != KALLE_OK) return rc;
         gemv_launch<true, PRO_BF16>(ao, nullptr, 0.f, L.wo, D, xa, xa, D, xin, D, D, st);
+        if ((rc = kalle_check_launch()) != KALLE_OK) return rc;
         gemv_launch<false, PRO_RMS>(xa, L.post_norm, eps, L.wug, D, hf, hf, 2 * inner, nullptr, 2 * inner, D, st);
+        if ((rc = kalle_check_launch()) != KALLE_OK) return rc;
         float* xo = l + 1 == n_layers ? out : xb;
         gemv_launch<true, PRO_SWIGLU>(hf, nullptr, 0.f, L.wdown, inner, xo, xo, D, xa, D, inner, st);
+        if ((rc = kalle_check_launch()) != KALLE_OK) return rc;
         xin = xo;
     }
-    return kalle_check_launch();
+    return KALLE_OK;
 }
 
 extern "C" int kalle_peak_normalize_int16(const void* x, int dtype, float* peak, int16_t* out, int64_t n, void* stream) {

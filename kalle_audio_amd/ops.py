@@ -636,6 +636,33 @@ def segment_copy(src, dst, src_off, dst_off, lens, nbatch, rows, *, src_strides,
 
 
 MAX_GROUP = 8
+WGRAD_PLAN_FIELDS = ("tiles", "whole", "slices", "cleared", "cached")
+
+
+def _wgrad_problems(shapes):
+    """(tokens, N, K) triples as a kalle_wgrad_problem array with placeholder pointers, for the host query"""
+    arr = (_lib.WgradProblem * len(shapes))()
+    for w, (tokens, n, k) in zip(arr, shapes):
+        w.dy = w.x = w.dw = 16
+        w.lddy, w.ldx, w.lddw, w.N, w.K, w.tokens = n, k, k, n, k, tokens
+    return arr
+
+
+def wgrad_group_plan(shapes, overwrite=False):
+    """kalle_gemm_wgrad_group_plan for problems given as (tokens, N, K): the plan kalle_gemm_wgrad_group would run now on this
+    thread, as a dict of WGRAD_PLAN_FIELDS (encoding: include/kalle_hip.h); host code only, no device needed"""
+    out = (ctypes.c_int * 5)()
+    arr = _wgrad_problems(shapes)
+    check(_lib.load().kalle_gemm_wgrad_group_plan(ctypes.cast(arr, ctypes.c_void_p), len(shapes), int(bool(overwrite)),
+                                                  ctypes.cast(out, ctypes.c_void_p)), "kalle_gemm_wgrad_group_plan")
+    return dict(zip(WGRAD_PLAN_FIELDS, out))
+
+
+def wgrad_group_last_plan():
+    """the calling thread's kalle_gemm_wgrad_group_last_plan as a dict of WGRAD_PLAN_FIELDS"""
+    out = (ctypes.c_int * 5)()
+    check(_lib.load().kalle_gemm_wgrad_group_last_plan(ctypes.cast(out, ctypes.c_void_p)), "kalle_gemm_wgrad_group_last_plan")
+    return dict(zip(WGRAD_PLAN_FIELDS, out))
 
 
 def gemm_wgrad_group(problems, overwrite=False):

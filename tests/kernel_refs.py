@@ -699,3 +699,66 @@ def attention_bwd_ref(q, k, v, dout, H, Hkv, dh, rot=0, cos=None, sin=None, key_
     mags = {"dq": flat(_unrotate_abs(a_dq, rot), Nq, H) + dq.abs(), "dk": flat(_unrotate_abs(a_dk, rot), Nk, Hkv) + dk.abs(),
             "dv": flat(a_dv, Nk, Hkv) + dv.abs()}
     return dq, dk, dv, delta, mags
+
+
+# ------------------------------------------------------------------------------------------------ Llama decode step
+# kalle_gemv_bf16 and the stages of kalle_llama_decode_step (include/kalle_hip.h), float64.  A GEMV with a prologue builds its
+# bf16 operand on the fly: the references return the prologue value BEFORE that rounding too, so that a test can tell which
+# elements sit so close to a bf16 rounding boundary that the kernel's fast-math value may round the other way.
+def gemv(W, x, residual=None):
+    """y[n] = sum_k W[n][k] x[k] (+ residual[n])"""
+    y = W @ x
+    return y if residual is None else y + residual
+
+
+def decode_rms_prologue(x, gamma, eps, wrong=None):
+    """x * (gamma * rsqrt(mean(x^2) + eps)), not yet rounded (LlamaRMSNorm)"""
+    rr = (x.pow(2).mean() + (0.0 if wrong == "no_eps" else eps)).rsqrt()
+    if wrong == "gamma_after_rounding":
+        return bf16r(x * rr) * gamma
+    return x * (gamma * rr)
+
+
+def decode_swiglu_prologue(hf, wrong=None):
+    """hf = up | gate -> up * silu(gate), not yet rounded (LlamaMLP)"""
+    inner = hf.shape[0] // 2
+    up, gate = hf[:inner], hf[inner:]
+    return gate * silu_fwd(up) if wrong == "gate_silu_up" else up * silu_fwd(gate)
+
+
+def bf16_ulp(v):
+    """spacing of the bf16 numbers around v (normal range)"""
+    return torch.exp2(torch.floor(torch.log2(v.abs().clamp_min(2.0 ** -126))) - 7)
+
+
+def bf16_ambiguous(v, window):
+    """elements of v (float64) within `window` (absolute, per element) of a bf16 rounding boundary - the midpoint of two
+    neighbouring bf16 numbers: a value computed with an error of up to `window` may round to either neighbour"""
+    ulp = bf16_ulp(v)
+    frac = torch.remainder(v.abs() / ulp, 1.0)                   # position between the two neighbours, in ulps
+    return (frac - 0.5).abs() * ulp <= window
+
+
+def decode_qkv(x, gamma, eps, wqkv, D, wrong=None):
+    """stage 1: (q [D], k | v row [2 Hkv 64]) = Wqkv . bf16(rmsnorm(x)) before the bf16 store, and the prologue value"""
+    xh = decode_rms_prologue(x, gamma, eps, wrong)
+    y = gemv(wqkv, bf16r(xh))
+    kv = y[D:]
+    if wrong == "kv_swapped":
+        kv = torch.cat([kv[kv.shape[0] // 2:], kv[:kv.shape[0] // 2]])
+    return y[:D], kv, xh
+
+
+def decode_attention(q, cache, H, Hkv, t0, cos, sin, round_points=False, wrong=None):
+    """stage 2: the query of position t0 against cache rows 0 .. t0 (k | v per row, un-rotated), rot 64, causal; returns
+    attention_ref's tuple with B = Nq = 1"""
+    rows = t0 if wrong == "t0_rows" else t0 + 1
+    kvw = Hkv * 64
+    return attention_ref(q[None, None, :], cache[None, :rows, :kvw], cache[None, :rows, kvw:], H, Hkv, 64, rot=64, cos=cos, sin=sin,
+                         causal=True, round_points=round_points)
+
+
+def decode_mlp_out(x2, hf, wdown, wrong=None, x=None):
+    """stage 5: x2 + Wdown . bf16(up * silu(gate)), and the prologue value"""
+    act = decode_swiglu_prologue(hf, "gate_silu_up" if wrong == "gate_silu_up" else None)
+    return gemv(wdown, bf16r(act), x if wrong == "residual_x" else x2), act

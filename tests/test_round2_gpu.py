@@ -785,11 +785,15 @@ def test_rccl_path_world1_forced_comm(dev, tmp_path):
 
 
 # ------------------------------------------------------------------------------------------------ grouped weight gradients
-@pytest.mark.parametrize("tokens,shapes", [(512, [(4096, 4096), (512, 256), (264, 136)]),     # 256 whole tiles + a sliced tail
-                                           (4096, [(512, 384), (256, 640), (128, 128)]),      # few tiles: all cut into K slices
-                                           (8064, [(1536, 1536), (4608, 1536), (1536, 768)]),
-                                           (2016, [(1536, 1536), (4608, 1536), (1536, 768)])])   # B = 16: ragged last K-tile
-def test_grouped_wgrad_kernel_vs_fp32(dev, tokens, shapes):
+# (tiles, whole, slices) as kalle_gemm_wgrad_group_last_plan reports them
+@pytest.mark.parametrize("tokens,shapes,plan", [
+    (512, [(4096, 4096), (512, 256), (264, 136)], (260, 260, 0)),     # 8 K-tiles are never sliced: 260 whole tiles
+    (4096, [(512, 384), (256, 640), (128, 128)], (8, 0, 8)),          # few tiles: all cut into K slices
+    (8064, [(1536, 1536), (4608, 1536), (1536, 768)], (162, 162, 0)),
+    (2016, [(1536, 1536), (4608, 1536), (1536, 768)], None),          # B = 16: ragged last K-tile
+    (1024, [(4096, 4096), (512, 256), (264, 136)], (260, 256, 2))],   # 256 whole tiles + a sliced tail
+    ids=["512-shapes0", "4096-shapes1", "8064-shapes2", "2016-shapes3", "1024-shapes4"])
+def test_grouped_wgrad_kernel_vs_fp32(dev, tokens, shapes, plan):
     """kalle_gemm_wgrad_group: several dW += dY^T X problems in one launch (whole tiles: read-add-store; sliced tiles: atomics)
     against an fp32 matmul of the same bf16 operands, accumulating onto a non-zero sink; and against one kalle_gemm_bf16 each"""
     from kalle_audio_amd import ops
@@ -802,7 +806,10 @@ def test_grouped_wgrad_kernel_vs_fp32(dev, tokens, shapes):
         probs.append((dy, x, base.clone()))
         refs.append(base.double() + dy.double().T @ x.double())
         singles.append(base + ops.gemm(dy, x, a_kmajor=True, b_kmajor=True, out_dtype=torch.float32))
+    want = ops.wgrad_group_plan([(tokens, n, k) for n, k in shapes])
     assert ops.gemm_wgrad_group(probs)
+    got = ops.wgrad_group_last_plan()
+    assert got == dict(want, cached=got["cached"]) and (plan is None or (got["tiles"], got["whole"], got["slices"]) == plan), (got, want)
     torch.cuda.synchronize()
     for (dy, x, out), ref, one in zip(probs, refs, singles):
         assert rel(out, ref.float()) < 2e-5, rel(out, ref.float())          # fp32 accumulation of exact bf16 products
