@@ -312,8 +312,9 @@ int kalle_fourier_features_bwd(const float* dout, const float* t, const float* w
  *   (self-attention: q,k,v all point into the fused to_qkv output, ld = 3*D, offsets 0, D, 2D;
  *    cross-attention: q from to_q (ld=D), k/v from to_kv output (ld=2*Dc, offsets 0, Dc); GQA repeat_interleave 337-340)
  * rope_cos/rope_sin: [Npos][rot/2] fp32 tables or NULL - rotary on the first `rot` dims of q and k, applied on the fly:
- *   rot = 32 the DiT's partial rotary (transformer.py:146-170, 430-444), rot = 64 the Llama decoder's (HF
- *   `apply_rotary_pos_emb`, the third-party model under model_sigmaVAE.py:17-29).
+ *   rot = 32 the DiT's partial rotary (transformer.py:146-170, 430-444), rot = head dim (64, or 128 through the _hd forms)
+ *   the Llama decoder's (HF `apply_rotary_pos_emb` over the whole head, partners head_dim / 2 apart; the third-party model
+ *   under model_sigmaVAE.py:17-29).
  * causal != 0: query i attends keys j <= i + (Nk - Nq) only (the Llama decoder called at model_sigmaVAE.py:78-81); the
  *   queries are then the LAST Nq positions (rotary position of query row i = i + Nk - Nq), which is what decoding against
  *   a KV cache needs (model_sigmaVAE.py:122-146 re-runs the prefix instead).
@@ -344,8 +345,10 @@ int kalle_attention_bwd(const void* q, int64_t ldq, int q_off, const void* k, in
  *   out[b, i, h*dh+d] = softmax_j(q_i . k_j / sqrt(dh) + maskbias_j) v_j      (scale 1/sqrt(dh) in fp32: 0.17678 / 0.125 / 0.088388)
  *   q head h at column q_off + h*dh, k / v head (h / (H/Hkv)) at k_off / v_off + (h / (H/Hkv))*dh; out / dout / dq / dk / dv
  *   likewise with dh-wide heads; lse / delta [B][H][Nq] as above.
- * rot in {0, 32, 64} and rot <= dh: rotary on the first rot dims of every head (RotaryEmbedding(max(dh // 2, 32)),
- * transformer.py:730: the DiT's rot is 32 at dh 32 - the whole head - and 64 at dh 128).
+ * rot in {0, 32, 64, 128} and rot <= dh: rotary on the first rot dims of every head (RotaryEmbedding(max(dh // 2, 32)),
+ * transformer.py:730: the DiT's rot is 32 at dh 32 - the whole head - and 64 at dh 128; rot 128 at dh 128 is a Llama decoder
+ * with 128-wide heads, `AutoModelForCausalLM.from_pretrained(config['llm_model_name_or_path'])` at model_sigmaVAE.py:17-29 with a
+ * Llama-3.2-3B / 3.1-8B checkpoint: tables [Npos][64]).
  * Anything else (head_dim not in {32, 64, 128}, rot > head_dim) returns KALLE_ERR_ARG.  head_dim 64 is exactly
  * kalle_attention_fwd / _bwd (which forward here); at 32 and 128 the backward is the two-pass kernel pair at every shape. */
 int kalle_attention_fwd_hd(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off,
@@ -357,16 +360,32 @@ int kalle_attention_bwd_hd(const void* q, int64_t ldq, int q_off, const void* k,
                            const float* lse, float* delta, void* dq, void* dk, void* dv,
                            const float* rope_cos, const float* rope_sin, int rot, const uint8_t* key_mask, int causal,
                            int B, int H, int Hkv, int Nq, int Nk, int head_dim, void* stream);
-/* which kernel family the calling thread's most recent kalle_attention_fwd / _bwd (_hd) launched; 0 when that call returned
- * before launching anything.
+/* Decoding against a KV cache: ONE query per batch row, the LAST position (rotary position Nk - 1, sees every key), against Nk
+ * cached keys (model_sigmaVAE.py:122-146 re-runs `self.base_model.model(inputs_embeds=...)` over the prefix for every frame; with a
+ * cache only this row is new).  q: [B][ldq], out: [B][ldo], lse: [B][H] or NULL, k / v / key_mask / tables as above.
+ *   head_dim 64:  exactly kalle_attention_fwd with causal != 0 and Nq == 1 (attn_decode_kernel<rot>, rot in {0, 32, 64}), bit for bit
+ *   head_dim 128: rot = 128 only (attn_decode128_kernel: vector-ALU scoring with two lanes per key, block softmax over the scores
+ *                 in LDS, P V with 16 lanes per key row; bf16 rounding of the rotated q / k and of the probabilities as in the tiled
+ *                 kernel, so the two agree to the rounding of fp32 sums)
+ *   Nk > 15360 (the scores no longer fit in LDS): the tiled kernel of kalle_attention_fwd_hd at either head dim.
+ * Anything else - head_dim 32 or any other, at head_dim 128 a rot other than 128, and whatever kalle_attention_fwd_hd refuses -
+ * returns KALLE_ERR_ARG and launches nothing. */
+int kalle_attention_decode_hd(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off,
+                              const void* v, int64_t ldv, int v_off, void* out, int64_t ldo, float* lse,
+                              const float* rope_cos, const float* rope_sin, int rot, const uint8_t* key_mask,
+                              int B, int H, int Hkv, int Nk, int head_dim, void* stream);
+/* which kernel family the calling thread's most recent kalle_attention_fwd / _bwd (_hd) / kalle_attention_decode_hd launched; 0
+ * when that call returned before launching anything.
  *   bits 0-3   family: 1 fwd_tiled (attn_fwd_kernel), 2 fwd_decode (attn_decode_kernel: head dim 64, Nq == 1, Nk <= 15360),
  *              3 bwd_two_pass (attn_bwd_kernel, dQ + delta then dK / dV), 4 bwd_fused (attn_bwd_fused_kernel: head dim 64, not
  *              causal, H == Hkv, Nq, Nk <= 128), 5 bwd_fused_gqa (attn_bwd_fused_gqa_kernel: head dim 64, not causal, rot 0,
- *              Nq <= 128, Nk - 128 <= min(16, 128 - Nq))
+ *              Nq <= 128, Nk - 128 <= min(16, 128 - Nq)), 6 fwd_decode_128 (attn_decode128_kernel: kalle_attention_decode_hd at
+ *              head dim 128, Nk <= 15360; a forward family: bit 4 is 0)
  *   bit 4      direction: 0 forward, 1 backward
  *   bits 8-15  head dim (32 / 64 / 128)
  *   bit 16     family 1: the keys 128 .. Nk - 1 were folded into the first block (Nk in (128, 160], rot 0, not causal)
- *   bits 17-23 family 2: the ROT instantiation (0 / 32 / 64) */
+ *   bits 17-24 families 2 and 6: the ROT instantiation (0 / 32 / 64; 128 for family 6, which is why the field has 8 bits - every
+ *              word of families 1-5 keeps the value it had with a 7-bit field) */
 int kalle_attn_last_plan(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -469,7 +488,7 @@ int kalle_conv_transpose1d_fwd(const void* x, int x_dtype, const float* w_packed
 int kalle_conv_last_plan(void);
 /* ------------------------------------------------------------------------------------------------
  * Llasa task model head / tail (model_sigmaVAE.py:53-104); the Llama decoder layers in between run on kalle_gemm_bf16,
- * kalle_rmsnorm_*, kalle_attention_* (causal, rot = 64, GQA).
+ * kalle_rmsnorm_*, kalle_attention_* (causal, rot = head_dim = 64 or 128, GQA).
  */
 /* out = a x + b y, fp32   (fixed-sigma sampling x = mean + std * randn, model_sigmaVAE.py:150-166) */
 int kalle_axpby(const float* x, const float* y, float* out, float a, float b, int64_t n, void* stream);
@@ -515,6 +534,17 @@ int kalle_llama_decode_ws_bytes(int H, int Hkv, int inner);
 int kalle_llama_decode_step(const kalle_llama_layer* layers, int n_layers, const float* x, float* out, int H, int Hkv,
                             int inner, float eps, int t0, int cache_rows, const float* rope_cos, const float* rope_sin,
                             void* workspace, void* stream);
+/* The same two for a decoder whose heads are head_dim = 64 or 128 wide (`AutoModelForCausalLM.from_pretrained(
+ * config['llm_model_name_or_path'])`, model_sigmaVAE.py:17-29, accepts any Llama checkpoint: Llama-3.2-1B has 64-wide heads,
+ * Llama-3.2-3B and Llama-3.1-8B 128-wide ones).  Everything above holds with D = H * head_dim, cache rows of 2 * Hkv * head_dim
+ * (k | v), rope tables [>= t0+1][head_dim / 2] and rotary over the whole head; the workspace layout is the one above with that D
+ * (kalle_llama_decode_ws_bytes_hd bytes); the limits D <= 32768 and inner <= 32768 are the GEMV's and do not depend on the head.
+ * The attention of a layer is kalle_attention_decode_hd.  head_dim = 64 is exactly the two functions above, which forward here;
+ * any other head_dim than 64 or 128 returns KALLE_ERR_ARG. */
+int kalle_llama_decode_ws_bytes_hd(int H, int Hkv, int inner, int head_dim);
+int kalle_llama_decode_step_hd(const kalle_llama_layer* layers, int n_layers, const float* x, float* out, int H, int Hkv,
+                               int inner, int head_dim, float eps, int t0, int cache_rows,
+                               const float* rope_cos, const float* rope_sin, void* workspace, void* stream);
 /* waveform -> int16 PCM as the inference scripts write it (infer_0723.py:293): out = int16(clamp(x / max|x|, -1, 1) * 32767);
  * peak: one fp32 of device scratch that receives max|x|; x fp32 or bf16 */
 int kalle_peak_normalize_int16(const void* x, int dtype, float* peak, int16_t* out, int64_t n, void* stream);

@@ -1,5 +1,6 @@
 // Fused attention for the DiT block and the Llama decoder layers (gfx950), forward and backward, head dim DH = 32, 64 or
-// 128, optional causal mask (keys j <= i + Nk - Nq), optional key-padding mask, rotary on the first 32 or 64 dims.
+// 128, optional causal mask (keys j <= i + Nk - Nq), optional key-padding mask, rotary on the first 32, 64 or (DH 128: the
+// Llama decoders with 128-wide heads) 128 dims.
 // Reference: stable_audio_tools/models/transformer.py:396-547 (Attention.forward: rotary 430-444, key mask 446-462,
 // softmax(QK^T/sqrt(d))V 502-530 / SDPA 382-387, GQA repeat_interleave 337-340, 505-508) and
 // transformer.py:146-170 (rotate_half / apply_rotary_pos_emb, partial rotary on the first 32 dims).
@@ -46,8 +47,8 @@ constexpr float LOG2E = 1.4426950408889634f;
 constexpr float M_INIT = -2.0e30f;         // running max before the first block: below a fully masked row's NEG_BIG
 
 // stage a [128][DH] bf16 tile (rows row0.., `nvalid` valid) into LDS, optionally applying rotary on the first `rot`
-// (32: DiT partial rotary at DH 32 / 64; 64: Llama, and the DiT at DH 128) dims: out = x cos + rotate_half(x) sin, tables
-// [pos][rot/2].
+// (32: DiT partial rotary at DH 32 / 64; 64: Llama at DH 64, and the DiT at DH 128; 128: Llama at DH 128) dims:
+// out = x cos + rotate_half(x) sin, tables [pos][rot/2].
 // Split in two so that a kernel can put the global loads of several tiles in flight together (one HBM latency instead
 // of one per tile) and do the rotary + LDS writes afterwards.
 // A staging slot is ONE row and TWO 8-element chunks of it: the two partners of a rotary pair (chunk j and j + rot/16), so the
@@ -61,7 +62,7 @@ struct TileRegs {
     i32x4 v[Hd<DH>::NP][2];
 };
 __device__ __forceinline__ void tile_chunks(int rot, int j, int& ca, int& cb) {
-    const int hc = rot >> 4;                            // 8-element chunks per rotary half: 0, 2 (DiT) or 4 (Llama)
+    const int hc = rot >> 4;                            // 8-element chunks per rotary half: 0, 2 (DiT), 4 or 8 (Llama)
     if (j < hc) { ca = j; cb = j + hc; }                // a rotary pair
     else if (hc == 2) { ca = 2 * j; cb = 2 * j + 1; }   // rot 32: j = 2, 3, .. -> chunks (4, 5), (6, 7), .. pass through
     else { ca = 2 * j; cb = 2 * j + 1; }                // rot 0 (and rot 64: j = 4.. -> chunks 8.. at DH 128)
@@ -818,15 +819,15 @@ __global__ __launch_bounds__(128 / (16 * OT) * 64, DH == 128 ? 2 : OT == 1 ? 4 :
         const int oi = o0 + wave * (16 * OT) + 16 * ot + li;
         if (oi >= nown) continue;
         if (p.rot) {
-            const int hts = p.rot >> 5;                 // 16-dim tiles per rotary half (1 or 2; 1 at DH 32)
+            const int hts = p.rot >> 5;                 // 16-dim tiles per rotary half (1 or 2; 1 at DH 32; 4 at DH 128, rot 128)
 #pragma unroll
-            for (int ht = 0; ht < (DH == 32 ? 1 : 2); ++ht) {
+            for (int ht = 0; ht < (DH == 32 ? 1 : DH == 64 ? 2 : 4); ++ht) {
                 if (ht >= hts) break;
                 const int64_t pos = oi + (KV ? 0 : p.qpos);
                 const f32x4 c4 = *reinterpret_cast<const f32x4*>(p.cosT + pos * (p.rot >> 1) + 16 * ht + 4 * g);
                 const f32x4 s4 = *reinterpret_cast<const f32x4*>(p.sinT + pos * (p.rot >> 1) + 16 * ht + 4 * g);
                 f32x4& lo = hts == 1 ? g2[0][ot] : g2[ht][ot];
-                f32x4& hi = hts == 1 ? g2[1][ot] : g2[DH == 32 ? 1 : ht + 2][ot];
+                f32x4& hi = hts == 1 ? g2[1][ot] : DH == 128 && hts == 4 ? g2[DH == 128 ? ht + 4 : 1][ot] : g2[DH == 32 ? 1 : ht + 2][ot];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const float a = lo[r], bb = hi[r];
@@ -1335,7 +1336,7 @@ bool check_common(const void* q, int64_t ldq, int q_off, const void* k, int64_t 
     if (!q || !k || !v || B <= 0 || H <= 0 || Hkv <= 0 || Nq <= 0 || Nk <= 0) return false;
     if (H % Hkv) return false;
     if ((ldq & 7) || (ldk & 7) || (ldv & 7) || (ldo & 7) || (q_off & 7) || (k_off & 7) || (v_off & 7)) return false;
-    if (rot != 0 && rot != 32 && rot != 64) return false;
+    if (rot != 0 && rot != 32 && rot != 64 && rot != 128) return false;     // (rot <= head dim: check_head_dim)
     if (H > 65535 || B > 65535) return false;
     return true;
 }
@@ -1462,11 +1463,153 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(AttnParams p) {
     }
 }
 
+// ---- single-query attention at head dim 128 (Llama decoders with 128-wide heads, rotary over the whole head) ------------------
+// Same shape as attn_decode_kernel: a workgroup per (head, batch), scores on the vector ALUs, block softmax over the scores in
+// LDS (Nk * 4 bytes: the same 15360-key ceiling), then P.V; bf16 rounding at the same points as the tiled kernel (rotated q,
+// rotated k, probabilities).  What differs is who owns a key.  A thread per key would hold 128 fp32 key values + 128 of q through
+// the rotary and the dot product: past the 256-VGPR ceiling once addresses and the table values are counted, so it spills.  Here
+// TWO adjacent lanes share a key and the workgroup scores DECODE128_KB = 128 keys per pass: lane i of the pair owns dims
+// [32 i, 32 i + 32) and [64 + 32 i, 64 + 32 i + 32), so both partners of every rotary pair (d, d + 64) sit in one lane, a lane
+// needs only its own 32 cos / sin values of the key's table row, and the dot product closes with one cross-lane add
+// (a shuffle, no LDS).  Per lane: 64 fp32 key values + its 64 of the rotated query, held in registers for all passes
+// (read once from LDS) - 204 VGPRs, no scratch; a workgroup is 4 waves, one per SIMD, so the count costs no occupancy.
+// Loads: 8 x 16 B per lane and key, the two lanes of a pair covering the 256-byte row between them in 64-byte runs; the table
+// rows likewise 2 x 128 B per lane.  The score array is written by the even lanes only, 32 consecutive dwords per wave and
+// pass: conflict-free; in P.V 16 threads share a key row (16-byte loads of v: 256 contiguous bytes per row) and read ONE
+// score each - 4 distinct consecutive dwords per wave, a broadcast.  DECODE128_PV_GROUPS = 16 key rows per P.V pass,
+// reduced over the 4 row groups of a wave by shuffles and over the waves through LDS.
+// What bounds it: one workgroup per head streams the head's whole K and V (512 B per key) with 8 loads per lane in flight -
+// latency, not bandwidth; at the decode shapes (24 - 32 heads on 256 CUs) the GEMVs around it own the step.
+constexpr int DECODE128_KB = 128, DECODE128_PV_GROUPS = 16;
+template <int ROT>
+__global__ __launch_bounds__(256) void attn_decode128_kernel(AttnParams p) {
+    static_assert(ROT == 128, "rotary over the whole head: the only caller");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* sc = reinterpret_cast<float*>(smem);  // [Nk] scores, then probabilities
+    __shared__ __attribute__((aligned(16))) float qs[128];
+    __shared__ float red[8];
+    __shared__ float osum[4][128];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int h = blockIdx.x, b = blockIdx.y;
+    const int hk = h / (p.H / p.Hkv);
+    const bf16_t* qsrc = p.q + (int64_t)b * p.ldq + p.q_off + h * 128;
+    const bf16_t* ksrc = p.k + (int64_t)b * p.Nk * p.ldk + p.k_off + hk * 128;
+    const bf16_t* vsrc = p.v + (int64_t)b * p.Nk * p.ldv + p.v_off + hk * 128;
+    auto rnd = [](float x) { return bf16_to_f32(f32_to_bf16(x)); };
+
+    if (tid < 128) {
+        const bool lo = tid < 64;
+        const float x = bf16_to_f32(qsrc[tid]), partner = bf16_to_f32(qsrc[tid ^ 64]);
+        const float c = p.cosT[(int64_t)p.qpos * 64 + (tid & 63)], sn = p.sinT[(int64_t)p.qpos * 64 + (tid & 63)];
+        qs[tid] = rnd(x * c + (lo ? -partner : partner) * sn);
+    }
+    __syncthreads();
+    const int half = tid & 1;                     // this lane's dims: [32 half, +32) and [64 + 32 half, +32)
+    float qa[32], qb[32];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const f32x4 a = reinterpret_cast<const f32x4*>(qs + 32 * half)[c], bb = reinterpret_cast<const f32x4*>(qs + 64 + 32 * half)[c];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { qa[4 * c + e] = a[e]; qb[4 * c + e] = bb[e]; }
+    }
+
+    float mx = NEG_BIG;
+    for (int j0 = 0; j0 < p.Nk; j0 += DECODE128_KB) {
+        const int j = j0 + (tid >> 1);
+        float part = 0.f;
+        if (j < p.Nk) {
+            const bf16_t* kp = ksrc + (int64_t)j * p.ldk + 32 * half;
+            float ka[32], kb[32];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const i32x4 wa = reinterpret_cast<const i32x4*>(kp)[c], wb = reinterpret_cast<const i32x4*>(kp + 64)[c];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    ka[8 * c + 2 * e] = bf16lo((uint32_t)wa[e]);
+                    ka[8 * c + 2 * e + 1] = bf16hi((uint32_t)wa[e]);
+                    kb[8 * c + 2 * e] = bf16lo((uint32_t)wb[e]);
+                    kb[8 * c + 2 * e + 1] = bf16hi((uint32_t)wb[e]);
+                }
+            }
+            const float* cp = p.cosT + (int64_t)j * 64 + 32 * half;
+            const float* sp = p.sinT + (int64_t)j * 64 + 32 * half;
+            float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+#pragma unroll
+            for (int i4 = 0; i4 < 8; ++i4) {
+                const f32x4 c = reinterpret_cast<const f32x4*>(cp)[i4], sn = reinterpret_cast<const f32x4*>(sp)[i4];
+#pragma unroll
+                for (int e = 0; e < 4; e += 2) {
+                    const int i = 4 * i4 + e;
+                    a0 += rnd(ka[i] * c[e] - kb[i] * sn[e]) * qa[i];
+                    a1 += rnd(ka[i + 1] * c[e + 1] - kb[i + 1] * sn[e + 1]) * qa[i + 1];
+                    a2 += rnd(kb[i] * c[e] + ka[i] * sn[e]) * qb[i];
+                    a3 += rnd(kb[i + 1] * c[e + 1] + ka[i + 1] * sn[e + 1]) * qb[i + 1];
+                }
+            }
+            part = (a0 + a1) + (a2 + a3);
+        }
+        float sv = (part + __shfl_xor(part, 1, 64)) * Hd<128>::SCALE;      // (both lanes of the pair: the same sum)
+        if (j < p.Nk) {
+            if (p.mask && !p.mask[(int64_t)b * p.Nk + j]) sv = NEG_BIG;
+            if (half == 0) sc[j] = sv;
+            mx = fmaxf(mx, sv);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    if (lane == 0) red[wave] = mx;
+    __syncthreads();
+    const float m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    float ls = 0.f;
+    for (int j = tid; j < p.Nk; j += 256) {
+        const float pv = __expf(sc[j] - m);
+        ls += pv;
+        sc[j] = rnd(pv);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) ls += __shfl_xor(ls, o, 64);
+    if (lane == 0) red[4 + wave] = ls;
+    __syncthreads();
+    const float l = red[4] + red[5] + red[6] + red[7];
+
+    const int kg = tid >> 4, d16 = tid & 15;
+    float acc[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] = 0.f;
+#pragma unroll 4
+    for (int j = kg; j < p.Nk; j += DECODE128_PV_GROUPS) {
+        const i32x4 w = *reinterpret_cast<const i32x4*>(vsrc + (int64_t)j * p.ldv + 8 * d16);
+        const float pj = sc[j];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            acc[2 * e] += pj * bf16lo((uint32_t)w[e]);
+            acc[2 * e + 1] += pj * bf16hi((uint32_t)w[e]);
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        acc[e] += __shfl_xor(acc[e], 16, 64);
+        acc[e] += __shfl_xor(acc[e], 32, 64);
+    }
+    if (lane < 16) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) osum[wave][8 * lane + e] = acc[e];
+    }
+    __syncthreads();
+    if (tid < 128) {
+        const float o = (osum[0][tid] + osum[1][tid] + osum[2][tid] + osum[3][tid]) / l;
+        p.out[(int64_t)b * p.ldo + h * 128 + tid] = f32_to_bf16(o);
+        if (tid == 0 && p.lse) p.lse[(int64_t)b * p.H + h] = m + __logf(l);
+    }
+}
+
 // kalle_attn_last_plan (encoding: include/kalle_hip.h)
 thread_local int g_attn_plan = 0;
-enum { PLAN_FWD_TILED = 1, PLAN_FWD_DECODE = 2, PLAN_BWD_TWO_PASS = 3, PLAN_BWD_FUSED = 4, PLAN_BWD_FUSED_GQA = 5 };
+enum { PLAN_FWD_TILED = 1, PLAN_FWD_DECODE = 2, PLAN_BWD_TWO_PASS = 3, PLAN_BWD_FUSED = 4, PLAN_BWD_FUSED_GQA = 5,
+       PLAN_FWD_DECODE_128 = 6 };
 constexpr int attn_plan(int family, int head_dim, bool fold_tail = false, int decode_rot = 0) {
-    return family | (family >= PLAN_BWD_TWO_PASS ? 1 << 4 : 0) | head_dim << 8 | (fold_tail ? 1 << 16 : 0) | decode_rot << 17;
+    return family | (family >= PLAN_BWD_TWO_PASS && family <= PLAN_BWD_FUSED_GQA ? 1 << 4 : 0) | head_dim << 8 |
+           (fold_tail ? 1 << 16 : 0) | decode_rot << 17;
 }
 }  // namespace
 
@@ -1477,7 +1620,8 @@ extern "C" __attribute__((visibility("hidden"))) void kalle_set_attn_plan(int pl
 static unsigned long long* g_attn_stamps = nullptr;      // diagnostics only
 extern "C" int kalle_attn_debug_stamps(void* buf) { g_attn_stamps = static_cast<unsigned long long*>(buf); return KALLE_OK; }
 
-// head dims other than 64 (DH 32 / 128): the tiled kernels, Nq == 1 included (the decode kernel is DH = 64 only)
+// head dims other than 64 (DH 32 / 128): the tiled kernels, Nq == 1 included (kalle_attention_decode_hd is the way to the
+// single-query kernel at DH 128)
 template <int DH>
 static int attention_fwd_dh(const AttnParams& p, hipStream_t st) {
     constexpr int lds = 3 * Hd<DH>::TILE + 160 * 4 + 2 * 32 * Hd<DH>::STRIDE;   // Q | K | V, key bias [128 + 32], tail tiles
@@ -1595,6 +1739,33 @@ extern "C" int kalle_attention_bwd_hd(const void* q, int64_t ldq, int q_off, con
     KALLE_LAUNCH((attn_bwd_kernel<false, 1>), dim3((Nq + 127) / 128, H, B), dim3(512), lds, st, p);
     KALLE_LAUNCH((attn_bwd_kernel<true, 1>), dim3((Nk + 127) / 128, Hkv, B), dim3(512), lds, st, p);
     kalle_set_attn_plan(attn_plan(PLAN_BWD_TWO_PASS, 64));
+    return kalle_check_launch();
+}
+
+// one query per batch row at the LAST position against Nk cached keys: the single-query kernels by head dim
+extern "C" int kalle_attention_decode_hd(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off,
+                                         const void* v, int64_t ldv, int v_off, void* out, int64_t ldo, float* lse,
+                                         const float* rope_cos, const float* rope_sin, int rot, const uint8_t* key_mask,
+                                         int B, int H, int Hkv, int Nk, int head_dim, void* stream) {
+    kalle_set_attn_plan(0);
+    if (head_dim != 64 && head_dim != 128) return KALLE_ERR_ARG;
+    if (head_dim == 128 && rot != 128) return KALLE_ERR_ARG;              // attn_decode128_kernel<128> is the one instantiation
+    // head dim 64: attn_decode_kernel<ROT> as kalle_attention_fwd launches it at Nq == 1; beyond the LDS score array: tiled
+    if (head_dim == 64 || Nk > 15360)
+        return kalle_attention_fwd_hd(q, ldq, q_off, k, ldk, k_off, v, ldv, v_off, out, ldo, lse, rope_cos, rope_sin, rot, key_mask,
+                                      1, B, H, Hkv, 1, Nk, head_dim, stream);
+    if (!out || !check_common(q, ldq, q_off, k, ldk, k_off, v, ldv, v_off, ldo, rot, B, H, Hkv, 1, Nk)) return KALLE_ERR_ARG;
+    if (!rope_cos || !rope_sin) return KALLE_ERR_ARG;
+    AttnParams p{};
+    p.q = static_cast<const bf16_t*>(q); p.ldq = ldq; p.q_off = q_off;
+    p.k = static_cast<const bf16_t*>(k); p.ldk = ldk; p.k_off = k_off;
+    p.v = static_cast<const bf16_t*>(v); p.ldv = ldv; p.v_off = v_off;
+    p.out = static_cast<bf16_t*>(out); p.ldo = ldo; p.lse = lse;
+    p.cosT = rope_cos; p.sinT = rope_sin; p.rot = rot; p.mask = key_mask;
+    p.B = B; p.H = H; p.Hkv = Hkv; p.Nq = 1; p.Nk = Nk; p.causal = 1;
+    p.qpos = Nk - 1;
+    KALLE_LAUNCH(attn_decode128_kernel<128>, dim3(H, B), dim3(256), (size_t)Nk * 4, static_cast<hipStream_t>(stream), p);
+    kalle_set_attn_plan(attn_plan(PLAN_FWD_DECODE_128, 128, false, 128));
     return kalle_check_launch();
 }
 

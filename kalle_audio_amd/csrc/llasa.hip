@@ -401,20 +401,24 @@ extern "C" int kalle_gemv_bf16(const void* x, const void* W, int64_t ldw, void* 
     return kalle_check_launch();
 }
 
-extern "C" int kalle_llama_decode_ws_bytes(int H, int Hkv, int inner) {
-    if (H <= 0 || Hkv <= 0 || inner <= 0) return KALLE_ERR_ARG;
-    const int64_t D = (int64_t)H * 64;
+extern "C" int kalle_llama_decode_ws_bytes_hd(int H, int Hkv, int inner, int head_dim) {
+    if (H <= 0 || Hkv <= 0 || inner <= 0 || (head_dim != 64 && head_dim != 128)) return KALLE_ERR_ARG;
+    const int64_t D = (int64_t)H * head_dim;
     // x2 | x3 fp32, lse fp32 (padded), q | ao | hf bf16
     return (int)(2 * D * 4 + ((H * 4 + 63) & ~63) + D * 2 + D * 2 + 2 * (int64_t)inner * 2);
 }
 
-extern "C" int kalle_llama_decode_step(const kalle_llama_layer* layers, int n_layers, const float* x, float* out, int H,
-                                       int Hkv, int inner, float eps, int t0, int cache_rows, const float* rope_cos,
-                                       const float* rope_sin, void* workspace, void* stream) {
+extern "C" __attribute__((visibility("hidden"))) void kalle_set_attn_plan(int plan);   // (attention.hip)
+
+extern "C" int kalle_llama_decode_step_hd(const kalle_llama_layer* layers, int n_layers, const float* x, float* out, int H,
+                                          int Hkv, int inner, int head_dim, float eps, int t0, int cache_rows,
+                                          const float* rope_cos, const float* rope_sin, void* workspace, void* stream) {
+    kalle_set_attn_plan(0);      // (a step refused before its first launch leaves no attention plan behind)
     if (!layers || n_layers <= 0 || !x || !out || !workspace || !rope_cos || !rope_sin) return KALLE_ERR_ARG;
     if (H <= 0 || Hkv <= 0 || H % Hkv || inner <= 0 || (inner & 7) || t0 < 0 || t0 >= cache_rows) return KALLE_ERR_ARG;
-    const int D = H * 64, kvw = 2 * Hkv * 64;
-    if (D > 32768 || inner > 32768) return KALLE_ERR_ARG;
+    if (head_dim != 64 && head_dim != 128) return KALLE_ERR_ARG;
+    if ((int64_t)H * head_dim > 32768 || inner > 32768) return KALLE_ERR_ARG;
+    const int D = H * head_dim, kvw = 2 * Hkv * head_dim;
     hipStream_t st = static_cast<hipStream_t>(stream);
     char* ws = static_cast<char*>(workspace);
     float* xa = reinterpret_cast<float*>(ws);               // x2: residual stream after the attention branch
@@ -431,11 +435,12 @@ extern "C" int kalle_llama_decode_step(const kalle_llama_layer* layers, int n_la
         // q -> scratch, k | v -> cache row t0 (un-rotated: the attention kernel rotates by row index)
         // (every launch is checked where it is made: KALLE_LAUNCH clears the error state, so a refused launch would otherwise be
         // forgotten by the next one and the step would report success over an unwritten buffer)
+        // (nsplit = D is a multiple of 64 at either head dim: a wave's two rows never straddle it)
         gemv_launch<false, PRO_RMS>(xin, L.input_norm, eps, L.wqkv, D, q, kv_row, D, nullptr, D + kvw, D, st);
         int rc = kalle_check_launch();
         if (rc != KALLE_OK) return rc;
-        rc = kalle_attention_fwd(q, D, 0, L.kv_cache, kvw, 0, L.kv_cache, kvw, Hkv * 64, ao, D, lse, rope_cos, rope_sin,
-                                     64, nullptr, 1, 1, H, Hkv, 1, t0 + 1, stream);
+        rc = kalle_attention_decode_hd(q, D, 0, L.kv_cache, kvw, 0, L.kv_cache, kvw, Hkv * head_dim, ao, D, lse, rope_cos, rope_sin,
+                                       head_dim, nullptr, 1, H, Hkv, t0 + 1, head_dim, stream);
         if (rc != KALLE_OK) return rc;
         gemv_launch<true, PRO_BF16>(ao, nullptr, 0.f, L.wo, D, xa, xa, D, xin, D, D, st);
         if ((rc = kalle_check_launch()) != KALLE_OK) return rc;
@@ -447,6 +452,15 @@ extern "C" int kalle_llama_decode_step(const kalle_llama_layer* layers, int n_la
         xin = xo;
     }
     return KALLE_OK;
+}
+
+// the head-dim-64 forms of the C ABI: forwarders
+extern "C" int kalle_llama_decode_ws_bytes(int H, int Hkv, int inner) { return kalle_llama_decode_ws_bytes_hd(H, Hkv, inner, 64); }
+extern "C" int kalle_llama_decode_step(const kalle_llama_layer* layers, int n_layers, const float* x, float* out, int H,
+                                       int Hkv, int inner, float eps, int t0, int cache_rows, const float* rope_cos,
+                                       const float* rope_sin, void* workspace, void* stream) {
+    return kalle_llama_decode_step_hd(layers, n_layers, x, out, H, Hkv, inner, 64, eps, t0, cache_rows, rope_cos, rope_sin,
+                                      workspace, stream);
 }
 
 extern "C" int kalle_peak_normalize_int16(const void* x, int dtype, float* peak, int16_t* out, int64_t n, void* stream) {

@@ -3,7 +3,7 @@ conventions as dit_ops.py: residual stream fp32, GEMM operands bf16, fp32 accumu
 
 The layer is the third-party `transformers` LlamaDecoderLayer that the reference's task model runs under
 `self.base_model.model(inputs_embeds=..., attention_mask=...)` (model_sigmaVAE.py:78-81): pre-norm, RMSNorm, rotary
-over the whole 64-wide head, grouped-query causal attention with a key-padding mask, SwiGLU MLP without biases.
+over the whole head (64 or 128 wide), grouped-query causal attention with a key-padding mask, SwiGLU MLP without biases.
 q/k/v and up/gate are single fused GEMMs over fused parameters (split back into the HF names only in state_dict()).
 """
 import math
@@ -49,6 +49,7 @@ def layer_params(layer):
     p.wug = bf16_of(layer.mlp.up_gate_proj.weight)
     p.wdown = bf16_of(layer.mlp.down_proj.weight)
     p.H, p.Hkv, p.eps = layer.self_attn.num_heads, layer.self_attn.num_kv_heads, layer.input_layernorm.variance_epsilon
+    p.hd = layer.self_attn.head_dim
     return p
 
 
@@ -58,13 +59,13 @@ PARAM_ORDER = ("input_layernorm.weight", "self_attn.qkv_proj.weight", "self_attn
 
 def layer_fwd(p, x, B, L, rope, mask8):
     """x: fp32 [B*L, D] residual stream -> (fp32 [B*L, D], saved)"""
-    H, Hkv = p.H, p.Hkv
-    D = H * 64
-    ld = (H + 2 * Hkv) * 64
+    H, Hkv, hd = p.H, p.Hkv, p.hd
+    D = H * hd
+    ld = (H + 2 * Hkv) * hd
     h1, rr1 = ops.rmsnorm_fwd(x, p.g1, eps=p.eps, out_dtype=BF16)
     qkv = ops.gemm(h1, p.wqkv)
-    ao, lse = ops.attention_fwd(qkv, qkv, qkv, ldq=ld, q_off=0, ldk=ld, k_off=D, ldv=ld, v_off=D + Hkv * 64, B=B, H=H,
-                                Hkv=Hkv, Nq=L, Nk=L, rope=rope, key_mask=mask8, causal=True)
+    ao, lse = ops.attention_fwd(qkv, qkv, qkv, ldq=ld, q_off=0, ldk=ld, k_off=D, ldv=ld, v_off=D + Hkv * hd, B=B, H=H,
+                                Hkv=Hkv, Nq=L, Nk=L, rope=rope, key_mask=mask8, causal=True, dh=hd)
     x2 = ops.gemm(ao.view(B * L, D), p.wo, out_dtype=F32, residual=x)
     h2, rr2 = ops.rmsnorm_fwd(x2, p.g2, eps=p.eps, out_dtype=BF16)
     inner = p.wug.shape[0] // 2
@@ -82,9 +83,9 @@ def layer_bwd(p, saved, g, B, L, rope, mask8, go=None, g_bf16=None, want_dx_bf16
     Returns (dx fp32, dx bf16 | None, go)."""
     go = (go or GradOut()).defer()          # the four weight gradients of the layer go out in one grouped launch
     x, h1, rr1, qkv, ao, lse, x2, h2, rr2, hf, act = saved
-    H, Hkv = p.H, p.Hkv
-    D = H * 64
-    ld = (H + 2 * Hkv) * 64
+    H, Hkv, hd = p.H, p.Hkv, p.hd
+    D = H * hd
+    ld = (H + 2 * Hkv) * hd
     M = B * L
     gb = g_bf16 if g_bf16 is not None else ops.cast(g, BF16)
     # ---- MLP branch: x3 = x2 + down(up * silu(gate))
@@ -102,7 +103,7 @@ def layer_bwd(p, saved, g, B, L, rope, mask8, go=None, g_bf16=None, want_dx_bf16
     dao = dgrad(dxb2, p.wo)
     dqkv = torch.empty_like(qkv)
     ops.attention_bwd(qkv, qkv, qkv, ao, dao, lse, dqkv, dqkv, dqkv, ldq=ld, q_off=0, ldk=ld, k_off=D, ldv=ld,
-                      v_off=D + Hkv * 64, B=B, H=H, Hkv=Hkv, Nq=L, Nk=L, rope=rope, key_mask=mask8, causal=True)
+                      v_off=D + Hkv * hd, B=B, H=H, Hkv=Hkv, Nq=L, Nk=L, rope=rope, key_mask=mask8, causal=True, dh=hd)
     go.wgrad("self_attn.qkv_proj.weight", dqkv, h1)
     dh1 = dgrad(dqkv, p.wqkv)
     dxb = torch.empty((M, D), device=g.device, dtype=BF16) if want_dx_bf16 else None
@@ -113,18 +114,19 @@ def layer_bwd(p, saved, g, B, L, rope, mask8, go=None, g_bf16=None, want_dx_bf16
 
 
 def layer_fwd_cached(p, x, kv_cache, t0, rope):
-    """inference with a KV cache (batch 1): x fp32 [n, D] are positions t0 .. t0+n-1; kv_cache bf16 [Lmax, 2*Hkv*64]
+    """inference with a KV cache (batch 1): x fp32 [n, D] are positions t0 .. t0+n-1; kv_cache bf16 [Lmax, 2*Hkv*hd]
     holds the un-rotated k | v rows of positions < t0 and receives the new ones (rotary is applied by the attention
     kernel from the row index, so cached keys need no re-rotation).  Returns fp32 [n, D]."""
-    H, Hkv = p.H, p.Hkv
-    D = H * 64
-    ld = (H + 2 * Hkv) * 64
+    H, Hkv, hd = p.H, p.Hkv, p.hd
+    D = H * hd
+    ld = (H + 2 * Hkv) * hd
     n = x.shape[0]
     h1, _ = ops.rmsnorm_fwd(x, p.g1, eps=p.eps, out_dtype=BF16)
     qkv = ops.gemm(h1, p.wqkv)
-    ops.copy_rows(qkv[:, D:], kv_cache[t0:], 1, n, 2 * Hkv * 64, 0, ld, 0, 2 * Hkv * 64)
-    ao, _ = ops.attention_fwd(qkv, kv_cache, kv_cache, ldq=ld, q_off=0, ldk=2 * Hkv * 64, k_off=0, ldv=2 * Hkv * 64,
-                              v_off=Hkv * 64, B=1, H=H, Hkv=Hkv, Nq=n, Nk=t0 + n, rope=rope, causal=True)
+    kvw = 2 * Hkv * hd
+    ops.copy_rows(qkv[:, D:], kv_cache[t0:], 1, n, kvw, 0, ld, 0, kvw)
+    ao, _ = ops.attention_fwd(qkv, kv_cache, kv_cache, ldq=ld, q_off=0, ldk=kvw, k_off=0, ldv=kvw,
+                              v_off=Hkv * hd, B=1, H=H, Hkv=Hkv, Nq=n, Nk=t0 + n, rope=rope, causal=True, dh=hd)
     x2 = ops.gemm(ao.view(n, D), p.wo, out_dtype=F32, residual=x)
     h2, _ = ops.rmsnorm_fwd(x2, p.g2, eps=p.eps, out_dtype=BF16)
     hf = ops.gemm(h2, p.wug)

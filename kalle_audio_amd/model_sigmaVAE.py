@@ -189,17 +189,24 @@ class LlamaRMSNorm(nn.Module):
         return Fn.RMSNormFn.apply(x, self.weight, self.variance_epsilon)
 
 
+LLAMA_HEAD_DIMS = (64, 128)     # what the attention kernels rotate a whole head at (Llama-3.2-1B; Llama-3.2-3B, Llama-3.1-8B)
+
+
 class LlamaAttention(nn.Module):
     def __init__(self, cfg):
         super().__init__()
         self.num_heads, self.num_kv_heads = cfg["num_attention_heads"], cfg["num_key_value_heads"]
-        hd = cfg.get("head_dim") or cfg["hidden_size"] // self.num_heads
-        if hd != 64 or cfg.get("attention_bias"):
-            raise NotImplementedError("the attention kernels are built for head_dim 64 without projection biases")
         D = cfg["hidden_size"]
-        self.qkv_proj = _FusedLinear(D, (("q_proj", self.num_heads * 64), ("k_proj", self.num_kv_heads * 64),
-                                         ("v_proj", self.num_kv_heads * 64)))
-        self.o_proj = _Holder(D, self.num_heads * 64)
+        hd = self.head_dim = cfg.get("head_dim") or D // self.num_heads
+        if hd not in LLAMA_HEAD_DIMS or D != self.num_heads * hd or self.num_heads % self.num_kv_heads or cfg.get("attention_bias"):
+            raise NotImplementedError(
+                f"Llama decoders are supported with head_dim in {LLAMA_HEAD_DIMS}, hidden_size == num_attention_heads * head_dim, "
+                f"num_attention_heads a multiple of num_key_value_heads and no projection biases; got head_dim={hd}, "
+                f"hidden_size={D}, num_attention_heads={self.num_heads}, num_key_value_heads={self.num_kv_heads}, "
+                f"attention_bias={bool(cfg.get('attention_bias'))}")
+        self.qkv_proj = _FusedLinear(D, (("q_proj", self.num_heads * hd), ("k_proj", self.num_kv_heads * hd),
+                                         ("v_proj", self.num_kv_heads * hd)))
+        self.o_proj = _Holder(D, self.num_heads * hd)
         _split_hooks(self, "qkv_proj")
 
 
@@ -207,7 +214,8 @@ class LlamaMLP(nn.Module):
     def __init__(self, cfg):
         super().__init__()
         if cfg.get("mlp_bias") or cfg.get("hidden_act", "silu") != "silu":
-            raise NotImplementedError("LlamaMLP: silu without biases only")
+            raise NotImplementedError(f"Llama decoders are supported with hidden_act='silu' and no MLP biases; got hidden_act="
+                                      f"{cfg.get('hidden_act', 'silu')!r}, mlp_bias={bool(cfg.get('mlp_bias'))}")
         D, I = cfg["hidden_size"], cfg["intermediate_size"]
         # value half first, gate half second: the layout of the fused GEMM + SwiGLU epilogue
         self.up_gate_proj = _FusedLinear(D, (("up_proj", I), ("gate_proj", I)))
@@ -253,6 +261,7 @@ class LlamaModel(nn.Module):
         self.layers = nn.ModuleList([LlamaDecoderLayer(cfg, i) for i in range(cfg["num_hidden_layers"])])
         self.norm = LlamaRMSNorm(cfg["hidden_size"], cfg.get("rms_norm_eps", 1e-6))
         hd = cfg.get("head_dim") or cfg["hidden_size"] // cfg["num_attention_heads"]
+        self.head_dim = hd
         self._inv_freq = LO.inv_freq(hd, cfg.get("rope_theta", 10000.0), cfg.get("rope_scaling"))
         self._rope_cache = {}
 
@@ -277,8 +286,8 @@ class LlamaModel(nn.Module):
 
     # ---- inference with a KV cache (batch 1) ---------------------------------------------------------------------
     def init_cache(self, max_len, device):
-        """one bf16 [max_len, 2 * kv_heads * 64] buffer per layer (un-rotated k | v rows)"""
-        w = 2 * self.cfg["num_key_value_heads"] * 64
+        """one bf16 [max_len, 2 * kv_heads * head_dim] buffer per layer (un-rotated k | v rows)"""
+        w = 2 * self.cfg["num_key_value_heads"] * self.head_dim
         return {"kv": [torch.zeros((max_len, w), device=device, dtype=BF16) for _ in self.layers], "len": 0,
                 "rope": LO.rope_tables(max_len, self._inv_freq, device)}
 
@@ -298,7 +307,7 @@ class LlamaModel(nn.Module):
                 ps = [LO.layer_params(layer) for layer in self.layers]
                 plan = cache["plan"] = ops.llama_decode_plan(
                     [(p.g1, p.wqkv, p.wo, p.g2, p.wug, p.wdown, kv) for p, kv in zip(ps, cache["kv"])],
-                    ps[0].H, ps[0].Hkv, ps[0].wug.shape[0] // 2, x.device)
+                    ps[0].H, ps[0].Hkv, ps[0].wug.shape[0] // 2, x.device, head_dim=ps[0].hd)
                 plan["eps"] = ps[0].eps
             x = ops.llama_decode_step(plan, x.view(Dm), t0, cache["kv"][0].shape[0], cache["rope"], plan["eps"])
         else:

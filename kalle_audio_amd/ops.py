@@ -414,6 +414,20 @@ def attention_fwd(q, k, v, *, ldq, q_off, ldk, k_off, ldv, v_off, B, H, Hkv, Nq,
     return out, lse
 
 
+def attention_decode(q, k, v, *, ldq, q_off, ldk, k_off, ldv, v_off, B, H, Hkv, Nk, rope=None, key_mask=None, dh=64):
+    """one query per batch row (q [B][ldq], the LAST position) against Nk cached keys: kalle_attention_decode_hd.
+    Returns (out [B,1,H*dh], lse [B,H,1])."""
+    lib = _lib.load()
+    out = torch.empty((B, 1, H * dh), device=q.device, dtype=torch.bfloat16)
+    lse = torch.empty((B, H, 1), device=q.device, dtype=torch.float32)
+    cos, sin, rot = (rope[0], rope[1], rope[0].shape[-1] * 2) if rope is not None else (None, None, 0)
+    m8 = key_mask.to(torch.uint8).contiguous() if key_mask is not None else None
+    check(lib.kalle_attention_decode_hd(_p(q), ldq, q_off, _p(k), ldk, k_off, _p(v), ldv, v_off, _p(out), H * dh, _p(lse),
+                                        _p(cos), _p(sin), rot, _p(m8), B, H, Hkv, Nk, dh, _stream()),
+          "kalle_attention_decode_hd")
+    return out, lse
+
+
 def attn_last_plan():
     """the calling thread's kalle_attn_last_plan word (encoding: include/kalle_hip.h)"""
     return _lib.load().kalle_attn_last_plan()
@@ -570,7 +584,7 @@ def gauss_kl_bwd(pred, label, mask_a, mask_b, sums, grad_a, grad_b, std):
     return dpred
 
 
-def llama_decode_plan(layer_tensors, H, Hkv, inner, device):
+def llama_decode_plan(layer_tensors, H, Hkv, inner, device, head_dim=64):
     """layer_tensors: per layer (input_norm fp32, wqkv bf16, wo bf16, post_norm fp32, wug bf16, wdown bf16, kv_cache bf16).
     Returns the host-side descriptor array + workspace of kalle_llama_decode_step (keeps the tensors alive)."""
     lib = _lib.load()
@@ -579,17 +593,20 @@ def llama_decode_plan(layer_tensors, H, Hkv, inner, device):
         for t in ts:
             assert t.is_contiguous() and t.device == torch.device(device)
         d.input_norm, d.wqkv, d.wo, d.post_norm, d.wug, d.wdown, d.kv_cache = (t.data_ptr() for t in ts)
-    ws = torch.empty(lib.kalle_llama_decode_ws_bytes(H, Hkv, inner), device=device, dtype=torch.uint8)
-    return {"layers": arr, "n": len(layer_tensors), "keep": layer_tensors, "ws": ws, "H": H, "Hkv": Hkv, "inner": inner}
+    nbytes = lib.kalle_llama_decode_ws_bytes_hd(H, Hkv, inner, head_dim)
+    check(min(nbytes, 0), "kalle_llama_decode_ws_bytes_hd")
+    ws = torch.empty(nbytes, device=device, dtype=torch.uint8)
+    return {"layers": arr, "n": len(layer_tensors), "keep": layer_tensors, "ws": ws, "H": H, "Hkv": Hkv, "inner": inner,
+            "head_dim": head_dim}
 
 
 def llama_decode_step(plan, x, t0, cache_rows, rope, eps):
     """x fp32 [D] -> fp32 [D]: every decoder layer at position t0 against the KV caches of `plan` (one host call)"""
     lib = _lib.load()
     out = torch.empty_like(x)
-    check(lib.kalle_llama_decode_step(ctypes.cast(plan["layers"], ctypes.c_void_p), plan["n"], _p(x), _p(out), plan["H"],
-                                      plan["Hkv"], plan["inner"], eps, t0, cache_rows, _p(rope[0]), _p(rope[1]),
-                                      _p(plan["ws"]), _stream()), "kalle_llama_decode_step")
+    check(lib.kalle_llama_decode_step_hd(ctypes.cast(plan["layers"], ctypes.c_void_p), plan["n"], _p(x), _p(out), plan["H"],
+                                         plan["Hkv"], plan["inner"], plan.get("head_dim", 64), eps, t0, cache_rows,
+                                         _p(rope[0]), _p(rope[1]), _p(plan["ws"]), _stream()), "kalle_llama_decode_step_hd")
     return out
 
 

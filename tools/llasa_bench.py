@@ -1,15 +1,26 @@
 """Llasa train step (model_sigmaVAE.Llasa.forward + backward + fused AdamW) at the Llama-3.2-1B shape the reference trains
 (hidden 2048, 16 layers, 32 heads / 8 kv heads, intermediate 8192, vocab 128256 + 8 special tokens, latent_dim 64),
-random weights, synthetic batch: text prefix + audio frames per sample.   python tools/llasa_bench.py [B] [L] [steps]"""
+random weights, synthetic batch: text prefix + audio frames per sample.   python tools/llasa_bench.py [B] [L] [steps]
+The decoder shape is an option (defaults: Llama-3.2-1B): --hidden --layers --heads --kv-heads --head-dim --inner, e.g. the
+Llama-3.2-3B shape  --hidden 3072 --layers 28 --heads 24 --kv-heads 8 --head-dim 128 --inner 8192"""
 import json, os, sys, tempfile, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from kalle_audio_amd.model_sigmaVAE import Llasa
 from kalle_audio_amd.engine import DataParallelTrainer
-B = int(sys.argv[1]) if len(sys.argv) > 1 else 8
-L = int(sys.argv[2]) if len(sys.argv) > 2 else 1024
-steps = int(sys.argv[3]) if len(sys.argv) > 3 else 5
-cfg = dict(model_type="llama", vocab_size=128256, hidden_size=2048, intermediate_size=8192, num_hidden_layers=16,
-           num_attention_heads=32, num_key_value_heads=8, head_dim=64, rms_norm_eps=1e-5, rope_theta=500000.0,
+SHAPE = {"--hidden": 2048, "--layers": 16, "--heads": 32, "--kv-heads": 8, "--head-dim": 64, "--inner": 8192}
+for _o in SHAPE:
+    if _o in sys.argv:
+        _i = sys.argv.index(_o)
+        SHAPE[_o] = int(sys.argv[_i + 1])
+        del sys.argv[_i:_i + 2]
+HID, NLAYER = SHAPE["--hidden"], SHAPE["--layers"]
+_pos = [a for a in sys.argv[1:] if not a.startswith("--")]
+B = int(_pos[0]) if len(_pos) > 0 else 8
+L = int(_pos[1]) if len(_pos) > 1 else 1024
+steps = int(_pos[2]) if len(_pos) > 2 else 5
+cfg = dict(model_type="llama", vocab_size=128256, hidden_size=HID, intermediate_size=SHAPE["--inner"], num_hidden_layers=NLAYER,
+           num_attention_heads=SHAPE["--heads"], num_key_value_heads=SHAPE["--kv-heads"], head_dim=SHAPE["--head-dim"],
+           rms_norm_eps=1e-5, rope_theta=500000.0,
            rope_scaling=dict(rope_type="llama3", factor=32.0, low_freq_factor=1.0, high_freq_factor=4.0,
                              original_max_position_embeddings=8192), tie_word_embeddings=True)
 d = tempfile.mkdtemp(prefix="kalle_llama_")
@@ -24,7 +35,7 @@ class Tok:
 dev = torch.device("cuda")
 torch.manual_seed(0)
 with torch.device(dev):
-    m = Llasa({"llm_model_name_or_path": d, "latent_dim": 64, "audio_proj_dim": 2048}, Tok(), use_flash_attention=False)
+    m = Llasa({"llm_model_name_or_path": d, "latent_dim": 64, "audio_proj_dim": HID}, Tok(), use_flash_attention=False)
 INFER_ONLY = "--infer-only" in sys.argv      # generation with the KV cache only (for profiling the decode step)
 tr = None if INFER_ONLY else DataParallelTrainer(m, lr=1e-5, optimizer="AdamW", weight_decay=0.01)
 nparam = sum(p.numel() for p in m.parameters())
@@ -52,10 +63,10 @@ for _ in range(0 if INFER_ONLY else steps):
 torch.cuda.synchronize()
 dt = (time.perf_counter() - t0) / steps
 # algorithmic FLOPs: 6 * (non-embedding params) per token + attention 12 * L * D per token per layer (causal: half)
-nonemb = nparam - 128264 * 2048
-fl = (6.0 * nonemb + 16 * 12.0 * L * 2048 * 0.5) * B * L
+nonemb = nparam - 128264 * HID
+fl = (6.0 * nonemb + NLAYER * 12.0 * L * HID * 0.5) * B * L
 if not INFER_ONLY:
-  print(f"Llasa Llama-3.2-1B-shape train step B={B} L={L}: {dt*1e3:.1f} ms/step, {B*L/dt:.0f} tokens/s, "
+  print(f"Llasa {'Llama-3.2-1B-shape' if HID == 2048 and NLAYER == 16 else f'hidden-{HID}-x-{NLAYER}-layers'} train step B={B} L={L}: {dt*1e3:.1f} ms/step, {B*L/dt:.0f} tokens/s, "
         f"{B*L/12.5/dt:.0f} audio-s/s (12.5 Hz frames), {fl/dt/1e12:.0f} TFLOP/s algorithmic, params {nparam/1e9:.2f} B, "
         f"loss {out['audio_loss'].item():.3f}")
 
