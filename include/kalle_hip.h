@@ -86,12 +86,22 @@ int kalle_gemm_bf16(const void* A, int64_t lda, int a_kmajor, const void* B, int
                     void* C, int64_t ldc, int c_dtype, int M, int N, int K,
                     const kalle_gemm_epilogue* ep, void* stream);
 
-/* which kernel the calling thread's most recent kalle_gemm_bf16 used: low byte 1 = gemm_bf16_kernel (128x128,
- * register-staged, any shape), 2 = gemm2_kernel (256x128, LDS-DMA 3-stage ring, K % 8 == 0), 3 = gemm3_kernel (256x256, 2 stages),
- * 4 = few-rows K slices (slabs + finishing pass), 5 = small tiles with two wave groups (gemm2_ks2_kernel); for 1-4 bits 8-23 =
- * split-K factor and bit 24 = mixed split-K (3 only: some tiles are cut into one K slice fewer than bits 8-23 say), for 5
- * bits 8-11 / 12-15 = tile rows / columns in units of 64, bits 16.. = K slices */
+/* which kernel the calling thread's most recent kalle_gemm_bf16 launched (unchanged by a call that returned an error before
+ * launching): low byte = family: 1 = gemm_bf16_kernel (128x128, register-staged, any shape), 2 = gemm2_kernel (256x128, LDS-DMA
+ * 3-stage ring, K % 8 == 0), 3 = gemm3_kernel (256x256, 2 stages), 4 = few-rows K slices (gemm2_kernel into slabs + finishing
+ * pass), 5 = small tiles with two wave groups (gemm2_ks2_kernel).  For 2 and 3 bits 8-23 = split-K factor (atomic adds into C
+ * when > 1) and bit 24 = mixed split-K (3 only: some tiles are cut into one K slice fewer than bits 8-23 say); 1 reports no
+ * factor (0) and 4 always 1 (its slab count is not reported); for 5 bits 8-11 / 12-15 = tile rows / columns in units of 64,
+ * bits 16.. = K slices (more than one: slabs + finishing pass).
+ * kalle_gemm_plan is the same planner as a pure host query: the arguments of kalle_gemm_bf16 without `stream` (pointers are
+ * tested for null and alignment only, never read), the same argument checks and return codes; on success *plan is the word
+ * that kalle_gemm_bf16 would leave now on this thread, otherwise *plan is left alone.  It launches nothing, needs no device,
+ * does not change kalle_gemm_last_plan and leaves the thread's cache of mixed split-K plans as it found it (kalle_gemm_bf16
+ * enters the plans it finds: a weight gradient's plan then serves every K of its 1024-deep bucket on that thread). */
 int kalle_gemm_last_plan(void);
+int kalle_gemm_plan(const void* A, int64_t lda, int a_kmajor, const void* B, int64_t ldb, int b_kmajor,
+                    void* C, int64_t ldc, int c_dtype, int M, int N, int K,
+                    const kalle_gemm_epilogue* ep, int* plan);
 
 /* diagnostics (tools/gemm_stamps.py), never set by the product path: with a non-NULL device buffer of
  * [workgroups][2][8] uint64 the 256x256 kernel's wave 0 / wave 7 leave s_memrealtime stamps (100 MHz) at: 0 entry, 1 first

@@ -256,11 +256,8 @@ int launch(const GemmParams& p, hipStream_t st) {
 
 }  // namespace
 
-int kalle_gemm_v1_launch(const GemmParams& pin, bool a_km, bool b_km, bool f32, hipStream_t st) {
-    GemmParams p = pin;
-    p.tiles_m = (p.M + BM - 1) / BM;
-    p.tiles_n = (p.N + BN - 1) / BN;
-    p.group_m = p.tiles_m < 8 ? p.tiles_m : 8;
+int launch_gemm_v1(const GemmParams& p, bool a_km, bool b_km, bool f32, hipStream_t st) {
+    static_assert(BM == 128 && BN == 128, "plan_gemm (gemm2.hip) counts family 1's tiles as 128 x 128");
     if (!a_km && !b_km) return f32 ? launch<false, false, true>(p, st) : launch<false, false, false>(p, st);
     if (!a_km && b_km) return f32 ? launch<false, true, true>(p, st) : launch<false, true, false>(p, st);
     if (a_km && !b_km) return f32 ? launch<true, false, true>(p, st) : launch<true, false, false>(p, st);

@@ -1181,7 +1181,7 @@ int launch2_layout(const GemmParams& p, bool a_km, bool b_km, bool f32, hipStrea
 }
 
 // Makespan model of a split-K weight-gradient dispatch on 256 CUs, shared by the two planners (mixed split-K in
-// kalle_gemm_v2_launch, kalle_gemm_wgrad_group): workgroups go out in grid order, each to the CU that falls free first, and one
+// plan_big_tiles, plan_group): workgroups go out in grid order, each to the CU that falls free first, and one
 // over k K-tiles takes 10 us + 1.6 us per K-tile (fitted to measured weight-gradient GEMMs).  Each planner adds its own atomic traffic.
 struct CuReplay {
     double cu[256] = {};                        // min-heap of the times at which the CUs fall free
@@ -1209,121 +1209,238 @@ struct CuReplay {
 
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-}  // namespace
+// ================================================================================================ kalle_gemm_bf16: the planner
+// plan_gemm decides what a call launches from its shapes, layouts and from WHICH epilogue fields are set; it makes no HIP call
+// and reads no operand.  The three cost models below are asked in order of preference and fill `g` only when they take the
+// call; what none of them takes goes to the 128 x 128 kernel of gemm.hip (family 1).
 
-int kalle_gemm_v2_launch(GemmParams& p, bool a_km, bool b_km, bool f32, hipStream_t st) {
-    p.mix_na = -1;
-    p.mix_sa = 0;
-    if (p.K & 7) return KALLE_ERR_UNSUPPORTED;        // (a ragged last K-tile is fine: K % 64 in multiples of 8)
-    if (a_km && !b_km) return KALLE_ERR_UNSUPPORTED;
-    if (a_km && !f32) return KALLE_ERR_UNSUPPORTED;
-    if (p.M < 256 || p.N < 128) return KALLE_ERR_UNSUPPORTED;
-    if (a_km && (p.M & 7)) return KALLE_ERR_UNSUPPORTED;
+// the accepted plan: bm x bn tiles in groups of up to 4 tile rows, K-tiles in `splits` slices of equal length (no empty last one)
+void fill_plan(GemmPlan& g, int family, const GemmParams& p, int bm, int bn, int splits) {
     const int nk = (p.K + BK2 - 1) / BK2;
-    if (p.glu_mode) {
-        // fused SwiGLU: 256 x 256 kernel only; forward pairs x/gate weight rows inside each wave's 64 tile columns
-        if (a_km || f32 || p.gate || p.residual || p.row_mask || p.c_rpb || p.accumulate) return KALLE_ERR_UNSUPPORTED;
-        if (p.glu_inner % 128 || p.N != (p.glu_mode == 1 ? 2 * p.glu_inner : p.glu_inner)) return KALLE_ERR_UNSUPPORTED;
-        if (p.glu_mode == 1 && b_km) return KALLE_ERR_UNSUPPORTED;
-        if (p.glu_mode == 2 && (!b_km || p.bias)) return KALLE_ERR_UNSUPPORTED;
-        p.tiles_m = (p.M + 255) / 256;
-        p.tiles_n = p.glu_mode == 1 ? p.glu_inner / 128 : (p.glu_inner + 255) / 256;
-        p.tile_n = 256;
-        p.group_m = p.tiles_m < 4 ? p.tiles_m : 4;
-        p.splits = 1;
-        p.atomic = 0;
-        p.ktiles_per_split = nk;
-        if (p.glu_mode == 1) return launch3<false, false, false, 1>(p, st);
-        return launch3<false, true, false, 2>(p, st);
-    }
-    const bool plain = !p.bias && !p.gate && !p.residual && !p.row_mask && p.c_rpb == 0;
-    const bool can_split = f32 && plain && a_km && nk >= 16;
-    // modelled time of a configuration: MFMA work / (tile rate x wave-quantisation efficiency) + split-K atomic bytes
-    const double flops = 2.0 * p.M * p.N * p.K;
-    double best = 1e30;
-    int best_bn = 128, best_s = 1;
-    for (int bn = 128; bn <= 256; bn += 128) {
-        if (bn == 256 && p.N < 256) continue;
-        const double rate = bn == 256 ? 1150e12 : 1000e12;
-        const int tiles = ((p.M + 255) / 256) * ((p.N + bn - 1) / bn);
-        for (int s = 1; s <= (can_split ? 16 : 1) && (s == 1 || nk / s >= 8); ++s) {
-            const int blocks = tiles * s;
-            const double eff = (double)blocks / (((blocks + 255) / 256) * 256.0);
-            const double t = flops / (rate * eff) + (s > 1 ? (double)s * p.M * p.N * 4.0 / 2.0e12 : 0.0);
-            if (t < best * 0.98) { best = t; best_bn = bn; best_s = s; }
-        }
-    }
-    // Weight gradients on the 256 x 256 kernel: mixed split-K.  `na` tiles get `sa` K slices, the others sa + 1, the longer
-    // slices are dispatched first: the last round of workgroups then consists of short slices instead of leaving most CUs idle
-    // (288 tiles x 3 slices = 3.4 rounds -> 4 with uniform splitting).  The plan comes from replaying the dispatch on 256 CUs
-    // (CuReplay, atomics at 2 TB/s) and is cached per shape.
-    if (can_split && best_bn == 256) {
-        struct Plan { int M, N, kb, sa, na; };          // kb: K-tiles / 16 (a plan is valid for any K; nearby K share it)
-        static thread_local Plan cache[32];
-        static thread_local int ncache = 0, victim = 0;
-        const Plan* hit = nullptr;
-        int sa_sel = 0, na_sel = -1;
-        for (int i = 0; i < ncache; ++i)
-            if (cache[i].M == p.M && cache[i].N == p.N && cache[i].kb == nk / 16) hit = &cache[i];
-        if (!hit) {
-            const int ntiles = ((p.M + 255) / 256) * ((p.N + 255) / 256);
-            auto replay = [&](int sa, int na) {        // makespan (us) + atomic traffic
-                CuReplay r;
-                r.run(na, nk, sa);
-                r.run(ntiles - na, nk, sa + 1);
-                const double savg = ((double)na * sa + (double)(ntiles - na) * (sa + 1)) / ntiles;
-                return r.makespan() + (savg > 1.0 ? savg * p.M * p.N * 4.0 / 2.0e12 * 1e6 : 0.0);
-            };
-            Plan best_plan{p.M, p.N, nk / 16, 0, -1};
-            double t_uniform = 1e30, t_best = 1e30;
-            const int step = ntiles / 12 > 4 ? (ntiles / 12 + 3) & ~3 : 4;
-            // uniform plans: every slice count; mixed plans: around the uniform model's choice (best_s slices)
-            for (int sl = 1; sl <= 16 && (sl == 1 || nk / sl >= 8); ++sl) {
-                const double t = replay(sl - 1, 0);
-                if (t < t_uniform) t_uniform = t;
-            }
-            for (int sa = best_s > 3 ? best_s - 3 : 1; sa <= best_s + 1 && sa <= 15; ++sa) {
-                if (nk / (sa + 1) < 8) break;
-                for (int na = step; na < ntiles; na += step) {
-                    const double t = replay(sa, na);
-                    if (t < t_best) { t_best = t; best_plan.sa = sa; best_plan.na = na; }
-                }
-            }
-            if (!(best_plan.na > 0 && t_best < 0.97 * t_uniform)) best_plan.na = -1;   // not worth leaving the uniform plan
-            if (ncache < 32) cache[ncache++] = best_plan;
-            else { cache[victim] = best_plan; victim = (victim + 1) & 31; }
-            sa_sel = best_plan.sa;
-            na_sel = best_plan.na;
-        } else {
-            sa_sel = hit->sa;
-            na_sel = hit->na;
-        }
-        if (na_sel > 0 && nk / (sa_sel + 1) < 8) na_sel = -1;    // (a cached plan of a longer K)
-        if (na_sel > 0) { p.mix_na = na_sel; p.mix_sa = sa_sel; best_s = sa_sel + 1; }
-    }
-    p.tiles_m = (p.M + 255) / 256;
-    p.tiles_n = (p.N + best_bn - 1) / best_bn;
-    p.tile_n = best_bn;
-    p.group_m = p.tiles_m < 4 ? p.tiles_m : 4;
-    p.splits = best_s;
-    p.atomic = best_s > 1;
-    if (p.atomic && !p.accumulate) {
-        if (hipMemset2DAsync(p.C, p.ldc * sizeof(float), 0, p.N * sizeof(float), p.M, st) != hipSuccess)
-            return KALLE_ERR_LAUNCH;
-    }
-    p.ktiles_per_split = (nk + p.splits - 1) / p.splits;
-    p.splits = (nk + p.ktiles_per_split - 1) / p.ktiles_per_split;
-    if (best_bn == 256) return launch3_layout(p, a_km, b_km, f32, st);
-    return launch2_layout<4, 2, 4>(p, a_km, b_km, f32, st);
+    g.family = family;
+    g.tile_n = bn;
+    g.tiles_m = (p.M + bm - 1) / bm;
+    g.tiles_n = (p.N + bn - 1) / bn;
+    g.group_m = g.tiles_m < 4 ? g.tiles_m : 4;
+    g.ktiles_per_split = (nk + splits - 1) / splits;
+    g.splits = (nk + g.ktiles_per_split - 1) / g.ktiles_per_split;
 }
 
-// ---- few rows (M <= 4096): split-K into a caller-provided fp32 scratch + finishing pass -----------------------------------
+// ---- family 5: few rows, k-contiguous A (every nn.Linear of the sampling path: M = 252 for one clip with CFG) ----------------
+// One workgroup's K loop is bound by the LDS-DMA ingest of its CU (~60 GB/s: 0.8 us per 64-deep K-tile of a 256 x 128 tile), and
+// every fp32 byte a K slice parks in a slab is paid twice (1.7 TB/s effective at this size: the write-back at the kernel's end, then
+// the finishing pass) - so instead of cutting K, the OUTPUT is cut into small tiles (64 x 64 with one wave, 128 x 64, 128 x 128) until
+// about a workgroup per CU exists, each over the whole K with the full epilogue in the same launch; only K > 2048 is also cut
+// into slices (slabs + finishing pass).
+bool plan_small_tiles(const GemmParams& p, const GemmLayout& l, const void* ws, int64_t ws_bytes, GemmPlan& g) {
+    if (l.a_km || p.M > 2048 || (p.N & 63) || (l.b_km && (p.N & 127))) return false;
+    // outputs with a chip's worth of 256 x 256 tiles belong to the big-tile kernels (twice the flops per ingested byte)
+    if ((int64_t)((p.M + 255) / 256) * ((p.N + 255) / 256) >= 256) return false;
+    const int nk = (p.K + BK2 - 1) / BK2;
+    // candidate tiles, smallest first; cost (us) = K-tiles per workgroup x the ingest time of the tiles sharing a CU + slab traffic
+    static const int cand[3][2] = {{1, 1}, {2, 1}, {2, 2}};
+    int wm = 0, wn = 0, splits = 1;
+    double best = 1e30;
+    for (int c = 0; c < 3; ++c) {
+        const int bm = cand[c][0] * 64, bn = cand[c][1] * 64;
+        if (p.glu_mode == 1 && (p.glu_inner % (bn / 2))) continue;
+        if (l.b_km && bn < 128) continue;               // k-major weights (data gradients): 128-column tiles only
+        const int tiles = ((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn);
+        for (int sp = 1; sp <= 8; ++sp) {
+            if (sp > 1 && (nk / sp < 12 || !ws || p.glu_mode)) break;
+            if (sp > 1 && (int64_t)sp * p.M * p.N * 4 > ws_bytes) break;
+            // more than a few tile rows (training at small batch): measured against the 256-row kernels, the small tiles win only
+            // while they fit one round of workgroups and K is moderate (B = 16: 2016 x 1536 x 1536 30 -> 25 us, x 4608 64 -> 50,
+            // x 6144 78 -> 65; but 2016 x 4608 x 1536 in 2.25 rounds 57 -> 65 and K = 12288 115 -> 122)
+            if (p.M > 512 && (tiles * sp > 256 || nk > 128)) continue;
+            const double wgs = (double)tiles * sp;
+            // 64 x 64 tiles (80 KiB of LDS) fit two to a CU and share its ingest - a fractional round is the right price; the larger
+            // tiles (120 / 128 KiB) run one per CU, so 288 of them ARE two rounds (M = 504, N = 4608: 128 x 64 tiles 28.3 us where
+            // 144 tiles of 128 x 128 take 19)
+            const double rounds = c == 0 ? (wgs / 256.0 > 1.0 ? wgs / 256.0 : 1.0) : (double)(((int64_t)wgs + 255) / 256);
+            const double tk = (bm + bn) * 128.0 / 60e3;                            // us per K-tile: the CU's LDS-DMA ingest ...
+            const double tk_floor = 0.30;                                          // ... or barrier + fragment reads + 16 MFMAs per wave
+            double t = 2.5 + rounds * (3.0 + (double)((nk + sp - 1) / sp) * (tk > tk_floor ? tk : tk_floor));
+            // slabs: second launch + write + read back.  (The slabs of these shapes are a few MB that the finishing pass finds in L2 /
+            // Infinity Cache: 3 TB/s fits M = 252 ... 1008 x 1536 x 6144, where 1.7 TB/s kept M = 504 on whole-K 64 x 64 tiles at 37 us)
+            if (sp > 1) t += 4.0 + 2.0 * sp * p.M * (double)p.N * 4.0 / 3.0e6;
+            if (t < best) { best = t; wm = cand[c][0]; wn = cand[c][1]; splits = sp; }
+        }
+    }
+    if (!wm) return false;
+    fill_plan(g, 5, p, wm * 64, wn * 64, splits);
+    g.wm = wm; g.wn = wn;
+    g.slabs = g.splits > 1;
+    return true;
+}
+
+// ---- family 4: few rows (M <= 4096), split-K into the caller's fp32 scratch + finishing pass --------------------------------
 // A GEMM whose output has only a few 256-row tile rows cannot fill 256 CUs with output tiles: the DiT forward at generation
 // batch sizes (B = 1 with CFG: 252 rows) gives 12 - 96 tiles, a B = 16 train step 96 - 384.  K is cut into slices that add
 // their partial tiles as plain fp32 slabs [slice][M][N] into the caller's scratch; the finishing pass sums the slabs in slice order
 // (bitwise reproducible) and applies the whole epilogue (alpha, bias, adaLN gate, row mask, residual, accumulate, output-row
-// remap, fused SwiGLU forward) while writing C.
-namespace {
+// remap, fused SwiGLU forward) while writing C.  Refuses the shapes that are better served by the big tiles.
+bool plan_few_rows(const GemmParams& p, const GemmLayout& l, const void* ws, int64_t ws_bytes, GemmPlan& g) {
+    if (l.a_km || !ws || !al16(ws) || p.M > 4096) return false;
+    const int nk = (p.K + BK2 - 1) / BK2;
+    // (256 x 64 tiles with 4 waves - twice the column tiles, half the K slices - measured 5 % slower on the sampling step)
+    constexpr int bn = 128;
+    const int tiles = ((p.M + 255) / 256) * ((p.N + bn - 1) / bn);
+    if (tiles >= 192) return false;                               // enough output tiles on their own
+    int splits = (320 + tiles - 1) / tiles;                       // ~1.25 workgroups per CU
+    // at least two K-tiles per slice; with more than a couple of tile rows (training at small batch) a slice must be long
+    // enough (16 K-tiles) to pay for its slab: M x N x 4 bytes written and read back per slice
+    const int min_per = p.M > 512 ? 16 : 2;
+    if (splits > nk / min_per) splits = nk / min_per;
+    const int64_t slab = (int64_t)p.M * p.N;
+    if (splits > ws_bytes / (4 * slab)) splits = (int)(ws_bytes / (4 * slab));   // one fp32 [M][N] slab per slice
+    if (splits < 2) return false;
+    fill_plan(g, 4, p, 256, bn, splits);
+    g.slabs = true;
+    return true;
+}
+
+// ---- families 2 and 3: 256-row tiles, 128 or 256 columns; weight gradients (k-major A, plain fp32 C) may split K atomically ----
+bool plan_big_tiles(const GemmParams& p, const GemmLayout& l, bool remember, GemmPlan& g) {
+    // (a ragged last K-tile is fine: K % 64 in multiples of 8)
+    if ((p.K & 7) || (l.a_km && (!l.b_km || !l.f32)) || p.M < 256 || p.N < 128) return false;
+    const int nk = (p.K + BK2 - 1) / BK2;
+    int best_bn = 256, best_s = 1;                    // fused SwiGLU: the 256 x 256 kernel only, whole K
+    if (!p.glu_mode) {
+        const bool plain = !p.bias && !p.gate && !p.residual && !p.row_mask && p.c_rpb == 0;
+        const bool can_split = l.f32 && plain && l.a_km && nk >= 16;
+        // modelled time of a configuration: MFMA work / (tile rate x wave-quantisation efficiency) + split-K atomic bytes
+        const double flops = 2.0 * p.M * p.N * p.K;
+        double best = 1e30;
+        best_bn = 128;
+        for (int bn = 128; bn <= 256; bn += 128) {
+            if (bn == 256 && p.N < 256) continue;
+            const double rate = bn == 256 ? 1150e12 : 1000e12;
+            const int tiles = ((p.M + 255) / 256) * ((p.N + bn - 1) / bn);
+            for (int s = 1; s <= (can_split ? 16 : 1) && (s == 1 || nk / s >= 8); ++s) {
+                const int blocks = tiles * s;
+                const double eff = (double)blocks / (((blocks + 255) / 256) * 256.0);
+                const double t = flops / (rate * eff) + (s > 1 ? (double)s * p.M * p.N * 4.0 / 2.0e12 : 0.0);
+                if (t < best * 0.98) { best = t; best_bn = bn; best_s = s; }
+            }
+        }
+        // Weight gradients on the 256 x 256 kernel: mixed split-K.  `na` tiles get `sa` K slices, the others sa + 1, the longer
+        // slices are dispatched first: the last round of workgroups then consists of short slices instead of leaving most CUs idle
+        // (288 tiles x 3 slices = 3.4 rounds -> 4 with uniform splitting).  The plan comes from replaying the dispatch on 256 CUs
+        // (CuReplay, atomics at 2 TB/s) and is cached per shape and thread: a fresh one is entered into the cache only with
+        // `remember` (the entry point; the host query leaves the cache as it found it).
+        if (can_split && best_bn == 256) {
+            struct Plan { int M, N, kb, sa, na; };          // kb: K-tiles / 16 (a plan is valid for any K; nearby K share it)
+            static thread_local Plan cache[32];
+            static thread_local int ncache = 0, victim = 0;
+            const Plan* hit = nullptr;
+            for (int i = 0; i < ncache; ++i)
+                if (cache[i].M == p.M && cache[i].N == p.N && cache[i].kb == nk / 16) hit = &cache[i];
+            Plan mixed{p.M, p.N, nk / 16, 0, -1};
+            if (hit) {
+                mixed = *hit;
+            } else {
+                const int ntiles = ((p.M + 255) / 256) * ((p.N + 255) / 256);
+                auto replay = [&](int sa, int na) {        // makespan (us) + atomic traffic
+                    CuReplay r;
+                    r.run(na, nk, sa);
+                    r.run(ntiles - na, nk, sa + 1);
+                    const double savg = ((double)na * sa + (double)(ntiles - na) * (sa + 1)) / ntiles;
+                    return r.makespan() + (savg > 1.0 ? savg * p.M * p.N * 4.0 / 2.0e12 * 1e6 : 0.0);
+                };
+                double t_uniform = 1e30, t_best = 1e30;
+                const int step = ntiles / 12 > 4 ? (ntiles / 12 + 3) & ~3 : 4;
+                // uniform plans: every slice count; mixed plans: around the uniform model's choice (best_s slices)
+                for (int sl = 1; sl <= 16 && (sl == 1 || nk / sl >= 8); ++sl) {
+                    const double t = replay(sl - 1, 0);
+                    if (t < t_uniform) t_uniform = t;
+                }
+                for (int sa = best_s > 3 ? best_s - 3 : 1; sa <= best_s + 1 && sa <= 15; ++sa) {
+                    if (nk / (sa + 1) < 8) break;
+                    for (int na = step; na < ntiles; na += step) {
+                        const double t = replay(sa, na);
+                        if (t < t_best) { t_best = t; mixed.sa = sa; mixed.na = na; }
+                    }
+                }
+                if (!(mixed.na > 0 && t_best < 0.97 * t_uniform)) mixed.na = -1;   // not worth leaving the uniform plan
+                if (remember) {
+                    if (ncache < 32) cache[ncache++] = mixed;
+                    else { cache[victim] = mixed; victim = (victim + 1) & 31; }
+                }
+            }
+            // (nk / (sa + 1) < 8: a cached plan of a longer K)
+            if (mixed.na > 0 && nk / (mixed.sa + 1) >= 8) { g.mix_na = mixed.na; g.mix_sa = mixed.sa; best_s = mixed.sa + 1; }
+        }
+    }
+    fill_plan(g, best_bn == 256 ? 3 : 2, p, 256, best_bn, best_s);
+    g.atomic = best_s > 1;
+    g.clear_c = g.atomic && !p.accumulate;
+    return true;
+}
+
+// Argument checks + plan of one kalle_gemm_bf16 call.  `p` and `g` are outputs: the kernel parameters built from the arguments
+// (but for the tile fields, which stay 0 until launch_gemm copies them from the plan) and the plan.  (Inlined into its two
+// callers: out of line it costs the entry point 20 ns per call, a quarter of the whole dispatch.)
+__forceinline__ int plan_gemm(const void* A, int64_t lda, int a_kmajor, const void* B, int64_t ldb, int b_kmajor, void* C, int64_t ldc, int c_dtype,
+              int M, int N, int K, const kalle_gemm_epilogue* ep, bool remember, GemmParams& p, GemmPlan& g) {
+    if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0) return KALLE_ERR_ARG;
+    if ((N & 7) || (lda & 7) || (ldb & 7) || (ldc & 7)) return KALLE_ERR_ARG;
+    if (((!a_kmajor || !b_kmajor) && (K & 7)) || (a_kmajor && (M & 7))) return KALLE_ERR_ARG;
+    if (!al16(A) || !al16(B) || !al16(C)) return KALLE_ERR_ARG;
+    if (c_dtype != KALLE_BF16 && c_dtype != KALLE_F32) return KALLE_ERR_ARG;
+    p = GemmParams{};
+    p.A = static_cast<const bf16_t*>(A); p.B = static_cast<const bf16_t*>(B); p.C = C;
+    p.lda = lda; p.ldb = ldb; p.ldc = ldc;
+    p.M = M; p.N = N; p.K = K;
+    p.alpha = 1.f;
+    p.rows_per_batch = 1;
+    g = GemmPlan{};
+    const GemmLayout l{a_kmajor != 0, b_kmajor != 0, c_dtype == KALLE_F32};
+    g.lay = l;
+    bool fused3 = true, fused4 = true, fused5 = true;       // the families whose kernels take the call's fused SwiGLU (none: all)
+    if (ep) {
+        p.bias = ep->bias;
+        p.gate = ep->gate; p.ldg = ep->ldg; p.rows_per_batch = ep->rows_per_batch > 0 ? ep->rows_per_batch : 1;
+        p.residual = ep->residual; p.ldr = ep->ldr;
+        p.accumulate = ep->accumulate;
+        if (ep->alpha != 0.f) p.alpha = ep->alpha;
+        p.row_mask = ep->row_mask;
+        p.c_rpb = ep->c_rows_per_batch; p.c_brows = ep->c_batch_rows; p.c_roff = ep->c_row_offset;
+        p.glu_mode = ep->glu_mode; p.glu_inner = ep->glu_inner; p.glu_aux = ep->glu_aux; p.glu_dbias = ep->glu_dbias;
+        if (p.glu_mode && (p.glu_mode > 2 || p.glu_mode < 0 || !p.glu_aux || p.glu_inner <= 0)) return KALLE_ERR_ARG;
+        if (p.glu_mode) {
+            // Fused SwiGLU, the whole rule.  The fused epilogues apply the bias (forward) or alpha (backward) and no other field: a
+            // call that asks for more is refused before any kernel runs, so that the caller un-fuses instead of losing a field.
+            if (p.gate || p.residual || p.row_mask || p.c_rpb || p.accumulate || l.f32 || l.a_km ||
+                (p.glu_mode == 1 && (p.alpha != 1.f || l.b_km || N != 2 * p.glu_inner)) ||
+                (p.glu_mode == 2 && (p.bias || !l.b_km || N != p.glu_inner)))
+                return KALLE_ERR_UNSUPPORTED;
+            // The 256 x 256 kernel pairs the x / gate weight rows inside each wave's 64 tile columns; forward only: the small tiles
+            // pair them inside half a tile's columns (32 and up: plan_small_tiles skips the tiles whose half does not divide
+            // glu_inner, and never cuts a fused call along K), the few-rows finishing pass handles 4 columns at a time.
+            fused3 = p.glu_inner % 128 == 0;
+            fused5 = p.glu_mode == 1 && p.glu_inner % 32 == 0;
+            fused4 = p.glu_mode == 1 && p.glu_inner % 4 == 0;
+        }
+        if (p.accumulate && !l.f32) return KALLE_ERR_ARG;
+        if ((p.bias && !al16(p.bias)) || (p.gate && (!al16(p.gate) || (p.ldg & 3))) ||
+            (p.residual && (!al16(p.residual) || (p.ldr & 3))))
+            return KALLE_ERR_ARG;
+    }
+    const void* ws = ep ? ep->workspace : nullptr; const int64_t ws_bytes = ep ? ep->workspace_bytes : 0;
+    if (!(fused5 && plan_small_tiles(p, l, ws, ws_bytes, g)) && !(fused4 && plan_few_rows(p, l, ws, ws_bytes, g)) &&
+        !(fused3 && plan_big_tiles(p, l, remember, g))) {
+        if (p.glu_mode) return KALLE_ERR_UNSUPPORTED;   // no kernel with this fused SwiGLU: the caller un-fuses
+        g.family = 1;
+        g.tiles_m = (M + 127) / 128;
+        g.tiles_n = (N + 127) / 128;
+        g.group_m = g.tiles_m < 8 ? g.tiles_m : 8;
+    }
+    g.word = gemm_plan_word(g);
+    return KALLE_OK;
+}
+
+// ================================================================================================ kalle_gemm_bf16: the launcher
 template <bool C_F32>
 __global__ __launch_bounds__(256) void gemm_finish_kernel(GemmParams p, const float* __restrict__ ws, int nslab) {
     const int64_t slab = (int64_t)p.M * p.N;
@@ -1383,14 +1500,7 @@ __global__ __launch_bounds__(256) void gemm_finish_kernel(GemmParams p, const fl
         }
     }
 }
-}  // namespace
 
-// ---- few rows, k-contiguous operands (every nn.Linear of the sampling path: M = 252 for one clip with CFG) -------------------
-// One workgroup's K loop is bound by the LDS-DMA ingest of its CU (~60 GB/s: 0.8 us per 64-deep K-tile of a 256 x 128 tile), and
-// every fp32 byte a K slice parks in a slab is paid twice (1.7 TB/s effective at this size: the write-back at the kernel's end, then
-// the finishing pass) - so instead of cutting K, the OUTPUT is cut into small tiles (64 x 64 with one wave, 128 x 64, 128 x 128) until
-// about a workgroup per CU exists, each over the whole K with the full epilogue in the same launch; only K > 2048 is also cut
-// into slices (slabs + finishing pass).  `cfg` packs the choice for kalle_gemm_last_plan: 5 | WM << 8 | WN << 12 | splits << 16.
 template <bool C_F32, int GLU>
 int launch_skinny_tile(int wm, int wn, const GemmParams& q, hipStream_t st, bool b_km = false) {
     if (b_km) {             // k-major weights (data gradients): 128-column tiles only
@@ -1406,125 +1516,69 @@ int launch_skinny_tile(int wm, int wn, const GemmParams& q, hipStream_t st, bool
     return KALLE_ERR_UNSUPPORTED;
 }
 
-int kalle_gemm_skinny_launch(const GemmParams& pin, bool a_km, bool b_km, bool f32, void* ws, int64_t ws_bytes, hipStream_t st,
-                             int* cfg) {
-    if (a_km || pin.M > 2048 || (pin.K & 7) || (pin.N & 63) || pin.atomic) return KALLE_ERR_UNSUPPORTED;
-    if (b_km && ((pin.N & 127) || pin.glu_mode)) return KALLE_ERR_UNSUPPORTED;
-    if (pin.glu_mode == 2 || (pin.glu_mode == 1 && (f32 || pin.N != 2 * pin.glu_inner || (pin.glu_inner & 31) || pin.gate ||
-                                                    pin.residual || pin.row_mask || pin.c_rpb || pin.accumulate)))
-        return KALLE_ERR_UNSUPPORTED;
-    // outputs with a chip's worth of 256 x 256 tiles belong to the big-tile kernels (twice the flops per ingested byte)
-    if ((int64_t)((pin.M + 255) / 256) * ((pin.N + 255) / 256) >= 256) return KALLE_ERR_UNSUPPORTED;
-    const int nk = (pin.K + BK2 - 1) / BK2;
-    const int ncol = pin.glu_mode == 1 ? pin.glu_inner * 2 : pin.N;
-    // candidate tiles, smallest first; cost (us) = K-tiles per workgroup x the ingest time of the tiles sharing a CU + slab traffic
-    static const int cand[3][2] = {{1, 1}, {2, 1}, {2, 2}};
-    int wm = 0, wn = 0, splits = 1;
-    double best = 1e30;
-    for (int c = 0; c < 3; ++c) {
-        const int bm = cand[c][0] * 64, bn = cand[c][1] * 64;
-        if (pin.glu_mode == 1 && (pin.glu_inner % (bn / 2))) continue;
-        if (b_km && bn < 128) continue;
-        const int tiles = ((pin.M + bm - 1) / bm) * ((ncol + bn - 1) / bn);
-        for (int sp = 1; sp <= 8; ++sp) {
-            if (sp > 1 && (nk / sp < 12 || !ws || pin.glu_mode)) break;
-            if (sp > 1 && (int64_t)sp * pin.M * pin.N * 4 > ws_bytes) break;
-            // more than a few tile rows (training at small batch): measured against the 256-row kernels, the small tiles win only
-            // while they fit one round of workgroups and K is moderate (B = 16: 2016 x 1536 x 1536 30 -> 25 us, x 4608 64 -> 50,
-            // x 6144 78 -> 65; but 2016 x 4608 x 1536 in 2.25 rounds 57 -> 65 and K = 12288 115 -> 122)
-            if (pin.M > 512 && (tiles * sp > 256 || nk > 128)) continue;
-            const double wgs = (double)tiles * sp;
-            // 64 x 64 tiles (80 KiB of LDS) fit two to a CU and share its ingest - a fractional round is the right price; the larger
-            // tiles (120 / 128 KiB) run one per CU, so 288 of them ARE two rounds (M = 504, N = 4608: 128 x 64 tiles 28.3 us where
-            // 144 tiles of 128 x 128 take 19)
-            const double rounds = c == 0 ? (wgs / 256.0 > 1.0 ? wgs / 256.0 : 1.0) : (double)(((int64_t)wgs + 255) / 256);
-            const double tk = (bm + bn) * 128.0 / 60e3;                            // us per K-tile: the CU's LDS-DMA ingest ...
-            const double tk_floor = 0.30;                                          // ... or barrier + fragment reads + 16 MFMAs per wave
-            double t = 2.5 + rounds * (3.0 + (double)((nk + sp - 1) / sp) * (tk > tk_floor ? tk : tk_floor));
-            // slabs: second launch + write + read back.  (The slabs of these shapes are a few MB that the finishing pass finds in L2 /
-            // Infinity Cache: 3 TB/s fits M = 252 ... 1008 x 1536 x 6144, where 1.7 TB/s kept M = 504 on whole-K 64 x 64 tiles at 37 us)
-            if (sp > 1) t += 4.0 + 2.0 * sp * pin.M * (double)pin.N * 4.0 / 3.0e6;
-            if (t < best) { best = t; wm = cand[c][0]; wn = cand[c][1]; splits = sp; }
-        }
+// the plan's tile fields into the kernel's parameters
+void set_plan(GemmParams& q, const GemmPlan& g) {
+    q.tile_n = g.tile_n; q.tiles_m = g.tiles_m; q.tiles_n = g.tiles_n; q.group_m = g.group_m;
+    q.splits = g.splits; q.ktiles_per_split = g.ktiles_per_split;
+    q.mix_na = g.mix_na; q.mix_sa = g.mix_sa;
+    q.atomic = g.atomic;
+}
+
+// parameters of a launch whose K slices go to fp32 slabs in `ws` (plain epilogue-free stores)
+GemmParams slab_params(const GemmParams& p, void* ws) {
+    GemmParams q{};
+    q.A = p.A; q.B = p.B; q.C = ws;
+    q.lda = p.lda; q.ldb = p.ldb; q.ldc = p.N;
+    q.M = p.M; q.N = p.N; q.K = p.K;
+    q.alpha = 1.f;
+    q.rows_per_batch = 1;
+    q.slab_stride = (int64_t)p.M * p.N;
+    return q;
+}
+
+// families 1, 2, 3 and 5.  What depends on the device (CU count, stream capture, the persistent kernel's counter set) is
+// decided in launch3.  (The order in which the launchers are named, here and in launch_gemm, is the order of the kernels in the
+// code object.)
+int launch_tiles(const GemmParams& q, const GemmPlan& g, bool f32, hipStream_t st) {
+    switch (g.family) {
+    case 1: return launch_gemm_v1(q, g.lay.a_km, g.lay.b_km, f32, st);
+    case 3:
+        if (q.glu_mode == 1) return launch3<false, false, false, 1>(q, st);
+        if (q.glu_mode == 2) return launch3<false, true, false, 2>(q, st);
+        return launch3_layout(q, g.lay.a_km, g.lay.b_km, f32, st);
+    case 2: return launch2_layout<4, 2, 4>(q, g.lay.a_km, g.lay.b_km, f32, st);
+    case 5:
+        if (q.glu_mode == 1) return launch_skinny_tile<false, 1>(g.wm, g.wn, q, st);
+        return f32 ? launch_skinny_tile<true, 0>(g.wm, g.wn, q, st, g.lay.b_km) : launch_skinny_tile<false, 0>(g.wm, g.wn, q, st, g.lay.b_km);
     }
-    if (!wm) return KALLE_ERR_UNSUPPORTED;
-    const int bm = wm * 64, bn = wn * 64;
-    GemmParams q = pin;
-    q.tiles_m = (pin.M + bm - 1) / bm;
-    q.tiles_n = (ncol + bn - 1) / bn;
-    q.tile_n = bn;
-    q.group_m = q.tiles_m < 4 ? q.tiles_m : 4;
-    q.atomic = 0;
-    q.mix_na = -1;
-    q.ktiles_per_split = (nk + splits - 1) / splits;
-    q.splits = (nk + q.ktiles_per_split - 1) / q.ktiles_per_split;
-    q.slab_stride = 0;
-    if (cfg) *cfg = 5 | (wm << 8) | (wn << 12) | (q.splits << 16);
-    if (q.splits == 1) {
-        if (pin.glu_mode == 1) return launch_skinny_tile<false, 1>(wm, wn, q, st);
-        return f32 ? launch_skinny_tile<true, 0>(wm, wn, q, st, b_km) : launch_skinny_tile<false, 0>(wm, wn, q, st, b_km);
-    }
-    // K slices into fp32 slabs (plain epilogue-free stores), then the finishing pass with the caller's epilogue
-    GemmParams sl{};
-    sl.A = pin.A; sl.B = pin.B; sl.C = ws;
-    sl.lda = pin.lda; sl.ldb = pin.ldb; sl.ldc = pin.N;
-    sl.M = pin.M; sl.N = pin.N; sl.K = pin.K;
-    sl.alpha = 1.f;
-    sl.rows_per_batch = 1;
-    sl.tiles_m = q.tiles_m; sl.tiles_n = q.tiles_n; sl.tile_n = bn; sl.group_m = q.group_m;
-    sl.mix_na = -1;
-    sl.ktiles_per_split = q.ktiles_per_split; sl.splits = q.splits;
-    sl.slab_stride = (int64_t)pin.M * pin.N;
-    const int rc = launch_skinny_tile<true, 0>(wm, wn, sl, st, b_km);
-    if (rc != KALLE_OK) return rc;
-    const int64_t work = (int64_t)pin.M * (pin.N >> 2);
+    return KALLE_ERR_UNSUPPORTED;
+}
+
+// the finishing pass: sums the `nslab` slabs in slice order and applies the caller's epilogue
+int launch_finish(const GemmParams& p, bool f32, const float* ws, int nslab, hipStream_t st) {
+    const int64_t work = (int64_t)p.M * ((p.glu_mode == 1 ? p.glu_inner : p.N) >> 2);
     const int grid = (int)((work + 255) / 256 > 2048 ? 2048 : (work + 255) / 256);
-    if (f32) KALLE_LAUNCH(gemm_finish_kernel<true>, dim3(grid), dim3(256), 0, st, pin, static_cast<const float*>(ws), q.splits);
-    else KALLE_LAUNCH(gemm_finish_kernel<false>, dim3(grid), dim3(256), 0, st, pin, static_cast<const float*>(ws), q.splits);
+    if (f32) KALLE_LAUNCH(gemm_finish_kernel<true>, dim3(grid), dim3(256), 0, st, p, ws, nslab);
+    else KALLE_LAUNCH(gemm_finish_kernel<false>, dim3(grid), dim3(256), 0, st, p, ws, nslab);
     return kalle_check_launch();
 }
 
-// returns KALLE_ERR_UNSUPPORTED when the shape is better served by the ordinary path (the caller goes on to it)
-int kalle_gemm_few_rows_launch(const GemmParams& pin, bool a_km, bool b_km, bool f32, void* ws, int64_t ws_bytes, hipStream_t st) {
-    if (a_km || !ws || pin.M > 4096 || (pin.K & 7) || (pin.N & 7)) return KALLE_ERR_UNSUPPORTED;
-    if (pin.glu_mode == 2 || (pin.glu_mode == 1 && (b_km || f32 || pin.N != 2 * pin.glu_inner || (pin.glu_inner & 3))))
-        return KALLE_ERR_UNSUPPORTED;
-    if (reinterpret_cast<uintptr_t>(ws) & 15) return KALLE_ERR_UNSUPPORTED;
-    const int nk = (pin.K + BK2 - 1) / BK2;
-    // (256 x 64 tiles with 4 waves - twice the column tiles, half the K slices - measured 5 % slower on the sampling step)
-    constexpr int bn = 128;
-    const int tiles = ((pin.M + 255) / 256) * ((pin.N + bn - 1) / bn);
-    if (tiles >= 192) return KALLE_ERR_UNSUPPORTED;                 // enough output tiles on their own
-    int splits = (320 + tiles - 1) / tiles;                       // ~1.25 workgroups per CU
-    // at least two K-tiles per slice; with more than a couple of tile rows (training at small batch) a slice must be long
-    // enough (16 K-tiles) to pay for its slab: M x N x 4 bytes written and read back per slice
-    const int min_per = pin.M > 512 ? 16 : 2;
-    if (splits > nk / min_per) splits = nk / min_per;
-    const int64_t slab = (int64_t)pin.M * pin.N;
-    if (splits > ws_bytes / (4 * slab)) splits = (int)(ws_bytes / (4 * slab));   // one fp32 [M][N] slab per slice
-    if (splits < 2) return KALLE_ERR_UNSUPPORTED;
-    GemmParams q{};
-    q.A = pin.A; q.B = pin.B; q.C = ws;
-    q.lda = pin.lda; q.ldb = pin.ldb; q.ldc = pin.N;
-    q.M = pin.M; q.N = pin.N; q.K = pin.K;
-    q.alpha = 1.f;
-    q.rows_per_batch = 1;
-    q.tiles_m = (pin.M + 255) / 256; q.tiles_n = (pin.N + bn - 1) / bn; q.tile_n = bn;
-    q.group_m = q.tiles_m < 4 ? q.tiles_m : 4;
-    q.atomic = 0;
-    q.mix_na = -1;
-    q.ktiles_per_split = (nk + splits - 1) / splits;
-    q.splits = (nk + q.ktiles_per_split - 1) / q.ktiles_per_split;
-    q.slab_stride = slab;
-    const int rc = b_km ? launch2<false, true, true, 4, 2, 4>(q, st) : launch2<false, false, true, 4, 2, 4>(q, st);
-    if (rc != KALLE_OK) return rc;
-    GemmParams f = pin;
-    const int64_t work = (int64_t)pin.M * ((pin.glu_mode == 1 ? pin.glu_inner : pin.N) >> 2);
-    const int grid = (int)((work + 255) / 256 > 2048 ? 2048 : (work + 255) / 256);
-    if (f32) KALLE_LAUNCH(gemm_finish_kernel<true>, dim3(grid), dim3(256), 0, st, f, static_cast<const float*>(ws), q.splits);
-    else KALLE_LAUNCH(gemm_finish_kernel<false>, dim3(grid), dim3(256), 0, st, f, static_cast<const float*>(ws), q.splits);
-    return kalle_check_launch();
+// `p`: the entry point's own parameters; the plan's tile fields are written into them (or into the slab launch's)
+int launch_gemm(GemmParams& p, const GemmPlan& g, void* ws, hipStream_t st) {
+    if (g.clear_c && hipMemset2DAsync(p.C, p.ldc * sizeof(float), 0, p.N * sizeof(float), p.M, st) != hipSuccess)
+        return KALLE_ERR_LAUNCH;
+    GemmParams slab;
+    if (g.slabs) slab = slab_params(p, ws);
+    GemmParams& q = g.slabs ? slab : p;
+    set_plan(q, g);
+    const bool f32 = g.slabs || g.lay.f32;
+    const int rc = g.family != 4 ? launch_tiles(q, g, f32, st)
+                   : g.lay.b_km  ? launch2<false, true, true, 4, 2, 4>(q, st)
+                                 : launch2<false, false, true, 4, 2, 4>(q, st);
+    if (rc != KALLE_OK || !g.slabs) return rc;
+    return launch_finish(p, g.lay.f32, static_cast<const float*>(ws), g.splits, st);
 }
+}  // namespace
 
 static unsigned long long* g_stamps = nullptr;      // diagnostics only (kalle_gemm_debug_stamps)
 extern "C" int kalle_gemm_debug_stamps(void* buf) { g_stamps = static_cast<unsigned long long*>(buf); return KALLE_OK; }
@@ -1546,72 +1600,25 @@ extern "C" int kalle_debug_hold_cus(int nwg, int lds_bytes, int microseconds, vo
 static thread_local int g_last_plan = 0;
 extern "C" int kalle_gemm_last_plan(void) { return g_last_plan; }
 
+extern "C" int kalle_gemm_plan(const void* A, int64_t lda, int a_kmajor, const void* B, int64_t ldb, int b_kmajor,
+                               void* C, int64_t ldc, int c_dtype, int M, int N, int K,
+                               const kalle_gemm_epilogue* ep, int* plan) {
+    if (!plan) return KALLE_ERR_ARG;
+    GemmParams p; GemmPlan g;
+    const int rc = plan_gemm(A, lda, a_kmajor, B, ldb, b_kmajor, C, ldc, c_dtype, M, N, K, ep, false, p, g);
+    if (rc == KALLE_OK) *plan = g.word;
+    return rc;
+}
+
 extern "C" int kalle_gemm_bf16(const void* A, int64_t lda, int a_kmajor, const void* B, int64_t ldb, int b_kmajor,
                                void* C, int64_t ldc, int c_dtype, int M, int N, int K,
                                const kalle_gemm_epilogue* ep, void* stream) {
-    if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0) return KALLE_ERR_ARG;
-    if ((N & 7) || (lda & 7) || (ldb & 7) || (ldc & 7)) return KALLE_ERR_ARG;
-    if (!a_kmajor && (K & 7)) return KALLE_ERR_ARG;
-    if (!b_kmajor && (K & 7)) return KALLE_ERR_ARG;
-    if (a_kmajor && (M & 7)) return KALLE_ERR_ARG;
-    if (!al16(A) || !al16(B) || !al16(C)) return KALLE_ERR_ARG;
-    if (c_dtype != KALLE_BF16 && c_dtype != KALLE_F32) return KALLE_ERR_ARG;
-    GemmParams p{};
-    p.A = static_cast<const bf16_t*>(A);
-    p.B = static_cast<const bf16_t*>(B);
-    p.C = C;
-    p.lda = lda; p.ldb = ldb; p.ldc = ldc;
-    p.M = M; p.N = N; p.K = K;
-    p.alpha = 1.f;
-    p.rows_per_batch = 1;
-    if (ep) {
-        p.bias = ep->bias;
-        p.gate = ep->gate; p.ldg = ep->ldg; p.rows_per_batch = ep->rows_per_batch > 0 ? ep->rows_per_batch : 1;
-        p.residual = ep->residual; p.ldr = ep->ldr;
-        p.accumulate = ep->accumulate;
-        if (ep->alpha != 0.f) p.alpha = ep->alpha;
-        p.row_mask = ep->row_mask;
-        p.c_rpb = ep->c_rows_per_batch; p.c_brows = ep->c_batch_rows; p.c_roff = ep->c_row_offset;
-        p.glu_mode = ep->glu_mode; p.glu_inner = ep->glu_inner; p.glu_aux = ep->glu_aux; p.glu_dbias = ep->glu_dbias;
-        if (p.glu_mode && (p.glu_mode > 2 || p.glu_mode < 0 || !p.glu_aux || p.glu_inner <= 0)) return KALLE_ERR_ARG;
-        // the fused SwiGLU epilogues apply the bias (forward) or alpha (backward) and no other field: a call that asks for more
-        // is refused before any kernel runs, so that the caller un-fuses instead of losing a field (the few-rows finishing pass
-        // took a forward call with a gate, residual, row mask or row remap and dropped them; every forward path dropped alpha)
-        if (p.glu_mode && (p.gate || p.residual || p.row_mask || p.c_rpb || p.accumulate || c_dtype != KALLE_BF16 || a_kmajor ||
-                           (p.glu_mode == 1 && (p.alpha != 1.f || b_kmajor || N != 2 * p.glu_inner)) ||
-                           (p.glu_mode == 2 && (p.bias || !b_kmajor || N != p.glu_inner))))
-            return KALLE_ERR_UNSUPPORTED;
-        if (p.accumulate && c_dtype != KALLE_F32) return KALLE_ERR_ARG;
-        if ((p.bias && !al16(p.bias)) || (p.gate && (!al16(p.gate) || (p.ldg & 3))) ||
-            (p.residual && (!al16(p.residual) || (p.ldr & 3))))
-            return KALLE_ERR_ARG;
-    }
+    GemmParams p; GemmPlan g;
+    const int rc = plan_gemm(A, lda, a_kmajor, B, ldb, b_kmajor, C, ldc, c_dtype, M, N, K, ep, true, p, g);
+    if (rc != KALLE_OK) return rc;
+    g_last_plan = g.word;
     p.stamps = g_stamps;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool f32 = c_dtype == KALLE_F32;
-    int cfg = 0;
-    int rc = kalle_gemm_skinny_launch(p, a_kmajor != 0, b_kmajor != 0, f32, ep ? ep->workspace : nullptr,
-                                      ep ? ep->workspace_bytes : 0, st, &cfg);
-    if (rc != KALLE_ERR_UNSUPPORTED) {
-        g_last_plan = cfg;
-        return rc;
-    }
-    if (ep && ep->workspace) {
-        rc = kalle_gemm_few_rows_launch(p, a_kmajor != 0, b_kmajor != 0, f32, ep->workspace, ep->workspace_bytes, st);
-        if (rc != KALLE_ERR_UNSUPPORTED) {
-            g_last_plan = 4 | (1 << 8);
-            return rc;
-        }
-    }
-    rc = kalle_gemm_v2_launch(p, a_kmajor != 0, b_kmajor != 0, f32, st);
-    if (rc != KALLE_ERR_UNSUPPORTED) {
-        g_last_plan = (p.tile_n == 256 ? 3 : 2) | (p.splits << 8) | (p.mix_na >= 0 ? 1 << 24 : 0);
-        return rc;
-    }
-    if (p.glu_mode) return KALLE_ERR_UNSUPPORTED;   // fused SwiGLU exists only in the 256x256 kernel: caller un-fuses
-    p.tiles_n = (N + 127) / 128;
-    g_last_plan = 1;
-    return kalle_gemm_v1_launch(p, a_kmajor != 0, b_kmajor != 0, f32, st);
+    return launch_gemm(p, g, ep ? ep->workspace : nullptr, static_cast<hipStream_t>(stream));
 }
 
 // ---- kalle_gemm_wgrad_group: host side -----------------------------------------------------------------------------------

@@ -105,5 +105,33 @@ __device__ __forceinline__ void gemm_epilogue4(const GemmParams& p, int gm, int 
     }
 }
 
-int kalle_gemm_v1_launch(const GemmParams& p, bool a_km, bool b_km, bool f32, hipStream_t st);
-int kalle_gemm_v2_launch(GemmParams& p, bool a_km, bool b_km, bool f32, hipStream_t st);  // KALLE_ERR_UNSUPPORTED if n/a
+// operand layouts and output type of a call: k-major A / B, fp32 C
+struct GemmLayout { bool a_km = false, b_km = false, f32 = false; };
+
+// Host side: what one kalle_gemm_bf16 call launches.  plan_gemm (gemm2.hip) fills it from the shapes alone, launch_gemm copies
+// the tile fields into the kernel's GemmParams and launches the family's kernel.
+struct GemmPlan {
+    // 1 gemm_bf16_kernel (128 x 128), 2 gemm2_kernel (256 x 128), 3 gemm3_kernel (256 x 256), 4 gemm2_kernel over K slices
+    // (few rows), 5 gemm2_ks2_kernel (small tiles)
+    int family = 0;
+    GemmLayout lay;                                    // the kernel's template arguments (the planner's input, kept for the launcher)
+    int wm = 0, wn = 0;                                // family 5: tile rows / columns in units of 64
+    // GemmParams fields of the same names (tile_n, splits, ktiles_per_split and atomic stay 0 for family 1, which has none)
+    int tile_n = 0, tiles_m = 0, tiles_n = 0, group_m = 0;
+    int splits = 0, ktiles_per_split = 0;
+    int mix_na = -1, mix_sa = 0;
+    int atomic = 0;
+    bool clear_c = false;      // atomic split-K that overwrites: C is zeroed first
+    bool slabs = false;        // the K slices go to fp32 slabs in the workspace, a finishing pass sums them and applies the epilogue
+    int word = 0;              // what kalle_gemm_last_plan reports
+};
+
+// the kalle_gemm_last_plan word (specified in include/kalle_hip.h)
+static inline int gemm_plan_word(const GemmPlan& g) {
+    if (g.family == 5) return 5 | (g.wm << 8) | (g.wn << 12) | (g.splits << 16);
+    if (g.family == 4) return 4 | (1 << 8);
+    return g.family | (g.splits << 8) | (g.mix_na >= 0 ? 1 << 24 : 0);
+}
+
+// gemm.hip: launches p as it is (family 1; tiles_m / tiles_n in 128 x 128 tiles, group_m up to 8)
+int launch_gemm_v1(const GemmParams& p, bool a_km, bool b_km, bool f32, hipStream_t st);

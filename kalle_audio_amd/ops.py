@@ -88,9 +88,9 @@ def gemm(a, b, *, a_kmajor=False, b_kmajor=False, out=None, out_dtype=torch.bflo
     ep.glu_mode, ep.glu_inner = glu_mode, glu_inner
     ep.glu_aux = glu_aux.data_ptr() if glu_aux is not None else None
     ep.glu_dbias = glu_dbias.data_ptr() if glu_dbias is not None else None
-    if M <= FEW_ROWS_MAX and not a_kmajor and FEW_ROWS:
-        # few output rows (sampling, small training batches): lend the kernel an fp32 [M][N] scratch so it may split K
-        ws = _workspace(a.device, 4 * M * N * 8)
+    lend = _lend_request(M, N, a_kmajor)
+    if lend:
+        ws = _workspace(a.device, lend)
         ep.workspace, ep.workspace_bytes = ws.data_ptr(), ws.numel()
     if bias is not None:
         assert bias.dtype == torch.float32
@@ -126,19 +126,67 @@ _WS = {}
 _WS_KEEP = []
 
 
+def _lend_request(M, N, a_kmajor):
+    """bytes gemm() asks _workspace for (0: the call is lent no scratch): few output rows (sampling, small training batches)
+    get 8 fp32 [M][N] slabs so that the kernel may split K.  The one rule for gemm() and gemm_plan()."""
+    return 4 * M * N * 8 if M <= FEW_ROWS_MAX and not a_kmajor and FEW_ROWS else 0
+
+
+def _workspace_size(key, nbytes):
+    """size of the scratch that _workspace hands out for a request: at least 64 MiB, capped at 1 GiB - the kernel is told the
+    size and splits K only as far as the scratch reaches - and never less than the (device, stream)'s scratch has grown to"""
+    t = _WS.get(key)
+    return max(min(nbytes, 1 << 30), 64 << 20, t.numel() if t is not None else 0)
+
+
 def _workspace(device, nbytes):
     """per (device, stream) scratch for kalle_gemm_bf16's few-rows path, grown on demand (never shrinks)"""
     key = (device.index, torch.cuda.current_stream(device).cuda_stream)
     t = _WS.get(key)
-    # (capped at 1 GiB - the kernel is told the size and splits K only as far as the scratch reaches.  The comparison must use
-    # the CAPPED size: comparing with the uncapped request re-allocated - and kept - a fresh GiB on every call once a shape asked
-    # for more than the cap, 4032 rows x 12288 columns at B = 32 per GPU: 11 GB per step until the device was full)
-    need = max(min(nbytes, 1 << 30), 64 << 20)
+    # (the comparison must use the CAPPED size: comparing with the uncapped request re-allocated - and kept - a fresh GiB on
+    # every call once a shape asked for more than the cap, 4032 rows x 12288 columns at B = 32 per GPU: 11 GB per step until
+    # the device was full)
+    need = _workspace_size(key, nbytes)
     if t is None or t.numel() < need:
         if t is not None:
             _WS_KEEP.append(t)          # a captured HIP graph may still point at the old scratch: never hand it back
         t = _WS[key] = torch.empty(need, device=device, dtype=torch.uint8)
     return t
+
+
+def _gemm_plan_args(M, N, K, *, a_kmajor=False, b_kmajor=False, f32=False, bias=False, gate=False, rows_per_batch=0,
+                    residual=False, accumulate=False, alpha=1.0, c_rows_per_batch=0, row_mask=False, glu_mode=0, glu_inner=0,
+                    workspace="lend", workspace_ptr=16):
+    """the arguments of kalle_gemm_bf16 in front of `stream` for a call given by its shape and by WHICH epilogue fields it sets,
+    with placeholder pointers (the planner tests them for null and alignment only); workspace: "lend" = the scratch gemm()
+    lends such a call on the current stream, None, or a byte count.  Returns (arguments, the epilogue they point to)."""
+    ep = GemmEpilogue()
+    ep.bias = 16 if bias else None
+    ep.gate, ep.ldg, ep.rows_per_batch = (16 if gate else None), (N if gate else 0), rows_per_batch
+    ep.residual, ep.ldr = (16 if residual else None), (N if residual else 0)
+    ep.accumulate = 1 if accumulate else 0
+    ep.alpha = alpha
+    ep.c_rows_per_batch = ep.c_batch_rows = c_rows_per_batch
+    ep.row_mask = 16 if row_mask else None
+    ep.glu_mode, ep.glu_inner, ep.glu_aux = glu_mode, glu_inner, (16 if glu_mode else None)
+    if workspace == "lend":
+        lend = _lend_request(M, N, a_kmajor)
+        key = (torch.cuda.current_device(), torch.cuda.current_stream().cuda_stream) if torch.cuda.is_initialized() else None
+        workspace = _workspace_size(key, lend) if lend else 0
+    if workspace:
+        ep.workspace, ep.workspace_bytes = workspace_ptr, workspace
+    ldc = 2 * glu_inner if glu_mode == 2 else N
+    return (16, M if a_kmajor else K, int(a_kmajor), 16, N if b_kmajor else K, int(b_kmajor), 16, ldc,
+            KALLE_F32 if f32 else KALLE_BF16, M, N, K, ctypes.byref(ep)), ep
+
+
+def gemm_plan(M, N, K, **call):
+    """kalle_gemm_plan for a call described as in _gemm_plan_args: (return code, the kalle_gemm_last_plan word kalle_gemm_bf16
+    would leave now on this thread, or None where it refuses the call); host code only, no device needed"""
+    args, _ep = _gemm_plan_args(M, N, K, **call)
+    plan = ctypes.c_int(0)
+    rc = _lib.load().kalle_gemm_plan(*args, ctypes.byref(plan))
+    return rc, plan.value if rc == 0 else None
 
 
 # bench.py sets this to a list to collect (kernel variant, algorithmic flops, start event, end event) per GEMM launch:

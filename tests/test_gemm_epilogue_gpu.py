@@ -9,15 +9,23 @@ the rel-L2 of the whole output (one wrong row or tile of a 32 256-row output hid
 Everything the call must not write (rows a remap skips, rows between batches, the columns between N and ldc, the tails of
 glu_aux and glu_dbias) starts as NaN and must still be NaN afterwards; the operands' padding (gate and residual columns
 beyond N, residual rows a remap skips, the bias tail) is NaN too, so a read at a wrong row or column shows in the output.
-Each case also asserts which plan ran (kalle_gemm_last_plan): the shapes below were chosen by reading the dispatcher
-(gemm2.hip: kalle_gemm_bf16, kalle_gemm_skinny_launch, kalle_gemm_few_rows_launch, kalle_gemm_v2_launch)."""
+Each case also asserts which plan ran (kalle_gemm_last_plan), and that it is the one the host query kalle_gemm_plan named just
+before the launch.  The shapes live in tests/gemm_cases.py, which tests/test_gemm_plan_cpu.py checks against the planner
+(gemm2.hip: plan_gemm) without a GPU: that every shape reaches the plan it names is known before this file runs."""
 import itertools
 import math
-import random
+import os
+import sys
 import zlib
 
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import gemm_cases as gc  # noqa: E402
+from gemm_cases import (FACTORS, GLU1, GLU2, HEADLINE, HEADLINE_GLU, PAIRWISE, PAIRWISE_ROUTES, PRODUCT, ROUTES,  # noqa: E402
+                        UNSUPPORTED, WGRAD, WGRAD_EPI)
+from gemm_cases import pairwise_valid as _valid  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -107,8 +115,17 @@ def _elementwise(out, ref, tol, what):
                              f"out {out[r, c].item():.6g} ref {ref[r, c].item():.6g} tol {tol[r, c].item():.3g}")
 
 
-def _plan_check(lib, s):
+def _query(ops, s):
+    """what the host query says the call of `s` will launch, asked on the launching thread"""
+    shape, kw = gc.plan_kwargs(gc.case(**{k: v for k, v in s.__dict__.items() if k in ("M", "N", "K") or k in gc.DEFAULTS}))
+    rc, word = ops.gemm_plan(*shape, **kw)
+    assert rc == 0, (s, rc)
+    return word
+
+
+def _plan_check(lib, s, queried):
     plan = lib.kalle_gemm_last_plan()
+    assert plan == queried, (s, hex(plan), hex(queried))
     if s.plan is not None:
         assert plan & 255 == s.plan, (s, hex(plan))
     if s.slices is not None:
@@ -151,10 +168,11 @@ def run_plain(ops, lib, s):
         kw["row_mask"] = mask
     if s.remap:
         kw.update(c_rows_per_batch=s.remap[0], c_batch_rows=s.remap[1], c_row_offset=s.remap[2])
+    queried = _query(ops, s)
     y = ops.gemm(a, b, a_kmajor=bool(s.akm), b_kmajor=bool(s.bkm), out=C[:, :N], accumulate=s.accumulate, alpha=s.alpha,
                  M=M, N=N, K=K, **kw)
     assert y is not None
-    _plan_check(lib, s)
+    _plan_check(lib, s, queried)
     torch.cuda.synchronize()
 
     A, B = _op(a, b, s)
@@ -201,35 +219,7 @@ def run_plain(ops, lib, s):
     assert torch.isnan(C[~written]).all(), (s, "stray writes", int((~torch.isnan(C[~written])).sum()))
 
 
-# ------------------------------------------------------------------------------------------------ plan routes
-# (plan, base shape (M, N, K), layout) - the M / N / K of most are ragged: M % 16 == 1, N % 64 != 0, K % 64 != 0
-P5 = dict(M=2017, N=1472, K=1480, plan=5, slices=False)          # small tiles (128 x 128), whole K
-P5S = dict(M=252, N=1536, K=6144, plan=5, slices=True)           # small tiles + K slices + finishing pass
-P5B = dict(M=2017, N=1536, K=1480, bkm=1, plan=5)                # small tiles, k-major B (data gradient)
-P4 = dict(M=2529, N=1544, K=4104, plan=4)                        # few-rows K slices + finishing pass
-P4B = dict(M=2520, N=1536, K=6144, bkm=1, plan=4)
-P3 = dict(M=8193, N=1544, K=1544, plan=3)                        # persistent 256 x 256
-P3B = dict(M=8193, N=1536, K=1480, bkm=1, plan=3)
-P2 = dict(M=5000, N=192, K=1544, plan=2)                         # 256 x 128
-P2B = dict(M=5000, N=192, K=1544, bkm=1, plan=2)
-P1 = dict(M=5000, N=64, K=1544, plan=1)                          # v1 128 x 128
-P1A = dict(M=520, N=1536, K=1544, akm=1, plan=1)                 # v1: k-major A with a k-contiguous B
-ROUTES = {"p5": P5, "p5s": P5S, "p5b": P5B, "p4": P4, "p4b": P4B, "p3": P3, "p3b": P3B, "p2": P2, "p2b": P2B, "p1": P1,
-          "p1a": P1A}
-
-# the epilogues the product uses (dit_ops.py), on every plan: rows_per_batch 126 = tokens per clip of the benchmark
-PRODUCT = {
-    "attn_out_f32": dict(residual=True, gate=126, mask=True),               # self-attention out-projection (dit_ops.py:236)
-    "attn_out_bf16": dict(f32=False, residual=True, gate=126, mask=True),
-    "ff_out": dict(bias=True, gate=126, residual=True),                     # FF-out (dit_ops.py:388)
-    "xattn_out": dict(residual=True, mask=True),                            # cross-attention out
-    "proj_in_off1": dict(bias=True, remap=(125, 130, 1)),                   # project_in behind 1 / 4 prepended tokens
-    "proj_in_off4": dict(bias=True, residual=True, remap=(126, 130, 4)),
-    "dgrad_acc": dict(accumulate=True, alpha=0.37),                          # data-gradient accumulate
-    "qkv_bf16": dict(f32=False, bias=True),
-}
-
-
+# ------------------------------------------------------------------------------------------------ plan routes (gemm_cases.ROUTES) x the product's epilogues
 def _product_cases():
     out = []
     for rn, r in ROUTES.items():
@@ -245,52 +235,9 @@ def test_product_epilogue_on_every_plan(kl, route, epi):
     run_plain(ops, lib, s)
 
 
-# seeded pairwise cover of every option on every plan: rows_per_batch values put batch boundaries inside tiles
-FACTORS = {
-    "f32": [True, False],
-    "bias": [False, True],
-    "gate": [0, 1, 126, 130, 257],
-    "residual": [False, True],
-    "mask": [False, True],
-    "remap": [None, (126, 130, 1), (130, 133, 3), (257, 260, 0)],
-    "accumulate": [False, True],
-    "alpha": [1.0, 0.37, -1.5, 0.0],
-    "ldc_pad": [0, 24],
-}
-
-
-def _valid(c):
-    return not (c["accumulate"] and not c["f32"])
-
-
-def _pairwise(seed, n_cand=400):
-    rnd = random.Random(seed)
-    keys = list(FACTORS)
-    need = {(k1, i1, k2, i2) for k1, k2 in itertools.combinations(keys, 2)
-            for i1 in range(len(FACTORS[k1])) for i2 in range(len(FACTORS[k2]))
-            if _valid({**{k: FACTORS[k][0] for k in keys}, k1: FACTORS[k1][i1], k2: FACTORS[k2][i2]})}
-    rows = []
-    while need:
-        best, best_cov = None, -1
-        for _ in range(n_cand):
-            ix = {k: rnd.randrange(len(FACTORS[k])) for k in keys}
-            c = {k: FACTORS[k][i] for k, i in ix.items()}
-            if not _valid(c):
-                continue
-            cov = sum((k1, ix[k1], k2, ix[k2]) in need for k1, k2 in itertools.combinations(keys, 2))
-            if cov > best_cov:
-                best, best_cov, best_ix = c, cov, ix
-        rows.append(best)
-        need -= {(k1, best_ix[k1], k2, best_ix[k2]) for k1, k2 in itertools.combinations(keys, 2)}
-    return rows
-
-
-PAIRWISE = _pairwise(20261016)
-
-
 def _pairwise_cases():
     out = []
-    for rn in ("p5", "p5s", "p4", "p3", "p2", "p1"):
+    for rn in PAIRWISE_ROUTES:
         for i, c in enumerate(PAIRWISE):
             out.append(pytest.param(rn, i, id=f"{rn}-pw{i}"))
     return out
@@ -316,19 +263,8 @@ def test_pairwise_cover_is_complete():
 # ------------------------------------------------------------------------------------------------ weight gradients
 # a_kmajor (dy^T x, K = tokens), fp32 out: plain calls take atomic split-K into C (zeroed first when overwriting); the 256 x 256
 # kernel may mix two slice counts.  Epilogue fields turn the split off (the whole K in one workgroup).
-# (shape, plan of a plain call, plan with epilogue fields: without the split the 256 x 128 tiles fill the chip better at 1536 x 1536)
-WGRAD = [
-    pytest.param(dict(M=1536, N=1536, K=32256), 3, 2, id="p3-split"),          # split / mixed split at the bench's token count
-    pytest.param(dict(M=6144, N=1536, K=32256), 3, 3, id="p3-split-ff"),
-    pytest.param(dict(M=1536, N=192, K=32256), 2, 2, id="p2-split"),
-    pytest.param(dict(M=1544, N=1544, K=4104), 2, 2, id="p2-ragged"),
-]
-
-
-@pytest.mark.parametrize("shape,plan,plan_ep", WGRAD)
-@pytest.mark.parametrize("epi", [dict(), dict(alpha=0.37), dict(accumulate=True), dict(accumulate=True, alpha=-1.5),
-                                 dict(bias=True, residual=True, alpha=0.5), dict(gate=257, mask=True, ldc_pad=24)],
-                         ids=["over", "over-alpha", "acc", "acc-alpha", "bias-res", "gate-mask"])
+@pytest.mark.parametrize("shape,plan,plan_ep", [pytest.param(shape, plan, plan_ep, id=i) for i, shape, plan, plan_ep in WGRAD])
+@pytest.mark.parametrize("epi", list(WGRAD_EPI.values()), ids=list(WGRAD_EPI))
 def test_wgrad_epilogue(kl, shape, plan, plan_ep, epi):
     ops, lib = kl
     plain = not any(epi.get(k) for k in ("bias", "gate", "residual", "mask", "remap"))
@@ -447,47 +383,20 @@ def run_glu2(ops, lib, M, inner, K, alpha=1.0, ldc_pad=0, seed=0):
     assert torch.isnan(db_buf[2 * inner:]).all(), "stray writes beyond glu_dbias"
 
 
-@pytest.mark.parametrize("M,inner,K,plan", [
-    (5000, 384, 1544, 3), (5000, 640, 1536, 3), (4113, 6144, 1536, 3),      # 256 x 256: 3 / 5 / 48 column tiles
-    (1000, 96, 520, 5), (2017, 160, 1480, 5),                               # small tiles, inner % 32 == 0
-    (2520, 768, 4096, 4), (300, 100, 1024, 4),                              # few-rows finishing pass (inner % 4 == 0)
-], ids=["p3-384", "p3-640", "p3-6144", "p5-96", "p5-160", "p4-768", "p4-100"])
+@pytest.mark.parametrize("M,inner,K,plan", list(GLU1.values()), ids=list(GLU1))
 def test_fused_swiglu_forward_vs_fp64(kl, M, inner, K, plan):
     ops, lib = kl
     run_glu1(ops, lib, M, inner, K, plan, ldc_pad=24 if plan == 3 else 0, seed=inner)
 
 
-@pytest.mark.parametrize("M,inner,K,alpha", [
-    (5000, 384, 1544, 1.0), (5000, 640, 1536, 0.37), (4113, 6144, 1536, 1.0), (257, 128, 1024, -1.5), (2017, 640, 1480, 1.0),
-], ids=["384", "640-alpha", "6144", "m257-alpha", "m2017"])
+@pytest.mark.parametrize("M,inner,K,alpha", list(GLU2.values()), ids=list(GLU2))
 def test_fused_swiglu_backward_vs_fp64(kl, M, inner, K, alpha):
     """inner 384 / 640: the last 256-column tile is half (a third) full: the h loads, the j0 < glu_inner guards, the dbias lanes"""
     ops, lib = kl
     run_glu2(ops, lib, M, inner, K, alpha=alpha, ldc_pad=8 if inner == 640 else 0, seed=inner)
 
 
-# combinations no fused kernel takes: None from ops.gemm (kalle_gemm_bf16: KALLE_ERR_UNSUPPORTED), C and glu_aux untouched
-UNSUPPORTED = {
-    "glu1-gate-few-rows": (1, dict(M=2520, inner=768, K=4096), dict(gate=126)),
-    "glu1-residual-few-rows": (1, dict(M=2520, inner=768, K=4096), dict(residual=True)),
-    "glu1-mask-few-rows": (1, dict(M=2520, inner=768, K=4096), dict(mask=True)),
-    "glu1-remap-few-rows": (1, dict(M=2520, inner=768, K=4096), dict(remap=(126, 130, 1))),
-    "glu1-gate-p3": (1, dict(M=5000, inner=384, K=1536), dict(gate=126)),
-    "glu1-residual-p5": (1, dict(M=1000, inner=96, K=512), dict(residual=True)),
-    "glu1-alpha-p3": (1, dict(M=5000, inner=384, K=1536), dict(alpha=0.5)),
-    "glu1-alpha-p5": (1, dict(M=1000, inner=96, K=512), dict(alpha=0.5)),
-    "glu1-alpha-few-rows": (1, dict(M=2520, inner=768, K=4096), dict(alpha=0.5)),
-    "glu1-f32": (1, dict(M=5000, inner=384, K=1536), dict(f32=True)),
-    "glu1-inner-not-128-large": (1, dict(M=5000, inner=96, K=1536), dict()),
-    "glu2-few-rows": (2, dict(M=200, inner=384, K=1536), dict()),
-    "glu2-bias": (2, dict(M=5000, inner=384, K=1536), dict(bias=True)),
-    "glu2-residual": (2, dict(M=5000, inner=384, K=1536), dict(residual=True)),
-    "glu2-gate": (2, dict(M=5000, inner=384, K=1536), dict(gate=126)),
-    "glu2-mask": (2, dict(M=5000, inner=384, K=1536), dict(mask=True)),
-    "glu2-inner-not-128": (2, dict(M=5000, inner=200, K=1536), dict()),
-}
-
-
+# combinations no fused kernel takes (gemm_cases.UNSUPPORTED): None from ops.gemm (kalle_gemm_bf16: KALLE_ERR_UNSUPPORTED), C and glu_aux untouched
 @pytest.mark.parametrize("name", list(UNSUPPORTED))
 def test_fused_swiglu_unsupported_is_reported(kl, name):
     ops, lib = kl
@@ -535,18 +444,6 @@ def test_fused_swiglu_unsupported_is_reported(kl, name):
 
 
 # ------------------------------------------------------------------------------------------------ headline shapes, M = 32 256
-HEADLINE_M = 126 * 256
-HEADLINE = {
-    "qkv": dict(M=HEADLINE_M, N=4608, K=1536, f32=False, bias=True, plan=3),
-    "attn_out": dict(M=HEADLINE_M, N=1536, K=1536, residual=True, gate=126, plan=3),
-    "attn_out_mask": dict(M=HEADLINE_M, N=1536, K=1536, residual=True, gate=126, mask=True, plan=3),
-    "ff_out": dict(M=HEADLINE_M, N=1536, K=6144, bias=True, gate=126, residual=True, plan=3),
-    "ff_out_dgrad": dict(M=HEADLINE_M, N=1536, K=1536, bkm=1, accumulate=True, alpha=0.5, plan=3),
-    "ragged_m": dict(M=HEADLINE_M - 8, N=1536, K=1536, residual=True, gate=126, mask=True, ldc_pad=8, plan=3),
-    "persist_16100": dict(M=16100, N=4608, K=1536, f32=False, bias=True, gate=130, plan=3),
-}
-
-
 @pytest.mark.parametrize("name", list(HEADLINE))
 def test_headline_shapes_vs_fp64(kl, name):
     ops, lib = kl
@@ -555,9 +452,25 @@ def test_headline_shapes_vs_fp64(kl, name):
 
 def test_headline_ff_in_glu1(kl):
     ops, lib = kl
-    run_glu1(ops, lib, HEADLINE_M, 6144, 1536, 3, seed=1)
+    run_glu1(ops, lib, *HEADLINE_GLU, 3, seed=1)
 
 
 def test_headline_ff_out_dgrad_glu2(kl):
     ops, lib = kl
-    run_glu2(ops, lib, HEADLINE_M, 6144, 1536, seed=1)
+    run_glu2(ops, lib, *HEADLINE_GLU, seed=1)
+
+
+# ------------------------------------------------------------------------------------------------ the mixed split-K plan cache
+def test_entry_point_remembers_the_mixed_plan(kl):
+    """a launched weight gradient enters its mixed plan into the thread's cache, where a K of the same 16-K-tile bucket finds
+    it; the same query on a thread that launched nothing gets that K's own (uniform) plan"""
+    ops, lib = kl
+    M, N, ka, plan_a, kb, plan_b = gc.REPLAY
+    s = Spec(M, N, ka, akm=1, bkm=1, f32=True, plan=3, seed=5)
+
+    def launch_then_query():
+        run_plain(ops, lib, s)
+        return lib.kalle_gemm_last_plan(), ops.gemm_plan(M, N, kb, a_kmajor=True, b_kmajor=True, f32=True)
+    launched, after = gc.fresh_thread(launch_then_query)
+    assert launched == plan_a and after == (0, plan_a), (hex(launched), after)
+    assert gc.fresh_thread(ops.gemm_plan, M, N, kb, a_kmajor=True, b_kmajor=True, f32=True) == (0, plan_b)

@@ -1,9 +1,15 @@
-"""time arbitrary GEMM shapes: python tools/gemm_shapes.py LAYOUT M N K [M N K ...]   (LAYOUT nt|nn|tn)"""
+"""time arbitrary GEMM shapes: python tools/gemm_shapes.py LAYOUT M N K [M N K ...]   (LAYOUT nt|nn|tn)
+python tools/gemm_shapes.py plan LAYOUT M N K [...]: only print the dispatcher's plan word (kalle_gemm_plan; needs no device)"""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from kalle_audio_amd import ops
 dev = torch.device("cuda")
 lay = sys.argv[1]
+if lay == "plan":
+    for M, N, K in zip(*[iter(map(int, sys.argv[3:]))] * 3):
+        rc, word = ops.gemm_plan(M, N, K, a_kmajor=sys.argv[2] == "tn", b_kmajor=sys.argv[2] != "nt", f32=sys.argv[2] == "tn")
+        print(f"{sys.argv[2]} {M}x{N}x{K}: " + (f"plan {word:#x}" if rc == 0 else f"refused ({rc})"))
+    sys.exit(0)
 dims = list(map(int, sys.argv[2:]))
 # KALLE_SHAPE_ZEROS=1: all-zero operands (how far the chip's clock under load holds the kernel back);
 # KALLE_SHAPE_PAD=P: leading dimensions padded by P elements (address-to-channel effects of power-of-two-ish row strides)
