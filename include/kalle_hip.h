@@ -496,6 +496,27 @@ int kalle_conv_transpose1d_fwd(const void* x, int x_dtype, const float* w_packed
  *                    input-channel split; > 1 means cfirst_finish_kernel ran too)
  *   family 8:        bits 8-12 TU, 13-17 KT;    family 9: bits 8-12 TU, 13-17 TV, 18-22 KM */
 int kalle_conv_last_plan(void);
+/* The dispatch as pure host queries: no device, nothing launched, kalle_conv_last_plan and every other state left alone.
+ * kalle_conv_plan / kalle_conv_transpose_plan answer for one conv what kalle_audio_amd/conv_ops.py asks them before every
+ * call, so a C caller that follows the answer gets the same dispatch.  Arguments: those of kalle_conv1d_fwd /
+ * kalle_conv_transpose1d_fwd without the tensors and the stream (in_act / epi as there, may be NULL; their pointers are tested
+ * for null only, never read) plus `prefer`: 0 = auto (the channels-per-lane kernels where their cost rule in csrc/conv1d.hip
+ * asks for them), 1 = the channels-per-lane kernels wherever the call is eligible, 2 = never.  Eligible: fp32 in and out, in_act
+ * not the gate (4), stride == 1 or dilation == 1; transposed: Lout at most the symmetric (Lin - 1) stride - 2 padding + ksize
+ * (trimmed, not extended).  The planner of the chosen entry point then checks the arguments: its return code is the query's,
+ * and a refused query leaves `out` alone.  On success out[0..5] =
+ *   family (bits 0-3 of the word: 1 / 2 call kalle_conv1d_fwd, 3 / 4 kalle_conv_transpose1d_fwd, 5 / 6 kalle_conv1d_cfirst_fwd,
+ *   7 kalle_conv_transpose1d_cfirst_fwd), the word kalle_conv_last_plan holds after that call, and for families 5-7 what the
+ *   call needs: Lp (length of x_padded), lead and phases (`padding` and `phases` of kalle_conv_pad_act), workspace floats (0:
+ *   pass NULL; the word's ks assumes a workspace of that size is lent).  Families 1-4 leave those four 0.
+ * kalle_conv_wgrad_plan: the arguments of kalle_conv_wgrad without tensors and stream; out[0..4] = family (8 / 9), word,
+ * grid x, y, z. */
+int kalle_conv_plan(int x_dtype, int y_dtype, int B, int Cin, int Lin, int Cout, int Lout, int ksize, int stride, int padding,
+                    int dilation, const kalle_act* in_act, const kalle_conv_epilogue* epi, int prefer, int32_t* out);
+int kalle_conv_transpose_plan(int x_dtype, int y_dtype, int B, int Cin, int Lin, int Cout, int Lout, int ksize, int stride,
+                              int padding, const kalle_act* in_act, const kalle_conv_epilogue* epi, int prefer, int32_t* out);
+int kalle_conv_wgrad_plan(int B, int CU, int CV, int MU, int LV, int ksize, int stride, int padding, int dilation, int act_on,
+                          const kalle_act* act, int32_t* out);
 /* ------------------------------------------------------------------------------------------------
  * Llasa task model head / tail (model_sigmaVAE.py:53-104); the Llama decoder layers in between run on kalle_gemm_bf16,
  * kalle_rmsnorm_*, kalle_attention_* (causal, rot = head_dim = 64 or 128, GQA).

@@ -34,6 +34,61 @@ def _epilogue(residual, out_scale, accumulate, tanh, post_act, y_raw=None):
     return _lib.ConvEpilogue(_p(residual), float(out_scale), int(accumulate), int(tanh), pa, _p(y_raw))
 
 
+def _prefer():
+    """KALLE_CONV_CFIRST -> the queries' `prefer`: unset = auto, "1" = the channels-per-lane kernels wherever eligible, else never"""
+    want = os.environ.get("KALLE_CONV_CFIRST")
+    return 0 if want is None else 1 if want == "1" else 2
+
+
+_PLANS = {}     # answers of the plan queries: a model asks for the same few layers again and again, and a query costs 4 us more than a lookup
+
+
+def _query(fn, what, ia, ep, *shape):
+    """(family, word, Lp, lead, phases, workspace floats) of a plan query, kept per distinct call: the key is every argument,
+    with every field of ia / ep, pointers as set / null (all the planners may do with them: include/kalle_hip.h)"""
+    pa, prefer = ep.post_act, _prefer()
+    key = (what, prefer, shape, ia.code, ia.logscale, ia.alpha is None, ia.beta is None, ia.param, ep.residual is None, ep.out_scale,
+           ep.accumulate, ep.tanh, pa.code, pa.logscale, pa.alpha is None, pa.beta is None, pa.param, ep.y_raw is None)
+    hit = _PLANS.get(key)
+    if hit is None:
+        out = (ctypes.c_int32 * 6)()
+        check(fn(*shape, ctypes.addressof(ia), ctypes.addressof(ep), prefer, out), what)
+        if len(_PLANS) >= 4096:
+            _PLANS.clear()
+        hit = _PLANS[key] = tuple(out)
+    return hit
+
+
+def _plan(fn, args, act, act_params, epilogue, prefer, x_f32, y_f32):
+    """(return code, None or dict) of a plan query for shapes alone: the pointers the planner only tests for null are placeholders"""
+    on = lambda f: 16 if f else None  # noqa: E731
+    ia = _lib.Act(int(act), 1, on(act_params), on(act_params), 0.0)
+    e = dict(residual=False, out_scale=1.0, accumulate=False, tanh=False, post_act=0, want_raw=False, post_params=True)
+    e.update(epilogue)
+    pa = _lib.Act(int(e["post_act"]), 1, on(e["post_params"]), on(e["post_params"]), 0.0)
+    ep = _lib.ConvEpilogue(on(e["residual"]), float(e["out_scale"]), int(e["accumulate"]), int(e["tanh"]), pa, on(e["want_raw"]))
+    out = (ctypes.c_int32 * 6)()
+    rc = fn(int(x_f32), int(y_f32), *args, ctypes.addressof(ia), ctypes.addressof(ep), _prefer() if prefer is None else prefer, out)
+    return rc, dict(zip(("family", "word", "Lp", "lead", "phases", "ws_floats"), out)) if rc == 0 else None
+
+
+def conv_plan(B, Cin, Lin, Cout, Lout, K, *, stride=1, padding=0, dilation=1, act=0, act_params=True, x_f32=True, y_f32=True,
+              prefer=None, **epilogue):
+    """what conv1d would launch for these shapes (kalle_conv_plan: no device, nothing launched): (return code, None or dict of
+    family, word, Lp, lead, phases, ws_floats).  Cin: the conv's (half of x's channels under act 4); prefer: None = from
+    KALLE_CONV_CFIRST, 0 auto, 1 always / 2 never the channels-per-lane kernels; epilogue: which of residual, accumulate, tanh,
+    want_raw are set, out_scale, post_act code; act_params / post_params: SnakeBeta's alpha and beta are given"""
+    return _plan(_lib.load().kalle_conv_plan, (B, Cin, Lin, Cout, Lout, K, stride, padding, dilation), act, act_params, epilogue, prefer,
+                 x_f32, y_f32)
+
+
+def conv_transpose_plan(B, Cin, Lin, Cout, Lout, K, *, stride, padding, act=0, act_params=True, x_f32=True, y_f32=True, prefer=None,
+                        **epilogue):
+    """the same for conv_transpose1d (kalle_conv_transpose_plan)"""
+    return _plan(_lib.load().kalle_conv_transpose_plan, (B, Cin, Lin, Cout, Lout, K, stride, padding), act, act_params, epilogue, prefer,
+                 x_f32, y_f32)
+
+
 def conv1d(x, w_packed, bias, *, Cout, K, stride=1, padding=0, dilation=1, act=0, alpha=None, beta=None,
            logscale=True, residual=None, post=0, out_dtype=None, pad_right=None, act_param=0.0, out_scale=1.0,
            accumulate_into=None, post_act=None, want_raw=False):
@@ -57,34 +112,14 @@ def conv1d(x, w_packed, bias, *, Cout, K, stride=1, padding=0, dilation=1, act=0
     ia = _act_struct(act, alpha, beta, logscale, act_param)
     y_raw = torch.empty_like(y) if want_raw else None      # dual output: (post_act(y), y)
     ep = _epilogue(residual, out_scale, accumulate_into is not None, post & 1, post_act, y_raw)
-    # few positions, many channels (the top of the VAE, all of a single-clip decode): channels-per-lane kernel over a padded,
-    # pre-activated copy of x.  Chosen when the position-per-lane tiling would leave most CUs without a workgroup.
-    want = os.environ.get("KALLE_CONV_CFIRST")
-    nwg64 = ((Lout + 511) // 512) * ((Cout + 63) // 64) * B
-    if stride > 1:
-        # strided convs (the encoder's down-samplers): the position-per-lane kernels reach 16-25 TFLOP/s at stride 8 and 38-46 at
-        # stride 4, the channels-per-lane kernel 43-57 at every batch size measured (512 -> 1024, k = 16, stride 8, 13760 inputs,
-        # B = 4: 5388 against 2379 us; 1024 -> 2048 x 1720, B = 8: 7237 against 2166; 256 -> 512, k = 8, stride 4, B = 8: 5021 against 3876)
-        small = Cout >= 256
-    elif Cout >= 256:
-        # The position-per-lane kernel runs these layers in 8-wave workgroups of 128 channels x 512 positions (256 for k = 1): one
-        # round of them takes the same time whether 100 or 256 exist, while the channels-per-lane kernel scales with the work
-        # (tools/cfirst_vs_v2.sh, 1024 channels x 1720 positions, k = 7: B = 4 -> 128 workgroups 2316 us against 1820; B = 5 -> 160
-        # workgroups 2262 against 2560; 512 channels x 13760, k = 1, B = 1 -> 216 workgroups 162 us against 222)
-        small = -(-Lout // (256 if K == 1 else 512)) * -(-Cout // 128) * B < 160
-    else:
-        # few output channels: while positions are few too - or the reduction is long and the position-per-lane grid a handful of
-        # workgroups that each walk all of it (2048 -> 128, k = 3, 215 positions, B = 16: 1089 against 222 us)
-        small = Cout >= 64 and nwg64 < 256 and (Lout * B <= 1024 or (Cin >= 1024 and nwg64 <= 64))
-    if ((stride == 1 or dilation == 1) and act != 4 and x.dtype == torch.float32 and y.dtype == torch.float32
-            and (want == "1" or (want is None and small))):
-        Lp = lib.kalle_conv_pad_len(Lout, K, stride, padding, dilation)
-        lead = padding if stride == 1 else (padding + stride - 1) // stride * stride
+    # the library picks the kernel family (kalle_conv_plan); families 5 / 6 run over a padded, pre-activated copy of x
+    family, _, Lp, lead, phases, nws = _query(lib.kalle_conv_plan, "kalle_conv_plan", ia, ep, _dt(x), _dt(y), B, Cin, Lin, Cout, Lout, K,
+                                              stride, padding, dilation)
+    if family >= 5:
         xp = torch.empty((B, Cin, Lp), device=x.device, dtype=torch.float32)
-        check(lib.kalle_conv_pad_act(_p(x), _p(xp), B, Cin, Lin, Lp, lead, ctypes.addressof(ia), stride, _stream()),
+        check(lib.kalle_conv_pad_act(_p(x), _p(xp), B, Cin, Lin, Lp, lead, ctypes.addressof(ia), phases, _stream()),
               "kalle_conv_pad_act")
-        nws = lib.kalle_conv_cfirst_ws_floats(B, Cin, Cout, Lout, K)    # > 0: input channels split over workgroups too
-        ws = torch.empty(nws, device=x.device, dtype=torch.float32) if nws > 0 else None
+        ws = torch.empty(nws, device=x.device, dtype=torch.float32) if nws > 0 else None    # input channels split over workgroups too
         check(lib.kalle_conv1d_cfirst_fwd(_p(xp), _p(w_packed), _p(bias), _p(y), B, Cin, Lp, Cout, Lout, K, stride, padding,
                                           dilation, ctypes.addressof(ep), _p(ws), _stream()), "kalle_conv1d_cfirst_fwd")
         return (y, y_raw) if want_raw else y
@@ -106,18 +141,12 @@ def conv_transpose1d(x, w_packed, bias, *, Cout, K, stride, padding, act=0, alph
     ia = _act_struct(act, alpha, beta, logscale, act_param)
     y_raw = torch.empty_like(y) if want_raw else None
     ep = _epilogue(None, 1.0, False, False, post_act, y_raw)
-    want = os.environ.get("KALLE_CONV_CFIRST")
-    nq = (Lout - 1 + padding) // stride + 1
-    # (tools/cfirst_vs_v2.sh: at 512+ output channels the channels-per-lane kernel holds 50-70 TFLOP/s where the phase-per-workgroup
-    # kernel needs far more positions to get there - 2048 -> 1024 x 215, B = 8: 2082 against 3463 us; 1024 -> 512 x 1720, B = 8: 3290
-    # against 3878; at 256 channels the two cross near 1500: 512 -> 256 x 13760, B = 3: 1465 against 1551, B = 4: 1870 against 1806)
-    small = ((nq + 511) // 512) * ((Cout + 63) // 64) * B * stride < (4096 if Cout >= 512 else 1536) and Cout >= 256
-    if (trim >= 0 and act != 4 and x.dtype == torch.float32 and y.dtype == torch.float32
-            and (want == "1" or (want is None and small))):
-        Lp = lib.kalle_convT_pad_len(Lout, K, stride, padding)
+    family, _, Lp, lead, phases, _ = _query(lib.kalle_conv_transpose_plan, "kalle_conv_transpose_plan", ia, ep, _dt(x), _dt(y), B, Cin,
+                                            Lin, Cout, Lout, K, stride, padding)
+    if family == 7:
         xp = torch.empty((B, Cin, Lp), device=x.device, dtype=torch.float32)
-        check(lib.kalle_conv_pad_act(_p(x), _p(xp), B, Cin, Lin, Lp, (K + stride - 1) // stride - 1, ctypes.addressof(ia), 1,
-                                     _stream()), "kalle_conv_pad_act")
+        check(lib.kalle_conv_pad_act(_p(x), _p(xp), B, Cin, Lin, Lp, lead, ctypes.addressof(ia), phases, _stream()),
+              "kalle_conv_pad_act")
         check(lib.kalle_conv_transpose1d_cfirst_fwd(_p(xp), _p(w_packed), _p(bias), _p(y), B, Cin, Lp, Cout, Lout, K, stride,
                                                     padding, ctypes.addressof(ep), _stream()),
               "kalle_conv_transpose1d_cfirst_fwd")

@@ -33,6 +33,16 @@ def conv_wgrad(U, V, dW, *, K, stride, padding, dilation, act_on, act=0, alpha=N
     return dW
 
 
+def conv_wgrad_plan(B, CU, CV, MU, LV, *, K, stride, padding, dilation, act_on, act=0, act_params=True):
+    """what conv_wgrad would launch for these shapes (kalle_conv_wgrad_plan: no device, nothing launched): (return code, None or
+    dict of family, word, grid)"""
+    ab = 16 if act_params else None                                         # (a placeholder: tested for null only)
+    a = _lib.Act(int(act), 1, ab, ab, 0.0)
+    out = (ctypes.c_int32 * 5)()
+    rc = _lib.load().kalle_conv_wgrad_plan(B, CU, CV, MU, LV, K, stride, padding, dilation, act_on, ctypes.addressof(a), out)
+    return rc, dict(family=out[0], word=out[1], grid=tuple(out[2:5])) if rc == 0 else None
+
+
 def act_bwd(x, g, act, alpha=None, beta=None, logscale=True, want_params=True):
     """returns (dx, dalpha, dbeta) for y = act(x), upstream g"""
     lib = _lib.load()

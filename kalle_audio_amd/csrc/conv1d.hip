@@ -1010,6 +1010,332 @@ constexpr int plan_dtypes(bool xf, bool yf) { return (xf ? 1 << 4 : 0) | (yf ? 1
 constexpr int plan_v2(int family, int cow, int lpt, int wco, int nw, int ci) {
     return family | cow << 8 | lpt << 13 | wco << 17 | nw << 21 | ilog2(ci / 8) << 25;
 }
+
+// What a planner decides about one call.  Filling it makes no HIP call and leaves g_conv_plan alone: the entry points launch
+// from it, kalle_conv_plan / kalle_conv_transpose_plan report it.
+struct TileForm { int cow, lpt, wco, ci, span, nw; };   // template arguments of the v2 kernels; cow 0: none
+struct ConvPlan {
+    int family = 0;            // 1-7, as in the plan word
+    TileForm form{};           // families 2, 4
+    int ntile = 0, nco = 0;    // families 2, 4: position tiles, channel tiles
+    dim3 grid, block;
+    int split = 0, ks = 0;     // families 5-7
+    int Lp = 0, lead = 0, phases = 0, ws_floats = 0;   // families 5-7: the padded copy kalle_conv_pad_act makes, the workspace
+    int word = 0;              // kalle_conv_last_plan after the launch
+};
+// a workgroup of form f covers 64 LPT NW / WCO positions and COW WCO channels
+void set_form(ConvPlan& pl, ConvParams& p, const TileForm& f, int npos) {
+    const int lt = 64 * f.lpt * (f.nw / f.wco), cot = f.cow * f.wco;
+    pl.form = f;
+    pl.ntile = p.ntile = (npos + lt - 1) / lt;
+    pl.nco = p.nco = (p.Cout + cot - 1) / cot;
+    pl.block = dim3(64 * f.nw);
+}
+
+// kalle_conv1d_fwd: argument checks, the kernel parameters (the entry point has set the four tensor pointers) and the plan
+int plan_conv1d(bool tensors, int x_dtype, int y_dtype, int B, int Cin, int Lin, int Cout, int Lout, int ksize, int stride,
+                int padding, int dilation, const kalle_act* in_act, const kalle_conv_epilogue* epi, ConvParams& p, ConvPlan& pl) {
+    if (!tensors || B <= 0 || Cin <= 0 || Cout <= 0 || Lin <= 0 || Lout <= 0) return KALLE_ERR_ARG;
+    if (ksize <= 0 || ksize > MAX_K || stride <= 0 || dilation <= 0 || padding < 0) return KALLE_ERR_ARG;
+    // `padding` is the LEFT pad; the right pad is implied by Lout (symmetric, 'same' or causal alike): taps beyond Lin read 0
+    if ((int64_t)(Lout - 1) * stride - padding >= Lin) return KALLE_ERR_ARG;
+    if (B > 65535 || (Cout + 7) / 8 > 65535) return KALLE_ERR_ARG;
+    if (!fill_params(p, in_act, epi)) return KALLE_ERR_ARG;
+    p.B = B; p.Cin = Cin; p.Lin = Lin; p.Cout = Cout; p.Lout = Lout; p.K = ksize; p.stride = stride; p.pad = padding;
+    p.dil = dilation; p.CoutP = (Cout + 7) & ~7; p.xC = p.act == 4 ? 2 * Cin : Cin;
+    const bool xf = x_dtype == KALLE_F32, yf = y_dtype == KALLE_F32;
+    const int halo = (ksize - 1) * dilation;
+    // weights small enough to stay in one XCD's L2: run the channel tiles of a position tile back to back (x re-read hits L2)
+    p.co_fast = (int64_t)Cin * ksize * p.CoutP * 4 <= (2 << 20);
+    const bool v2_stride = stride == 1 || (dilation == 1 && (stride == 2 || stride == 4 || stride == 8) && ksize <= 32);
+    TileForm f{};
+    if (v2_stride && p.act != 4 && xf == yf) {
+        if (stride == 1) {
+            const TileChoice tc = pick_tile(Lout, Cout, B, halo, V2_SPAN, 0, 1);
+            if (Cout <= 4) {
+                if (halo + 512 <= V2_SPAN) f = TileForm{2, 2, 1, 8, 640, 4};
+            } else if (tc.cow == 16) {
+                // 8 waves share one staged x tile for 128 output channels (pointwise convs: 32-channel chunks to cover
+                // the HBM latency; measured +15 % at C >= 256, +8 % on the k = 7 convs at C = 256, neutral at C = 128)
+                // pointwise convs: 256 positions x 128 channels per workgroup (64 accumulator registers per wave, 66 KiB of LDS) so
+                // that TWO workgroups share a CU - one's residual loads / stores run under the other's FMAs; with 512 positions
+                // (128 accumulator registers, 133 KiB) a CU runs one workgroup whose memory phases nothing overlaps
+                if (ksize == 1 && Cout > 64) f = TileForm{16, 4, 8, 32, 256, 8};
+                // (the same halving for the wide k = 7 convs - 7 x the FMAs per byte - is worth 0.4 % of a decode: not taken)
+                else if (ksize != 1 && Cout >= 256 && halo + 512 <= 640) f = TileForm{16, 8, 8, 8, 640, 8};
+                else if (ksize == 1) f = TileForm{16, 8, 4, 16, 512, 4};   // pointwise conv: longer chunks cover the HBM latency
+                else f = TileForm{16, 8, 4, 8, 640, 4};
+            } else if (tc.lpt) {                         // (0: not even the shortest tile fits its halo into the span)
+                f = TileForm{8, tc.lpt, 4, 8, 640, 4};
+            }
+        } else if (Cout > 4) {                           // stride 2 / 4 / 8: de-interleaved staging, 1024/stride positions
+            const bool wide = Cout >= 64 && p.CoutP % 16 == 0;
+            if (stride == 2) f = TileForm{8, 8, 4, 8, 1088, 4};
+            else if (stride == 4) f = wide ? TileForm{16, 4, 4, 8, 1088, 4} : TileForm{8, 4, 4, 8, 1088, 4};
+            else if ((int64_t)Lout * B <= 1024) f = TileForm{8, 2, 4, 8, 1088, 4};   // stride 8; longer: fallback is faster
+        }
+    }
+    if (f.cow) {
+        set_form(pl, p, f, Lout);
+        if ((int64_t)p.ntile * p.nco > 0x7fffffff) return KALLE_ERR_ARG;
+        pl.grid = dim3(p.ntile * p.nco, 1, B);
+        pl.family = 2;
+        pl.word = plan_v2(2, f.cow, f.lpt, f.wco, f.nw, f.ci) | plan_dtypes(xf, yf) | ilog2(stride) << 28;
+        return KALLE_OK;
+    }
+    if ((L_T - 1) * stride + halo + 1 > MAX_SPAN) return KALLE_ERR_UNSUPPORTED;
+    pl.grid = dim3((Lout + L_T - 1) / L_T, (Cout + CO_T - 1) / CO_T, B);
+    pl.block = dim3(256);
+    pl.family = 1;
+    pl.word = 1 | plan_dtypes(xf, yf);
+    return KALLE_OK;
+}
+
+// kalle_conv_transpose1d_fwd
+int plan_convT(bool tensors, int x_dtype, int y_dtype, int B, int Cin, int Lin, int Cout, int Lout, int ksize, int stride,
+               int padding, const kalle_act* in_act, const kalle_conv_epilogue* epi, ConvParams& p, ConvPlan& pl) {
+    if (!tensors || B <= 0 || Cin <= 0 || Cout <= 0 || Lin <= 0 || Lout <= 0) return KALLE_ERR_ARG;
+    if (ksize <= 0 || stride <= 0 || padding < 0) return KALLE_ERR_ARG;
+    // shorter than (Lin-1)*stride - 2*padding + K = causal trim of the tail; up to `padding` longer = the outputs the symmetric
+    // trim would drop on the right (the data gradient of a strided conv whose input length is not a multiple of the stride)
+    if (Lout > (Lin - 1) * stride - padding + ksize) return KALLE_ERR_ARG;
+    if (B > 65535 || (Cout + 7) / 8 > 65535) return KALLE_ERR_ARG;
+    if (!fill_params(p, in_act, epi)) return KALLE_ERR_ARG;
+    if (p.act == 4) return KALLE_ERR_UNSUPPORTED;
+    p.B = B; p.Cin = Cin; p.Lin = Lin; p.Cout = Cout; p.Lout = Lout; p.K = ksize; p.stride = stride; p.pad = padding;
+    p.dil = 1; p.CoutP = (Cout + 7) & ~7; p.xC = Cin;
+    const bool xf = x_dtype == KALLE_F32, yf = y_dtype == KALLE_F32;
+    const int mmax = (ksize + stride - 1) / stride;
+    TileForm f{};
+    const int nq = (Lout - 1 + padding) / stride + 1;      // input positions that reach an output
+    if (xf == yf && mmax <= 64) {
+        const TileChoice tc = pick_tile(nq, Cout, B, mmax - 1, V2_SPAN, 0, stride);
+        if (Cout <= 4) {
+            if (mmax - 1 + 512 <= V2_SPAN) f = TileForm{2, 2, 1, 8, 640, 4};
+        } else if (tc.cow == 16) {
+            f = TileForm{16, 8, 4, 8, 640, 4};
+        } else if (tc.lpt) {
+            f = TileForm{8, tc.lpt, 4, 8, 640, 4};
+        }
+    }
+    if (f.cow) {
+        set_form(pl, p, f, nq);
+        const int64_t nwg = (((int64_t)p.ntile * p.nco + 7) / 8) * 8 * stride;      // one pass per output phase
+        if (nwg > 0x7fffffff) return KALLE_ERR_ARG;
+        pl.grid = dim3((unsigned)nwg, 1, B);
+        pl.family = 4;
+        pl.word = plan_v2(4, f.cow, f.lpt, f.wco, 4, 8) | plan_dtypes(xf, yf);
+        return KALLE_OK;
+    }
+    if (ksize > MAX_K + 2 || ksize > 2 * stride + 1 || p.res || p.post || p.pact || p.y_raw || p.out_scale != 1.f)
+        return KALLE_ERR_UNSUPPORTED;
+    pl.grid = dim3((Lout + L_T - 1) / L_T, (Cout + CO_T - 1) / CO_T, B);
+    pl.block = dim3(256);
+    pl.family = 3;
+    pl.word = 3 | plan_dtypes(xf, yf);
+    return KALLE_OK;
+}
+
+// ---- launchers: the plan's tile form -> the instantiation.  The tables are the whole set of v2 code objects.
+constexpr int64_t form_key(int cow, int lpt, int wco, int ci, int span, int nw) {
+    return (int64_t)span << 32 | plan_v2(0, cow, lpt, wco, nw, ci);
+}
+int64_t form_key(const TileForm& f) { return form_key(f.cow, f.lpt, f.wco, f.ci, f.span, f.nw); }
+
+template <int COW, int LPT, int WCO, int CI, int SPAN, int NW>
+void launch_v2(const ConvPlan& pl, const ConvParams& p, bool f32, hipStream_t st) {
+    if (f32) KALLE_LAUNCH((conv1d_v2_kernel<COW, LPT, WCO, CI, SPAN, true, true, NW>), pl.grid, pl.block, 0, st, p);
+    else KALLE_LAUNCH((conv1d_v2_kernel<COW, LPT, WCO, CI, SPAN, false, false, NW>), pl.grid, pl.block, 0, st, p);
+}
+template <int COW, int LPT, int WCO>
+void launch_tv2(const ConvPlan& pl, const ConvParams& p, bool f32, hipStream_t st) {
+    if (f32) KALLE_LAUNCH((convT1d_v2_kernel<COW, LPT, WCO, 8, 640, true, true>), pl.grid, pl.block, 0, st, p);
+    else KALLE_LAUNCH((convT1d_v2_kernel<COW, LPT, WCO, 8, 640, false, false>), pl.grid, pl.block, 0, st, p);
+}
+// false: the plan names a form that was never compiled (a planner bug; nothing is launched)
+bool launch_conv1d(const ConvPlan& pl, const ConvParams& p, bool xf, bool yf, hipStream_t st) {
+    if (pl.family == 1) {
+        if (xf && yf) KALLE_LAUNCH((conv1d_kernel<true, true>), pl.grid, pl.block, 0, st, p);
+        else if (xf) KALLE_LAUNCH((conv1d_kernel<true, false>), pl.grid, pl.block, 0, st, p);
+        else if (yf) KALLE_LAUNCH((conv1d_kernel<false, true>), pl.grid, pl.block, 0, st, p);
+        else KALLE_LAUNCH((conv1d_kernel<false, false>), pl.grid, pl.block, 0, st, p);
+        return true;
+    }
+    switch (form_key(pl.form)) {
+#define KALLE_FORM(...) case form_key(__VA_ARGS__): launch_v2<__VA_ARGS__>(pl, p, xf, st); break;
+        KALLE_FORM(2, 2, 1, 8, 640, 4)
+        KALLE_FORM(8, 2, 4, 8, 640, 4)
+        KALLE_FORM(8, 4, 4, 8, 640, 4)
+        KALLE_FORM(8, 8, 4, 8, 640, 4)
+        KALLE_FORM(16, 8, 4, 8, 640, 4)
+        KALLE_FORM(16, 8, 4, 16, 512, 4)
+        KALLE_FORM(16, 4, 8, 32, 256, 8)
+        KALLE_FORM(16, 8, 8, 8, 640, 8)
+        KALLE_FORM(8, 8, 4, 8, 1088, 4)
+        KALLE_FORM(8, 4, 4, 8, 1088, 4)
+        KALLE_FORM(16, 4, 4, 8, 1088, 4)
+        KALLE_FORM(8, 2, 4, 8, 1088, 4)
+#undef KALLE_FORM
+        default: return false;
+    }
+    return true;
+}
+bool launch_convT(const ConvPlan& pl, const ConvParams& p, bool xf, bool yf, hipStream_t st) {
+    if (pl.family == 3) {
+        if (xf && yf) KALLE_LAUNCH((convT1d_kernel<true, true>), pl.grid, pl.block, 0, st, p);
+        else if (xf) KALLE_LAUNCH((convT1d_kernel<true, false>), pl.grid, pl.block, 0, st, p);
+        else if (yf) KALLE_LAUNCH((convT1d_kernel<false, true>), pl.grid, pl.block, 0, st, p);
+        else KALLE_LAUNCH((convT1d_kernel<false, false>), pl.grid, pl.block, 0, st, p);
+        return true;
+    }
+    switch (form_key(pl.form)) {
+#define KALLE_FORM(COW, LPT, WCO) case form_key(COW, LPT, WCO, 8, 640, 4): launch_tv2<COW, LPT, WCO>(pl, p, xf, st); break;
+        KALLE_FORM(2, 2, 1)
+        KALLE_FORM(8, 2, 4)
+        KALLE_FORM(8, 4, 4)
+        KALLE_FORM(8, 8, 4)
+        KALLE_FORM(16, 8, 4)
+#undef KALLE_FORM
+        default: return false;
+    }
+    return true;
+}
+
+// ---- channels-per-lane kernels (families 5-7)
+// The padded copy x_padded [B][C][Lp] that kalle_conv_pad_act(..., padding = lead, phases) makes for them.  A conv reads
+// 16-position tiles plus the halo.  Strided (dilation 1): the copy is de-interleaved into `stride` phase rows of Lp / stride
+// slots behind a left pad of padq * stride: tap k of output l reads phase (k + d) % stride at slot l + (k + d) / stride.
+struct PadGeom { int Lp, lead, phases, d; };
+PadGeom conv_pad_geom(int Lout, int ksize, int stride, int padding, int dilation) {
+    const int l16 = (Lout + 15) & ~15;
+    if (stride == 1) return PadGeom{l16 + (ksize - 1) * dilation, padding, 1, 0};
+    const int padq = (padding + stride - 1) / stride, d = padq * stride - padding;
+    return PadGeom{stride * (l16 + (ksize - 1 + d) / stride + 1), padq * stride, stride, d};
+}
+// transposed: nq input positions reach an output, each tap m of input position q reads slot q + (mmax - 1) - m
+PadGeom convT_pad_geom(int Lout, int ksize, int stride, int padding) {
+    const int nq = (Lout - 1 + padding) / stride + 1, mmax = (ksize + stride - 1) / stride;
+    return PadGeom{((nq + 15) & ~15) + mmax - 1, mmax - 1, 1, 0};
+}
+// waves of a workgroup that share one position tile and split its input channels: `waves` counts the tiles; aim for >= 2048
+// waves (two per SIMD)
+int cfirst_split(int64_t waves) { return waves >= 2048 ? 1 : (waves >= 1024 ? 2 : 4); }
+// workgroup-level input-channel split of the channels-per-lane conv: with few positions AND few output channels even 4
+// waves per tile leave most SIMDs idle while every wave walks Cin * K dependent prefetch steps (the 1024 -> 2048 stride-8
+// and 2048 -> 128 convs at the bottom of a single-clip encode: 112 / 14 position-channel tiles)
+int cfirst_ksplit(int B, int Cin, int Cout, int Lout, int ksize) {
+    const int64_t waves = (int64_t)((Lout + 15) / 16) * ((Cout + 255) / 256) * B * 4;
+    int ks = 1;
+    while (ks < 16 && waves * ks < 4096 && (int64_t)Cin * ksize / (8 * ks) >= 64) ks *= 2;
+    return ks;
+}
+// fp32 elements of the workspace that lets a launch use that split; 0: not split (or the slabs would pass 2^31 elements)
+int cfirst_ws_floats(int B, int Cin, int Cout, int Lout, int ksize) {
+    const int ks = cfirst_ksplit(B, Cin, Cout, Lout, ksize);
+    const int64_t n = ks > 1 ? (int64_t)ks * B * Cout * Lout : 0;
+    return n > 0x7fffffff ? 0 : (int)n;
+}
+// what the two forms share: tensors, sizes, the epilogue; false: a bad epilogue
+bool cfirst_params(ConvCParams& p, const kalle_conv_epilogue* epi, int B, int Cin, int Lp, int Cout, int Lout, int ksize) {
+    ConvParams q{};
+    if (!fill_params(q, nullptr, epi)) return false;
+    p.res = static_cast<const float*>(q.res); p.y_raw = static_cast<float*>(q.y_raw);
+    p.B = B; p.Cin = Cin; p.Lp = Lp; p.Cout = Cout; p.CoutP = (Cout + 7) & ~7; p.Lout = Lout; p.K = ksize;
+    p.post = q.post; p.out_scale = q.out_scale;
+    p.pact = q.pact; p.paa = q.paa; p.pab = q.pab; p.plogscale = q.plogscale; p.pparam = q.pparam;
+    return true;
+}
+void cfirst_word(ConvPlan& pl, int family, int split, int ks) {
+    pl.family = family; pl.split = split; pl.ks = ks;
+    pl.block = dim3(256);
+    pl.word = family | plan_dtypes(true, true) | split << 8 | ks << 12;
+}
+
+// kalle_conv1d_cfirst_fwd (the entry point has set xp, w, bias, y and part); have_ws: the caller lends a workspace
+int plan_cfirst(bool tensors, int B, int Cin, int Lp, int Cout, int Lout, int ksize, int stride, int padding, int dilation,
+                const kalle_conv_epilogue* epi, bool have_ws, ConvCParams& p, ConvPlan& pl) {
+    if (!tensors || B <= 0 || Cin <= 0 || Cout <= 0 || Lout <= 0 || ksize <= 0 || dilation <= 0 || stride <= 0 || padding < 0)
+        return KALLE_ERR_ARG;
+    if (stride > 1 && dilation != 1) return KALLE_ERR_UNSUPPORTED;
+    const PadGeom g = conv_pad_geom(Lout, ksize, stride, padding, dilation);
+    if (Lp < g.Lp || (stride > 1 && Lp % stride) || B > 65535) return KALLE_ERR_ARG;
+    if (!cfirst_params(p, epi, B, Cin, Lp, Cout, Lout, ksize)) return KALLE_ERR_ARG;
+    const int split = cfirst_split((int64_t)((Lout + 15) / 16) * ((Cout + 255) / 256) * B);
+    const int ks = have_ws ? cfirst_ksplit(B, Cin, Cout, Lout, ksize) : 1;   // (the caller sized it with ..._ws_floats)
+    const int Lq = stride > 1 ? Lp / stride : 0;
+    p.dil = dilation; p.split = split; p.ks = ks;
+    p.nphase = 1; p.npos = Lout; p.xtap = dilation; p.ostride = 1; p.opad = 0; p.xlead = g.d * Lq;
+    p.xS = stride; p.xLq = Lq; p.xph0 = g.d;
+    if (p.CoutP < 4) return KALLE_ERR_UNSUPPORTED;
+    const int tiles_per_wg = 4 / split;
+    if ((int64_t)B * ks > 65535) return KALLE_ERR_ARG;
+    pl.grid = dim3(((Lout + 15) / 16 + tiles_per_wg - 1) / tiles_per_wg, (Cout + 255) / 256, B * ks);
+    cfirst_word(pl, stride > 1 ? 6 : 5, split, ks);
+    pl.Lp = g.Lp; pl.lead = g.lead; pl.phases = g.phases;
+    pl.ws_floats = have_ws ? cfirst_ws_floats(B, Cin, Cout, Lout, ksize) : 0;
+    return KALLE_OK;
+}
+
+// kalle_conv_transpose1d_cfirst_fwd: one pass per output phase, no workspace
+int plan_cfirst_T(bool tensors, int B, int Cin, int Lp, int Cout, int Lout, int ksize, int stride, int padding,
+                  const kalle_conv_epilogue* epi, ConvCParams& p, ConvPlan& pl) {
+    if (!tensors || B <= 0 || Cin <= 0 || Cout <= 0 || Lout <= 0 || ksize <= 0 || stride <= 0 || padding < 0) return KALLE_ERR_ARG;
+    const PadGeom g = convT_pad_geom(Lout, ksize, stride, padding);
+    if (Lp < g.Lp || B > 65535) return KALLE_ERR_ARG;
+    if (!cfirst_params(p, epi, B, Cin, Lp, Cout, Lout, ksize)) return KALLE_ERR_ARG;
+    const int nq = (Lout - 1 + padding) / stride + 1;
+    const int split = cfirst_split((int64_t)((nq + 15) / 16) * ((Cout + 255) / 256) * B * stride);
+    p.dil = 1; p.split = split; p.ks = 1;
+    p.nphase = stride; p.npos = nq; p.xtap = -1; p.ostride = stride; p.opad = padding; p.xlead = g.lead;
+    p.xS = 1; p.xLq = 0; p.xph0 = 0;
+    if (p.CoutP < 4) return KALLE_ERR_UNSUPPORTED;
+    const int tiles_per_wg = 4 / split;
+    const int64_t gx = (int64_t)(((nq + 15) / 16 + tiles_per_wg - 1) / tiles_per_wg) * stride;
+    if (gx > 0x7fffffff) return KALLE_ERR_ARG;
+    pl.grid = dim3((unsigned)gx, (Cout + 255) / 256, B);
+    cfirst_word(pl, 7, split, 1);
+    pl.Lp = g.Lp; pl.lead = g.lead; pl.phases = g.phases;
+    return KALLE_OK;
+}
+
+void launch_cfirst(const ConvPlan& pl, const ConvCParams& p, hipStream_t st) {
+    KALLE_LAUNCH(conv1d_cfirst_kernel, pl.grid, pl.block, 0, st, p);
+    if (pl.ks > 1) {
+        const int64_t n = (int64_t)p.B * p.Cout * p.Lout;
+        KALLE_LAUNCH(cfirst_finish_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 2048)), dim3(256), 0, st, p);
+    }
+}
+
+// ---- which family a call gets (kalle_conv_plan / kalle_conv_transpose_plan; kalle_audio_amd/conv_ops.py asks them)
+// Few positions, many channels (the top of the VAE, all of a single-clip decode): the channels-per-lane kernel over a padded,
+// pre-activated copy of x, where the position-per-lane tiling would leave most CUs without a workgroup.
+bool conv_prefers_cfirst(int B, int Cin, int Cout, int Lout, int ksize, int stride) {
+    // strided convs (the encoder's down-samplers): the position-per-lane kernels reach 16-25 TFLOP/s at stride 8 and 38-46 at
+    // stride 4, the channels-per-lane kernel 43-57 at every batch size measured (512 -> 1024, k = 16, stride 8, 13760 inputs,
+    // B = 4: 5388 against 2379 us; 1024 -> 2048 x 1720, B = 8: 7237 against 2166; 256 -> 512, k = 8, stride 4, B = 8: 5021 against 3876)
+    if (stride > 1) return Cout >= 256;
+    // The position-per-lane kernel runs these layers in 8-wave workgroups of 128 channels x 512 positions (256 for k = 1): one
+    // round of them takes the same time whether 100 or 256 exist, while the channels-per-lane kernel scales with the work
+    // (tools/cfirst_vs_v2.sh, 1024 channels x 1720 positions, k = 7: B = 4 -> 128 workgroups 2316 us against 1820; B = 5 -> 160
+    // workgroups 2262 against 2560; 512 channels x 13760, k = 1, B = 1 -> 216 workgroups 162 us against 222)
+    const int lt = ksize == 1 ? 256 : 512;
+    if (Cout >= 256) return (int64_t)((Lout + lt - 1) / lt) * ((Cout + 127) / 128) * B < 160;
+    // few output channels: while positions are few too - or the reduction is long and the position-per-lane grid a handful of
+    // workgroups that each walk all of it (2048 -> 128, k = 3, 215 positions, B = 16: 1089 against 222 us)
+    const int64_t nwg64 = (int64_t)((Lout + 511) / 512) * ((Cout + 63) / 64) * B;
+    return Cout >= 64 && nwg64 < 256 && ((int64_t)Lout * B <= 1024 || (Cin >= 1024 && nwg64 <= 64));
+}
+// (tools/cfirst_vs_v2.sh: at 512+ output channels the channels-per-lane kernel holds 50-70 TFLOP/s where the phase-per-workgroup
+// kernel needs far more positions to get there - 2048 -> 1024 x 215, B = 8: 2082 against 3463 us; 1024 -> 512 x 1720, B = 8: 3290
+// against 3878; at 256 channels the two cross near 1500: 512 -> 256 x 13760, B = 3: 1465 against 1551, B = 4: 1870 against 1806)
+bool convT_prefers_cfirst(int B, int Cout, int Lout, int stride, int padding) {
+    const int nq = (Lout - 1 + padding) / stride + 1;
+    return (int64_t)((nq + 511) / 512) * ((Cout + 63) / 64) * B * stride < (Cout >= 512 ? 4096 : 1536) && Cout >= 256;
+}
+enum { PREFER_AUTO = 0, PREFER_CFIRST = 1, PREFER_POSITIONS = 2 };
+void report(const ConvPlan& pl, int32_t* out) {
+    out[0] = pl.family; out[1] = pl.word; out[2] = pl.Lp; out[3] = pl.lead; out[4] = pl.phases; out[5] = pl.ws_floats;
+}
 }  // namespace
 
 extern "C" int kalle_conv_last_plan(void) { return g_conv_plan; }
@@ -1021,83 +1347,40 @@ extern "C" int kalle_conv1d_fwd(const void* x, int x_dtype, const float* w_packe
                                 int padding, int dilation, const kalle_act* in_act, const kalle_conv_epilogue* epi,
                                 void* stream) {
     g_conv_plan = 0;
-    if (!x || !w_packed || !y || B <= 0 || Cin <= 0 || Cout <= 0 || Lin <= 0 || Lout <= 0) return KALLE_ERR_ARG;
-    if (ksize <= 0 || ksize > MAX_K || stride <= 0 || dilation <= 0 || padding < 0) return KALLE_ERR_ARG;
-    // `padding` is the LEFT pad; the right pad is implied by Lout (symmetric, 'same' or causal alike): taps beyond Lin read 0
-    if ((int64_t)(Lout - 1) * stride - padding >= Lin) return KALLE_ERR_ARG;
-    if (B > 65535 || (Cout + 7) / 8 > 65535) return KALLE_ERR_ARG;
     ConvParams p{};
-    if (!fill_params(p, in_act, epi)) return KALLE_ERR_ARG;
+    ConvPlan pl;
     p.x = x; p.w = w_packed; p.bias = bias; p.y = y;
-    p.B = B; p.Cin = Cin; p.Lin = Lin; p.Cout = Cout; p.Lout = Lout; p.K = ksize; p.stride = stride; p.pad = padding;
-    p.dil = dilation; p.CoutP = (Cout + 7) & ~7; p.xC = p.act == 4 ? 2 * Cin : Cin;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool xf = x_dtype == KALLE_F32, yf = y_dtype == KALLE_F32;
-    const int halo = (ksize - 1) * dilation;
-    // weights small enough to stay in one XCD's L2: run the channel tiles of a position tile back to back (x re-read hits L2)
-    p.co_fast = (int64_t)Cin * ksize * p.CoutP * 4 <= (2 << 20);
-    const bool v2_stride = stride == 1 || (dilation == 1 && (stride == 2 || stride == 4 || stride == 8) && ksize <= 32);
-    if (v2_stride && p.act != 4 && xf == yf) {
-#define KALLE_CONV_V2N(COW, LPT, WCO, CI, SPAN, NW)                                                                    \
-    do {                                                                                                                \
-        p.ntile = (Lout + 64 * LPT * (NW / WCO) - 1) / (64 * LPT * (NW / WCO));                                        \
-        p.nco = (Cout + COW * WCO - 1) / (COW * WCO);                                                                   \
-        if ((int64_t)p.ntile * p.nco > 0x7fffffff) return KALLE_ERR_ARG;                                                \
-        dim3 g(p.ntile * p.nco, 1, B);                                                                                  \
-        g_conv_plan = plan_v2(2, COW, LPT, WCO, NW, CI) | plan_dtypes(xf, yf) | ilog2(stride) << 28;                    \
-        if (xf)                                                                                                         \
-            KALLE_LAUNCH((conv1d_v2_kernel<COW, LPT, WCO, CI, SPAN, true, true, NW>), g, dim3(64 * NW), 0, st, p);      \
-        else                                                                                                            \
-            KALLE_LAUNCH((conv1d_v2_kernel<COW, LPT, WCO, CI, SPAN, false, false, NW>), g, dim3(64 * NW), 0, st, p);    \
-        return kalle_check_launch();                                                                                    \
-    } while (0)
-#define KALLE_CONV_V2(COW, LPT, WCO, CI, SPAN) KALLE_CONV_V2N(COW, LPT, WCO, CI, SPAN, 4)
-        if (stride == 1) {
-            const TileChoice tc = pick_tile(Lout, Cout, B, halo, V2_SPAN, 0, 1);
-            if (Cout <= 4) {
-                if (halo + 512 <= V2_SPAN) KALLE_CONV_V2(2, 2, 1, 8, 640);
-            } else if (tc.cow == 16) {
-                // 8 waves share one staged x tile for 128 output channels (pointwise convs: 32-channel chunks to cover
-                // the HBM latency; measured +15 % at C >= 256, +8 % on the k = 7 convs at C = 256, neutral at C = 128)
-                // pointwise convs: 256 positions x 128 channels per workgroup (64 accumulator registers per wave, 66 KiB of LDS) so
-                // that TWO workgroups share a CU - one's residual loads / stores run under the other's FMAs; with 512 positions
-                // (128 accumulator registers, 133 KiB) a CU runs one workgroup whose memory phases nothing overlaps
-                if (ksize == 1 && Cout > 64) KALLE_CONV_V2N(16, 4, 8, 32, 256, 8);
-                // (the same halving for the wide k = 7 convs - 7 x the FMAs per byte - is worth 0.4 % of a decode: not taken)
-                if (ksize != 1 && Cout >= 256 && halo + 512 <= 640) KALLE_CONV_V2N(16, 8, 8, 8, 640, 8);
-                if (ksize == 1) KALLE_CONV_V2(16, 8, 4, 16, 512);   // pointwise conv: longer chunks cover the HBM latency
-                KALLE_CONV_V2(16, 8, 4, 8, 640);
-            } else {
-                switch (tc.lpt) {
-                    case 8: KALLE_CONV_V2(8, 8, 4, 8, 640);
-                    case 4: KALLE_CONV_V2(8, 4, 4, 8, 640);
-                    case 2: KALLE_CONV_V2(8, 2, 4, 8, 640);
-                    default: break;
-                }
-            }
-        } else if (Cout > 4) {                           // stride 2 / 4 / 8: de-interleaved staging, 1024/stride positions
-            const bool wide = Cout >= 64 && p.CoutP % 16 == 0;
-            if (stride == 2) KALLE_CONV_V2(8, 8, 4, 8, 1088);
-            if (stride == 4) { if (wide) KALLE_CONV_V2(16, 4, 4, 8, 1088); else KALLE_CONV_V2(8, 4, 4, 8, 1088); }
-            if (stride == 8 && (int64_t)Lout * B <= 1024) KALLE_CONV_V2(8, 2, 4, 8, 1088);   // longer: fallback is faster
-        }
-#undef KALLE_CONV_V2
-#undef KALLE_CONV_V2N
-    }
-    if ((L_T - 1) * stride + halo + 1 > MAX_SPAN) return KALLE_ERR_UNSUPPORTED;
-    dim3 grid((Lout + L_T - 1) / L_T, (Cout + CO_T - 1) / CO_T, B), block(256);
-    g_conv_plan = 1 | plan_dtypes(xf, yf);
-    if (xf && yf) KALLE_LAUNCH((conv1d_kernel<true, true>), grid, block, 0, st, p);
-    else if (xf) KALLE_LAUNCH((conv1d_kernel<true, false>), grid, block, 0, st, p);
-    else if (yf) KALLE_LAUNCH((conv1d_kernel<false, true>), grid, block, 0, st, p);
-    else KALLE_LAUNCH((conv1d_kernel<false, false>), grid, block, 0, st, p);
+    const int rc = plan_conv1d(x && w_packed && y, x_dtype, y_dtype, B, Cin, Lin, Cout, Lout, ksize, stride, padding, dilation,
+                               in_act, epi, p, pl);
+    if (rc != KALLE_OK) return rc;
+    if (!launch_conv1d(pl, p, x_dtype == KALLE_F32, y_dtype == KALLE_F32, static_cast<hipStream_t>(stream)))
+        return KALLE_ERR_UNSUPPORTED;
+    g_conv_plan = pl.word;
+    return kalle_check_launch();
+}
+
+extern "C" int kalle_conv_transpose1d_fwd(const void* x, int x_dtype, const float* w_packed, const float* bias, void* y,
+                                          int y_dtype, int B, int Cin, int Lin, int Cout, int Lout, int ksize,
+                                          int stride, int padding, const kalle_act* in_act,
+                                          const kalle_conv_epilogue* epi, void* stream) {
+    g_conv_plan = 0;
+    ConvParams p{};
+    ConvPlan pl;
+    p.x = x; p.w = w_packed; p.bias = bias; p.y = y;
+    const int rc = plan_convT(x && w_packed && y, x_dtype, y_dtype, B, Cin, Lin, Cout, Lout, ksize, stride, padding, in_act, epi,
+                              p, pl);
+    if (rc != KALLE_OK) return rc;
+    if (!launch_convT(pl, p, x_dtype == KALLE_F32, y_dtype == KALLE_F32, static_cast<hipStream_t>(stream)))
+        return KALLE_ERR_UNSUPPORTED;
+    g_conv_plan = pl.word;
     return kalle_check_launch();
 }
 
 extern "C" int kalle_conv_pad_len(int Lout, int ksize, int stride, int padding, int dilation) {
-    if (stride == 1) return ((Lout + 15) & ~15) + (ksize - 1) * dilation;
-    const int padq = (padding + stride - 1) / stride, d = padq * stride - padding;   // phase rows of Lq slots each
-    return stride * (((Lout + 15) & ~15) + (ksize - 1 + d) / stride + 1);
+    return conv_pad_geom(Lout, ksize, stride, padding, dilation).Lp;
+}
+extern "C" int kalle_convT_pad_len(int Lout, int ksize, int stride, int padding) {
+    return convT_pad_geom(Lout, ksize, stride, padding).Lp;
 }
 
 extern "C" int kalle_conv_pad_act(const float* x, float* x_padded, int B, int C, int Lin, int Lp, int padding,
@@ -1114,149 +1397,91 @@ extern "C" int kalle_conv_pad_act(const float* x, float* x_padded, int B, int C,
     return kalle_check_launch();
 }
 
-// workgroup-level input-channel split of the channels-per-lane conv: with few positions AND few output channels even 4
-// waves per tile leave most SIMDs idle while every wave walks Cin * K dependent prefetch steps (the 1024 -> 2048 stride-8
-// and 2048 -> 128 convs at the bottom of a single-clip encode: 112 / 14 position-channel tiles)
-static int cfirst_ksplit(int B, int Cin, int Cout, int Lout, int ksize) {
-    const int64_t waves = (int64_t)((Lout + 15) / 16) * ((Cout + 255) / 256) * B * 4;
-    int ks = 1;
-    while (ks < 16 && waves * ks < 4096 && (int64_t)Cin * ksize / (8 * ks) >= 64) ks *= 2;
-    return ks;
-}
 extern "C" int kalle_conv_cfirst_ws_floats(int B, int Cin, int Cout, int Lout, int ksize) {
     if (B <= 0 || Cin <= 0 || Cout <= 0 || Lout <= 0 || ksize <= 0) return KALLE_ERR_ARG;
-    const int ks = cfirst_ksplit(B, Cin, Cout, Lout, ksize);
-    const int64_t n = ks > 1 ? (int64_t)ks * B * Cout * Lout : 0;
-    return n > 0x7fffffff ? 0 : (int)n;
+    return cfirst_ws_floats(B, Cin, Cout, Lout, ksize);
 }
 
 extern "C" int kalle_conv1d_cfirst_fwd(const float* x_padded, const float* w_packed, const float* bias, float* y, int B,
                                        int Cin, int Lp, int Cout, int Lout, int ksize, int stride, int padding,
                                        int dilation, const kalle_conv_epilogue* epi, float* workspace, void* stream) {
     g_conv_plan = 0;
-    if (!x_padded || !w_packed || !y || B <= 0 || Cin <= 0 || Cout <= 0 || Lout <= 0 || ksize <= 0 || dilation <= 0 ||
-        stride <= 0 || padding < 0)
-        return KALLE_ERR_ARG;
-    if (stride > 1 && dilation != 1) return KALLE_ERR_UNSUPPORTED;
-    if (Lp < kalle_conv_pad_len(Lout, ksize, stride, padding, dilation) || (stride > 1 && Lp % stride) || B > 65535)
-        return KALLE_ERR_ARG;
-    ConvParams q{};
-    if (!fill_params(q, nullptr, epi)) return KALLE_ERR_ARG;
-    // waves without splitting the input channels; aim for >= 2048 (two per SIMD)
-    const int64_t waves = (int64_t)((Lout + 15) / 16) * ((Cout + 255) / 256) * B;
-    const int split = waves >= 2048 ? 1 : (waves >= 1024 ? 2 : 4);
-    const int ks = workspace ? cfirst_ksplit(B, Cin, Cout, Lout, ksize) : 1;   // (the caller sized it with ..._ws_floats)
-    // stride > 1: x_padded is de-interleaved into `stride` phase rows (left pad padq * stride): tap k of output l reads
-    // phase (k + d) % stride at slot l + (k + d) / stride
-    const int padq = (padding + stride - 1) / stride, d = padq * stride - padding;
-    const int Lq = stride > 1 ? Lp / stride : 0;
-    ConvCParams p{x_padded, w_packed, bias, static_cast<const float*>(q.res), y, static_cast<float*>(q.y_raw), B, Cin, Lp, Cout, (Cout + 7) & ~7, Lout, ksize,
-                  dilation, q.post, split, ks, workspace, 1, Lout, dilation, 1, 0, stride > 1 ? d * Lq : 0, stride, Lq,
-                  stride > 1 ? d : 0, q.out_scale, q.pact, q.paa, q.pab, q.plogscale, q.pparam};
-    if (p.CoutP < 4) return KALLE_ERR_UNSUPPORTED;
-    const int tiles_per_wg = 4 / split;
-    if ((int64_t)B * ks > 65535) return KALLE_ERR_ARG;
-    dim3 grid(((Lout + 15) / 16 + tiles_per_wg - 1) / tiles_per_wg, (Cout + 255) / 256, B * ks);
-    g_conv_plan = (stride > 1 ? 6 : 5) | plan_dtypes(true, true) | split << 8 | ks << 12;
-    KALLE_LAUNCH(conv1d_cfirst_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), p);
-    if (ks > 1) {
-        const int64_t n = (int64_t)B * Cout * Lout;
-        KALLE_LAUNCH(cfirst_finish_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 2048)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), p);
-    }
+    ConvCParams p{};
+    ConvPlan pl;
+    p.xp = x_padded; p.w = w_packed; p.bias = bias; p.y = y; p.part = workspace;
+    const int rc = plan_cfirst(x_padded && w_packed && y, B, Cin, Lp, Cout, Lout, ksize, stride, padding, dilation, epi,
+                               workspace != nullptr, p, pl);
+    if (rc != KALLE_OK) return rc;
+    launch_cfirst(pl, p, static_cast<hipStream_t>(stream));
+    g_conv_plan = pl.word;
     return kalle_check_launch();
-}
-
-extern "C" int kalle_convT_pad_len(int Lout, int ksize, int stride, int padding) {
-    const int nq = (Lout - 1 + padding) / stride + 1, mmax = (ksize + stride - 1) / stride;
-    return ((nq + 15) & ~15) + mmax - 1;
 }
 
 extern "C" int kalle_conv_transpose1d_cfirst_fwd(const float* x_padded, const float* w_packed, const float* bias, float* y,
                                                  int B, int Cin, int Lp, int Cout, int Lout, int ksize, int stride,
                                                  int padding, const kalle_conv_epilogue* epi, void* stream) {
     g_conv_plan = 0;
-    if (!x_padded || !w_packed || !y || B <= 0 || Cin <= 0 || Cout <= 0 || Lout <= 0 || ksize <= 0 || stride <= 0 ||
-        padding < 0)
-        return KALLE_ERR_ARG;
-    if (Lp < kalle_convT_pad_len(Lout, ksize, stride, padding) || B > 65535) return KALLE_ERR_ARG;
-    ConvParams q{};
-    if (!fill_params(q, nullptr, epi)) return KALLE_ERR_ARG;
-    const int nq = (Lout - 1 + padding) / stride + 1, mmax = (ksize + stride - 1) / stride;
-    const int64_t waves = (int64_t)((nq + 15) / 16) * ((Cout + 255) / 256) * B * stride;
-    const int split = waves >= 2048 ? 1 : (waves >= 1024 ? 2 : 4);
-    // x_padded has mmax-1 leading zeros: tap m of input position q reads slot q + (mmax-1) - m
-    ConvCParams p{x_padded, w_packed, bias, static_cast<const float*>(q.res), y, static_cast<float*>(q.y_raw), B, Cin, Lp, Cout, (Cout + 7) & ~7, Lout, ksize,
-                  1, q.post, split, 1, nullptr, stride, nq, -1, stride, padding, mmax - 1, 1, 0, 0, q.out_scale, q.pact, q.paa,
-                  q.pab, q.plogscale, q.pparam};
-    if (p.CoutP < 4) return KALLE_ERR_UNSUPPORTED;
-    const int tiles_per_wg = 4 / split;
-    const int64_t gx = (int64_t)(((nq + 15) / 16 + tiles_per_wg - 1) / tiles_per_wg) * stride;
-    if (gx > 0x7fffffff) return KALLE_ERR_ARG;
-    dim3 grid((unsigned)gx, (Cout + 255) / 256, B);
-    g_conv_plan = 7 | plan_dtypes(true, true) | split << 8 | 1 << 12;
-    KALLE_LAUNCH(conv1d_cfirst_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), p);
+    ConvCParams p{};
+    ConvPlan pl;
+    p.xp = x_padded; p.w = w_packed; p.bias = bias; p.y = y;
+    const int rc = plan_cfirst_T(x_padded && w_packed && y, B, Cin, Lp, Cout, Lout, ksize, stride, padding, epi, p, pl);
+    if (rc != KALLE_OK) return rc;
+    launch_cfirst(pl, p, static_cast<hipStream_t>(stream));
+    g_conv_plan = pl.word;
     return kalle_check_launch();
 }
 
-extern "C" int kalle_conv_transpose1d_fwd(const void* x, int x_dtype, const float* w_packed, const float* bias, void* y,
-                                          int y_dtype, int B, int Cin, int Lin, int Cout, int Lout, int ksize,
-                                          int stride, int padding, const kalle_act* in_act,
-                                          const kalle_conv_epilogue* epi, void* stream) {
-    g_conv_plan = 0;
-    if (!x || !w_packed || !y || B <= 0 || Cin <= 0 || Cout <= 0 || Lin <= 0 || Lout <= 0) return KALLE_ERR_ARG;
-    if (ksize <= 0 || stride <= 0 || padding < 0) return KALLE_ERR_ARG;
-    // shorter than (Lin-1)*stride - 2*padding + K = causal trim of the tail; up to `padding` longer = the outputs the symmetric
-    // trim would drop on the right (the data gradient of a strided conv whose input length is not a multiple of the stride)
-    if (Lout > (Lin - 1) * stride - padding + ksize) return KALLE_ERR_ARG;
-    if (B > 65535 || (Cout + 7) / 8 > 65535) return KALLE_ERR_ARG;
-    ConvParams p{};
-    if (!fill_params(p, in_act, epi)) return KALLE_ERR_ARG;
-    if (p.act == 4) return KALLE_ERR_UNSUPPORTED;
-    p.x = x; p.w = w_packed; p.bias = bias; p.y = y;
-    p.B = B; p.Cin = Cin; p.Lin = Lin; p.Cout = Cout; p.Lout = Lout; p.K = ksize; p.stride = stride; p.pad = padding;
-    p.dil = 1; p.CoutP = (Cout + 7) & ~7; p.xC = Cin;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool xf = x_dtype == KALLE_F32, yf = y_dtype == KALLE_F32;
-    const int mmax = (ksize + stride - 1) / stride;
-    if (xf == yf && mmax <= 64) {
-        const int nq = (Lout - 1 + padding) / stride + 1;      // input positions that reach an output
-#define KALLE_CONVT_V2(COW, LPT, WCO)                                                                                  \
-    do {                                                                                                                \
-        p.ntile = (nq + 64 * LPT * (4 / WCO) - 1) / (64 * LPT * (4 / WCO));                                             \
-        p.nco = (Cout + COW * WCO - 1) / (COW * WCO);                                                                   \
-        const int64_t nwg = (((int64_t)p.ntile * p.nco + 7) / 8) * 8 * stride;                                          \
-        if (nwg > 0x7fffffff) return KALLE_ERR_ARG;                                                                     \
-        dim3 g((unsigned)nwg, 1, B);                                                                                    \
-        g_conv_plan = plan_v2(4, COW, LPT, WCO, 4, 8) | plan_dtypes(xf, yf);                                            \
-        if (xf) KALLE_LAUNCH((convT1d_v2_kernel<COW, LPT, WCO, 8, 640, true, true>), g, dim3(256), 0, st, p);           \
-        else KALLE_LAUNCH((convT1d_v2_kernel<COW, LPT, WCO, 8, 640, false, false>), g, dim3(256), 0, st, p);            \
-        return kalle_check_launch();                                                                                    \
-    } while (0)
-        const TileChoice tc = pick_tile(nq, Cout, B, mmax - 1, V2_SPAN, 0, stride);
-        if (Cout <= 4) {
-            if (mmax - 1 + 512 <= V2_SPAN) KALLE_CONVT_V2(2, 2, 1);
-        } else if (tc.cow == 16) {
-            KALLE_CONVT_V2(16, 8, 4);
-        } else {
-            switch (tc.lpt) {
-                case 8: KALLE_CONVT_V2(8, 8, 4);
-                case 4: KALLE_CONVT_V2(8, 4, 4);
-                case 2: KALLE_CONVT_V2(8, 2, 4);
-                default: break;
-            }
-        }
-#undef KALLE_CONVT_V2
+// The two queries: the dispatch of conv_ops.conv1d / conv_transpose1d for any caller, without a device.  The channels-per-lane
+// family is taken where the call is eligible (fp32 in and out, no gate, not strided and dilated at once; transposed: not
+// extended past the symmetric trim) and `prefer` forces it or, left at auto, the cost rule above asks for it; the planner of
+// the family's entry point then checks the arguments and answers.
+extern "C" int kalle_conv_plan(int x_dtype, int y_dtype, int B, int Cin, int Lin, int Cout, int Lout, int ksize, int stride,
+                               int padding, int dilation, const kalle_act* in_act, const kalle_conv_epilogue* epi, int prefer,
+                               int32_t* out) {
+    if (!out || prefer < PREFER_AUTO || prefer > PREFER_POSITIONS) return KALLE_ERR_ARG;
+    ConvPlan pl;
+    int rc;
+    const bool sane = B > 0 && Cin > 0 && Lin > 0 && Cout > 0 && Lout > 0 && ksize > 0 && stride > 0 && dilation > 0 && padding >= 0;
+    const bool eligible = sane && (stride == 1 || dilation == 1) && (!in_act || in_act->code != 4) && x_dtype == KALLE_F32 &&
+                          y_dtype == KALLE_F32;
+    if (eligible && (prefer == PREFER_CFIRST ||
+                     (prefer == PREFER_AUTO && conv_prefers_cfirst(B, Cin, Cout, Lout, ksize, stride)))) {
+        ActArgs a;
+        if (!read_act(in_act, a, false)) return KALLE_ERR_ARG;             // (kalle_conv_pad_act applies it)
+        ConvCParams p{};
+        const bool ws = cfirst_ws_floats(B, Cin, Cout, Lout, ksize) > 0;
+        rc = plan_cfirst(true, B, Cin, conv_pad_geom(Lout, ksize, stride, padding, dilation).Lp, Cout, Lout, ksize, stride,
+                         padding, dilation, epi, ws, p, pl);
+    } else {
+        ConvParams p{};
+        rc = plan_conv1d(true, x_dtype, y_dtype, B, Cin, Lin, Cout, Lout, ksize, stride, padding, dilation, in_act, epi, p, pl);
     }
-    if (ksize > MAX_K + 2 || ksize > 2 * stride + 1 || p.res || p.post || p.pact || p.y_raw || p.out_scale != 1.f)
-        return KALLE_ERR_UNSUPPORTED;
-    dim3 grid((Lout + L_T - 1) / L_T, (Cout + CO_T - 1) / CO_T, B), block(256);
-    g_conv_plan = 3 | plan_dtypes(xf, yf);
-    if (xf && yf) KALLE_LAUNCH((convT1d_kernel<true, true>), grid, block, 0, st, p);
-    else if (xf) KALLE_LAUNCH((convT1d_kernel<true, false>), grid, block, 0, st, p);
-    else if (yf) KALLE_LAUNCH((convT1d_kernel<false, true>), grid, block, 0, st, p);
-    else KALLE_LAUNCH((convT1d_kernel<false, false>), grid, block, 0, st, p);
-    return kalle_check_launch();
+    if (rc == KALLE_OK) report(pl, out);
+    return rc;
+}
+
+extern "C" int kalle_conv_transpose_plan(int x_dtype, int y_dtype, int B, int Cin, int Lin, int Cout, int Lout, int ksize,
+                                         int stride, int padding, const kalle_act* in_act, const kalle_conv_epilogue* epi,
+                                         int prefer, int32_t* out) {
+    if (!out || prefer < PREFER_AUTO || prefer > PREFER_POSITIONS) return KALLE_ERR_ARG;
+    ConvPlan pl;
+    int rc;
+    const bool sane = B > 0 && Cin > 0 && Lin > 0 && Cout > 0 && Lout > 0 && ksize > 0 && stride > 0 && padding >= 0;
+    // trimmed (Lout at most the symmetric length) or extended (the data gradient of a strided conv): only the former
+    const bool eligible = sane && (int64_t)Lout <= (int64_t)(Lin - 1) * stride - 2 * padding + ksize &&
+                          (!in_act || in_act->code != 4) && x_dtype == KALLE_F32 && y_dtype == KALLE_F32;
+    if (eligible && (prefer == PREFER_CFIRST || (prefer == PREFER_AUTO && convT_prefers_cfirst(B, Cout, Lout, stride, padding)))) {
+        ActArgs a;
+        if (!read_act(in_act, a, false)) return KALLE_ERR_ARG;
+        ConvCParams p{};
+        rc = plan_cfirst_T(true, B, Cin, convT_pad_geom(Lout, ksize, stride, padding).Lp, Cout, Lout, ksize, stride, padding, epi,
+                           p, pl);
+    } else {
+        ConvParams p{};
+        rc = plan_convT(true, x_dtype, y_dtype, B, Cin, Lin, Cout, Lout, ksize, stride, padding, in_act, epi, p, pl);
+    }
+    if (rc == KALLE_OK) report(pl, out);
+    return rc;
 }
 
 extern "C" int kalle_snake_beta_fwd(const void* x, void* y, int dtype, const float* alpha, const float* beta,

@@ -333,76 +333,112 @@ __global__ __launch_bounds__(256) void wn_bwd_kernel(const float* __restrict__ d
 
 extern "C" __attribute__((visibility("hidden"))) void kalle_set_conv_plan(int plan);   // conv1d.hip: the thread's kalle_conv_last_plan word
 
-extern "C" int kalle_conv_wgrad(const float* U, const float* V, float* dW, int B, int CU, int CV, int MU, int LV, int ksize,
-                                int stride, int padding, int dilation, int act_on, const kalle_act* act, void* stream) {
-    kalle_set_conv_plan(0);
-    if (!U || !V || !dW || B <= 0 || CU <= 0 || CV <= 0 || MU <= 0 || LV <= 0) return KALLE_ERR_ARG;
+namespace {
+// What kalle_conv_wgrad launches: decided without a HIP call (kalle_conv_wgrad_plan reports it)
+struct WgradPlan {
+    int family = 0;                 // 8 conv_wgrad_lds_kernel<TU, KT>, 9 conv_wgrad_kernel<TU, TV, KT> (KT is its KM)
+    int tu = 0, tv = 0, kt = 0;
+    int P = 0, rows = 0, chunks = 0, lds = 0;   // family 8: positions per step, staged rows of V, position ranges, LDS bytes
+    int64_t per_wg = 0;             // positions per workgroup
+    dim3 grid;
+    int code = 0, logscale = 0;     // the activation
+    const float *alpha = nullptr, *beta = nullptr;
+    int word = 0;
+};
+int plan_wgrad(bool tensors, int B, int CU, int CV, int MU, int LV, int ksize, int stride, int padding, int dilation, int act_on,
+               const kalle_act* act, WgradPlan& pl) {
+    if (!tensors || B <= 0 || CU <= 0 || CV <= 0 || MU <= 0 || LV <= 0) return KALLE_ERR_ARG;
     if (ksize <= 0 || ksize > 16 || stride <= 0 || dilation <= 0 || padding < 0 || (act_on != 0 && act_on != 1)) return KALLE_ERR_ARG;
-    int code = 0, logscale = 0;
-    const float *al = nullptr, *be = nullptr;
     if (act) {
-        code = act->code; logscale = act->logscale; al = act->alpha; be = act->beta;
-        if (code < 0 || code > 2 || (code == 1 && (!al || !be))) return KALLE_ERR_ARG;
+        pl.code = act->code; pl.logscale = act->logscale; pl.alpha = act->alpha; pl.beta = act->beta;
+        if (pl.code < 0 || pl.code > 2 || (pl.code == 1 && (!pl.alpha || !pl.beta))) return KALLE_ERR_ARG;
     }
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    // LDS-staged kernel: the activation (if any) sits on V, V has at least a quarter of a wave's worth of channels
-    if ((act_on == 0 || code == 0) && CV >= 16) {
+    // LDS-staged kernel: the activation (if any) sits on V, V has at least a quarter of a wave's worth of channels, and the
+    // tap count is one it was compiled for (other tap counts: the per-lane-load kernel below)
+    const bool staged = (act_on == 0 || pl.code == 0) && CV >= 16 && (ksize == 1 || ksize == 4 || ksize == 7 || ksize == 8 || ksize == 16);
+    if (staged) {
+        pl.tu = ksize == 16 ? 8 : 16; pl.kt = ksize;
         int P = 64;
         auto rows_of = [&](int p) { return (p - 1) * stride + (ksize - 1) * dilation + 1; };
         while (P > 4 && rows_of(P) * 65 * 4 > 48 * 1024) P >>= 1;
-        const int rows = rows_of(P);
-        auto launch2 = [&](auto tu_c, auto k_c) {
-            constexpr int TU = decltype(tu_c)::value, KT = decltype(k_c)::value;
-            const int ty = (CV + 63) / 64, tz = (CU + 4 * TU - 1) / (4 * TU);
-            if (ty > 65535 || tz > 65535) return KALLE_ERR_ARG;
-            // ~1536 workgroups in all, at least 4 tiles of positions each (the final atomics cost what ~100 positions do)
-            int64_t cpb = (1536 + (int64_t)ty * tz * B - 1) / ((int64_t)ty * tz * B);
-            const int64_t max_cpb = (MU + 4 * P - 1) / (4 * P);
-            cpb = cpb < 1 ? 1 : (cpb > max_cpb ? max_cpb : cpb);
-            const int per_wg = (int)(((MU + cpb - 1) / cpb + P - 1) / P * P);
-            const int chunks = (MU + per_wg - 1) / per_wg;
-            if ((int64_t)chunks * B > 0x7fffffff) return KALLE_ERR_ARG;
-            const int lds = std::max(rows * 65 * 4, 4 * 64 * KT * 4);
-            kalle_set_conv_plan(8 | 3 << 4 | TU << 8 | KT << 13);
-            KALLE_LAUNCH((conv_wgrad_lds_kernel<TU, KT>), dim3(chunks * B, ty, tz), dim3(256), lds, st, U, V, dW, CU, CV, MU, LV,
-                         stride, padding, dilation, code, al, be, logscale, chunks, per_wg, P, rows);
-            return kalle_check_launch();
-        };
-        using I16_ = std::integral_constant<int, 16>;
-        using I8_ = std::integral_constant<int, 8>;
-        switch (ksize) {
-            case 1: return launch2(I16_{}, std::integral_constant<int, 1>{});
-            case 4: return launch2(I16_{}, std::integral_constant<int, 4>{});
-            case 7: return launch2(I16_{}, std::integral_constant<int, 7>{});
-            case 8: return launch2(I16_{}, I8_{});
-            case 16: return launch2(I8_{}, I16_{});
-            default: break;                  // other tap counts: the per-lane-load kernel below
-        }
+        pl.P = P; pl.rows = rows_of(P);
+        const int ty = (CV + 63) / 64, tz = (CU + 4 * pl.tu - 1) / (4 * pl.tu);
+        if (ty > 65535 || tz > 65535) return KALLE_ERR_ARG;
+        // ~1536 workgroups in all, at least 4 tiles of positions each (the final atomics cost what ~100 positions do)
+        int64_t cpb = (1536 + (int64_t)ty * tz * B - 1) / ((int64_t)ty * tz * B);
+        const int64_t max_cpb = (MU + 4 * P - 1) / (4 * P);
+        cpb = cpb < 1 ? 1 : (cpb > max_cpb ? max_cpb : cpb);
+        pl.per_wg = (int)(((MU + cpb - 1) / cpb + P - 1) / P * P);
+        pl.chunks = (MU + (int)pl.per_wg - 1) / (int)pl.per_wg;
+        if ((int64_t)pl.chunks * B > 0x7fffffff) return KALLE_ERR_ARG;
+        pl.lds = std::max(pl.rows * 65 * 4, 4 * 64 * pl.kt * 4);
+        pl.grid = dim3(pl.chunks * B, ty, tz);
+        pl.family = 8;
+        pl.word = 8 | 3 << 4 | pl.tu << 8 | pl.kt << 13;
+        return KALLE_OK;
     }
+    if (ksize <= 4) { pl.tu = 4; pl.tv = 8; pl.kt = 4; }
+    else if (ksize <= 8) { pl.tu = 4; pl.tv = 4; pl.kt = 8; }
+    else { pl.tu = 2; pl.tv = 4; pl.kt = 16; }
     const int64_t total = (int64_t)B * MU;
     // position ranges: enough workgroups to fill the chip a few times over, at least 2048 positions each (the final fold costs
     // TU*TV*K shuffles + atomics per wave)
-    auto launch = [&](auto tu_c, auto tv_c, auto km_c) {
-        constexpr int TU = decltype(tu_c)::value, TV = decltype(tv_c)::value, KM = decltype(km_c)::value;
-        const int ty = (CV + TV - 1) / TV, tz = (CU + TU - 1) / TU;
-        if (ty > 65535 || tz > 65535) return KALLE_ERR_ARG;
-        int64_t chunks = (2048 + (int64_t)ty * tz - 1) / ((int64_t)ty * tz);         // ~2048 workgroups in all
-        const int64_t max_chunks = (total + 2047) / 2048;
-        chunks = chunks < 1 ? 1 : (chunks > max_chunks ? max_chunks : chunks);
-        const int64_t per_wg = ((total + chunks - 1) / chunks + 255) / 256 * 256;
-        const int gx = (int)((total + per_wg - 1) / per_wg);
-        kalle_set_conv_plan(9 | 3 << 4 | TU << 8 | TV << 13 | KM << 18);
-        KALLE_LAUNCH((conv_wgrad_kernel<TU, TV, KM>), dim3(gx, ty, tz), dim3(256), 0, st, U, V, dW, B, CU, CV, MU, LV, ksize,
-                     stride, padding, dilation, act_on, code, al, be, logscale, per_wg);
-        return kalle_check_launch();
-    };
-    using I2 = std::integral_constant<int, 2>;
-    using I4 = std::integral_constant<int, 4>;
-    using I8 = std::integral_constant<int, 8>;
-    using I16 = std::integral_constant<int, 16>;
-    if (ksize <= 4) return launch(I4{}, I8{}, I4{});
-    if (ksize <= 8) return launch(I4{}, I4{}, I8{});
-    return launch(I2{}, I4{}, I16{});
+    const int ty = (CV + pl.tv - 1) / pl.tv, tz = (CU + pl.tu - 1) / pl.tu;
+    if (ty > 65535 || tz > 65535) return KALLE_ERR_ARG;
+    int64_t chunks = (2048 + (int64_t)ty * tz - 1) / ((int64_t)ty * tz);         // ~2048 workgroups in all
+    const int64_t max_chunks = (total + 2047) / 2048;
+    chunks = chunks < 1 ? 1 : (chunks > max_chunks ? max_chunks : chunks);
+    pl.per_wg = ((total + chunks - 1) / chunks + 255) / 256 * 256;
+    pl.grid = dim3((int)((total + pl.per_wg - 1) / pl.per_wg), ty, tz);
+    pl.family = 9;
+    pl.word = 9 | 3 << 4 | pl.tu << 8 | pl.tv << 13 | pl.kt << 18;
+    return KALLE_OK;
+}
+}  // namespace
+
+extern "C" int kalle_conv_wgrad_plan(int B, int CU, int CV, int MU, int LV, int ksize, int stride, int padding, int dilation,
+                                     int act_on, const kalle_act* act, int32_t* out) {
+    WgradPlan pl;
+    if (!out) return KALLE_ERR_ARG;
+    const int rc = plan_wgrad(true, B, CU, CV, MU, LV, ksize, stride, padding, dilation, act_on, act, pl);
+    if (rc != KALLE_OK) return rc;
+    out[0] = pl.family; out[1] = pl.word; out[2] = (int32_t)pl.grid.x; out[3] = (int32_t)pl.grid.y; out[4] = (int32_t)pl.grid.z;
+    return KALLE_OK;
+}
+
+extern "C" int kalle_conv_wgrad(const float* U, const float* V, float* dW, int B, int CU, int CV, int MU, int LV, int ksize,
+                                int stride, int padding, int dilation, int act_on, const kalle_act* act, void* stream) {
+    kalle_set_conv_plan(0);
+    WgradPlan pl;
+    const int rc = plan_wgrad(U && V && dW, B, CU, CV, MU, LV, ksize, stride, padding, dilation, act_on, act, pl);
+    if (rc != KALLE_OK) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int tile = pl.tu << 16 | pl.tv << 8 | pl.kt;
+    switch (pl.family << 24 | tile) {
+#define KALLE_STAGED(TU, KT)                                                                                                   \
+    case 8 << 24 | TU << 16 | KT:                                                                                              \
+        KALLE_LAUNCH((conv_wgrad_lds_kernel<TU, KT>), pl.grid, dim3(256), pl.lds, st, U, V, dW, CU, CV, MU, LV, stride, padding, \
+                     dilation, pl.code, pl.alpha, pl.beta, pl.logscale, pl.chunks, (int)pl.per_wg, pl.P, pl.rows);              \
+        break;
+        KALLE_STAGED(16, 1)
+        KALLE_STAGED(16, 4)
+        KALLE_STAGED(16, 7)
+        KALLE_STAGED(16, 8)
+        KALLE_STAGED(8, 16)
+#undef KALLE_STAGED
+#define KALLE_PER_LANE(TU, TV, KM)                                                                                             \
+    case 9 << 24 | TU << 16 | TV << 8 | KM:                                                                                    \
+        KALLE_LAUNCH((conv_wgrad_kernel<TU, TV, KM>), pl.grid, dim3(256), 0, st, U, V, dW, B, CU, CV, MU, LV, ksize, stride,     \
+                     padding, dilation, act_on, pl.code, pl.alpha, pl.beta, pl.logscale, pl.per_wg);                            \
+        break;
+        KALLE_PER_LANE(4, 8, 4)
+        KALLE_PER_LANE(4, 4, 8)
+        KALLE_PER_LANE(2, 4, 16)
+#undef KALLE_PER_LANE
+        default: return KALLE_ERR_UNSUPPORTED;   // a tile that was never compiled (a planner bug; nothing is launched)
+    }
+    kalle_set_conv_plan(pl.word);
+    return kalle_check_launch();
 }
 
 extern "C" int kalle_act_bwd(const float* x, const float* g, float* dx, const kalle_act* act, float* dalpha, float* dbeta, int B,

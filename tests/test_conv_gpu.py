@@ -5,8 +5,9 @@ Conventions: those of test_norm_elementwise_gpu.py; the checks the two files sha
 every element bounded and the first offender reported, NaN before and after every operand and output buffer (the tensors are
 dense: `guarded`, the one-dimensional form of `Guard`), accumulating
 outputs started from random contents and checked as before + ref, pure data movement bit-exact.  Every forward / wgrad case
-names the plan word (kalle_conv_last_plan, encoding in the header) it expects and asserts it; the shapes were found by reading
-pick_tile / cfirst_ksplit / the split rule, a case whose plan does not come out is a wrong case.
+names the plan word (kalle_conv_last_plan, encoding in the header) it expects and asserts it; the shapes can be checked without
+a device through the queries kalle_conv_plan / kalle_conv_transpose_plan / kalle_conv_wgrad_plan (tests/test_conv_plan_cpu.py
+does, over tests/conv_cases.py), a case whose plan does not come out is a wrong case.
 
 Error model, u = 2^-24.  A conv output before the activation is an n-term fp32 sum, n = Cin K + 4 (bias, residual, scale,
 accumulate), in any order (so the ks > 1 partial sums and the wgrad atomics are covered): |err| <= n u abs_sum, abs_sum = the sum
@@ -1094,6 +1095,84 @@ def test_wrong_references_are_caught(kl, wrong, kind, c):
     with pytest.raises(AssertionError, match="out of bound"):
         run(kl, c, wrong=wrong)
     print(f"wrong reference {wrong}: caught")
+
+
+# ================================================================================================ the host queries
+def _query_cases():
+    """(family, ks > 1, plan case): one tiny shape per family, each checked against tests/golden/conv_plans.json.  (conv_cases
+    imports this module's lists, so it is imported here and not at the top)"""
+    import conv_cases as cc
+    return [
+        (2, False, cc.conv(3, 9, 20, 3, 200)),
+        (1, False, cc.conv(3, 9, 20, 3, 200, xdt=BF16)),
+        (4, False, cc.convT(2, 8, 20, 4, 50, 2)),
+        (3, False, cc.convT(2, 8, 20, 4, 50, 2, ydt=BF16)),
+        (5, False, cc.conv(1, 8, 256, 3, 32)),
+        (5, True, cc.conv(1, 352, 64, 3, 16)),
+        (6, False, cc.conv(1, 8, 256, 4, 64, stride=2)),
+        (7, False, cc.convT(1, 8, 256, 4, 16, 2)),
+        (8, False, cc.wgrad(1, 8, 16, 7, 64, pl=3)),
+        (9, False, cc.wgrad(1, 8, 8, 7, 64, pl=3)),
+    ]
+
+
+@pytest.mark.parametrize("i", range(10), ids=["family2", "family1", "family4", "family3", "family5", "family5ks", "family6", "family7", "family8", "family9"])
+def test_conv_query_matches_launch(kl, i):
+    """conv_ops / conv_train launch what the host query predicts: the plan word, and bit for bit the output of the entry point the
+    query names, called directly with the query's Lp / lead / phases / workspace"""
+    import json
+    import conv_cases as cc
+    from kalle_audio_amd import conv_ops, conv_train
+    family, split, c = _query_cases()[i]
+    ops, lib, L = kl
+    P, st = ops._p, ops._stream()
+    row = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "conv_plans.json")))[cc.key(c)]
+    assert row[1] == 0 and row[2] & 15 == family and (family in (5, 6, 7) and ((row[2] >> 12) & 31) > 1) == split, (row, "a wrong case")
+    q = cc.query(c)
+    assert q == row, (q, row)
+    f, g = cc.full(c), _gen(5)
+    tdt = lambda d: torch.float32 if d == F32 else torch.bfloat16  # noqa: E731
+    if f["kind"] == "wgrad":
+        U_, V_ = _randn((f["B"], f["CU"], f["MU"]), g), _randn((f["B"], f["CV"], f["LV"]), g)
+        geo = dict(K=f["K"], stride=f["stride"], padding=f["pl"], dilation=f["dil"], act_on=0)
+        dW = conv_train.conv_wgrad(U_, V_, torch.zeros((f["CU"], f["CV"], f["K"]), device="cuda"), **geo)
+        assert lib.kalle_conv_last_plan() == q[2]
+        dW2 = torch.zeros_like(dW)
+        assert lib.kalle_conv_wgrad(P(U_), P(V_), P(dW2), f["B"], f["CU"], f["CV"], f["MU"], f["LV"], f["K"], f["stride"], f["pl"], f["dil"], 0,
+                                    None, st) == 0
+        assert lib.kalle_conv_last_plan() == q[2]
+        torch.cuda.synchronize()
+        assert torch.equal(dW, dW2) and dW.abs().sum() > 0
+        return
+    B, Cin, Lin, Cout, Lout, K, s, pl, dil = (f[k] for k in ("B", "Cin", "Lin", "Cout", "Lout", "K", "stride", "pl", "dil"))
+    x = _randn((B, Cin, Lin), g).to(tdt(f["xdt"]))
+    tr = f["kind"] == "convT"
+    w = conv_ops.weight_norm_fold(_randn((Cin, Cout, K) if tr else (Cout, Cin, K), g, 0.3), None, transposed=tr)
+    bias = _randn((Cout,), g)
+    if tr:
+        y = conv_ops.conv_transpose1d(x, w, bias, Cout=Cout, K=K, stride=s, padding=pl, out_dtype=tdt(f["ydt"]))
+    else:
+        y = conv_ops.conv1d(x, w, bias, Cout=Cout, K=K, stride=s, padding=pl, dilation=dil, out_dtype=tdt(f["ydt"]))
+    assert lib.kalle_conv_last_plan() == q[2] and tuple(y.shape) == (B, Cout, Lout)
+    y2 = torch.full_like(y, NAN)
+    entry, word = q[0], q[2]
+    Lp, lead, phases, nws = q[3:] or (0, 0, 0, 0)
+    if entry.startswith("cfirst"):
+        xp = torch.full((B, Cin, Lp), NAN, device="cuda")
+        assert lib.kalle_conv_pad_act(P(x), P(xp), B, Cin, Lin, Lp, lead, None, phases, st) == 0
+        ws = torch.full((nws,), NAN, device="cuda") if nws else None
+        assert (nws > 0) == split
+    if entry == "conv":
+        rc = lib.kalle_conv1d_fwd(P(x), f["xdt"], P(w), P(bias), P(y2), f["ydt"], B, Cin, Lin, Cout, Lout, K, s, pl, dil, None, None, st)
+    elif entry == "convT":
+        rc = lib.kalle_conv_transpose1d_fwd(P(x), f["xdt"], P(w), P(bias), P(y2), f["ydt"], B, Cin, Lin, Cout, Lout, K, s, pl, None, None, st)
+    elif entry == "cfirst":
+        rc = lib.kalle_conv1d_cfirst_fwd(P(xp), P(w), P(bias), P(y2), B, Cin, Lp, Cout, Lout, K, s, pl, dil, None, P(ws), st)
+    else:
+        rc = lib.kalle_conv_transpose1d_cfirst_fwd(P(xp), P(w), P(bias), P(y2), B, Cin, Lp, Cout, Lout, K, s, pl, None, st)
+    assert rc == 0 and lib.kalle_conv_last_plan() == word
+    torch.cuda.synchronize()
+    assert torch.equal(y, y2) and not torch.isnan(y.float()).any()
 
 
 # ================================================================================================ coverage and allowances
