@@ -384,17 +384,34 @@ int kalle_attention_decode_hd(const void* q, int64_t ldq, int q_off, const void*
                               const void* v, int64_t ldv, int v_off, void* out, int64_t ldo, float* lse,
                               const float* rope_cos, const float* rope_sin, int rot, const uint8_t* key_mask,
                               int B, int H, int Hkv, int Nk, int head_dim, void* stream);
-/* which kernel family the calling thread's most recent kalle_attention_fwd / _bwd (_hd) / kalle_attention_decode_hd launched; 0
- * when that call returned before launching anything.
+/* Batched decoding: R sequences (rows) of different lengths share one call.  Row r has ONE query q[r] at rotary position
+ * nk[r] - 1 and attends keys 0 .. nk[r] - 1 of ITS OWN cache at k + r * kv_row_stride (elements; v likewise), rows of ldk / ldv
+ * inside it; out: [R][ldo], lse: [R][H] or NULL.  nk is a HOST array of R ints, copied into the kernel's parameter block (as the
+ * `layers` of kalle_llama_decode_step are read on the host): no device read-back, no copy.  nk[r] <= 0: row r is INACTIVE -
+ * nothing of it is read (q, cache, tables) and nothing written (out, lse).  Cache rows >= nk[r] and table rows >= max(nk) are
+ * never read.  The kernels are the per-row launch forms of attn_decode_kernel<rot> (head_dim 64, rot 64 or 0) and
+ * attn_decode128_kernel<128> (head_dim 128, rot 128): the same statements, so the same arithmetic and rounding points; the LDS
+ * score array is sized by max(nk).
+ * KALLE_ERR_ARG, nothing launched: R outside 1 .. KALLE_DECODE_MAX_ROWS, max(nk) > 15360 (there is no tiled fallback with per-row
+ * lengths), kv_row_stride not a multiple of 8, rot 32, and whatever kalle_attention_decode_hd refuses.  Every row inactive:
+ * KALLE_OK, nothing launched (plan word 0). */
+#define KALLE_DECODE_MAX_ROWS 16
+int kalle_attention_decode_rows(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off,
+                                const void* v, int64_t ldv, int v_off, int64_t kv_row_stride, void* out, int64_t ldo,
+                                float* lse, const float* rope_cos, const float* rope_sin, int rot, const int32_t* nk,
+                                int R, int H, int Hkv, int head_dim, void* stream);
+/* which kernel family the calling thread's most recent kalle_attention_fwd / _bwd (_hd) / kalle_attention_decode_hd /
+ * kalle_attention_decode_rows launched; 0 when that call returned before launching anything.
  *   bits 0-3   family: 1 fwd_tiled (attn_fwd_kernel), 2 fwd_decode (attn_decode_kernel: head dim 64, Nq == 1, Nk <= 15360),
  *              3 bwd_two_pass (attn_bwd_kernel, dQ + delta then dK / dV), 4 bwd_fused (attn_bwd_fused_kernel: head dim 64, not
  *              causal, H == Hkv, Nq, Nk <= 128), 5 bwd_fused_gqa (attn_bwd_fused_gqa_kernel: head dim 64, not causal, rot 0,
  *              Nq <= 128, Nk - 128 <= min(16, 128 - Nq)), 6 fwd_decode_128 (attn_decode128_kernel: kalle_attention_decode_hd at
- *              head dim 128, Nk <= 15360; a forward family: bit 4 is 0)
+ *              head dim 128, Nk <= 15360; a forward family: bit 4 is 0), 7 fwd_decode_rows (attn_decode_rows_kernel /
+ *              attn_decode128_rows_kernel: kalle_attention_decode_rows; a forward family, head dim and ROT in their fields)
  *   bit 4      direction: 0 forward, 1 backward
  *   bits 8-15  head dim (32 / 64 / 128)
  *   bit 16     family 1: the keys 128 .. Nk - 1 were folded into the first block (Nk in (128, 160], rot 0, not causal)
- *   bits 17-24 families 2 and 6: the ROT instantiation (0 / 32 / 64; 128 for family 6, which is why the field has 8 bits - every
+ *   bits 17-24 families 2, 6 and 7: the ROT instantiation (0 / 32 / 64; 128 for family 6 and for 7 at head dim 128, which is why the field has 8 bits - every
  *              word of families 1-5 keeps the value it had with a 7-bit field) */
 int kalle_attn_last_plan(void);
 
@@ -576,6 +593,52 @@ int kalle_llama_decode_ws_bytes_hd(int H, int Hkv, int inner, int head_dim);
 int kalle_llama_decode_step_hd(const kalle_llama_layer* layers, int n_layers, const float* x, float* out, int H, int Hkv,
                                int inner, int head_dim, float eps, int t0, int cache_rows,
                                const float* rope_cos, const float* rope_sin, void* workspace, void* stream);
+/* ---- batched KV-cached decoding: R = 1 .. KALLE_DECODE_MAX_ROWS sequences (rows) per step ------------------------------------
+ * The reference's inference scripts run a list of utterances through `model.infer` one after the other (infer_0828_sigma.py:313);
+ * a decode step reads every decoder weight once and does one multiply-add per weight read, so R rows per step share that stream.
+ *
+ * Skinny GEMM: Y[r][n] = sum_k W[n][k] X[r][k] (+ residual[r][n]) for R rows; W bf16 [N][ldw] is read from HBM once for all rows
+ * (gemm_rows_kernel: 8 weight rows per workgroup below N = 8192 and 16 from there - as many workgroups as kalle_gemv_bf16 has or
+ * more - x 16 batch columns of v_mfma_f32_16x16x32_bf16, the unused columns zero, the four waves splitting K; fp32 accumulation,
+ * order unspecified but fixed).  X bf16 [R][ldx], Y bf16 or fp32 [R][ldy], residual
+ * fp32 [R][ldres] or NULL.  K % 8 == 0, ldx % 8 == 0, ldw % 8 == 0, K <= 32768 (as kalle_gemv_bf16), 1 <= R <= 16. */
+int kalle_gemm_rows_bf16(const void* x, int64_t ldx, const void* W, int64_t ldw, void* y, int64_t ldy, int y_dtype,
+                         const float* residual, int64_t ldres, int R, int N, int K, void* stream);
+/* The form the batched step uses.  On top of the above:
+ *   prologue (the three of the one-row kernel, per row, rounded to bf16 at the same points):
+ *     KALLE_PRO_BF16   x bf16 [R][ldx] used as is (gamma, eps, xhat unused)
+ *     KALLE_PRO_RMS    x fp32 [R][ldx] (ldx % 4 == 0) -> bf16(x * (gamma * rsqrt(mean(x^2) + eps)))
+ *     KALLE_PRO_SWIGLU x bf16 [R][ldx] = up [K] | gate [K] per row -> bf16(up * silu(gate))
+ *     the last two run as a pre-pass (one launch, a workgroup per row) that writes the operand once into xhat, bf16 [R][K]
+ *     caller scratch, instead of once per workgroup of the GEMM;
+ *   nsplit / y2 / y2_off: output columns n >= nsplit of row r go to y2 + y2_off[r] + (n - nsplit) (elements of y's dtype; y2_off
+ *     a HOST array [R]): k | v of the fused q|k|v projection land in cache row t0[r] of sequence r.  nsplit = N: no second
+ *     destination (y2, y2_off may be NULL);
+ *   active: HOST int32 [R] or NULL (all rows).  active[r] == 0: nothing of row r is read (x, residual) or written (xhat, y, y2).
+ * Both arrays travel in the kernel's parameter block. */
+#define KALLE_PRO_BF16 0
+#define KALLE_PRO_RMS 1
+#define KALLE_PRO_SWIGLU 2
+int kalle_gemm_rows_fused(const void* x, int64_t ldx, int prologue, const float* gamma, float eps, void* xhat, const void* W,
+                          int64_t ldw, void* y, int64_t ldy, int y_dtype, void* y2, int nsplit, const int64_t* y2_off,
+                          const float* residual, int64_t ldres, const int32_t* active, int R, int N, int K, void* stream);
+/* kalle_llama_decode_step_hd on R rows.  x, out: fp32 [R][D]; t0: HOST int32 [R], the new position of each row, NEGATIVE = the
+ * row is inactive (finished, or padding): nothing is read or written for it anywhere - not its cache, not its workspace rows,
+ * not its out row.  kv_cache of a layer: bf16 [R][cache_rows][2*Hkv*head_dim]; only row t0[r] of sequence r is written.
+ * rope tables: [>= max(t0)+1][head_dim/2].  Per layer (8 launches): RMSNorm pre-pass -> q|k|v skinny GEMM (k|v into the caches)
+ * -> kalle_attention_decode_rows (nk = t0 + 1) -> o_proj + residual -> RMSNorm pre-pass -> up|gate -> SwiGLU pre-pass -> down +
+ * residual.  Limits: those of the _hd step, 1 <= R <= 16, t0[r] < cache_rows, max(t0) < 15360; anything else returns
+ * KALLE_ERR_ARG before the first launch and leaves no attention plan.  Every launch is checked where it is made.  Every row
+ * inactive: KALLE_OK, nothing launched.
+ * Workspace (kalle_llama_decode_ws_bytes_rows bytes, 64-byte aligned), the regions of the one-row step, each [R][...] row-major,
+ * and one more for the pre-pass operand:
+ *   x2  fp32 [R][D] | x3 fp32 [R][D] | lse fp32 [R][H], the region padded to a multiple of 64 bytes | q bf16 [R][D] |
+ *   ao bf16 [R][D] | hf bf16 [R][2*inner] | xn bf16 [R][max(D, inner)]: the LAST pre-pass's operand (up * silu(gate), row
+ *   stride max(D, inner), the first `inner` of each row) */
+int kalle_llama_decode_ws_bytes_rows(int R, int H, int Hkv, int inner, int head_dim);
+int kalle_llama_decode_step_rows(const kalle_llama_layer* layers, int n_layers, const float* x, float* out, int R, int H,
+                                 int Hkv, int inner, int head_dim, float eps, const int32_t* t0, int cache_rows,
+                                 const float* rope_cos, const float* rope_sin, void* workspace, void* stream);
 /* waveform -> int16 PCM as the inference scripts write it (infer_0723.py:293): out = int16(clamp(x / max|x|, -1, 1) * 32767);
  * peak: one fp32 of device scratch that receives max|x|; x fp32 or bf16 */
 int kalle_peak_normalize_int16(const void* x, int dtype, float* peak, int16_t* out, int64_t n, void* stream);

@@ -1347,6 +1347,7 @@ bool check_common(const void* q, int64_t ldq, int q_off, const void* k, int64_t 
 // to the key from its row index), block softmax over the scores in LDS, then P.V with 8 threads per key row (16-byte
 // loads of v) and a shuffle + LDS reduction over the 32 key groups.  Operands are rounded to bf16 at the same points as
 // the tiled kernel (rotated q / k, probabilities) so both paths agree to rounding of the fp32 sums.
+// (attn_decode_body below is a copy of these statements for per-row lengths: a change here belongs there too.)
 template <int ROT>
 __global__ __launch_bounds__(256) void attn_decode_kernel(AttnParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1463,6 +1464,144 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(AttnParams p) {
     }
 }
 
+// ---- the same kernel with per-row lengths (batched decoding) -------------------------------------------------------------------
+// attn_decode_kernel's statements with the key count, the query position and the cache base of batch row b = blockIdx.y as
+// arguments (Nk, qpos, kbase, vbase) instead of p.Nk, p.qpos and b * p.Nk rows; p.mask is NULL here.  A COPY, not a shared body:
+// routing attn_decode_kernel through this function changed its instruction stream (same source statements, another schedule:
+// 1144 -> 1068 lines at ROT 64), and the one-row decode path keeps the code it was measured with.  Keep the two in step.
+template <int ROT>
+__device__ __forceinline__ void attn_decode_body(const AttnParams& p, const int b, const int Nk, const int qpos,
+                                                 const bf16_t* kbase, const bf16_t* vbase) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* sc = reinterpret_cast<float*>(smem);  // [Nk] scores, then probabilities
+    __shared__ float qs[64];
+    __shared__ float red[8];
+    __shared__ float osum[4][64];
+    constexpr int HALF = ROT / 2;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int h = blockIdx.x;
+    const int hk = h / (p.H / p.Hkv);
+    const bf16_t* qsrc = p.q + (int64_t)b * p.ldq + p.q_off + h * 64;
+    const bf16_t* ksrc = kbase + p.k_off + hk * 64;
+    const bf16_t* vsrc = vbase + p.v_off + hk * 64;
+    auto rnd = [](float x) { return bf16_to_f32(f32_to_bf16(x)); };
+
+    if (tid < 64) {
+        float x = bf16_to_f32(qsrc[tid]);
+        if constexpr (ROT > 0) {
+            if (tid < ROT) {
+                const bool lo = tid < HALF;
+                const float partner = bf16_to_f32(qsrc[lo ? tid + HALF : tid - HALF]);
+                const int i = lo ? tid : tid - HALF;
+                const float c = p.cosT[(int64_t)qpos * HALF + i], sn = p.sinT[(int64_t)qpos * HALF + i];
+                x = rnd(x * c + (lo ? -partner : partner) * sn);
+            }
+        }
+        qs[tid] = x;
+    }
+    __syncthreads();
+
+    float mx = NEG_BIG;
+    for (int j = tid; j < Nk; j += 256) {
+        const bf16_t* kp = ksrc + (int64_t)j * p.ldk;
+        float kf[64];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            const i32x4 w = reinterpret_cast<const i32x4*>(kp)[c];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                kf[8 * c + 2 * e] = bf16lo((uint32_t)w[e]);
+                kf[8 * c + 2 * e + 1] = bf16hi((uint32_t)w[e]);
+            }
+        }
+        if constexpr (ROT > 0) {
+            const float* cp = p.cosT + (int64_t)j * HALF;
+            const float* sp = p.sinT + (int64_t)j * HALF;
+#pragma unroll
+            for (int i4 = 0; i4 < HALF / 4; ++i4) {
+                const f32x4 c = reinterpret_cast<const f32x4*>(cp)[i4], sn = reinterpret_cast<const f32x4*>(sp)[i4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int i = 4 * i4 + e;
+                    const float a = kf[i], bb = kf[i + HALF];
+                    kf[i] = rnd(a * c[e] - bb * sn[e]);
+                    kf[i + HALF] = rnd(bb * c[e] + a * sn[e]);
+                }
+            }
+        }
+        float a0 = 0.f, a1 = 0.f;
+#pragma unroll
+        for (int d = 0; d < 64; d += 2) { a0 += kf[d] * qs[d]; a1 += kf[d + 1] * qs[d + 1]; }
+        float sv = (a0 + a1) * SM_SCALE;
+        if (p.mask && !p.mask[(int64_t)b * Nk + j]) sv = NEG_BIG;
+        sc[j] = sv;
+        mx = fmaxf(mx, sv);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    if (lane == 0) red[wave] = mx;
+    __syncthreads();
+    const float m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    float ls = 0.f;
+    for (int j = tid; j < Nk; j += 256) {
+        const float pv = __expf(sc[j] - m);
+        ls += pv;
+        sc[j] = rnd(pv);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) ls += __shfl_xor(ls, o, 64);
+    if (lane == 0) red[4 + wave] = ls;
+    __syncthreads();
+    const float l = red[4] + red[5] + red[6] + red[7];
+
+    const int kg = tid >> 3, d8 = tid & 7;
+    float acc[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] = 0.f;
+#pragma unroll 4
+    for (int j = kg; j < Nk; j += 32) {
+        const i32x4 w = *reinterpret_cast<const i32x4*>(vsrc + (int64_t)j * p.ldv + 8 * d8);
+        const float pj = sc[j];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            acc[2 * e] += pj * bf16lo((uint32_t)w[e]);
+            acc[2 * e + 1] += pj * bf16hi((uint32_t)w[e]);
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        acc[e] += __shfl_xor(acc[e], 8, 64);
+        acc[e] += __shfl_xor(acc[e], 16, 64);
+        acc[e] += __shfl_xor(acc[e], 32, 64);
+    }
+    if (lane < 8) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) osum[wave][8 * lane + e] = acc[e];
+    }
+    __syncthreads();
+    if (tid < 64) {
+        const float o = (osum[0][tid] + osum[1][tid] + osum[2][tid] + osum[3][tid]) / l;
+        p.out[(int64_t)b * p.ldo + h * 64 + tid] = f32_to_bf16(o);
+        if (tid == 0 && p.lse) p.lse[(int64_t)b * p.H + h] = m + __logf(l);
+    }
+}
+// Batched decoding: row b has nk[b] keys in its own cache at b * kv_row_stride elements and its query at rotary position
+// nk[b] - 1; nk[b] <= 0: the row is inactive, its workgroups leave before reading or writing anything.  nk travels in the
+// kernel's parameter block (a host array at the C ABI): no device read-back, no copy.  p.Nk / p.qpos / p.mask are not used.
+constexpr int DECODE_MAX_ROWS = KALLE_DECODE_MAX_ROWS;
+struct AttnRowsParams {
+    AttnParams p;
+    int64_t kv_row_stride;
+    int nk[DECODE_MAX_ROWS];
+};
+template <int ROT>
+__global__ __launch_bounds__(256) void attn_decode_rows_kernel(AttnRowsParams rp) {
+    const int b = blockIdx.y;
+    const int Nk = rp.nk[b];
+    if (Nk <= 0) return;
+    attn_decode_body<ROT>(rp.p, b, Nk, Nk - 1, rp.p.k + b * rp.kv_row_stride, rp.p.v + b * rp.kv_row_stride);
+}
+
 // ---- single-query attention at head dim 128 (Llama decoders with 128-wide heads, rotary over the whole head) ------------------
 // Same shape as attn_decode_kernel: a workgroup per (head, batch), scores on the vector ALUs, block softmax over the scores in
 // LDS (Nk * 4 bytes: the same 15360-key ceiling), then P.V; bf16 rounding at the same points as the tiled kernel (rotated q,
@@ -1480,6 +1619,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(AttnParams p) {
 // reduced over the 4 row groups of a wave by shuffles and over the waves through LDS.
 // What bounds it: one workgroup per head streams the head's whole K and V (512 B per key) with 8 loads per lane in flight -
 // latency, not bandwidth; at the decode shapes (24 - 32 heads on 256 CUs) the GEMVs around it own the step.
+// (attn_decode128_body below is a copy of these statements for per-row lengths: a change here belongs there too.)
 constexpr int DECODE128_KB = 128, DECODE128_PV_GROUPS = 16;
 template <int ROT>
 __global__ __launch_bounds__(256) void attn_decode128_kernel(AttnParams p) {
@@ -1603,10 +1743,141 @@ __global__ __launch_bounds__(256) void attn_decode128_kernel(AttnParams p) {
     }
 }
 
+// (attn_decode128_kernel with per-row lengths: a copy for the same reason as attn_decode_body)
+template <int ROT>
+__device__ __forceinline__ void attn_decode128_body(const AttnParams& p, const int b, const int Nk, const int qpos,
+                                                    const bf16_t* kbase, const bf16_t* vbase) {
+    static_assert(ROT == 128, "rotary over the whole head: the only caller");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* sc = reinterpret_cast<float*>(smem);  // [Nk] scores, then probabilities
+    __shared__ __attribute__((aligned(16))) float qs[128];
+    __shared__ float red[8];
+    __shared__ float osum[4][128];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int h = blockIdx.x;
+    const int hk = h / (p.H / p.Hkv);
+    const bf16_t* qsrc = p.q + (int64_t)b * p.ldq + p.q_off + h * 128;
+    const bf16_t* ksrc = kbase + p.k_off + hk * 128;
+    const bf16_t* vsrc = vbase + p.v_off + hk * 128;
+    auto rnd = [](float x) { return bf16_to_f32(f32_to_bf16(x)); };
+
+    if (tid < 128) {
+        const bool lo = tid < 64;
+        const float x = bf16_to_f32(qsrc[tid]), partner = bf16_to_f32(qsrc[tid ^ 64]);
+        const float c = p.cosT[(int64_t)qpos * 64 + (tid & 63)], sn = p.sinT[(int64_t)qpos * 64 + (tid & 63)];
+        qs[tid] = rnd(x * c + (lo ? -partner : partner) * sn);
+    }
+    __syncthreads();
+    const int half = tid & 1;                     // this lane's dims: [32 half, +32) and [64 + 32 half, +32)
+    float qa[32], qb[32];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const f32x4 a = reinterpret_cast<const f32x4*>(qs + 32 * half)[c], bb = reinterpret_cast<const f32x4*>(qs + 64 + 32 * half)[c];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { qa[4 * c + e] = a[e]; qb[4 * c + e] = bb[e]; }
+    }
+
+    float mx = NEG_BIG;
+    for (int j0 = 0; j0 < Nk; j0 += DECODE128_KB) {
+        const int j = j0 + (tid >> 1);
+        float part = 0.f;
+        if (j < Nk) {
+            const bf16_t* kp = ksrc + (int64_t)j * p.ldk + 32 * half;
+            float ka[32], kb[32];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const i32x4 wa = reinterpret_cast<const i32x4*>(kp)[c], wb = reinterpret_cast<const i32x4*>(kp + 64)[c];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    ka[8 * c + 2 * e] = bf16lo((uint32_t)wa[e]);
+                    ka[8 * c + 2 * e + 1] = bf16hi((uint32_t)wa[e]);
+                    kb[8 * c + 2 * e] = bf16lo((uint32_t)wb[e]);
+                    kb[8 * c + 2 * e + 1] = bf16hi((uint32_t)wb[e]);
+                }
+            }
+            const float* cp = p.cosT + (int64_t)j * 64 + 32 * half;
+            const float* sp = p.sinT + (int64_t)j * 64 + 32 * half;
+            float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+#pragma unroll
+            for (int i4 = 0; i4 < 8; ++i4) {
+                const f32x4 c = reinterpret_cast<const f32x4*>(cp)[i4], sn = reinterpret_cast<const f32x4*>(sp)[i4];
+#pragma unroll
+                for (int e = 0; e < 4; e += 2) {
+                    const int i = 4 * i4 + e;
+                    a0 += rnd(ka[i] * c[e] - kb[i] * sn[e]) * qa[i];
+                    a1 += rnd(ka[i + 1] * c[e + 1] - kb[i + 1] * sn[e + 1]) * qa[i + 1];
+                    a2 += rnd(kb[i] * c[e] + ka[i] * sn[e]) * qb[i];
+                    a3 += rnd(kb[i + 1] * c[e + 1] + ka[i + 1] * sn[e + 1]) * qb[i + 1];
+                }
+            }
+            part = (a0 + a1) + (a2 + a3);
+        }
+        float sv = (part + __shfl_xor(part, 1, 64)) * Hd<128>::SCALE;      // (both lanes of the pair: the same sum)
+        if (j < Nk) {
+            if (p.mask && !p.mask[(int64_t)b * Nk + j]) sv = NEG_BIG;
+            if (half == 0) sc[j] = sv;
+            mx = fmaxf(mx, sv);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    if (lane == 0) red[wave] = mx;
+    __syncthreads();
+    const float m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    float ls = 0.f;
+    for (int j = tid; j < Nk; j += 256) {
+        const float pv = __expf(sc[j] - m);
+        ls += pv;
+        sc[j] = rnd(pv);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) ls += __shfl_xor(ls, o, 64);
+    if (lane == 0) red[4 + wave] = ls;
+    __syncthreads();
+    const float l = red[4] + red[5] + red[6] + red[7];
+
+    const int kg = tid >> 4, d16 = tid & 15;
+    float acc[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] = 0.f;
+#pragma unroll 4
+    for (int j = kg; j < Nk; j += DECODE128_PV_GROUPS) {
+        const i32x4 w = *reinterpret_cast<const i32x4*>(vsrc + (int64_t)j * p.ldv + 8 * d16);
+        const float pj = sc[j];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            acc[2 * e] += pj * bf16lo((uint32_t)w[e]);
+            acc[2 * e + 1] += pj * bf16hi((uint32_t)w[e]);
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        acc[e] += __shfl_xor(acc[e], 16, 64);
+        acc[e] += __shfl_xor(acc[e], 32, 64);
+    }
+    if (lane < 16) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) osum[wave][8 * lane + e] = acc[e];
+    }
+    __syncthreads();
+    if (tid < 128) {
+        const float o = (osum[0][tid] + osum[1][tid] + osum[2][tid] + osum[3][tid]) / l;
+        p.out[(int64_t)b * p.ldo + h * 128 + tid] = f32_to_bf16(o);
+        if (tid == 0 && p.lse) p.lse[(int64_t)b * p.H + h] = m + __logf(l);
+    }
+}
+template <int ROT>
+__global__ __launch_bounds__(256) void attn_decode128_rows_kernel(AttnRowsParams rp) {
+    const int b = blockIdx.y;
+    const int Nk = rp.nk[b];
+    if (Nk <= 0) return;
+    attn_decode128_body<ROT>(rp.p, b, Nk, Nk - 1, rp.p.k + b * rp.kv_row_stride, rp.p.v + b * rp.kv_row_stride);
+}
+
 // kalle_attn_last_plan (encoding: include/kalle_hip.h)
 thread_local int g_attn_plan = 0;
 enum { PLAN_FWD_TILED = 1, PLAN_FWD_DECODE = 2, PLAN_BWD_TWO_PASS = 3, PLAN_BWD_FUSED = 4, PLAN_BWD_FUSED_GQA = 5,
-       PLAN_FWD_DECODE_128 = 6 };
+       PLAN_FWD_DECODE_128 = 6, PLAN_FWD_DECODE_ROWS = 7 };
 constexpr int attn_plan(int family, int head_dim, bool fold_tail = false, int decode_rot = 0) {
     return family | (family >= PLAN_BWD_TWO_PASS && family <= PLAN_BWD_FUSED_GQA ? 1 << 4 : 0) | head_dim << 8 |
            (fold_tail ? 1 << 16 : 0) | decode_rot << 17;
@@ -1766,6 +2037,41 @@ extern "C" int kalle_attention_decode_hd(const void* q, int64_t ldq, int q_off, 
     p.qpos = Nk - 1;
     KALLE_LAUNCH(attn_decode128_kernel<128>, dim3(H, B), dim3(256), (size_t)Nk * 4, static_cast<hipStream_t>(stream), p);
     kalle_set_attn_plan(attn_plan(PLAN_FWD_DECODE_128, 128, false, 128));
+    return kalle_check_launch();
+}
+
+// one query per row with per-row key counts and caches (batched generation): the per-row launch forms of the two kernels above
+extern "C" int kalle_attention_decode_rows(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off,
+                                           const void* v, int64_t ldv, int v_off, int64_t kv_row_stride, void* out, int64_t ldo,
+                                           float* lse, const float* rope_cos, const float* rope_sin, int rot, const int32_t* nk,
+                                           int R, int H, int Hkv, int head_dim, void* stream) {
+    kalle_set_attn_plan(0);
+    if (!nk || R < 1 || R > DECODE_MAX_ROWS) return KALLE_ERR_ARG;
+    if (head_dim != 64 && head_dim != 128) return KALLE_ERR_ARG;
+    if (head_dim == 128 ? rot != 128 : (rot != 0 && rot != 64)) return KALLE_ERR_ARG;       // the instantiations below
+    int max_nk = 0;
+    for (int r = 0; r < R; ++r) max_nk = nk[r] > max_nk ? nk[r] : max_nk;
+    if (max_nk > 15360 || (kv_row_stride & 7) || kv_row_stride < 0) return KALLE_ERR_ARG;  // (scores in LDS; no tiled fallback per row)
+    if (!out || !check_common(q, ldq, q_off, k, ldk, k_off, v, ldv, v_off, ldo, rot, R, H, Hkv, 1, max_nk > 0 ? max_nk : 1))
+        return KALLE_ERR_ARG;
+    if (rot && (!rope_cos || !rope_sin)) return KALLE_ERR_ARG;
+    if (max_nk <= 0) return KALLE_OK;                                                       // every row inactive: nothing to launch
+    AttnRowsParams rp{};
+    AttnParams& p = rp.p;
+    p.q = static_cast<const bf16_t*>(q); p.ldq = ldq; p.q_off = q_off;
+    p.k = static_cast<const bf16_t*>(k); p.ldk = ldk; p.k_off = k_off;
+    p.v = static_cast<const bf16_t*>(v); p.ldv = ldv; p.v_off = v_off;
+    p.out = static_cast<bf16_t*>(out); p.ldo = ldo; p.lse = lse;
+    p.cosT = rope_cos; p.sinT = rope_sin; p.rot = rot;
+    p.B = R; p.H = H; p.Hkv = Hkv; p.Nq = 1; p.causal = 1;
+    rp.kv_row_stride = kv_row_stride;
+    for (int r = 0; r < R; ++r) rp.nk[r] = nk[r];
+    const dim3 grid(H, R), block(256);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (head_dim == 128) KALLE_LAUNCH(attn_decode128_rows_kernel<128>, grid, block, (size_t)max_nk * 4, st, rp);
+    else if (rot == 64) KALLE_LAUNCH(attn_decode_rows_kernel<64>, grid, block, (size_t)max_nk * 4, st, rp);
+    else KALLE_LAUNCH(attn_decode_rows_kernel<0>, grid, block, (size_t)max_nk * 4, st, rp);
+    kalle_set_attn_plan(attn_plan(PLAN_FWD_DECODE_ROWS, head_dim, false, rot));
     return kalle_check_launch();
 }
 

@@ -154,6 +154,162 @@ inline void gemv_launch(const void* x, const float* gamma, float eps, const void
                  eps, static_cast<const bf16_t*>(W), ldw, y, y2, nsplit, res, N, K, rpw);
 }
 
+// ---- R-row GEMM for batched decoding: Y[r][n] = sum_k W[n][k] X[r][k] (+ residual[r][n]), 1 <= R <= 16 -------------------------
+// Still pure weight streaming: W is read from HBM once for all rows.  A workgroup owns TR weight rows and every row of the batch:
+// v_mfma_f32_16x16x32_bf16 with the weight rows on the M side and the batch on the 16-wide N side, rows >= R or inactive held
+// at zero.  TR = 8 for N < 8192 (the upper M half of the tile stays zero: the MFMA is idle anyway) and 16 from there, so the
+// grid is N / 8 workgroups where the one-row kernel has N / 8 (every decoder GEMM but up|gate: 256 - 640 workgroups at the 1B / 3B
+// shapes on 256 CUs) and N / 16 where it has N / 16 or N / 32.  The dot product over k does not care which k a lane supplies
+// as long as A and B agree, so lane (row i, group g) supplies the SAME 16-byte chunk of weight row i (A) and of batch row i (B)
+// to an MFMA: both operands come straight from global memory in the layout the instruction wants, and X needs no LDS at any
+// K (16 rows x 32768 x 2 B would be 1 MiB against the CU's 160 KiB).  One load instruction covers 64 contiguous bytes of each
+// weight row (the four groups side by side), eight consecutive ones a 512-byte run.  X is R x K x 2 bytes out of L2 per
+// workgroup.  The four waves take every fourth 256-element K block and their partial tiles meet in LDS (4 KiB), summed in a
+// fixed order; thread t then owns output (row t / TR, column t % TR).  Loads of the next K block are issued before the MFMAs
+// of the current one.
+// The RMSNorm / SwiGLU prologues cannot be rebuilt per workgroup here the way the one-row kernel does it: each of the N / 8
+// or N / 16 workgroups would re-read R x K fp32 from L2 (qkv at the 3B shape: 640 x 192 KiB = 120 MiB against 31 MiB of weights) and redo
+// R row norms.  rows_prologue_kernel writes the bf16 operand once per GEMM instead (R x K x 2 bytes, one short launch), with the
+// one-row kernel's expressions, so the rounding points are the same.
+struct RowsArgs {
+    int64_t y2_off[KALLE_DECODE_MAX_ROWS];   // element offset into y2 of row r's second destination
+    unsigned active;                         // bit r: row r takes part
+    int R;
+};
+
+template <int PRO>
+__global__ __launch_bounds__(256) void rows_prologue_kernel(const void* __restrict__ xall, int64_t ldx,
+                                                            const float* __restrict__ gamma, float eps,
+                                                            bf16_t* __restrict__ xhat, int64_t ldh, int K, unsigned active) {
+    static_assert(PRO == PRO_RMS || PRO == PRO_SWIGLU, "PRO_BF16 has no pre-pass");
+    const int r = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (!(active >> r & 1)) return;
+    bf16_t* xs = xhat + r * ldh;
+    if constexpr (PRO == PRO_RMS) {
+        __shared__ float red[4];
+        const float* x = static_cast<const float*>(xall) + r * ldx;
+        float q = 0.f;
+        for (int i = threadIdx.x; i < (K >> 2); i += 256) {
+            const f32x4 v = reinterpret_cast<const f32x4*>(x)[i];
+            q += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
+        }
+        q = wave_sum(q);
+        if (lane == 0) red[wave] = q;
+        __syncthreads();
+        const float rr = rsqrtf((red[0] + red[1] + red[2] + red[3]) / (float)K + eps);
+        for (int i = threadIdx.x; i < (K >> 2); i += 256) {
+            const f32x4 v = reinterpret_cast<const f32x4*>(x)[i];
+            const f32x4 g = reinterpret_cast<const f32x4*>(gamma)[i];
+            i32x2 o;
+            o[0] = (int)pack_bf16x2(v[0] * (g[0] * rr), v[1] * (g[1] * rr));
+            o[1] = (int)pack_bf16x2(v[2] * (g[2] * rr), v[3] * (g[3] * rr));
+            reinterpret_cast<i32x2*>(xs)[i] = o;
+        }
+    } else {
+        const bf16_t* h = static_cast<const bf16_t*>(xall) + r * ldx;
+        for (int i = threadIdx.x; i < (K >> 3); i += 256) {
+            const i32x4 xv = reinterpret_cast<const i32x4*>(h)[i];
+            const i32x4 gv = reinterpret_cast<const i32x4*>(h + K)[i];
+            i32x4 o;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                o[j] = (int)pack_bf16x2(bf16lo((uint32_t)xv[j]) * siluf_(bf16lo((uint32_t)gv[j])),
+                                        bf16hi((uint32_t)xv[j]) * siluf_(bf16hi((uint32_t)gv[j])));
+            reinterpret_cast<i32x4*>(xs)[i] = o;
+        }
+    }
+}
+
+template <bool YF32, int TR>
+__global__ __launch_bounds__(256) void gemm_rows_kernel(const bf16_t* __restrict__ X, int64_t ldx, const bf16_t* __restrict__ W,
+                                                        int64_t ldw, void* __restrict__ y, int64_t ldy, void* __restrict__ y2,
+                                                        int nsplit, const float* __restrict__ res, int64_t ldres, int N, int K,
+                                                        RowsArgs a) {
+    static_assert(TR == 8 || TR == 16, "weight rows per workgroup");
+    __shared__ __attribute__((aligned(16))) float part[4][64][4];
+    constexpr int CH = 8;                         // 16-byte chunks per lane and K block: a block is 8 x 4 groups x 8 = 256 elements
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i16 = lane & 15, g = lane >> 4;
+    const int n0 = blockIdx.x * TR;
+    const bool wrow = TR == 16 || i16 < TR;                   // (TR = 8: M rows 8 .. 15 of the tile stay zero, nothing loaded)
+    const int nc = K >> 3, NB = (nc + 4 * CH - 1) / (4 * CH);
+    const bool live = i16 < a.R && (a.active >> i16 & 1);
+    const bf16_t* wr = W + (int64_t)(n0 + i16 < N ? n0 + i16 : N - 1) * ldw;
+    const bf16_t* xr = X + (live ? i16 : 0) * ldx;            // (not read unless live)
+    auto load = [&](int kb, i32x4* wq, i32x4* xq) {
+#pragma unroll
+        for (int j = 0; j < CH; ++j) {
+            const int c = (kb * CH + j) * 4 + g;
+            const bool in = c < nc;
+            const int cc = in ? c : nc - 1;
+            wq[j] = i32x4{0, 0, 0, 0};                        // past K: a zero weight chunk against a chunk of x that exists
+            if (wrow && in) wq[j] = *reinterpret_cast<const i32x4*>(wr + 8 * cc);
+            xq[j] = i32x4{0, 0, 0, 0};
+            if (live) xq[j] = *reinterpret_cast<const i32x4*>(xr + 8 * cc);
+        }
+    };
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    i32x4 wv[CH], xv[CH];
+    int kb = wave;
+    if (kb < NB) load(kb, wv, xv);
+    for (; kb < NB; kb += 4) {
+        i32x4 wn[CH], xn[CH];
+        const bool more = kb + 4 < NB;
+        if (more) load(kb + 4, wn, xn);
+#pragma unroll
+        for (int j = 0; j < CH; ++j)
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wv[j]), __builtin_bit_cast(bf16x8, xv[j]),
+                                                          acc, 0, 0, 0);
+        if (more) {
+#pragma unroll
+            for (int j = 0; j < CH; ++j) { wv[j] = wn[j]; xv[j] = xn[j]; }
+        }
+    }
+    // lane (i16, g) holds weight rows n0 + 4 g + {0 .. 3} of batch row i16
+    *reinterpret_cast<f32x4*>(part[wave][lane]) = acc;
+    __syncthreads();
+    const int r = threadIdx.x / TR, j = threadIdx.x % TR, n = n0 + j;
+    if (r < a.R && (a.active >> r & 1) && n < N) {
+        const int src = (j >> 2) * 16 + r, e = j & 3;
+        float s = (part[0][src][e] + part[1][src][e]) + (part[2][src][e] + part[3][src][e]);
+        if (res) s += res[r * ldres + n];
+        const int64_t at = n < nsplit ? r * ldy + n : a.y2_off[r] + (n - nsplit);
+        void* yo = n < nsplit ? y : y2;
+        if constexpr (YF32) static_cast<float*>(yo)[at] = s;
+        else static_cast<bf16_t*>(yo)[at] = f32_to_bf16(s);
+    }
+}
+
+// the pre-pass (if any) and the GEMM; returns the first failed launch
+inline int gemm_rows_run(const void* x, int64_t ldx, int pro, const float* gamma, float eps, bf16_t* xhat, int64_t ldh,
+                         const void* W, int64_t ldw, void* y, int64_t ldy, bool yf32, void* y2, int nsplit,
+                         const float* res, int64_t ldres, const RowsArgs& a, int N, int K, hipStream_t st) {
+    const bf16_t* X = static_cast<const bf16_t*>(x);
+    if (pro != PRO_BF16) {
+        if (pro == PRO_RMS)
+            KALLE_LAUNCH((rows_prologue_kernel<PRO_RMS>), dim3(a.R), dim3(256), 0, st, x, ldx, gamma, eps, xhat, ldh, K, a.active);
+        else
+            KALLE_LAUNCH((rows_prologue_kernel<PRO_SWIGLU>), dim3(a.R), dim3(256), 0, st, x, ldx, gamma, eps, xhat, ldh, K, a.active);
+        const int rc = kalle_check_launch();
+        if (rc != KALLE_OK) return rc;
+        X = xhat;
+        ldx = ldh;
+    }
+    const bf16_t* Wb = static_cast<const bf16_t*>(W);
+    const dim3 block(256);
+    // never fewer workgroups streaming weights than gemv_launch has for this N: N / 8 below 8192 rows, N / 16 from there
+    if (N < 8192) {
+        const dim3 grid((N + 7) / 8);
+        if (yf32) KALLE_LAUNCH((gemm_rows_kernel<true, 8>), grid, block, 0, st, X, ldx, Wb, ldw, y, ldy, y2, nsplit, res, ldres, N, K, a);
+        else KALLE_LAUNCH((gemm_rows_kernel<false, 8>), grid, block, 0, st, X, ldx, Wb, ldw, y, ldy, y2, nsplit, res, ldres, N, K, a);
+    } else {
+        const dim3 grid((N + 15) / 16);
+        if (yf32) KALLE_LAUNCH((gemm_rows_kernel<true, 16>), grid, block, 0, st, X, ldx, Wb, ldw, y, ldy, y2, nsplit, res, ldres, N, K, a);
+        else KALLE_LAUNCH((gemm_rows_kernel<false, 16>), grid, block, 0, st, X, ldx, Wb, ldw, y, ldy, y2, nsplit, res, ldres, N, K, a);
+    }
+    return kalle_check_launch();
+}
+
 // peak normalisation to int16 (infer_0723.py:293: x / max|x| -> clamp(-1, 1) * 32767 -> int16, truncating like .to(int16))
 template <bool F32>
 __global__ __launch_bounds__(256) void absmax_kernel(const void* __restrict__ x, unsigned* __restrict__ peak_bits, int64_t n) {
@@ -461,6 +617,106 @@ extern "C" int kalle_llama_decode_step(const kalle_llama_layer* layers, int n_la
                                        const float* rope_sin, void* workspace, void* stream) {
     return kalle_llama_decode_step_hd(layers, n_layers, x, out, H, Hkv, inner, 64, eps, t0, cache_rows, rope_cos, rope_sin,
                                       workspace, stream);
+}
+
+// ---- batched decoding (R rows per step) ----------------------------------------------------------------------------------------
+extern "C" int kalle_gemm_rows_fused(const void* x, int64_t ldx, int prologue, const float* gamma, float eps, void* xhat,
+                                     const void* W, int64_t ldw, void* y, int64_t ldy, int y_dtype, void* y2, int nsplit,
+                                     const int64_t* y2_off, const float* residual, int64_t ldres, const int32_t* active, int R,
+                                     int N, int K, void* stream) {
+    if (!x || !W || !y || R < 1 || R > KALLE_DECODE_MAX_ROWS || N <= 0 || K <= 0 || (K & 7) || (ldw & 7) || K > 32768)
+        return KALLE_ERR_ARG;
+    if (y_dtype != KALLE_F32 && y_dtype != KALLE_BF16) return KALLE_ERR_ARG;
+    if (prologue != PRO_BF16 && prologue != PRO_RMS && prologue != PRO_SWIGLU) return KALLE_ERR_ARG;
+    if (prologue == PRO_RMS ? (!gamma || (ldx & 3)) : (ldx & 7)) return KALLE_ERR_ARG;
+    if (prologue != PRO_BF16 && !xhat) return KALLE_ERR_ARG;
+    if (ldx < (prologue == PRO_SWIGLU ? 2 * (int64_t)K : K) || ldw < K || ldy < 0 || ldres < 0) return KALLE_ERR_ARG;
+    if (nsplit < 0 || nsplit > N || (nsplit < N && (!y2 || !y2_off))) return KALLE_ERR_ARG;
+    RowsArgs a{};
+    a.R = R;
+    for (int r = 0; r < R; ++r) {
+        if (!active || active[r]) a.active |= 1u << r;
+        a.y2_off[r] = nsplit < N ? y2_off[r] : 0;
+    }
+    if (!a.active) return KALLE_OK;
+    return gemm_rows_run(x, ldx, prologue, gamma, eps, static_cast<bf16_t*>(xhat), K, W, ldw, y, ldy, y_dtype == KALLE_F32, y2,
+                         nsplit, residual, ldres, a, N, K, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int kalle_gemm_rows_bf16(const void* x, int64_t ldx, const void* W, int64_t ldw, void* y, int64_t ldy, int y_dtype,
+                                    const float* residual, int64_t ldres, int R, int N, int K, void* stream) {
+    return kalle_gemm_rows_fused(x, ldx, PRO_BF16, nullptr, 0.f, nullptr, W, ldw, y, ldy, y_dtype, nullptr, N, nullptr, residual,
+                                 ldres, nullptr, R, N, K, stream);
+}
+
+extern "C" int kalle_llama_decode_ws_bytes_rows(int R, int H, int Hkv, int inner, int head_dim) {
+    if (R < 1 || R > KALLE_DECODE_MAX_ROWS || H <= 0 || Hkv <= 0 || inner <= 0 || (head_dim != 64 && head_dim != 128))
+        return KALLE_ERR_ARG;
+    if ((int64_t)H * head_dim > 32768 || inner > 32768) return KALLE_ERR_ARG;
+    const int64_t D = (int64_t)H * head_dim, xw = D > inner ? D : inner;
+    // x2 | x3 fp32, lse fp32 (padded), q | ao | hf | xn bf16: each [R][...]
+    return (int)(2 * R * D * 4 + (((int64_t)R * H * 4 + 63) & ~63) + 2 * R * D * 2 + 2 * R * (int64_t)inner * 2 + R * xw * 2);
+}
+
+extern "C" int kalle_llama_decode_step_rows(const kalle_llama_layer* layers, int n_layers, const float* x, float* out, int R,
+                                            int H, int Hkv, int inner, int head_dim, float eps, const int32_t* t0,
+                                            int cache_rows, const float* rope_cos, const float* rope_sin, void* workspace,
+                                            void* stream) {
+    kalle_set_attn_plan(0);
+    if (!layers || n_layers <= 0 || !x || !out || !workspace || !rope_cos || !rope_sin || !t0) return KALLE_ERR_ARG;
+    if (R < 1 || R > KALLE_DECODE_MAX_ROWS) return KALLE_ERR_ARG;
+    if (H <= 0 || Hkv <= 0 || H % Hkv || inner <= 0 || (inner & 7) || cache_rows <= 0) return KALLE_ERR_ARG;
+    if (head_dim != 64 && head_dim != 128) return KALLE_ERR_ARG;
+    if ((int64_t)H * head_dim > 32768 || inner > 32768) return KALLE_ERR_ARG;
+    const int D = H * head_dim, kvw = 2 * Hkv * head_dim, xw = D > inner ? D : inner;
+    RowsArgs a{};
+    a.R = R;
+    int32_t nk[KALLE_DECODE_MAX_ROWS];
+    for (int r = 0; r < R; ++r) {
+        if (t0[r] >= cache_rows || t0[r] >= 15360) return KALLE_ERR_ARG;      // (the attention's LDS score array: nk <= 15360)
+        nk[r] = t0[r] < 0 ? 0 : t0[r] + 1;
+        if (t0[r] >= 0) a.active |= 1u << r;
+        a.y2_off[r] = t0[r] < 0 ? 0 : ((int64_t)r * cache_rows + t0[r]) * kvw;
+    }
+    for (int l = 0; l < n_layers; ++l) {
+        const kalle_llama_layer& L = layers[l];
+        if (!L.input_norm || !L.wqkv || !L.wo || !L.post_norm || !L.wug || !L.wdown || !L.kv_cache) return KALLE_ERR_ARG;
+    }
+    if (!a.active) return KALLE_OK;
+    RowsArgs plain = a;                                      // (no second destination)
+    for (int r = 0; r < R; ++r) plain.y2_off[r] = 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char* ws = static_cast<char*>(workspace);
+    float* xa = reinterpret_cast<float*>(ws);               // x2 [R][D]
+    float* xb = xa + (int64_t)R * D;                        // x3 [R][D]
+    float* lse = xb + (int64_t)R * D;                       // [R][H]
+    bf16_t* q = reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(lse) + ((R * H * 4 + 63) & ~63));
+    bf16_t* ao = q + (int64_t)R * D;
+    bf16_t* hf = ao + (int64_t)R * D;
+    bf16_t* xn = hf + (int64_t)R * 2 * inner;
+    const float* xin = x;
+    for (int l = 0; l < n_layers; ++l) {
+        const kalle_llama_layer& L = layers[l];
+        // q -> scratch, k | v -> cache row t0[r] of sequence r (un-rotated: the attention kernel rotates by row index)
+        int rc = gemm_rows_run(xin, D, PRO_RMS, L.input_norm, eps, xn, xw, L.wqkv, D, q, D, false, L.kv_cache, D, nullptr, 0, a,
+                               D + kvw, D, st);
+        if (rc != KALLE_OK) return rc;
+        rc = kalle_attention_decode_rows(q, D, 0, L.kv_cache, kvw, 0, L.kv_cache, kvw, Hkv * head_dim, (int64_t)cache_rows * kvw, ao,
+                                         D, lse, rope_cos, rope_sin, head_dim, nk, R, H, Hkv, head_dim, stream);
+        if (rc != KALLE_OK) return rc;
+        if ((rc = gemm_rows_run(ao, D, PRO_BF16, nullptr, 0.f, nullptr, 0, L.wo, D, xa, D, true, xa, D, xin, D, plain, D, D, st)) !=
+            KALLE_OK)
+            return rc;
+        if ((rc = gemm_rows_run(xa, D, PRO_RMS, L.post_norm, eps, xn, xw, L.wug, D, hf, 2 * inner, false, hf, 2 * inner, nullptr, 0,
+                                plain, 2 * inner, D, st)) != KALLE_OK)
+            return rc;
+        float* xo = l + 1 == n_layers ? out : xb;
+        if ((rc = gemm_rows_run(hf, 2 * inner, PRO_SWIGLU, nullptr, 0.f, xn, xw, L.wdown, inner, xo, D, true, xo, D, xa, D, plain,
+                                D, inner, st)) != KALLE_OK)
+            return rc;
+        xin = xo;
+    }
+    return KALLE_OK;
 }
 
 extern "C" int kalle_peak_normalize_int16(const void* x, int dtype, float* peak, int16_t* out, int64_t n, void* stream) {

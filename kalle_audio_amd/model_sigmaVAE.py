@@ -316,6 +316,56 @@ class LlamaModel(nn.Module):
         cache["len"] = t0 + n
         return self.norm(x.view(1, n, Dm))
 
+    # ---- inference with a KV cache, R sequences of different lengths per step -------------------------------------------------
+    def init_cache_batch(self, R, max_len, device):
+        """one bf16 [R, max_len, 2 * kv_heads * head_dim] buffer per layer, a length per row, rope tables for max_len"""
+        if not 1 <= R <= ops.DECODE_MAX_ROWS:
+            raise ValueError(f"a batch cache holds 1 .. {ops.DECODE_MAX_ROWS} sequences, got {R}")
+        w = 2 * self.cfg["num_key_value_heads"] * self.head_dim
+        return {"kv": [torch.zeros((R, max_len, w), device=device, dtype=BF16) for _ in self.layers], "len": [0] * R,
+                "rope": LO.rope_tables(max_len, self._inv_freq, device)}
+
+    @torch.no_grad()
+    def prefill_row(self, inputs_embeds, cache, r):
+        """appends the positions of `inputs_embeds` [1, n, D] to row r of a batch cache (the layers of forward_cached on that
+        row's slice) and returns their last hidden states"""
+        _need_gpu(inputs_embeds)
+        _, n, Dm = inputs_embeds.shape
+        t0 = cache["len"][r]
+        if t0 + n > cache["kv"][0].shape[1]:
+            raise ValueError("KV cache too short")
+        x = Fn._to_f32(inputs_embeds.contiguous()).view(n, Dm)
+        for layer, kv in zip(self.layers, cache["kv"]):
+            x = LO.layer_fwd_cached(LO.layer_params(layer), x, kv[r], t0, cache["rope"])
+        cache["len"][r] = t0 + n
+        return self.norm(x.view(1, n, Dm))
+
+    @torch.no_grad()
+    def forward_cached_batch(self, inputs_embeds, cache, active=None):
+        """one new position for every active row: appends `inputs_embeds` [R, 1, D] row by row to the caches and returns the last
+        hidden states [R, 1, D].  active: R host booleans (default: all); an inactive row's cache and length stay as they are
+        and its output row is that of its last active step (zero before the first).  The whole stack is sequenced by kalle_llama_decode_step_rows (one host call)."""
+        _need_gpu(inputs_embeds)
+        R, n, Dm = inputs_embeds.shape
+        if n != 1 or R != len(cache["len"]):
+            raise ValueError("forward_cached_batch takes one position for each row of the cache")
+        active = [True] * R if active is None else [bool(a) for a in active]
+        rows = cache["kv"][0].shape[1]
+        t0 = [t if a else -1 for t, a in zip(cache["len"], active)]
+        if max(t0) >= rows:
+            raise ValueError("KV cache too short")
+        x = Fn._to_f32(inputs_embeds.contiguous()).view(R, Dm)
+        plan = cache.get("plan")
+        if plan is None:
+            ps = [LO.layer_params(layer) for layer in self.layers]
+            plan = cache["plan"] = ops.llama_decode_plan_rows(
+                [(p.g1, p.wqkv, p.wo, p.g2, p.wug, p.wdown, kv) for p, kv in zip(ps, cache["kv"])],
+                R, ps[0].H, ps[0].Hkv, ps[0].wug.shape[0] // 2, x.device, head_dim=ps[0].hd)
+            plan["eps"] = ps[0].eps
+        x = ops.llama_decode_step_rows(plan, x, t0, rows, cache["rope"], plan["eps"])
+        cache["len"] = [t + 1 if a else t for t, a in zip(cache["len"], active)]
+        return self.norm(x.view(R, 1, Dm))
+
 
 class LlamaForCausalLM(nn.Module):
     """the parts of transformers' LlamaForCausalLM the task model touches: `.model`, `.config`, `.vocab_size`,
@@ -463,6 +513,56 @@ class Llasa(nn.Module):
                 input_embed = torch.cat((input_embed, step_in), dim=1)
         out = torch.stack(final[:-1], dim=1).squeeze(1).squeeze(2)
         return out.transpose(1, 2)
+
+    infer_batch_rows = ops.DECODE_MAX_ROWS      # sequences decoded per step by infer_batch (the kernels take up to DECODE_MAX_ROWS)
+
+    @torch.no_grad()
+    def infer_batch(self, prompts, end_disp_kl_thres=0.5, max_length=200):
+        """`infer` (KV-cached) for a list of (input_ids, audio_latents or None): the utterances of a group are generated together,
+        one decoder pass per frame for all of them, so the decoder weights are read once per frame instead of once per frame
+        and utterance.  Returns a list with what `infer` returns for each prompt.  The prompts are prefilled one by one (they
+        differ in length); a row that meets `infer`'s stop rule leaves the batch (its cache is not touched again) while the
+        others go on.  Lists longer than `infer_batch_rows` are processed in groups; one prompt is `infer` itself."""
+        prompts = list(prompts)
+        if not prompts:
+            return []
+        if len(prompts) == 1:
+            return [self.infer(prompts[0][0], prompts[0][1], end_disp_kl_thres=end_disp_kl_thres, max_length=max_length)]
+        G = max(1, min(int(self.infer_batch_rows), ops.DECODE_MAX_ROWS))
+        if len(prompts) > G:
+            return [o for i in range(0, len(prompts), G)
+                    for o in self.infer_batch(prompts[i:i + G], end_disp_kl_thres=end_disp_kl_thres, max_length=max_length)]
+        model = self.base_model.model
+        embeds = []
+        for ids, lat in prompts:
+            parts = [model.embed_tokens(ids.unsqueeze(0))]
+            if lat is not None:
+                parts.append(self.audio_linear(lat))
+            embeds.append(torch.cat(parts, dim=1))
+        R = len(embeds)
+        cache = model.init_cache_batch(R, max(e.shape[1] for e in embeds) + max_length, embeds[0].device)
+        hidden = None
+        final = [[] for _ in range(R)]
+        active = [True] * R
+        s, e = float(self.std), float(torch.e)
+        for i in range(max_length):
+            if i == 0:      # prefill: the last position's hidden state of every prompt
+                hidden = torch.cat([model.prefill_row(emb, cache, r)[:, -1:, :] for r, emb in enumerate(embeds)], dim=0)
+            else:
+                hidden = model.forward_cached_batch(step_in, cache, active)
+            mean2 = self.distribution_linear(hidden.contiguous())                    # [R, 1, d]: every row at once
+            audio_latent = self.sample(mean2)
+            kl = (torch.log(torch.tensor(e / s)) + (s * s + (mean2.float() - 1.0) ** 2) / (2 * e * e) - 0.5).sum(2)
+            kl = (kl / mean2.shape[2]).view(R).tolist()                              # the one host read of the frame
+            for r in range(R):
+                if active[r]:
+                    final[r].append(audio_latent[r:r + 1])
+                    if kl[r] < end_disp_kl_thres and i > 3:
+                        active[r] = False
+            if not any(active):
+                break
+            step_in = self.audio_linear(audio_latent)
+        return [torch.stack(f[:-1], dim=1).squeeze(1).squeeze(2).transpose(1, 2) for f in final]
 
     def init_sigmaVAE(self):
         self.std = torch.tensor(0.5)

@@ -658,6 +658,77 @@ def llama_decode_step(plan, x, t0, cache_rows, rope, eps):
     return out
 
 
+# ---- batched decoding: R <= DECODE_MAX_ROWS sequences per step (include/kalle_hip.h) ----------------------------------------
+DECODE_MAX_ROWS = 16
+
+
+def _i32(vals):
+    return (ctypes.c_int32 * len(vals))(*[int(v) for v in vals])
+
+
+def gemm_rows(x, w, *, residual=None, out_dtype=torch.float32):
+    """Y[r] = W . x[r] (+ residual[r]) for the R <= 16 rows of x (bf16 [R, K], rows may be strided); W bf16 [N, K] is read once
+    for all rows: kalle_gemm_rows_bf16"""
+    lib = _lib.load()
+    assert x.dim() == 2 and w.dim() == 2 and x.stride(1) == 1 and w.stride(1) == 1 and x.shape[1] == w.shape[1]
+    assert x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16
+    R, K = x.shape
+    y = torch.empty((R, w.shape[0]), device=x.device, dtype=out_dtype)
+    if residual is not None:
+        assert residual.dtype == torch.float32 and residual.shape == y.shape and residual.stride(1) == 1
+    check(lib.kalle_gemm_rows_bf16(_p(x), x.stride(0), _p(w), w.stride(0), _p(y), y.stride(0), _dt(y), _p(residual),
+                                   residual.stride(0) if residual is not None else 0, R, w.shape[0], K, _stream()),
+          "kalle_gemm_rows_bf16")
+    return y
+
+
+def attention_decode_rows(q, k, v, nk, *, ldq, q_off, ldk, k_off, ldv, v_off, kv_row_stride, H, Hkv, rope=None, dh=64):
+    """one query per row r (q [R][ldq]) at position nk[r] - 1 against the nk[r] keys of row r's own cache (k + r * kv_row_stride);
+    nk: host ints, <= 0 = inactive row (its out / lse rows are not written): kalle_attention_decode_rows.
+    Returns (out [R, 1, H*dh], lse [R, H, 1])."""
+    lib = _lib.load()
+    R = len(nk)
+    out = torch.empty((R, 1, H * dh), device=q.device, dtype=torch.bfloat16)
+    lse = torch.empty((R, H, 1), device=q.device, dtype=torch.float32)
+    cos, sin, rot = (rope[0], rope[1], rope[0].shape[-1] * 2) if rope is not None else (None, None, 0)
+    check(lib.kalle_attention_decode_rows(_p(q), ldq, q_off, _p(k), ldk, k_off, _p(v), ldv, v_off, kv_row_stride, _p(out), H * dh,
+                                          _p(lse), _p(cos), _p(sin), rot, ctypes.cast(_i32(nk), ctypes.c_void_p), R, H, Hkv, dh,
+                                          _stream()), "kalle_attention_decode_rows")
+    return out, lse
+
+
+def llama_decode_plan_rows(layer_tensors, R, H, Hkv, inner, device, head_dim=64):
+    """llama_decode_plan for R rows: kv_cache of a layer is bf16 [R, cache_rows, 2*Hkv*head_dim]"""
+    lib = _lib.load()
+    arr = (_lib.LlamaLayer * len(layer_tensors))()
+    for d, ts in zip(arr, layer_tensors):
+        for t in ts:
+            assert t.is_contiguous() and t.device == torch.device(device)
+        assert ts[6].dim() == 3 and ts[6].shape[0] == R
+        d.input_norm, d.wqkv, d.wo, d.post_norm, d.wug, d.wdown, d.kv_cache = (t.data_ptr() for t in ts)
+    nbytes = lib.kalle_llama_decode_ws_bytes_rows(R, H, Hkv, inner, head_dim)
+    check(min(nbytes, 0), "kalle_llama_decode_ws_bytes_rows")
+    ws = torch.empty(nbytes, device=device, dtype=torch.uint8)
+    return {"layers": arr, "n": len(layer_tensors), "keep": layer_tensors, "ws": ws, "R": R, "H": H, "Hkv": Hkv, "inner": inner,
+            "head_dim": head_dim}
+
+
+def llama_decode_step_rows(plan, x, t0, cache_rows, rope, eps):
+    """x fp32 [R, D] -> fp32 [R, D]: every decoder layer for row r at position t0[r] (host ints; negative = inactive row) against
+    the KV caches of `plan` (one host call).  The result is the plan's own buffer, reused by the next step: an inactive row keeps
+    what its last active step left there (zeros before the first)"""
+    lib = _lib.load()
+    assert x.shape[0] == plan["R"] == len(t0) and x.is_contiguous() and x.dtype == torch.float32
+    out = plan.get("out")
+    if out is None:
+        out = plan["out"] = torch.zeros_like(x)
+    check(lib.kalle_llama_decode_step_rows(ctypes.cast(plan["layers"], ctypes.c_void_p), plan["n"], _p(x), _p(out), plan["R"],
+                                           plan["H"], plan["Hkv"], plan["inner"], plan["head_dim"], eps,
+                                           ctypes.cast(_i32(t0), ctypes.c_void_p), cache_rows, _p(rope[0]), _p(rope[1]),
+                                           _p(plan["ws"]), _stream()), "kalle_llama_decode_step_rows")
+    return out
+
+
 def gauss_kl2_fwd(pred, label_mean, label_std, mask_a, mask_b, std_mult=1.25):
     """two-Gaussian KL (model.py:84-100); label_std None -> label_mean is the raw mean | scale label [rows, 2 dim]"""
     lib = _lib.load()

@@ -2,7 +2,8 @@
 (hidden 2048, 16 layers, 32 heads / 8 kv heads, intermediate 8192, vocab 128256 + 8 special tokens, latent_dim 64),
 random weights, synthetic batch: text prefix + audio frames per sample.   python tools/llasa_bench.py [B] [L] [steps]
 The decoder shape is an option (defaults: Llama-3.2-1B): --hidden --layers --heads --kv-heads --head-dim --inner, e.g. the
-Llama-3.2-3B shape  --hidden 3072 --layers 28 --heads 24 --kv-heads 8 --head-dim 128 --inner 8192"""
+Llama-3.2-3B shape  --hidden 3072 --layers 28 --heads 24 --kv-heads 8 --head-dim 128 --inner 8192
+--infer-only: KV-cached generation only; --infer-batch R: also Llasa.infer_batch on R prompts (aggregate and per-row frames/s)"""
 import json, os, sys, tempfile, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from kalle_audio_amd.model_sigmaVAE import Llasa
@@ -13,6 +14,13 @@ for _o in SHAPE:
         _i = sys.argv.index(_o)
         SHAPE[_o] = int(sys.argv[_i + 1])
         del sys.argv[_i:_i + 2]
+INFER_BATCH = 0                              # --infer-batch R: Llasa.infer_batch on R prompts next to the batch-1 line
+if "--infer-batch" in sys.argv:
+    _i = sys.argv.index("--infer-batch")
+    INFER_BATCH = int(sys.argv[_i + 1])
+    del sys.argv[_i:_i + 2]
+    if "--infer-only" not in sys.argv and "--infer" not in sys.argv:
+        sys.argv.append("--infer-only")
 HID, NLAYER = SHAPE["--hidden"], SHAPE["--layers"]
 _pos = [a for a in sys.argv[1:] if not a.startswith("--")]
 B = int(_pos[0]) if len(_pos) > 0 else 8
@@ -83,3 +91,23 @@ if "--infer" in sys.argv or INFER_ONLY:
         dt = time.perf_counter() - t0
         print(f"infer use_cache={use_cache}: {nfr} frames in {dt*1e3:.0f} ms = {nfr/dt:.1f} frames/s "
               f"({nfr/dt/12.5:.2f} x real time at 12.5 Hz), out {tuple(out.shape)}")
+        if use_cache:
+            one_fps = nfr / dt
+
+if INFER_BATCH:
+    # the same generation for R utterances at once (Llasa.infer_batch): prompts of 64, 56, 48, ... tokens, 200 frames each
+    m.eval()
+    m.infer_batch_rows = max(m.infer_batch_rows, INFER_BATCH)
+    nfr = 200
+    prompts = [(torch.randint(0, 128264, (64 - 8 * (r % 4),), device=dev), None) for r in range(INFER_BATCH)]
+    m.infer_batch(prompts, end_disp_kl_thres=-1.0, max_length=4)
+    for rep in range(3):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        outs = m.infer_batch(prompts, end_disp_kl_thres=-1.0, max_length=nfr)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        R = len(outs)
+        print(f"infer_batch R={R} (repeat {rep}): {nfr} frames x {R} rows in {dt*1e3:.0f} ms = {dt/nfr*1e3:.3f} ms/step incl. prefill, "
+              f"{R*nfr/dt:.1f} frames/s aggregate, {nfr/dt:.1f} frames/s per row, "
+              f"{R*nfr/dt/one_fps:.2f} x {R} sequential infer calls ({one_fps:.1f} frames/s), out {tuple(outs[0].shape)}")
