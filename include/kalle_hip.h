@@ -639,6 +639,66 @@ int kalle_llama_decode_ws_bytes_rows(int R, int H, int Hkv, int inner, int head_
 int kalle_llama_decode_step_rows(const kalle_llama_layer* layers, int n_layers, const float* x, float* out, int R, int H,
                                  int Hkv, int inner, int head_dim, float eps, const int32_t* t0, int cache_rows,
                                  const float* rope_cos, const float* rope_sin, void* workspace, void* stream);
+/* ---- weight-only FP8 decoding: the decoder weights as OCP e4m3 codes with one fp32 scale per output row ------------------------
+ * A decode step reads every decoder weight once, so a frame costs the bytes of the weights; this halves them.  Activations,
+ * accumulation (fp32) and every bf16 rounding point of the steps above stay where they are.  Opt-in: nothing above changes.
+ * Format:
+ *   W8    uint8 [N][ldq], OCP `e4m3fn` codes (sign, 4 exponent bits with bias 7, 3 mantissa bits: exponent 0 is man/8 * 2^-6,
+ *         otherwise (1 + man/8) * 2^(exp-7); 0x7E = 448 is the largest) - NOT the `e4m3fnuz` codes of MI300.  ldq % 16 == 0 and
+ *         K % 16 == 0: a lane's unit is one 16-byte load of 16 weights.
+ *   scale fp32 [N]; weight (n, k) stands for scale[n] * e4m3(W8[n][k]).
+ *   The codes 0x7F and 0xFF are NaN.  The quantiser never emits them; a GEMM that reads one may produce NaN.
+ *
+ * Quantiser, reproducible bit for bit: per row n of W (bf16 [N][ldw], ldw % 8 == 0), amax = max_k |W[n][k]| exactly;
+ * scale[n] = amax / 448 and t = W[n][k] / scale[n], both correctly rounded fp32 divisions; code = e4m3(clamp(t, -448, 448)),
+ * round to nearest even.  An all-zero row gets scale 1 and codes 0.  Writes [N][K] of W8 and [N] of scale, nothing else. */
+int kalle_quantize_rows_e4m3(const void* W, int64_t ldw, void* W8, int64_t ldq, float* scale, int N, int K, void* stream);
+/* kalle_gemv_bf16 on such weights: y[n] = scale[n] * (fp32 sum over k of e4m3(W8[n][k]) * x[k]) (+ residual[n]); x bf16 [K],
+ * y bf16 or fp32 [N], residual fp32 [N] or NULL; K % 16 == 0, ldq % 16 == 0, K <= 32768 (x is kept in LDS as bf16).  The
+ * products are exact in fp32 (4 significant bits times 8); the order of the sum is unspecified but fixed. */
+int kalle_gemv_e4m3(const void* x, const void* W8, int64_t ldq, const float* scale, void* y, int y_dtype,
+                    const float* residual, int N, int K, void* stream);
+/* The form the one-row step uses: the prologues of kalle_gemm_rows_fused for one row, built inside the kernel (no scratch) with
+ * the expressions of the bf16 step's GEMV - KALLE_PRO_BF16 x bf16 [K]; KALLE_PRO_RMS x fp32 [K], gamma fp32 [K];
+ * KALLE_PRO_SWIGLU x bf16 [2K] = up | gate - and a second destination: outputs n >= nsplit go to y2[n - nsplit] (y's dtype;
+ * nsplit = N: none, y2 may be NULL).  It has no bf16 counterpart and no Python wrapper: it is the step's internal launcher with
+ * argument checks, exported so that the tests can drive each prologue and the second destination of the kernel alone; a caller
+ * wants kalle_gemv_e4m3 or the steps below. */
+int kalle_gemv_fused_e4m3(const void* x, int prologue, const float* gamma, float eps, const void* W8, int64_t ldq,
+                          const float* scale, void* y, int y_dtype, void* y2, int nsplit, const float* residual, int N, int K,
+                          void* stream);
+/* kalle_gemm_rows_fused with W8, ldq and scale in place of W and ldw: the same kernel structure, the weight fragment widened from
+ * e4m3 to bf16 in registers (exact) in front of the same v_mfma_f32_16x16x32_bf16, activations bf16, scale[n] applied where
+ * output (r, n) is written.  Prologues, xhat, nsplit / y2 / y2_off, residual and active as there; K % 16 == 0, ldq % 16 == 0,
+ * K <= 32768, 1 <= R <= 16. */
+int kalle_gemm_rows_fused_e4m3(const void* x, int64_t ldx, int prologue, const float* gamma, float eps, void* xhat,
+                               const void* W8, int64_t ldq, const float* scale, void* y, int64_t ldy, int y_dtype, void* y2,
+                               int nsplit, const int64_t* y2_off, const float* residual, int64_t ldres, const int32_t* active,
+                               int R, int N, int K, void* stream);
+/* kalle_llama_decode_step_hd and kalle_llama_decode_step_rows on e4m3 weights: the arguments, the per-layer sequence, the
+ * attention calls, the workspace layout and size (kalle_llama_decode_ws_bytes_hd / kalle_llama_decode_ws_bytes_rows serve both)
+ * and the refusals of those two, plus D % 16 != 0 (no supported head dim has it) and inner % 16 != 0.  Weights: uint8 row-major
+ * with row stride K ([out][in]; wqkv = [q;k;v], wug = [up;gate]), each with its fp32 scale per output row; norm weights and the
+ * KV cache as in kalle_llama_layer.  Every launch is checked where it is made. */
+typedef struct kalle_llama_layer_w8 {
+    const float* input_norm;
+    const void* wqkv;
+    const float* sqkv;
+    const void* wo;
+    const float* so;
+    const float* post_norm;
+    const void* wug;
+    const float* sug;
+    const void* wdown;
+    const float* sdown;
+    void* kv_cache;
+} kalle_llama_layer_w8;
+int kalle_llama_decode_step_w8(const kalle_llama_layer_w8* layers, int n_layers, const float* x, float* out, int H, int Hkv,
+                               int inner, int head_dim, float eps, int t0, int cache_rows, const float* rope_cos,
+                               const float* rope_sin, void* workspace, void* stream);
+int kalle_llama_decode_step_rows_w8(const kalle_llama_layer_w8* layers, int n_layers, const float* x, float* out, int R, int H,
+                                    int Hkv, int inner, int head_dim, float eps, const int32_t* t0, int cache_rows,
+                                    const float* rope_cos, const float* rope_sin, void* workspace, void* stream);
 /* waveform -> int16 PCM as the inference scripts write it (infer_0723.py:293): out = int16(clamp(x / max|x|, -1, 1) * 32767);
  * peak: one fp32 of device scratch that receives max|x|; x fp32 or bf16 */
 int kalle_peak_normalize_int16(const void* x, int dtype, float* peak, int16_t* out, int64_t n, void* stream);

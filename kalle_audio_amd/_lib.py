@@ -64,6 +64,14 @@ class LlamaLayer(ctypes.Structure):
                 ("kv_cache", ctypes.c_void_p)]
 
 
+class LlamaLayerW8(ctypes.Structure):
+    """Mirror of `kalle_llama_layer_w8`: e4m3 codes and a per-row fp32 scale for each of the four projections."""
+    _fields_ = [("input_norm", ctypes.c_void_p), ("wqkv", ctypes.c_void_p), ("sqkv", ctypes.c_void_p),
+                ("wo", ctypes.c_void_p), ("so", ctypes.c_void_p), ("post_norm", ctypes.c_void_p),
+                ("wug", ctypes.c_void_p), ("sug", ctypes.c_void_p), ("wdown", ctypes.c_void_p), ("sdown", ctypes.c_void_p),
+                ("kv_cache", ctypes.c_void_p)]
+
+
 class WgradProblem(ctypes.Structure):
     """Mirror of `kalle_wgrad_problem`."""
     _fields_ = [("dy", ctypes.c_void_p), ("lddy", ctypes.c_int64), ("x", ctypes.c_void_p), ("ldx", ctypes.c_int64),

@@ -310,6 +310,321 @@ inline int gemm_rows_run(const void* x, int64_t ldx, int pro, const float* gamma
     return kalle_check_launch();
 }
 
+// ---- weight-only OCP e4m3 decoding: W8 uint8 [N][ldq] codes, scale fp32 [N]; weight (n, k) = scale[n] * e4m3(W8[n][k]) -----------
+// The decode step is weight streaming, so the one thing left to cut per frame is the bytes per weight.  v_cvt_pk_f32_fp8 turns
+// two codes into two fp32 values; an e4m3 value (4 significant bits) times a bf16 value (8) is exact in fp32, so the only
+// differences from the bf16 kernels above are the weights themselves, the fp32 summation order and one multiply by scale[n].
+
+// a / b correctly rounded (the IEEE sequence the compiler emits for a precise fdiv): the library is built with -ffast-math, where
+// `/` - and __fdiv_rn, which is `/` in this HIP - is v_rcp_f32 times the numerator, an ulp or so off
+__device__ __forceinline__ float div_rn(float a, float b) {
+    bool fd, fn;
+    const float d = __builtin_amdgcn_div_scalef(a, b, false, &fd);
+    const float n = __builtin_amdgcn_div_scalef(a, b, true, &fn);
+    float r = __builtin_amdgcn_rcpf(d);
+    r = __builtin_fmaf(__builtin_fmaf(-d, r, 1.f), r, r);
+    float q = n * r;
+    q = __builtin_fmaf(__builtin_fmaf(-d, q, n), r, q);
+    return __builtin_amdgcn_div_fixupf(__builtin_amdgcn_div_fmasf(__builtin_fmaf(-d, q, n), r, q, fn), b, a);
+}
+
+// per row: scale = max|w| / 448 (1 for an all-zero row), code = e4m3_rne(clamp(w / scale, +-448)), both divisions correctly
+// rounded.  A wave per row, 4 rows per workgroup; a lane's unit is 16 weights in (two 16-byte loads), 16 codes out (one store).
+__global__ __launch_bounds__(256) void quantize_rows_e4m3_kernel(const bf16_t* __restrict__ W, int64_t ldw,
+                                                                 uint8_t* __restrict__ W8, int64_t ldq,
+                                                                 float* __restrict__ scale, int N, int K) {
+    const int lane = threadIdx.x & 63, n = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (n >= N) return;
+    const bf16_t* w = W + (int64_t)n * ldw;
+    const int nc = K >> 4;
+    float m = 0.f;
+    for (int c = lane; c < nc; c += 64) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const i32x4 v = *reinterpret_cast<const i32x4*>(w + 16 * c + 8 * h);
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                m = fmaxf(m, fmaxf(fabsf(bf16lo((uint32_t)v[e])), fabsf(bf16hi((uint32_t)v[e]))));
+        }
+    }
+    m = wave_max(m);
+    const float s = m > 0.f ? div_rn(m, 448.f) : 1.f;
+    if (lane == 0) scale[n] = s;
+    for (int c = lane; c < nc; c += 64) {
+        i32x4 o;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const i32x4 v = *reinterpret_cast<const i32x4*>(w + 16 * c + 8 * h);
+            float t[8];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                t[2 * e] = fminf(fmaxf(div_rn(bf16lo((uint32_t)v[e]), s), -448.f), 448.f);
+                t[2 * e + 1] = fminf(fmaxf(div_rn(bf16hi((uint32_t)v[e]), s), -448.f), 448.f);
+            }
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                int word = __builtin_amdgcn_cvt_pk_fp8_f32(t[4 * p], t[4 * p + 1], 0, false);
+                word = __builtin_amdgcn_cvt_pk_fp8_f32(t[4 * p + 2], t[4 * p + 3], word, true);
+                o[2 * h + p] = word;
+            }
+        }
+        *reinterpret_cast<i32x4*>(W8 + (int64_t)n * ldq + 16 * c) = o;
+    }
+}
+
+// gemv_kernel on e4m3 weights: y[n] = scale[n] * sum_k e4m3(W8[n][k]) x[k] (+ residual[n]), the three prologues with the
+// expressions of gemv_kernel (the operand stays bf16 in LDS, rounded at the same points).
+// Byte budget: a weight row is K bytes now, so 16 bytes of it hold 16 weights and 64 lanes x 16 bytes cover 1024 of them - at
+// K = 2048 (every Llama-3.2-1B GEMV but down) a row is two loads per lane.  To keep gemv_kernel's 128 bytes per lane in flight
+// (2 rows x 4 x 16 B) a wave owns FOUR rows and issues 2 x 16 B of each per item, one item ahead; a workgroup is two such waves
+// (128 threads), so it still owns 8 rpw rows and the grid is gemv_launch's for every N.  Vector ALU per 16-byte load: 8
+// v_cvt_pk_f32_fp8 + 16 FMA (8 packed), and 16 unpacks of x shared by the four rows: 112 instructions per 64 weight bytes and lane
+// against gemv_kernel's 40 per 32 - 1.4 x the ALU work per byte on half the bytes.
+template <bool YF32, int PRO>
+__global__ __launch_bounds__(128) void gemv_e4m3_kernel(const void* __restrict__ xin, const float* __restrict__ gamma, float eps,
+                                                        const uint8_t* __restrict__ W8, int64_t ldq,
+                                                        const float* __restrict__ scale, void* __restrict__ y,
+                                                        void* __restrict__ y2, int nsplit, const float* __restrict__ res,
+                                                        int N, int K, int rpw) {
+    extern __shared__ __attribute__((aligned(16))) char gsm[];
+    bf16_t* xs = reinterpret_cast<bf16_t*>(gsm);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    constexpr int PF = 2, RW = 4;                 // 16-byte loads per row and item; rows per wave
+    const int nc = K >> 4;
+    const int NB = (nc + 64 * PF - 1) / (64 * PF);
+    const int T = rpw * NB;
+    // a wave walks `rpw` row groups (rows ((blockIdx * rpw + p) * 2 + wave) * 4 + {0 .. 3}) as the flat sequence of (group, K
+    // batch) items; rows past N and chunks past K re-read the last one (in bounds) and are not used
+    auto load = [&](int pr, int bb, i32x4 (*q)[PF]) {
+        const int n = ((blockIdx.x * rpw + pr) * 2 + wave) * RW;
+#pragma unroll
+        for (int i = 0; i < RW; ++i) {
+            const uint8_t* r = W8 + (int64_t)(n + i < N ? n + i : N - 1) * ldq;
+#pragma unroll
+            for (int j = 0; j < PF; ++j) {
+                const int c = bb * (64 * PF) + lane + 64 * j;
+                q[i][j] = *reinterpret_cast<const i32x4*>(r + 16 * (c < nc ? c : nc - 1));
+            }
+        }
+    };
+    i32x4 u[RW][PF];
+    load(0, 0, u);
+    if constexpr (PRO == PRO_BF16) {
+        const bf16_t* x = static_cast<const bf16_t*>(xin);
+        for (int i = threadIdx.x; i < (K >> 3); i += 128)
+            reinterpret_cast<i32x4*>(xs)[i] = reinterpret_cast<const i32x4*>(x)[i];
+    } else if constexpr (PRO == PRO_RMS) {
+        __shared__ float red[2];
+        const float* x = static_cast<const float*>(xin);
+        float q = 0.f;
+        for (int i = threadIdx.x; i < (K >> 2); i += 128) {
+            const f32x4 v = reinterpret_cast<const f32x4*>(x)[i];
+            q += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
+        }
+        q = wave_sum(q);
+        if (lane == 0) red[wave] = q;
+        __syncthreads();
+        const float rr = rsqrtf((red[0] + red[1]) / (float)K + eps);
+        for (int i = threadIdx.x; i < (K >> 2); i += 128) {
+            const f32x4 v = reinterpret_cast<const f32x4*>(x)[i];
+            const f32x4 g = reinterpret_cast<const f32x4*>(gamma)[i];
+            i32x2 o;
+            o[0] = (int)pack_bf16x2(v[0] * (g[0] * rr), v[1] * (g[1] * rr));
+            o[1] = (int)pack_bf16x2(v[2] * (g[2] * rr), v[3] * (g[3] * rr));
+            reinterpret_cast<i32x2*>(xs)[i] = o;
+        }
+    } else {
+        const bf16_t* h = static_cast<const bf16_t*>(xin);
+        for (int i = threadIdx.x; i < (K >> 3); i += 128) {
+            const i32x4 xv = reinterpret_cast<const i32x4*>(h)[i];
+            const i32x4 gv = reinterpret_cast<const i32x4*>(h + K)[i];
+            i32x4 o;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                o[j] = (int)pack_bf16x2(bf16lo((uint32_t)xv[j]) * siluf_(bf16lo((uint32_t)gv[j])),
+                                        bf16hi((uint32_t)xv[j]) * siluf_(bf16hi((uint32_t)gv[j])));
+            reinterpret_cast<i32x4*>(xs)[i] = o;
+        }
+    }
+    __syncthreads();
+    f32x2 a[RW];
+#pragma unroll
+    for (int i = 0; i < RW; ++i) a[i] = f32x2{0.f, 0.f};
+    int pr = 0, bb = 0;
+    for (int t = 0; t < T; ++t) {
+        i32x4 un[RW][PF];
+        const bool more = t + 1 < T;
+        const int npr = bb + 1 == NB ? pr + 1 : pr, nbb = bb + 1 == NB ? 0 : bb + 1;
+        if (more) load(npr, nbb, un);
+#pragma unroll
+        for (int j = 0; j < PF; ++j) {
+            const int c = bb * (64 * PF) + lane + 64 * j;
+            if (c < nc) {
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {          // 8 of the chunk's 16 operand elements at a time
+                    const i32x4 xv = reinterpret_cast<const i32x4*>(xs)[2 * c + h];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const f32x2 x2 = {bf16lo((uint32_t)xv[e]), bf16hi((uint32_t)xv[e])};
+#pragma unroll
+                        for (int i = 0; i < RW; ++i) {
+                            // word 2 h + (e >> 1) of the chunk, its low or high pair of codes
+                            const int w = u[i][j][2 * h + (e >> 1)];
+                            const f32x2 wf = (e & 1) ? __builtin_amdgcn_cvt_pk_f32_fp8(w, true) : __builtin_amdgcn_cvt_pk_f32_fp8(w, false);
+                            a[i] += wf * x2;
+                        }
+                    }
+                }
+            }
+        }
+        if (bb + 1 == NB) {   // row group done
+            const int n0 = ((blockIdx.x * rpw + pr) * 2 + wave) * RW;
+#pragma unroll
+            for (int i = 0; i < RW; ++i) {
+                const float s = wave_sum(a[i][0] + a[i][1]);
+                const int n = n0 + i;
+                if (lane == 0 && n < N) {
+                    float v = scale[n] * s;
+                    if (res) v += res[n];
+                    void* yo = n < nsplit ? y : y2;
+                    const int at = n < nsplit ? n : n - nsplit;
+                    if constexpr (YF32) static_cast<float*>(yo)[at] = v;
+                    else static_cast<bf16_t*>(yo)[at] = f32_to_bf16(v);
+                }
+                a[i] = f32x2{0.f, 0.f};
+            }
+        }
+        if (more) {
+#pragma unroll
+            for (int i = 0; i < RW; ++i)
+#pragma unroll
+                for (int j = 0; j < PF; ++j) u[i][j] = un[i][j];
+        }
+        pr = npr; bb = nbb;
+    }
+}
+
+template <bool YF32, int PRO>
+inline void gemv_e4m3_launch(const void* x, const float* gamma, float eps, const void* W8, int64_t ldq, const float* scale,
+                             void* y, void* y2, int nsplit, const float* res, int N, int K, hipStream_t st) {
+    const int rpw = N >= 8 * 4 * 512 ? 4 : N >= 8 * 2 * 512 ? 2 : 1;        // gemv_launch's rule: the same grid for every N
+    KALLE_LAUNCH((gemv_e4m3_kernel<YF32, PRO>), dim3((N + 8 * rpw - 1) / (8 * rpw)), dim3(128), (size_t)K * 2, st, x, gamma,
+                 eps, static_cast<const uint8_t*>(W8), ldq, scale, y, y2, nsplit, res, N, K, rpw);
+}
+
+// gemm_rows_kernel on e4m3 weights: the same tile, grid, K split over the waves and LDS meeting point.  Lane (row i, group g)
+// takes 16 bytes of weight row i - 16 weights, two of the MFMA's K chunks - widens them to bf16 in registers (exact: 4
+// significant bits) and feeds v_mfma_f32_16x16x32_bf16 twice, each time against the 16-byte chunk of batch row i that holds the
+// same k.  The activations stay bf16.  A K block is 256 elements as before: 4 weight loads and 8 x loads per lane.  scale[n] is
+// applied by the thread that owns output (r, n).
+template <bool YF32, int TR>
+__global__ __launch_bounds__(256) void gemm_rows_e4m3_kernel(const bf16_t* __restrict__ X, int64_t ldx,
+                                                             const uint8_t* __restrict__ W8, int64_t ldq,
+                                                             const float* __restrict__ scale, void* __restrict__ y, int64_t ldy,
+                                                             void* __restrict__ y2, int nsplit, const float* __restrict__ res,
+                                                             int64_t ldres, int N, int K, RowsArgs a) {
+    static_assert(TR == 8 || TR == 16, "weight rows per workgroup");
+    __shared__ __attribute__((aligned(16))) float part[4][64][4];
+    constexpr int CH = 4;                         // 16-byte weight loads per lane and K block: 4 x 4 groups x 16 = 256 elements
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i16 = lane & 15, g = lane >> 4;
+    const int n0 = blockIdx.x * TR;
+    const bool wrow = TR == 16 || i16 < TR;
+    const int nc = K >> 4, NB = (nc + 4 * CH - 1) / (4 * CH);
+    const bool live = i16 < a.R && (a.active >> i16 & 1);
+    const uint8_t* wr = W8 + (int64_t)(n0 + i16 < N ? n0 + i16 : N - 1) * ldq;
+    const bf16_t* xr = X + (live ? i16 : 0) * ldx;            // (not read unless live)
+    auto load = [&](int kb, i32x4* wq, i32x4* xq) {
+#pragma unroll
+        for (int j = 0; j < CH; ++j) {
+            const int c = (kb * CH + j) * 4 + g;
+            const bool in = c < nc;
+            const int cc = in ? c : nc - 1;
+            wq[j] = i32x4{0, 0, 0, 0};                        // past K: zero codes (+0) against a chunk of x that exists
+            if (wrow && in) wq[j] = *reinterpret_cast<const i32x4*>(wr + 16 * cc);
+            xq[2 * j] = xq[2 * j + 1] = i32x4{0, 0, 0, 0};
+            if (live) {
+                xq[2 * j] = *reinterpret_cast<const i32x4*>(xr + 16 * cc);
+                xq[2 * j + 1] = *reinterpret_cast<const i32x4*>(xr + 16 * cc + 8);
+            }
+        }
+    };
+    // codes -> bf16 pairs: v_cvt_pk_f32_fp8, then the (exact) rounding to bf16
+    auto widen = [](int lo, int hi) {
+        i32x4 o;
+        f32x2 p = __builtin_amdgcn_cvt_pk_f32_fp8(lo, false);
+        o[0] = (int)pack_bf16x2(p[0], p[1]);
+        p = __builtin_amdgcn_cvt_pk_f32_fp8(lo, true);
+        o[1] = (int)pack_bf16x2(p[0], p[1]);
+        p = __builtin_amdgcn_cvt_pk_f32_fp8(hi, false);
+        o[2] = (int)pack_bf16x2(p[0], p[1]);
+        p = __builtin_amdgcn_cvt_pk_f32_fp8(hi, true);
+        o[3] = (int)pack_bf16x2(p[0], p[1]);
+        return o;
+    };
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    i32x4 wv[CH], xv[2 * CH];
+    int kb = wave;
+    if (kb < NB) load(kb, wv, xv);
+    for (; kb < NB; kb += 4) {
+        i32x4 wn[CH], xn[2 * CH];
+        const bool more = kb + 4 < NB;
+        if (more) load(kb + 4, wn, xn);
+#pragma unroll
+        for (int j = 0; j < CH; ++j) {
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, widen(wv[j][0], wv[j][1])),
+                                                          __builtin_bit_cast(bf16x8, xv[2 * j]), acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, widen(wv[j][2], wv[j][3])),
+                                                          __builtin_bit_cast(bf16x8, xv[2 * j + 1]), acc, 0, 0, 0);
+        }
+        if (more) {
+#pragma unroll
+            for (int j = 0; j < CH; ++j) { wv[j] = wn[j]; xv[2 * j] = xn[2 * j]; xv[2 * j + 1] = xn[2 * j + 1]; }
+        }
+    }
+    *reinterpret_cast<f32x4*>(part[wave][lane]) = acc;
+    __syncthreads();
+    const int r = threadIdx.x / TR, j = threadIdx.x % TR, n = n0 + j;
+    if (r < a.R && (a.active >> r & 1) && n < N) {
+        const int src = (j >> 2) * 16 + r, e = j & 3;
+        float s = scale[n] * ((part[0][src][e] + part[1][src][e]) + (part[2][src][e] + part[3][src][e]));
+        if (res) s += res[r * ldres + n];
+        const int64_t at = n < nsplit ? r * ldy + n : a.y2_off[r] + (n - nsplit);
+        void* yo = n < nsplit ? y : y2;
+        if constexpr (YF32) static_cast<float*>(yo)[at] = s;
+        else static_cast<bf16_t*>(yo)[at] = f32_to_bf16(s);
+    }
+}
+
+// gemm_rows_run for e4m3 weights: rows_prologue_kernel as the pre-pass (unchanged), then the GEMM under gemm_rows_run's tile rule
+inline int gemm_rows_e4m3_run(const void* x, int64_t ldx, int pro, const float* gamma, float eps, bf16_t* xhat, int64_t ldh,
+                              const void* W8, int64_t ldq, const float* scale, void* y, int64_t ldy, bool yf32, void* y2,
+                              int nsplit, const float* res, int64_t ldres, const RowsArgs& a, int N, int K, hipStream_t st) {
+    const bf16_t* X = static_cast<const bf16_t*>(x);
+    if (pro != PRO_BF16) {
+        if (pro == PRO_RMS)
+            KALLE_LAUNCH((rows_prologue_kernel<PRO_RMS>), dim3(a.R), dim3(256), 0, st, x, ldx, gamma, eps, xhat, ldh, K, a.active);
+        else
+            KALLE_LAUNCH((rows_prologue_kernel<PRO_SWIGLU>), dim3(a.R), dim3(256), 0, st, x, ldx, gamma, eps, xhat, ldh, K, a.active);
+        const int rc = kalle_check_launch();
+        if (rc != KALLE_OK) return rc;
+        X = xhat;
+        ldx = ldh;
+    }
+    const uint8_t* Wq = static_cast<const uint8_t*>(W8);
+    const dim3 block(256);
+    if (N < 8192) {
+        const dim3 grid((N + 7) / 8);
+        if (yf32) KALLE_LAUNCH((gemm_rows_e4m3_kernel<true, 8>), grid, block, 0, st, X, ldx, Wq, ldq, scale, y, ldy, y2, nsplit, res, ldres, N, K, a);
+        else KALLE_LAUNCH((gemm_rows_e4m3_kernel<false, 8>), grid, block, 0, st, X, ldx, Wq, ldq, scale, y, ldy, y2, nsplit, res, ldres, N, K, a);
+    } else {
+        const dim3 grid((N + 15) / 16);
+        if (yf32) KALLE_LAUNCH((gemm_rows_e4m3_kernel<true, 16>), grid, block, 0, st, X, ldx, Wq, ldq, scale, y, ldy, y2, nsplit, res, ldres, N, K, a);
+        else KALLE_LAUNCH((gemm_rows_e4m3_kernel<false, 16>), grid, block, 0, st, X, ldx, Wq, ldq, scale, y, ldy, y2, nsplit, res, ldres, N, K, a);
+    }
+    return kalle_check_launch();
+}
+
 // peak normalisation to int16 (infer_0723.py:293: x / max|x| -> clamp(-1, 1) * 32767 -> int16, truncating like .to(int16))
 template <bool F32>
 __global__ __launch_bounds__(256) void absmax_kernel(const void* __restrict__ x, unsigned* __restrict__ peak_bits, int64_t n) {
@@ -713,6 +1028,170 @@ extern "C" int kalle_llama_decode_step_rows(const kalle_llama_layer* layers, int
         float* xo = l + 1 == n_layers ? out : xb;
         if ((rc = gemm_rows_run(hf, 2 * inner, PRO_SWIGLU, nullptr, 0.f, xn, xw, L.wdown, inner, xo, D, true, xo, D, xa, D, plain,
                                 D, inner, st)) != KALLE_OK)
+            return rc;
+        xin = xo;
+    }
+    return KALLE_OK;
+}
+
+// ---- weight-only e4m3 decoding -----------------------------------------------------------------------------------------------
+extern "C" int kalle_quantize_rows_e4m3(const void* W, int64_t ldw, void* W8, int64_t ldq, float* scale, int N, int K,
+                                        void* stream) {
+    if (!W || !W8 || !scale || N <= 0 || K <= 0 || (K & 15) || (ldw & 7) || (ldq & 15) || ldw < K || ldq < K) return KALLE_ERR_ARG;
+    KALLE_LAUNCH(quantize_rows_e4m3_kernel, dim3((N + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream),
+                 static_cast<const bf16_t*>(W), ldw, static_cast<uint8_t*>(W8), ldq, scale, N, K);
+    return kalle_check_launch();
+}
+
+extern "C" int kalle_gemv_e4m3(const void* x, const void* W8, int64_t ldq, const float* scale, void* y, int y_dtype,
+                               const float* residual, int N, int K, void* stream) {
+    if (!x || !W8 || !scale || !y || N <= 0 || K <= 0 || (K & 15) || (ldq & 15) || ldq < K || K > 32768) return KALLE_ERR_ARG;
+    if (y_dtype != KALLE_F32 && y_dtype != KALLE_BF16) return KALLE_ERR_ARG;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (y_dtype == KALLE_F32) gemv_e4m3_launch<true, PRO_BF16>(x, nullptr, 0.f, W8, ldq, scale, y, y, N, residual, N, K, st);
+    else gemv_e4m3_launch<false, PRO_BF16>(x, nullptr, 0.f, W8, ldq, scale, y, y, N, residual, N, K, st);
+    return kalle_check_launch();
+}
+
+extern "C" int kalle_gemv_fused_e4m3(const void* x, int prologue, const float* gamma, float eps, const void* W8, int64_t ldq,
+                                     const float* scale, void* y, int y_dtype, void* y2, int nsplit, const float* residual,
+                                     int N, int K, void* stream) {
+    if (!x || !W8 || !scale || !y || N <= 0 || K <= 0 || (K & 15) || (ldq & 15) || ldq < K || K > 32768) return KALLE_ERR_ARG;
+    if (y_dtype != KALLE_F32 && y_dtype != KALLE_BF16) return KALLE_ERR_ARG;
+    if (prologue != PRO_BF16 && prologue != PRO_RMS && prologue != PRO_SWIGLU) return KALLE_ERR_ARG;
+    if (prologue == PRO_RMS && !gamma) return KALLE_ERR_ARG;
+    if (nsplit < 0 || nsplit > N || (nsplit < N && !y2)) return KALLE_ERR_ARG;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool f = y_dtype == KALLE_F32;
+    if (nsplit == N) y2 = y;
+#define KALLE_GEMV8(F, P) gemv_e4m3_launch<F, P>(x, gamma, eps, W8, ldq, scale, y, y2, nsplit, residual, N, K, st)
+    if (prologue == PRO_BF16) { if (f) KALLE_GEMV8(true, PRO_BF16); else KALLE_GEMV8(false, PRO_BF16); }
+    else if (prologue == PRO_RMS) { if (f) KALLE_GEMV8(true, PRO_RMS); else KALLE_GEMV8(false, PRO_RMS); }
+    else { if (f) KALLE_GEMV8(true, PRO_SWIGLU); else KALLE_GEMV8(false, PRO_SWIGLU); }
+#undef KALLE_GEMV8
+    return kalle_check_launch();
+}
+
+extern "C" int kalle_gemm_rows_fused_e4m3(const void* x, int64_t ldx, int prologue, const float* gamma, float eps, void* xhat,
+                                          const void* W8, int64_t ldq, const float* scale, void* y, int64_t ldy, int y_dtype,
+                                          void* y2, int nsplit, const int64_t* y2_off, const float* residual, int64_t ldres,
+                                          const int32_t* active, int R, int N, int K, void* stream) {
+    if (!x || !W8 || !scale || !y || R < 1 || R > KALLE_DECODE_MAX_ROWS || N <= 0 || K <= 0 || (K & 15) || (ldq & 15) || K > 32768)
+        return KALLE_ERR_ARG;
+    if (y_dtype != KALLE_F32 && y_dtype != KALLE_BF16) return KALLE_ERR_ARG;
+    if (prologue != PRO_BF16 && prologue != PRO_RMS && prologue != PRO_SWIGLU) return KALLE_ERR_ARG;
+    if (prologue == PRO_RMS ? (!gamma || (ldx & 3)) : (ldx & 7)) return KALLE_ERR_ARG;
+    if (prologue != PRO_BF16 && !xhat) return KALLE_ERR_ARG;
+    if (ldx < (prologue == PRO_SWIGLU ? 2 * (int64_t)K : K) || ldq < K || ldy < 0 || ldres < 0) return KALLE_ERR_ARG;
+    if (nsplit < 0 || nsplit > N || (nsplit < N && (!y2 || !y2_off))) return KALLE_ERR_ARG;
+    RowsArgs a{};
+    a.R = R;
+    for (int r = 0; r < R; ++r) {
+        if (!active || active[r]) a.active |= 1u << r;
+        a.y2_off[r] = nsplit < N ? y2_off[r] : 0;
+    }
+    if (!a.active) return KALLE_OK;
+    return gemm_rows_e4m3_run(x, ldx, prologue, gamma, eps, static_cast<bf16_t*>(xhat), K, W8, ldq, scale, y, ldy,
+                              y_dtype == KALLE_F32, y2, nsplit, residual, ldres, a, N, K, static_cast<hipStream_t>(stream));
+}
+
+static inline bool layer_w8_complete(const kalle_llama_layer_w8& L) {
+    return L.input_norm && L.wqkv && L.sqkv && L.wo && L.so && L.post_norm && L.wug && L.sug && L.wdown && L.sdown && L.kv_cache;
+}
+
+extern "C" int kalle_llama_decode_step_w8(const kalle_llama_layer_w8* layers, int n_layers, const float* x, float* out, int H,
+                                          int Hkv, int inner, int head_dim, float eps, int t0, int cache_rows,
+                                          const float* rope_cos, const float* rope_sin, void* workspace, void* stream) {
+    kalle_set_attn_plan(0);
+    if (!layers || n_layers <= 0 || !x || !out || !workspace || !rope_cos || !rope_sin) return KALLE_ERR_ARG;
+    if (H <= 0 || Hkv <= 0 || H % Hkv || inner <= 0 || (inner & 15) || t0 < 0 || t0 >= cache_rows) return KALLE_ERR_ARG;
+    if (head_dim != 64 && head_dim != 128) return KALLE_ERR_ARG;                // (so D % 16 == 0)
+    if ((int64_t)H * head_dim > 32768 || inner > 32768) return KALLE_ERR_ARG;
+    for (int l = 0; l < n_layers; ++l)                       // (every layer before the first launch)
+        if (!layer_w8_complete(layers[l])) return KALLE_ERR_ARG;
+    const int D = H * head_dim, kvw = 2 * Hkv * head_dim;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char* ws = static_cast<char*>(workspace);                // (the layout of kalle_llama_decode_step_hd)
+    float* xa = reinterpret_cast<float*>(ws);
+    float* xb = xa + D;
+    float* lse = xb + D;
+    bf16_t* q = reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(lse) + ((H * 4 + 63) & ~63));
+    bf16_t* ao = q + D;
+    bf16_t* hf = ao + D;
+    const float* xin = x;
+    for (int l = 0; l < n_layers; ++l) {
+        const kalle_llama_layer_w8& L = layers[l];
+        bf16_t* kv_row = static_cast<bf16_t*>(L.kv_cache) + (int64_t)t0 * kvw;
+        gemv_e4m3_launch<false, PRO_RMS>(xin, L.input_norm, eps, L.wqkv, D, L.sqkv, q, kv_row, D, nullptr, D + kvw, D, st);
+        int rc = kalle_check_launch();
+        if (rc != KALLE_OK) return rc;
+        rc = kalle_attention_decode_hd(q, D, 0, L.kv_cache, kvw, 0, L.kv_cache, kvw, Hkv * head_dim, ao, D, lse, rope_cos, rope_sin,
+                                       head_dim, nullptr, 1, H, Hkv, t0 + 1, head_dim, stream);
+        if (rc != KALLE_OK) return rc;
+        gemv_e4m3_launch<true, PRO_BF16>(ao, nullptr, 0.f, L.wo, D, L.so, xa, xa, D, xin, D, D, st);
+        if ((rc = kalle_check_launch()) != KALLE_OK) return rc;
+        gemv_e4m3_launch<false, PRO_RMS>(xa, L.post_norm, eps, L.wug, D, L.sug, hf, hf, 2 * inner, nullptr, 2 * inner, D, st);
+        if ((rc = kalle_check_launch()) != KALLE_OK) return rc;
+        float* xo = l + 1 == n_layers ? out : xb;
+        gemv_e4m3_launch<true, PRO_SWIGLU>(hf, nullptr, 0.f, L.wdown, inner, L.sdown, xo, xo, D, xa, D, inner, st);
+        if ((rc = kalle_check_launch()) != KALLE_OK) return rc;
+        xin = xo;
+    }
+    return KALLE_OK;
+}
+
+extern "C" int kalle_llama_decode_step_rows_w8(const kalle_llama_layer_w8* layers, int n_layers, const float* x, float* out,
+                                               int R, int H, int Hkv, int inner, int head_dim, float eps, const int32_t* t0,
+                                               int cache_rows, const float* rope_cos, const float* rope_sin, void* workspace,
+                                               void* stream) {
+    kalle_set_attn_plan(0);
+    if (!layers || n_layers <= 0 || !x || !out || !workspace || !rope_cos || !rope_sin || !t0) return KALLE_ERR_ARG;
+    if (R < 1 || R > KALLE_DECODE_MAX_ROWS) return KALLE_ERR_ARG;
+    if (H <= 0 || Hkv <= 0 || H % Hkv || inner <= 0 || (inner & 15) || cache_rows <= 0) return KALLE_ERR_ARG;
+    if (head_dim != 64 && head_dim != 128) return KALLE_ERR_ARG;                // (so D % 16 == 0)
+    if ((int64_t)H * head_dim > 32768 || inner > 32768) return KALLE_ERR_ARG;
+    const int D = H * head_dim, kvw = 2 * Hkv * head_dim, xw = D > inner ? D : inner;
+    RowsArgs a{};
+    a.R = R;
+    int32_t nk[KALLE_DECODE_MAX_ROWS];
+    for (int r = 0; r < R; ++r) {
+        if (t0[r] >= cache_rows || t0[r] >= 15360) return KALLE_ERR_ARG;
+        nk[r] = t0[r] < 0 ? 0 : t0[r] + 1;
+        if (t0[r] >= 0) a.active |= 1u << r;
+        a.y2_off[r] = t0[r] < 0 ? 0 : ((int64_t)r * cache_rows + t0[r]) * kvw;
+    }
+    for (int l = 0; l < n_layers; ++l)
+        if (!layer_w8_complete(layers[l])) return KALLE_ERR_ARG;
+    if (!a.active) return KALLE_OK;
+    RowsArgs plain = a;                                      // (no second destination)
+    for (int r = 0; r < R; ++r) plain.y2_off[r] = 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char* ws = static_cast<char*>(workspace);                // (the layout of kalle_llama_decode_step_rows)
+    float* xa = reinterpret_cast<float*>(ws);
+    float* xb = xa + (int64_t)R * D;
+    float* lse = xb + (int64_t)R * D;
+    bf16_t* q = reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(lse) + ((R * H * 4 + 63) & ~63));
+    bf16_t* ao = q + (int64_t)R * D;
+    bf16_t* hf = ao + (int64_t)R * D;
+    bf16_t* xn = hf + (int64_t)R * 2 * inner;
+    const float* xin = x;
+    for (int l = 0; l < n_layers; ++l) {
+        const kalle_llama_layer_w8& L = layers[l];
+        int rc = gemm_rows_e4m3_run(xin, D, PRO_RMS, L.input_norm, eps, xn, xw, L.wqkv, D, L.sqkv, q, D, false, L.kv_cache, D,
+                                    nullptr, 0, a, D + kvw, D, st);
+        if (rc != KALLE_OK) return rc;
+        rc = kalle_attention_decode_rows(q, D, 0, L.kv_cache, kvw, 0, L.kv_cache, kvw, Hkv * head_dim, (int64_t)cache_rows * kvw, ao,
+                                         D, lse, rope_cos, rope_sin, head_dim, nk, R, H, Hkv, head_dim, stream);
+        if (rc != KALLE_OK) return rc;
+        if ((rc = gemm_rows_e4m3_run(ao, D, PRO_BF16, nullptr, 0.f, nullptr, 0, L.wo, D, L.so, xa, D, true, xa, D, xin, D, plain,
+                                     D, D, st)) != KALLE_OK)
+            return rc;
+        if ((rc = gemm_rows_e4m3_run(xa, D, PRO_RMS, L.post_norm, eps, xn, xw, L.wug, D, L.sug, hf, 2 * inner, false, hf,
+                                     2 * inner, nullptr, 0, plain, 2 * inner, D, st)) != KALLE_OK)
+            return rc;
+        float* xo = l + 1 == n_layers ? out : xb;
+        if ((rc = gemm_rows_e4m3_run(hf, 2 * inner, PRO_SWIGLU, nullptr, 0.f, xn, xw, L.wdown, inner, L.sdown, xo, D, true, xo,
+                                     D, xa, D, plain, D, inner, st)) != KALLE_OK)
             return rc;
         xin = xo;
     }

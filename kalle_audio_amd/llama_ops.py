@@ -53,6 +53,31 @@ def layer_params(layer):
     return p
 
 
+def e4m3_of(p):
+    """(codes uint8 [N, K], scale fp32 [N]) of a projection weight: ops.quantize_rows_e4m3 of its bf16 compute copy, re-made only
+    when the parameter changed - its `_version`, or ops.WEIGHTS_EPOCH for writes through a raw pointer (the rule of the sampler's
+    graph cache)"""
+    key = (p._version, ops.WEIGHTS_EPOCH, p.device)
+    c = getattr(p, "_kalle_e4m3", None)
+    if c is None or c[0] != key:
+        c = (key,) + ops.quantize_rows_e4m3(bf16_of(p))
+        p._kalle_e4m3 = c
+    return c[1], c[2]
+
+
+def layer_params_w8(layer):
+    """layer_params with the four projections as e4m3 codes + scales (made lazily, per layer): the fields of
+    ops.llama_decode_plan_w8 in order, without the cache"""
+    p = layer_params(layer)
+    out = [p.g1]
+    for w in (layer.self_attn.qkv_proj.weight, layer.self_attn.o_proj.weight):
+        out.extend(e4m3_of(w))
+    out.append(p.g2)
+    for w in (layer.mlp.up_gate_proj.weight, layer.mlp.down_proj.weight):
+        out.extend(e4m3_of(w))
+    return p, tuple(out)
+
+
 PARAM_ORDER = ("input_layernorm.weight", "self_attn.qkv_proj.weight", "self_attn.o_proj.weight",
                "post_attention_layernorm.weight", "mlp.up_gate_proj.weight", "mlp.down_proj.weight")
 

@@ -63,6 +63,11 @@ class Llasa(nn.Module):
             GELU(),
             Linear(config['latent_dim'] * 2, config['latent_dim'] * 2))
 
+    def quantize_decoder(self, fmt="e4m3"):
+        """LlamaModel.quantize_decode_weights on the (shared) decoder: `infer` then streams e4m3 weights per frame"""
+        self.base_model.model.quantize_decode_weights(fmt)
+        return self
+
     def forward(self, input_ids, audio_latents, audio_distribution_l, ids_mask, audio_mask, target_mask, end_mask):
         _need_gpu(input_ids)
         f = lambda m: m.to(F32).contiguous()

@@ -264,6 +264,70 @@ class LlamaModel(nn.Module):
         self.head_dim = hd
         self._inv_freq = LO.inv_freq(hd, cfg.get("rope_theta", 10000.0), cfg.get("rope_scaling"))
         self._rope_cache = {}
+        self._decode_fmt = None
+
+    DECODE_WEIGHT_FORMATS = ("e4m3",)
+
+    def quantize_decode_weights(self, fmt="e4m3"):
+        """fmt "e4m3": the KV-cached single-position steps (forward_cached at n == 1, forward_cached_batch) read the four
+        projections of every layer as OCP e4m3 codes with one fp32 scale per output row (kalle_llama_decode_step_w8 /
+        _rows_w8): half the bytes a generated frame streams.  Activations, accumulation and every bf16 rounding point stay.
+        The quantised copies are made lazily, per layer, at the next step and re-made when a weight changes; prefill (n > 1,
+        prefill_row), training and forward() keep the bf16 weights and kernels, so the copies are 0.5 x the bf16 bytes ON TOP.
+        fmt None: back to the bf16 steps; the quantised copies are dropped."""
+        if fmt is not None and fmt not in self.DECODE_WEIGHT_FORMATS:
+            raise NotImplementedError(f"decode weight format {fmt!r}: supported formats are {self.DECODE_WEIGHT_FORMATS} (or None)")
+        if fmt is not None:
+            D, I = self.cfg["hidden_size"], self.cfg["intermediate_size"]
+            if D % 16 or I % 16:
+                raise NotImplementedError(f"decode weight format {fmt!r} needs hidden_size and intermediate_size to be multiples "
+                                          f"of 16 (a 16-byte load holds 16 weights); got hidden_size={D}, intermediate_size={I}")
+        self._decode_fmt = fmt
+        if fmt is None:          # drop the quantised copies (a KV cache built meanwhile holds its plan's until its next step)
+            self.__dict__.pop("_decode_weight_list", None)
+            for layer in self.layers:
+                for w in self._layer_weights(layer):
+                    w.__dict__.pop("_kalle_e4m3", None)
+        return self
+
+    def _decode_plan(self, cache, device, rows=None):
+        """the cache's plan for the current decode weight format; rebuilt when the format changed or (quantised) a weight did"""
+        fmt = self._decode_fmt
+        plan = cache.get("plan")
+        if fmt is None:
+            if plan is None or plan.get("fmt") is not None:
+                ps = [LO.layer_params(layer) for layer in self.layers]
+                ts = [(p.g1, p.wqkv, p.wo, p.g2, p.wug, p.wdown, kv) for p, kv in zip(ps, cache["kv"])]
+                H, Hkv, inner, hd = ps[0].H, ps[0].Hkv, ps[0].wug.shape[0] // 2, ps[0].hd
+                plan = (ops.llama_decode_plan(ts, H, Hkv, inner, device, head_dim=hd) if rows is None else
+                        ops.llama_decode_plan_rows(ts, rows, H, Hkv, inner, device, head_dim=hd))
+                plan["eps"] = ps[0].eps
+                cache["plan"] = plan
+            return plan
+        key = (ops.WEIGHTS_EPOCH,) + tuple(p._version for p in self._decode_weights(plan is None))
+        if plan is None or plan.get("fmt") != fmt or plan["wkey"] != key:
+            pts = [LO.layer_params_w8(layer) for layer in self.layers]
+            ts = [t + (kv,) for (_, t), kv in zip(pts, cache["kv"])]
+            p0 = pts[0][0]
+            H, Hkv, inner, hd = p0.H, p0.Hkv, self.cfg["intermediate_size"], p0.hd
+            plan = (ops.llama_decode_plan_w8(ts, H, Hkv, inner, device, head_dim=hd) if rows is None else
+                    ops.llama_decode_plan_rows_w8(ts, rows, H, Hkv, inner, device, head_dim=hd))
+            plan["eps"], plan["wkey"] = p0.eps, key
+            cache["plan"] = plan
+        return plan
+
+    def _decode_weights(self, refresh):
+        """the projection weights whose versions key a quantised plan; collected once per cache (module attribute lookups are
+        too slow to repeat for every frame), the versions themselves are read at every step"""
+        ws = self.__dict__.get("_decode_weight_list")
+        if ws is None or refresh:
+            ws = self.__dict__["_decode_weight_list"] = [w for layer in self.layers for w in self._layer_weights(layer)]
+        return ws
+
+    @staticmethod
+    def _layer_weights(layer):
+        return (layer.self_attn.qkv_proj.weight, layer.self_attn.o_proj.weight, layer.mlp.up_gate_proj.weight,
+                layer.mlp.down_proj.weight)
 
     def _rope(self, L, device):
         key = (L, str(device))
@@ -302,14 +366,9 @@ class LlamaModel(nn.Module):
         x = Fn._to_f32(inputs_embeds.contiguous()).view(n, Dm)
         if n == 1:
             # one generated frame: the whole stack is sequenced by kalle_llama_decode_step (one host call)
-            plan = cache.get("plan")
-            if plan is None:
-                ps = [LO.layer_params(layer) for layer in self.layers]
-                plan = cache["plan"] = ops.llama_decode_plan(
-                    [(p.g1, p.wqkv, p.wo, p.g2, p.wug, p.wdown, kv) for p, kv in zip(ps, cache["kv"])],
-                    ps[0].H, ps[0].Hkv, ps[0].wug.shape[0] // 2, x.device, head_dim=ps[0].hd)
-                plan["eps"] = ps[0].eps
-            x = ops.llama_decode_step(plan, x.view(Dm), t0, cache["kv"][0].shape[0], cache["rope"], plan["eps"])
+            plan = self._decode_plan(cache, x.device)
+            step = ops.llama_decode_step if plan.get("fmt") is None else ops.llama_decode_step_w8
+            x = step(plan, x.view(Dm), t0, cache["kv"][0].shape[0], cache["rope"], plan["eps"])
         else:
             for layer, kv in zip(self.layers, cache["kv"]):
                 x = LO.layer_fwd_cached(LO.layer_params(layer), x, kv, t0, cache["rope"])
@@ -355,14 +414,9 @@ class LlamaModel(nn.Module):
         if max(t0) >= rows:
             raise ValueError("KV cache too short")
         x = Fn._to_f32(inputs_embeds.contiguous()).view(R, Dm)
-        plan = cache.get("plan")
-        if plan is None:
-            ps = [LO.layer_params(layer) for layer in self.layers]
-            plan = cache["plan"] = ops.llama_decode_plan_rows(
-                [(p.g1, p.wqkv, p.wo, p.g2, p.wug, p.wdown, kv) for p, kv in zip(ps, cache["kv"])],
-                R, ps[0].H, ps[0].Hkv, ps[0].wug.shape[0] // 2, x.device, head_dim=ps[0].hd)
-            plan["eps"] = ps[0].eps
-        x = ops.llama_decode_step_rows(plan, x, t0, rows, cache["rope"], plan["eps"])
+        plan = self._decode_plan(cache, x.device, rows=R)
+        step = ops.llama_decode_step_rows if plan.get("fmt") is None else ops.llama_decode_step_rows_w8
+        x = step(plan, x, t0, rows, cache["rope"], plan["eps"])
         cache["len"] = [t + 1 if a else t for t, a in zip(cache["len"], active)]
         return self.norm(x.view(R, 1, Dm))
 
@@ -458,6 +512,11 @@ class Llasa(nn.Module):
             GELU(),
             Linear(config['latent_dim'], config['latent_dim']))
         self.init_sigmaVAE()
+
+    def quantize_decoder(self, fmt="e4m3"):
+        """LlamaModel.quantize_decode_weights on the decoder: `infer` and `infer_batch` then stream e4m3 weights per frame"""
+        self.base_model.model.quantize_decode_weights(fmt)
+        return self
 
     def forward(self, input_ids, audio_latents, audio_distribution_l, ids_mask, audio_mask, target_mask, end_mask,
                 noise=None):

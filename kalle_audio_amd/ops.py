@@ -729,6 +729,119 @@ def llama_decode_step_rows(plan, x, t0, cache_rows, rope, eps):
     return out
 
 
+# ---- weight-only e4m3 decoding (include/kalle_hip.h): uint8 OCP e4m3fn codes [N, K] + one fp32 scale per output row -----------
+W8_FIELDS = ("input_norm", "wqkv", "sqkv", "wo", "so", "post_norm", "wug", "sug", "wdown", "sdown", "kv_cache")
+
+
+def quantize_rows_e4m3(w):
+    """w bf16 [N, K] (rows may be strided, K % 16 == 0) -> (w8 uint8 [N, K], scale fp32 [N]): kalle_quantize_rows_e4m3"""
+    lib = _lib.load()
+    assert w.dim() == 2 and w.stride(1) == 1 and w.dtype == torch.bfloat16
+    N, K = w.shape
+    w8 = torch.empty((N, K), device=w.device, dtype=torch.uint8)
+    scale = torch.empty((N,), device=w.device, dtype=torch.float32)
+    check(lib.kalle_quantize_rows_e4m3(_p(w), w.stride(0), _p(w8), K, _p(scale), N, K, _stream()), "kalle_quantize_rows_e4m3")
+    return w8, scale
+
+
+def _w8_args(x, w8, scale):
+    assert w8.dim() == 2 and w8.stride(1) == 1 and w8.dtype == torch.uint8 and x.shape[-1] == w8.shape[1]
+    assert scale.dtype == torch.float32 and scale.shape == (w8.shape[0],) and scale.is_contiguous()
+    assert x.dtype == torch.bfloat16 and x.stride(-1) == 1
+
+
+def gemv_e4m3(x, w8, scale, *, residual=None, out_dtype=torch.float32):
+    """y = scale * (e4m3(w8) . x) (+ residual) for one bf16 row x [K]: kalle_gemv_e4m3"""
+    lib = _lib.load()
+    assert x.dim() == 1
+    _w8_args(x, w8, scale)
+    N, K = w8.shape
+    y = torch.empty((N,), device=x.device, dtype=out_dtype)
+    if residual is not None:
+        assert residual.dtype == torch.float32 and residual.shape == y.shape and residual.is_contiguous()
+    check(lib.kalle_gemv_e4m3(_p(x), _p(w8), w8.stride(0), _p(scale), _p(y), _dt(y), _p(residual), N, K, _stream()),
+          "kalle_gemv_e4m3")
+    return y
+
+
+def gemm_rows_e4m3(x, w8, scale, *, residual=None, out_dtype=torch.float32):
+    """gemm_rows on e4m3 weights: Y[r] = scale * (e4m3(w8) . x[r]) (+ residual[r]) for the R <= 16 rows of x (bf16 [R, K]):
+    kalle_gemm_rows_fused_e4m3 without a prologue"""
+    lib = _lib.load()
+    assert x.dim() == 2
+    _w8_args(x, w8, scale)
+    R, K = x.shape
+    N = w8.shape[0]
+    y = torch.empty((R, N), device=x.device, dtype=out_dtype)
+    if residual is not None:
+        assert residual.dtype == torch.float32 and residual.shape == y.shape and residual.stride(1) == 1
+    check(lib.kalle_gemm_rows_fused_e4m3(_p(x), x.stride(0), 0, None, 0.0, None, _p(w8), w8.stride(0), _p(scale), _p(y),
+                                         y.stride(0), _dt(y), None, N, None, _p(residual),
+                                         residual.stride(0) if residual is not None else 0, None, R, N, K, _stream()),
+          "kalle_gemm_rows_fused_e4m3")
+    return y
+
+
+def _w8_plan(layer_tensors, device, rows=None):
+    arr = (_lib.LlamaLayerW8 * len(layer_tensors))()
+    for d, ts in zip(arr, layer_tensors):
+        assert len(ts) == len(W8_FIELDS)
+        for t in ts:
+            assert t.is_contiguous() and t.device == torch.device(device)
+        if rows is not None:
+            assert ts[-1].dim() == 3 and ts[-1].shape[0] == rows
+        for f, t in zip(W8_FIELDS, ts):
+            setattr(d, f, t.data_ptr())
+    return arr
+
+
+def llama_decode_plan_w8(layer_tensors, H, Hkv, inner, device, head_dim=64):
+    """llama_decode_plan on e4m3 weights.  layer_tensors: per layer (input_norm fp32, wqkv uint8, sqkv fp32, wo uint8, so fp32,
+    post_norm fp32, wug uint8, sug fp32, wdown uint8, sdown fp32, kv_cache bf16), the pairs as quantize_rows_e4m3 returns them"""
+    lib = _lib.load()
+    arr = _w8_plan(layer_tensors, device)
+    nbytes = lib.kalle_llama_decode_ws_bytes_hd(H, Hkv, inner, head_dim)
+    check(min(nbytes, 0), "kalle_llama_decode_ws_bytes_hd")
+    ws = torch.empty(nbytes, device=device, dtype=torch.uint8)
+    return {"layers": arr, "n": len(layer_tensors), "keep": layer_tensors, "ws": ws, "H": H, "Hkv": Hkv, "inner": inner,
+            "head_dim": head_dim, "fmt": "e4m3"}
+
+
+def llama_decode_step_w8(plan, x, t0, cache_rows, rope, eps):
+    """llama_decode_step against a plan of llama_decode_plan_w8: kalle_llama_decode_step_w8"""
+    lib = _lib.load()
+    out = torch.empty_like(x)
+    check(lib.kalle_llama_decode_step_w8(ctypes.cast(plan["layers"], ctypes.c_void_p), plan["n"], _p(x), _p(out), plan["H"],
+                                         plan["Hkv"], plan["inner"], plan["head_dim"], eps, t0, cache_rows, _p(rope[0]),
+                                         _p(rope[1]), _p(plan["ws"]), _stream()), "kalle_llama_decode_step_w8")
+    return out
+
+
+def llama_decode_plan_rows_w8(layer_tensors, R, H, Hkv, inner, device, head_dim=64):
+    """llama_decode_plan_w8 for R rows: kv_cache of a layer is bf16 [R, cache_rows, 2*Hkv*head_dim]"""
+    lib = _lib.load()
+    arr = _w8_plan(layer_tensors, device, rows=R)
+    nbytes = lib.kalle_llama_decode_ws_bytes_rows(R, H, Hkv, inner, head_dim)
+    check(min(nbytes, 0), "kalle_llama_decode_ws_bytes_rows")
+    ws = torch.empty(nbytes, device=device, dtype=torch.uint8)
+    return {"layers": arr, "n": len(layer_tensors), "keep": layer_tensors, "ws": ws, "R": R, "H": H, "Hkv": Hkv, "inner": inner,
+            "head_dim": head_dim, "fmt": "e4m3"}
+
+
+def llama_decode_step_rows_w8(plan, x, t0, cache_rows, rope, eps):
+    """llama_decode_step_rows against a plan of llama_decode_plan_rows_w8: kalle_llama_decode_step_rows_w8"""
+    lib = _lib.load()
+    assert x.shape[0] == plan["R"] == len(t0) and x.is_contiguous() and x.dtype == torch.float32
+    out = plan.get("out")
+    if out is None:
+        out = plan["out"] = torch.zeros_like(x)
+    check(lib.kalle_llama_decode_step_rows_w8(ctypes.cast(plan["layers"], ctypes.c_void_p), plan["n"], _p(x), _p(out), plan["R"],
+                                              plan["H"], plan["Hkv"], plan["inner"], plan["head_dim"], eps,
+                                              ctypes.cast(_i32(t0), ctypes.c_void_p), cache_rows, _p(rope[0]), _p(rope[1]),
+                                              _p(plan["ws"]), _stream()), "kalle_llama_decode_step_rows_w8")
+    return out
+
+
 def gauss_kl2_fwd(pred, label_mean, label_std, mask_a, mask_b, std_mult=1.25):
     """two-Gaussian KL (model.py:84-100); label_std None -> label_mean is the raw mean | scale label [rows, 2 dim]"""
     lib = _lib.load()

@@ -3,7 +3,8 @@
 random weights, synthetic batch: text prefix + audio frames per sample.   python tools/llasa_bench.py [B] [L] [steps]
 The decoder shape is an option (defaults: Llama-3.2-1B): --hidden --layers --heads --kv-heads --head-dim --inner, e.g. the
 Llama-3.2-3B shape  --hidden 3072 --layers 28 --heads 24 --kv-heads 8 --head-dim 128 --inner 8192
---infer-only: KV-cached generation only; --infer-batch R: also Llasa.infer_batch on R prompts (aggregate and per-row frames/s)"""
+--infer-only: KV-cached generation only; --infer-batch R: also Llasa.infer_batch on R prompts (aggregate and per-row frames/s)
+--decode-weights e4m3: the --infer-only and --infer-batch lines with Llasa.quantize_decoder("e4m3") (weight-only FP8 decode steps)"""
 import json, os, sys, tempfile, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from kalle_audio_amd.model_sigmaVAE import Llasa
@@ -21,6 +22,11 @@ if "--infer-batch" in sys.argv:
     del sys.argv[_i:_i + 2]
     if "--infer-only" not in sys.argv and "--infer" not in sys.argv:
         sys.argv.append("--infer-only")
+DECODE_WEIGHTS = None                        # --decode-weights e4m3: generation streams e4m3 weights (prefill stays bf16)
+if "--decode-weights" in sys.argv:
+    _i = sys.argv.index("--decode-weights")
+    DECODE_WEIGHTS = sys.argv[_i + 1]
+    del sys.argv[_i:_i + 2]
 HID, NLAYER = SHAPE["--hidden"], SHAPE["--layers"]
 _pos = [a for a in sys.argv[1:] if not a.startswith("--")]
 B = int(_pos[0]) if len(_pos) > 0 else 8
@@ -81,16 +87,20 @@ if not INFER_ONLY:
 if "--infer" in sys.argv or INFER_ONLY:
     # frame-by-frame generation (Llasa.infer): 64 prompt tokens, 200 frames, KV cache vs the reference's full re-forward
     m.eval()
+    if DECODE_WEIGHTS:
+        m.quantize_decoder(DECODE_WEIGHTS)
+        print(f"decode weights: {DECODE_WEIGHTS} (use_cache=True lines; quantised at the first step, inside the warm-up call)")
     pid = torch.randint(0, 128264, (64,), device=dev)
     for use_cache, nfr in ((True, 200),) if INFER_ONLY else ((True, 200), (False, 200)):
         m.infer(pid, None, end_disp_kl_thres=-1.0, max_length=4, use_cache=use_cache)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        out = m.infer(pid, None, end_disp_kl_thres=-1.0, max_length=nfr, use_cache=use_cache)
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
-        print(f"infer use_cache={use_cache}: {nfr} frames in {dt*1e3:.0f} ms = {nfr/dt:.1f} frames/s "
-              f"({nfr/dt/12.5:.2f} x real time at 12.5 Hz), out {tuple(out.shape)}")
+        for rep in range(3 if INFER_ONLY else 1):          # (--infer-only: three repeats, for a min and a max)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = m.infer(pid, None, end_disp_kl_thres=-1.0, max_length=nfr, use_cache=use_cache)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            print(f"infer use_cache={use_cache}: {nfr} frames in {dt*1e3:.0f} ms = {nfr/dt:.1f} frames/s "
+                  f"({nfr/dt/12.5:.2f} x real time at 12.5 Hz), out {tuple(out.shape)}")
         if use_cache:
             one_fps = nfr / dt
 

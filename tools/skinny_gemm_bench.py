@@ -1,9 +1,76 @@
 """the forward GEMMs of one DiT block at generation batch sizes (M = 252 rows for B = 1 with CFG), each timed alone with HIP events
-over graph-free back-to-back launches: python tools/skinny_gemm_bench.py [M]"""
+over launches captured into a HIP graph: python tools/skinny_gemm_bench.py [M]
+--decode [R ...]: the eight decoder GEMMs of a KV-cached step (Llama-3.2-1B / 3B shapes) instead - gemv_kernel against
+gemv_e4m3_kernel, and gemm_rows_kernel against gemm_rows_e4m3_kernel at each R (default 1 8 16) - fp32 output, no residual, the
+weights rotating through > 600 MB of copies so that no call finds them in a cache; per kernel the median of 5 runs (min - max)
+in microseconds and the TB/s of weight bytes"""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from kalle_audio_amd import ops, _lib
 dev = torch.device("cuda")
+
+
+def decode_bench(rows):
+    shapes = [("1B q|k|v", 3072, 2048), ("1B o", 2048, 2048), ("1B up|gate", 16384, 2048), ("1B down", 2048, 8192),
+              ("3B q|k|v", 5120, 3072), ("3B o", 3072, 3072), ("3B up|gate", 16384, 3072), ("3B down", 3072, 8192)]
+
+    def timed(fns):
+        """median, min, max over 5 runs of the mean time per call over one pass through the rotating copies, microseconds.  The
+        pass is captured into one HIP graph (as the DiT shapes below are): device time per launch, without the host's per-call
+        cost (a torch.empty, the wrapper's asserts, ctypes), which differs between the wrappers and exceeds the small GEMVs"""
+        side = torch.cuda.Stream()
+        with torch.cuda.stream(side):
+            for f in fns[:2]:
+                f()
+            side.synchronize()
+            gr = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(gr, stream=side):
+                for f in fns:
+                    f()
+        gr.replay()
+        torch.cuda.synchronize()
+        runs = []
+        for _ in range(5):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            gr.replay()
+            e1.record()
+            torch.cuda.synchronize()
+            runs.append(e0.elapsed_time(e1) * 1e3 / len(fns))
+        runs.sort()
+        return runs[2], runs[0], runs[-1]
+
+    for name, n, k in shapes:
+        copies = 600 * 2 ** 20 // (n * k) + 2              # > 600 MB of e4m3 copies (twice that in bf16)
+        ws = [(torch.randn(n, k, device=dev) / k ** 0.5).bfloat16() for _ in range(copies)]
+        qs = [ops.quantize_rows_e4m3(w) for w in ws]
+        x1 = torch.randn(k, device=dev).bfloat16()
+        cols = []
+        for what, bytes_per, fns in (("gemv_kernel", 2, [lambda w=w: _gemv(x1, w) for w in ws]),
+                                     ("gemv_e4m3", 1, [lambda q=q: ops.gemv_e4m3(x1, q[0], q[1]) for q in qs])):
+            med, lo, hi = timed(fns)
+            cols.append(f"{what} {med:5.1f} ({lo:.1f} - {hi:.1f}) us {n * k * bytes_per / med / 1e6:4.1f} TB/s")
+        for R in rows:
+            xr = torch.randn(R, k, device=dev).bfloat16()
+            for what, bytes_per, fns in ((f"rows R={R}", 2, [lambda w=w: ops.gemm_rows(xr, w) for w in ws]),
+                                         (f"rows_e4m3 R={R}", 1, [lambda q=q: ops.gemm_rows_e4m3(xr, q[0], q[1]) for q in qs])):
+                med, lo, hi = timed(fns)
+                cols.append(f"{what} {med:5.1f} ({lo:.1f} - {hi:.1f}) us {n * k * bytes_per / med / 1e6:4.1f} TB/s")
+        print(f"{name:10s} {n} x {k}: " + " | ".join(cols), flush=True)
+        del ws, qs
+
+
+def _gemv(x, w):
+    lib = _lib.load()
+    y = torch.empty(w.shape[0], device=dev)
+    _lib.check(lib.kalle_gemv_bf16(ops._p(x), ops._p(w), w.stride(0), ops._p(y), 1, None, w.shape[0], w.shape[1], ops._stream()),
+               "kalle_gemv_bf16")
+    return y
+
+
+if "--decode" in sys.argv:
+    decode_bench([int(a) for a in sys.argv[sys.argv.index("--decode") + 1:]] or [1, 8, 16])
+    sys.exit(0)
 M = int(sys.argv[1]) if len(sys.argv) > 1 else 252
 Mc = M // 126 * 130
 shapes = [("qkv", M, 4608, 1536, {}), ("out+res", M, 1536, 1536, {"res": True}), ("q", M, 1536, 1536, {}), ("kv", Mc, 1536, 768, {}),
