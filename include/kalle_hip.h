@@ -554,8 +554,10 @@ int kalle_gemv_bf16(const void* x, const void* W, int64_t ldw, void* y, int y_dt
  *   x: fp32 [D] input embedding of position t0; out: fp32 [D] residual stream after the last layer (final norm not applied)
  *   rope_cos / rope_sin: fp32 [>= t0+1][32]; workspace: kalle_llama_decode_ws_bytes(H, Hkv, inner) bytes, 64-byte aligned
  *   H % Hkv == 0, inner % 8 == 0, 0 <= t0 < cache_rows, D = 64 H <= 32768, inner <= 32768 (a GEMV keeps its K-long bf16 operand in
- *   LDS: 64 KiB at the bound); anything else, or a NULL field in a descriptor, returns KALLE_ERR_ARG.  Every launch is checked
- *   where it is made: a refused launch returns KALLE_ERR_LAUNCH at once.
+ *   LDS: 64 KiB at the bound); anything else, or a NULL field in the descriptor of ANY layer, returns KALLE_ERR_ARG before the
+ *   first launch.  Every launch is checked where it is made: a refused launch returns KALLE_ERR_LAUNCH at once.
+ * This step and its head-dim, R-row and e4m3 forms below are argument adapters of one sequencer (decode_step, csrc/llasa.hip):
+ * the argument checks, the workspace carve-up and the per-layer sequence exist once.
  * Only row t0 of each cache is written (all 2*Hkv*64 of it); rows above t0 and rope rows above t0 are never read.
  * The workspace is caller-owned and its layout is part of this contract (D = 64 H), in this order:
  *   x2  fp32 [D]                         residual stream after the attention branch: x_in + Wo . ao

@@ -2,6 +2,8 @@
 // the shared GEMM / attention / RMSNorm kernels): fixed-sigma latent sampling, token-embedding gather mixed with the
 // projected audio latents under the two row masks (+ its scatter-add backward), exact GELU, and the masked fixed-sigma
 // Gaussian KL losses.  All HBM-bound: vectorised where rows are long, fp32 math.
+#include <type_traits>
+
 #include "common.h"
 #include "../../include/kalle_hip.h"
 
@@ -145,15 +147,6 @@ __global__ __launch_bounds__(256) void gemv_kernel(const void* __restrict__ xin,
     }
 }
 
-template <bool YF32, int PRO>
-inline void gemv_launch(const void* x, const float* gamma, float eps, const void* W, int64_t ldw, void* y, void* y2,
-                        int nsplit, const float* res, int N, int K, hipStream_t st) {
-    // several row pairs per wave once there are enough workgroups: the per-workgroup x preparation is amortised
-    const int rpw = N >= 8 * 4 * 512 ? 4 : N >= 8 * 2 * 512 ? 2 : 1;
-    KALLE_LAUNCH((gemv_kernel<YF32, PRO>), dim3((N + 8 * rpw - 1) / (8 * rpw)), dim3(256), (size_t)K * 2, st, x, gamma,
-                 eps, static_cast<const bf16_t*>(W), ldw, y, y2, nsplit, res, N, K, rpw);
-}
-
 // ---- R-row GEMM for batched decoding: Y[r][n] = sum_k W[n][k] X[r][k] (+ residual[r][n]), 1 <= R <= 16 -------------------------
 // Still pure weight streaming: W is read from HBM once for all rows.  A workgroup owns TR weight rows and every row of the batch:
 // v_mfma_f32_16x16x32_bf16 with the weight rows on the M side and the batch on the 16-wide N side, rows >= R or inactive held
@@ -280,36 +273,6 @@ __global__ __launch_bounds__(256) void gemm_rows_kernel(const bf16_t* __restrict
     }
 }
 
-// the pre-pass (if any) and the GEMM; returns the first failed launch
-inline int gemm_rows_run(const void* x, int64_t ldx, int pro, const float* gamma, float eps, bf16_t* xhat, int64_t ldh,
-                         const void* W, int64_t ldw, void* y, int64_t ldy, bool yf32, void* y2, int nsplit,
-                         const float* res, int64_t ldres, const RowsArgs& a, int N, int K, hipStream_t st) {
-    const bf16_t* X = static_cast<const bf16_t*>(x);
-    if (pro != PRO_BF16) {
-        if (pro == PRO_RMS)
-            KALLE_LAUNCH((rows_prologue_kernel<PRO_RMS>), dim3(a.R), dim3(256), 0, st, x, ldx, gamma, eps, xhat, ldh, K, a.active);
-        else
-            KALLE_LAUNCH((rows_prologue_kernel<PRO_SWIGLU>), dim3(a.R), dim3(256), 0, st, x, ldx, gamma, eps, xhat, ldh, K, a.active);
-        const int rc = kalle_check_launch();
-        if (rc != KALLE_OK) return rc;
-        X = xhat;
-        ldx = ldh;
-    }
-    const bf16_t* Wb = static_cast<const bf16_t*>(W);
-    const dim3 block(256);
-    // never fewer workgroups streaming weights than gemv_launch has for this N: N / 8 below 8192 rows, N / 16 from there
-    if (N < 8192) {
-        const dim3 grid((N + 7) / 8);
-        if (yf32) KALLE_LAUNCH((gemm_rows_kernel<true, 8>), grid, block, 0, st, X, ldx, Wb, ldw, y, ldy, y2, nsplit, res, ldres, N, K, a);
-        else KALLE_LAUNCH((gemm_rows_kernel<false, 8>), grid, block, 0, st, X, ldx, Wb, ldw, y, ldy, y2, nsplit, res, ldres, N, K, a);
-    } else {
-        const dim3 grid((N + 15) / 16);
-        if (yf32) KALLE_LAUNCH((gemm_rows_kernel<true, 16>), grid, block, 0, st, X, ldx, Wb, ldw, y, ldy, y2, nsplit, res, ldres, N, K, a);
-        else KALLE_LAUNCH((gemm_rows_kernel<false, 16>), grid, block, 0, st, X, ldx, Wb, ldw, y, ldy, y2, nsplit, res, ldres, N, K, a);
-    }
-    return kalle_check_launch();
-}
-
 // ---- weight-only OCP e4m3 decoding: W8 uint8 [N][ldq] codes, scale fp32 [N]; weight (n, k) = scale[n] * e4m3(W8[n][k]) -----------
 // The decode step is weight streaming, so the one thing left to cut per frame is the bytes per weight.  v_cvt_pk_f32_fp8 turns
 // two codes into two fp32 values; an e4m3 value (4 significant bits) times a bf16 value (8) is exact in fp32, so the only
@@ -377,7 +340,7 @@ __global__ __launch_bounds__(256) void quantize_rows_e4m3_kernel(const bf16_t* _
 // Byte budget: a weight row is K bytes now, so 16 bytes of it hold 16 weights and 64 lanes x 16 bytes cover 1024 of them - at
 // K = 2048 (every Llama-3.2-1B GEMV but down) a row is two loads per lane.  To keep gemv_kernel's 128 bytes per lane in flight
 // (2 rows x 4 x 16 B) a wave owns FOUR rows and issues 2 x 16 B of each per item, one item ahead; a workgroup is two such waves
-// (128 threads), so it still owns 8 rpw rows and the grid is gemv_launch's for every N.  Vector ALU per 16-byte load: 8
+// (128 threads), so it still owns 8 rpw rows and the grid is gemv_kernel's for every N.  Vector ALU per 16-byte load: 8
 // v_cvt_pk_f32_fp8 + 16 FMA (8 packed), and 16 unpacks of x shared by the four rows: 112 instructions per 64 weight bytes and lane
 // against gemv_kernel's 40 per 32 - 1.4 x the ALU work per byte on half the bytes.
 template <bool YF32, int PRO>
@@ -504,14 +467,6 @@ __global__ __launch_bounds__(128) void gemv_e4m3_kernel(const void* __restrict__
     }
 }
 
-template <bool YF32, int PRO>
-inline void gemv_e4m3_launch(const void* x, const float* gamma, float eps, const void* W8, int64_t ldq, const float* scale,
-                             void* y, void* y2, int nsplit, const float* res, int N, int K, hipStream_t st) {
-    const int rpw = N >= 8 * 4 * 512 ? 4 : N >= 8 * 2 * 512 ? 2 : 1;        // gemv_launch's rule: the same grid for every N
-    KALLE_LAUNCH((gemv_e4m3_kernel<YF32, PRO>), dim3((N + 8 * rpw - 1) / (8 * rpw)), dim3(128), (size_t)K * 2, st, x, gamma,
-                 eps, static_cast<const uint8_t*>(W8), ldq, scale, y, y2, nsplit, res, N, K, rpw);
-}
-
 // gemm_rows_kernel on e4m3 weights: the same tile, grid, K split over the waves and LDS meeting point.  Lane (row i, group g)
 // takes 16 bytes of weight row i - 16 weights, two of the MFMA's K chunks - widens them to bf16 in registers (exact: 4
 // significant bits) and feeds v_mfma_f32_16x16x32_bf16 twice, each time against the 16-byte chunk of batch row i that holds the
@@ -596,10 +551,47 @@ __global__ __launch_bounds__(256) void gemm_rows_e4m3_kernel(const bf16_t* __res
     }
 }
 
-// gemm_rows_run for e4m3 weights: rows_prologue_kernel as the pre-pass (unchanged), then the GEMM under gemm_rows_run's tile rule
-inline int gemm_rows_e4m3_run(const void* x, int64_t ldx, int pro, const float* gamma, float eps, bf16_t* xhat, int64_t ldh,
-                              const void* W8, int64_t ldq, const float* scale, void* y, int64_t ldy, bool yf32, void* y2,
-                              int nsplit, const float* res, int64_t ldres, const RowsArgs& a, int N, int K, hipStream_t st) {
+// ---- the one projection launcher: every GEMV and R-row GEMM of this file, public or inside the decode step, is launched here ---
+struct Proj {
+    const void* w;          // [N][ld]: bf16, or e4m3 codes when `scale` is set
+    int64_t ld;
+    const float* scale;     // fp32 [N] (e4m3) or NULL (bf16)
+};
+
+// f(std::bool_constant<yf32>, std::integral_constant<int, v>) for the runtime pair; v must be one of Vs
+template <int... Vs, class F>
+inline void for_instance(bool yf32, int v, F&& f) {
+    auto on = [&](auto yf) { ((v == Vs ? (f(yf, std::integral_constant<int, Vs>{}), 0) : 0), ...); };
+    if (yf32) on(std::true_type{});
+    else on(std::false_type{});
+}
+
+// y (columns n >= nsplit: y2) = W . pro(x) (+ res); returns the first failed launch.
+// rows == NULL: one row, the prologue built inside the GEMV (ldx, xhat, ldh, ldy, ldres unused).  Otherwise the R-row GEMM: the
+// prologue, if any, as a pre-pass into xhat (row stride ldh), y2 columns of row r at rows->y2_off[r].
+inline int proj_launch(const Proj& P, const void* x, int64_t ldx, int pro, const float* gamma, float eps, bf16_t* xhat,
+                       int64_t ldh, void* y, int64_t ldy, bool yf32, void* y2, int nsplit, const float* res, int64_t ldres,
+                       const RowsArgs* rows, int N, int K, hipStream_t st) {
+    const bf16_t* Wb = static_cast<const bf16_t*>(P.w);
+    const uint8_t* Wq = static_cast<const uint8_t*>(P.w);
+    if (!rows) {
+        // several row pairs (e4m3: row groups) per wave once there are enough workgroups: the per-workgroup x preparation is
+        // amortised.  A workgroup owns 8 rpw rows in both kernels, so the grid is the same for every N.
+        const int rpw = N >= 8 * 4 * 512 ? 4 : N >= 8 * 2 * 512 ? 2 : 1;
+        const dim3 grid((N + 8 * rpw - 1) / (8 * rpw));
+        const size_t lds = (size_t)K * 2;
+        for_instance<PRO_BF16, PRO_RMS, PRO_SWIGLU>(yf32, pro, [&](auto yf, auto p) {
+            constexpr bool F = decltype(yf)::value;
+            constexpr int PRO = decltype(p)::value;
+            if (P.scale)
+                KALLE_LAUNCH((gemv_e4m3_kernel<F, PRO>), grid, dim3(128), lds, st, x, gamma, eps, Wq, P.ld, P.scale, y, y2, nsplit,
+                             res, N, K, rpw);
+            else
+                KALLE_LAUNCH((gemv_kernel<F, PRO>), grid, dim3(256), lds, st, x, gamma, eps, Wb, P.ld, y, y2, nsplit, res, N, K, rpw);
+        });
+        return kalle_check_launch();
+    }
+    const RowsArgs& a = *rows;
     const bf16_t* X = static_cast<const bf16_t*>(x);
     if (pro != PRO_BF16) {
         if (pro == PRO_RMS)
@@ -611,17 +603,18 @@ inline int gemm_rows_e4m3_run(const void* x, int64_t ldx, int pro, const float* 
         X = xhat;
         ldx = ldh;
     }
-    const uint8_t* Wq = static_cast<const uint8_t*>(W8);
-    const dim3 block(256);
-    if (N < 8192) {
-        const dim3 grid((N + 7) / 8);
-        if (yf32) KALLE_LAUNCH((gemm_rows_e4m3_kernel<true, 8>), grid, block, 0, st, X, ldx, Wq, ldq, scale, y, ldy, y2, nsplit, res, ldres, N, K, a);
-        else KALLE_LAUNCH((gemm_rows_e4m3_kernel<false, 8>), grid, block, 0, st, X, ldx, Wq, ldq, scale, y, ldy, y2, nsplit, res, ldres, N, K, a);
-    } else {
-        const dim3 grid((N + 15) / 16);
-        if (yf32) KALLE_LAUNCH((gemm_rows_e4m3_kernel<true, 16>), grid, block, 0, st, X, ldx, Wq, ldq, scale, y, ldy, y2, nsplit, res, ldres, N, K, a);
-        else KALLE_LAUNCH((gemm_rows_e4m3_kernel<false, 16>), grid, block, 0, st, X, ldx, Wq, ldq, scale, y, ldy, y2, nsplit, res, ldres, N, K, a);
-    }
+    // never fewer workgroups streaming weights than the one-row form has for this N: N / 8 below 8192 rows, N / 16 from there
+    const int tr = N < 8192 ? 8 : 16;
+    const dim3 grid((N + tr - 1) / tr), block(256);
+    for_instance<8, 16>(yf32, tr, [&](auto yf, auto t) {
+        constexpr bool F = decltype(yf)::value;
+        constexpr int TR = decltype(t)::value;
+        if (P.scale)
+            KALLE_LAUNCH((gemm_rows_e4m3_kernel<F, TR>), grid, block, 0, st, X, ldx, Wq, P.ld, P.scale, y, ldy, y2, nsplit, res, ldres,
+                         N, K, a);
+        else
+            KALLE_LAUNCH((gemm_rows_kernel<F, TR>), grid, block, 0, st, X, ldx, Wb, P.ld, y, ldy, y2, nsplit, res, ldres, N, K, a);
+    });
     return kalle_check_launch();
 }
 
@@ -866,65 +859,173 @@ extern "C" int kalle_gemv_bf16(const void* x, const void* W, int64_t ldw, void* 
                                int N, int K, void* stream) {
     if (!x || !W || !y || N <= 0 || K <= 0 || (K & 7) || (ldw & 7) || K > 32768) return KALLE_ERR_ARG;
     if (y_dtype != KALLE_F32 && y_dtype != KALLE_BF16) return KALLE_ERR_ARG;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (y_dtype == KALLE_F32) gemv_launch<true, PRO_BF16>(x, nullptr, 0.f, W, ldw, y, y, N, residual, N, K, st);
-    else gemv_launch<false, PRO_BF16>(x, nullptr, 0.f, W, ldw, y, y, N, residual, N, K, st);
-    return kalle_check_launch();
+    return proj_launch({W, ldw, nullptr}, x, 0, PRO_BF16, nullptr, 0.f, nullptr, 0, y, 0, y_dtype == KALLE_F32, y, N, residual, 0,
+                       nullptr, N, K, static_cast<hipStream_t>(stream));
 }
 
-extern "C" int kalle_llama_decode_ws_bytes_hd(int H, int Hkv, int inner, int head_dim) {
-    if (H <= 0 || Hkv <= 0 || inner <= 0 || (head_dim != 64 && head_dim != 128)) return KALLE_ERR_ARG;
-    const int64_t D = (int64_t)H * head_dim;
-    // x2 | x3 fp32, lse fp32 (padded), q | ao | hf bf16
-    return (int)(2 * D * 4 + ((H * 4 + 63) & ~63) + D * 2 + D * 2 + 2 * (int64_t)inner * 2);
-}
-
+// ---- KV-cached decoding: ONE sequencer for bf16 / e4m3 weights and one row / R rows ----------------------------------------------
 extern "C" __attribute__((visibility("hidden"))) void kalle_set_attn_plan(int plan);   // (attention.hip)
 
-extern "C" int kalle_llama_decode_step_hd(const kalle_llama_layer* layers, int n_layers, const float* x, float* out, int H,
-                                          int Hkv, int inner, int head_dim, float eps, int t0, int cache_rows,
-                                          const float* rope_cos, const float* rope_sin, void* workspace, void* stream) {
+namespace {
+
+// The workspace the header publishes, carved in its order; the one-row layout is this at R = 1 without the trailing xn.
+struct DecodeWs {                // byte offsets
+    int64_t x2, x3, lse;         // fp32 [R][D] | [R][D] | [R][H], the lse region padded to a multiple of 64 bytes
+    int64_t q, ao, hf, xn;       // bf16 [R][D] | [R][D] | [R][2*inner] | [R][max(D, inner)]
+    int64_t end;
+};
+
+inline DecodeWs decode_ws(int R, int H, int inner, int head_dim) {
+    const int64_t D = (int64_t)H * head_dim, xw = D > inner ? D : inner;
+    DecodeWs w;
+    w.x2 = 0;
+    w.x3 = w.x2 + R * D * 4;
+    w.lse = w.x3 + R * D * 4;
+    w.q = w.lse + (((int64_t)R * H * 4 + 63) & ~(int64_t)63);
+    w.ao = w.q + R * D * 2;
+    w.hf = w.ao + R * D * 2;
+    w.xn = w.hf + R * 2 * (int64_t)inner * 2;
+    w.end = w.xn + R * xw * 2;
+    return w;
+}
+
+// one decoder layer of either descriptor form
+struct LayerView {
+    const float* input_norm;
+    Proj qkv, o;
+    const float* post_norm;
+    Proj ug, down;
+    void* kv_cache;
+    bool complete(bool w8) const {
+        return input_norm && qkv.w && o.w && post_norm && ug.w && down.w && kv_cache &&
+               (!w8 || (qkv.scale && o.scale && ug.scale && down.scale));
+    }
+};
+inline LayerView layer_view(const kalle_llama_layer& L, int D, int inner) {
+    return {L.input_norm, {L.wqkv, D, nullptr}, {L.wo, D, nullptr}, L.post_norm, {L.wug, D, nullptr}, {L.wdown, inner, nullptr},
+            L.kv_cache};
+}
+inline LayerView layer_view(const kalle_llama_layer_w8& L, int D, int inner) {
+    return {L.input_norm, {L.wqkv, D, L.sqkv}, {L.wo, D, L.so}, L.post_norm, {L.wug, D, L.sug}, {L.wdown, inner, L.sdown},
+            L.kv_cache};
+}
+
+// The step behind the six exported ones.  Exactly one of lb / l8 is set.  batched: the R-row form (t0[r] < 0 = row r inactive,
+// skinny GEMMs, kalle_attention_decode_rows); otherwise R = 1, GEMVs and kalle_attention_decode_hd.  Nothing is launched unless
+// every argument and every layer passes.
+int decode_step(const kalle_llama_layer* lb, const kalle_llama_layer_w8* l8, int n_layers, const float* x, float* out,
+                bool batched, int R, int H, int Hkv, int inner, int head_dim, float eps, const int32_t* t0, int cache_rows,
+                const float* rope_cos, const float* rope_sin, void* workspace, void* stream) {
     kalle_set_attn_plan(0);      // (a step refused before its first launch leaves no attention plan behind)
-    if (!layers || n_layers <= 0 || !x || !out || !workspace || !rope_cos || !rope_sin) return KALLE_ERR_ARG;
-    if (H <= 0 || Hkv <= 0 || H % Hkv || inner <= 0 || (inner & 7) || t0 < 0 || t0 >= cache_rows) return KALLE_ERR_ARG;
+    if ((!lb && !l8) || n_layers <= 0 || !x || !out || !workspace || !rope_cos || !rope_sin || !t0) return KALLE_ERR_ARG;
+    if (R < 1 || R > KALLE_DECODE_MAX_ROWS) return KALLE_ERR_ARG;
+    // (a lane's unit of a weight row is 16 bytes: 8 bf16 weights, 16 e4m3 codes; D is a multiple of 64)
+    if (H <= 0 || Hkv <= 0 || H % Hkv || inner <= 0 || (inner & (l8 ? 15 : 7)) || cache_rows <= 0) return KALLE_ERR_ARG;
     if (head_dim != 64 && head_dim != 128) return KALLE_ERR_ARG;
     if ((int64_t)H * head_dim > 32768 || inner > 32768) return KALLE_ERR_ARG;
-    const int D = H * head_dim, kvw = 2 * Hkv * head_dim;
+    const int D = H * head_dim, kvw = 2 * Hkv * head_dim, xw = D > inner ? D : inner;
+    RowsArgs a{};
+    a.R = R;
+    int32_t nk[KALLE_DECODE_MAX_ROWS];
+    for (int r = 0; r < R; ++r) {
+        // (batched: the attention's LDS score array holds nk <= 15360 keys; the one-row attention falls back to the tiled kernel)
+        if (t0[r] >= cache_rows || (batched ? t0[r] >= 15360 : t0[r] < 0)) return KALLE_ERR_ARG;
+        nk[r] = t0[r] < 0 ? 0 : t0[r] + 1;
+        if (t0[r] >= 0) a.active |= 1u << r;
+        a.y2_off[r] = t0[r] < 0 ? 0 : ((int64_t)r * cache_rows + t0[r]) * kvw;
+    }
+    auto layer = [&](int l) { return lb ? layer_view(lb[l], D, inner) : layer_view(l8[l], D, inner); };
+    for (int l = 0; l < n_layers; ++l)
+        if (!layer(l).complete(l8 != nullptr)) return KALLE_ERR_ARG;
+    if (!a.active) return KALLE_OK;
+    RowsArgs plain = a;                                      // (no second destination)
+    for (int r = 0; r < R; ++r) plain.y2_off[r] = 0;
+    const RowsArgs* rows_kv = batched ? &a : nullptr;
+    const RowsArgs* rows = batched ? &plain : nullptr;
     hipStream_t st = static_cast<hipStream_t>(stream);
+    const DecodeWs o = decode_ws(R, H, inner, head_dim);
     char* ws = static_cast<char*>(workspace);
-    float* xa = reinterpret_cast<float*>(ws);               // x2: residual stream after the attention branch
-    float* xb = xa + D;                                     // x3: layer output (input of the next layer)
-    float* lse = xb + D;
-    bf16_t* q = reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(lse) + ((H * 4 + 63) & ~63));
-    bf16_t* ao = q + D;
-    bf16_t* hf = ao + D;
+    float* x2 = reinterpret_cast<float*>(ws + o.x2);        // residual stream after the attention branch
+    float* x3 = reinterpret_cast<float*>(ws + o.x3);        // layer output (input of the next layer)
+    float* lse = reinterpret_cast<float*>(ws + o.lse);
+    bf16_t* q = reinterpret_cast<bf16_t*>(ws + o.q);
+    bf16_t* ao = reinterpret_cast<bf16_t*>(ws + o.ao);
+    bf16_t* hf = reinterpret_cast<bf16_t*>(ws + o.hf);
+    bf16_t* xn = batched ? reinterpret_cast<bf16_t*>(ws + o.xn) : nullptr;      // (the one-row workspace ends before it)
     const float* xin = x;
     for (int l = 0; l < n_layers; ++l) {
-        const kalle_llama_layer& L = layers[l];
-        if (!L.input_norm || !L.wqkv || !L.wo || !L.post_norm || !L.wug || !L.wdown || !L.kv_cache) return KALLE_ERR_ARG;
-        bf16_t* kv_row = static_cast<bf16_t*>(L.kv_cache) + (int64_t)t0 * kvw;
-        // q -> scratch, k | v -> cache row t0 (un-rotated: the attention kernel rotates by row index)
+        const LayerView L = layer(l);
+        // q -> scratch, k | v -> cache row t0[r] of sequence r (un-rotated: the attention kernel rotates by row index); the one-row
+        // GEMV takes the row's address, the R-row GEMM the cache and y2_off.
         // (every launch is checked where it is made: KALLE_LAUNCH clears the error state, so a refused launch would otherwise be
         // forgotten by the next one and the step would report success over an unwritten buffer)
-        // (nsplit = D is a multiple of 64 at either head dim: a wave's two rows never straddle it)
-        gemv_launch<false, PRO_RMS>(xin, L.input_norm, eps, L.wqkv, D, q, kv_row, D, nullptr, D + kvw, D, st);
-        int rc = kalle_check_launch();
+        // (nsplit = D is a multiple of 64 at either head dim: a wave's rows never straddle it)
+        void* kv = batched ? L.kv_cache : static_cast<bf16_t*>(L.kv_cache) + a.y2_off[0];
+        int rc = proj_launch(L.qkv, xin, D, PRO_RMS, L.input_norm, eps, xn, xw, q, D, false, kv, D, nullptr, 0, rows_kv, D + kvw,
+                             D, st);
         if (rc != KALLE_OK) return rc;
-        rc = kalle_attention_decode_hd(q, D, 0, L.kv_cache, kvw, 0, L.kv_cache, kvw, Hkv * head_dim, ao, D, lse, rope_cos, rope_sin,
-                                       head_dim, nullptr, 1, H, Hkv, t0 + 1, head_dim, stream);
+        rc = batched ? kalle_attention_decode_rows(q, D, 0, L.kv_cache, kvw, 0, L.kv_cache, kvw, Hkv * head_dim,
+                                                   (int64_t)cache_rows * kvw, ao, D, lse, rope_cos, rope_sin, head_dim, nk, R, H,
+                                                   Hkv, head_dim, stream)
+                     : kalle_attention_decode_hd(q, D, 0, L.kv_cache, kvw, 0, L.kv_cache, kvw, Hkv * head_dim, ao, D, lse,
+                                                 rope_cos, rope_sin, head_dim, nullptr, 1, H, Hkv, nk[0], head_dim, stream);
         if (rc != KALLE_OK) return rc;
-        gemv_launch<true, PRO_BF16>(ao, nullptr, 0.f, L.wo, D, xa, xa, D, xin, D, D, st);
-        if ((rc = kalle_check_launch()) != KALLE_OK) return rc;
-        gemv_launch<false, PRO_RMS>(xa, L.post_norm, eps, L.wug, D, hf, hf, 2 * inner, nullptr, 2 * inner, D, st);
-        if ((rc = kalle_check_launch()) != KALLE_OK) return rc;
-        float* xo = l + 1 == n_layers ? out : xb;
-        gemv_launch<true, PRO_SWIGLU>(hf, nullptr, 0.f, L.wdown, inner, xo, xo, D, xa, D, inner, st);
-        if ((rc = kalle_check_launch()) != KALLE_OK) return rc;
+        rc = proj_launch(L.o, ao, D, PRO_BF16, nullptr, 0.f, nullptr, 0, x2, D, true, x2, D, xin, D, rows, D, D, st);
+        if (rc != KALLE_OK) return rc;
+        rc = proj_launch(L.ug, x2, D, PRO_RMS, L.post_norm, eps, xn, xw, hf, 2 * inner, false, hf, 2 * inner, nullptr, 0, rows,
+                         2 * inner, D, st);
+        if (rc != KALLE_OK) return rc;
+        float* xo = l + 1 == n_layers ? out : x3;
+        rc = proj_launch(L.down, hf, 2 * inner, PRO_SWIGLU, nullptr, 0.f, xn, xw, xo, D, true, xo, D, x2, D, rows, D, inner, st);
+        if (rc != KALLE_OK) return rc;
         xin = xo;
     }
     return KALLE_OK;
 }
 
+}  // namespace
+
+extern "C" int kalle_llama_decode_ws_bytes_hd(int H, int Hkv, int inner, int head_dim) {
+    if (H <= 0 || Hkv <= 0 || inner <= 0 || (head_dim != 64 && head_dim != 128)) return KALLE_ERR_ARG;
+    return (int)decode_ws(1, H, inner, head_dim).xn;         // (one row: no pre-pass, no xn)
+}
+
+extern "C" int kalle_llama_decode_ws_bytes_rows(int R, int H, int Hkv, int inner, int head_dim) {
+    if (R < 1 || R > KALLE_DECODE_MAX_ROWS || H <= 0 || Hkv <= 0 || inner <= 0 || (head_dim != 64 && head_dim != 128))
+        return KALLE_ERR_ARG;
+    if ((int64_t)H * head_dim > 32768 || inner > 32768) return KALLE_ERR_ARG;
+    return (int)decode_ws(R, H, inner, head_dim).end;
+}
+
+// the six exported steps: argument adapters of decode_step
+extern "C" int kalle_llama_decode_step_hd(const kalle_llama_layer* layers, int n_layers, const float* x, float* out, int H,
+                                          int Hkv, int inner, int head_dim, float eps, int t0, int cache_rows,
+                                          const float* rope_cos, const float* rope_sin, void* workspace, void* stream) {
+    const int32_t t = t0;
+    return decode_step(layers, nullptr, n_layers, x, out, false, 1, H, Hkv, inner, head_dim, eps, &t, cache_rows, rope_cos, rope_sin,
+                       workspace, stream);
+}
+extern "C" int kalle_llama_decode_step_w8(const kalle_llama_layer_w8* layers, int n_layers, const float* x, float* out, int H,
+                                          int Hkv, int inner, int head_dim, float eps, int t0, int cache_rows,
+                                          const float* rope_cos, const float* rope_sin, void* workspace, void* stream) {
+    const int32_t t = t0;
+    return decode_step(nullptr, layers, n_layers, x, out, false, 1, H, Hkv, inner, head_dim, eps, &t, cache_rows, rope_cos, rope_sin,
+                       workspace, stream);
+}
+extern "C" int kalle_llama_decode_step_rows(const kalle_llama_layer* layers, int n_layers, const float* x, float* out, int R,
+                                            int H, int Hkv, int inner, int head_dim, float eps, const int32_t* t0,
+                                            int cache_rows, const float* rope_cos, const float* rope_sin, void* workspace,
+                                            void* stream) {
+    return decode_step(layers, nullptr, n_layers, x, out, true, R, H, Hkv, inner, head_dim, eps, t0, cache_rows, rope_cos, rope_sin,
+                       workspace, stream);
+}
+extern "C" int kalle_llama_decode_step_rows_w8(const kalle_llama_layer_w8* layers, int n_layers, const float* x, float* out,
+                                               int R, int H, int Hkv, int inner, int head_dim, float eps, const int32_t* t0,
+                                               int cache_rows, const float* rope_cos, const float* rope_sin, void* workspace,
+                                               void* stream) {
+    return decode_step(nullptr, layers, n_layers, x, out, true, R, H, Hkv, inner, head_dim, eps, t0, cache_rows, rope_cos, rope_sin,
+                       workspace, stream);
+}
 // the head-dim-64 forms of the C ABI: forwarders
 extern "C" int kalle_llama_decode_ws_bytes(int H, int Hkv, int inner) { return kalle_llama_decode_ws_bytes_hd(H, Hkv, inner, 64); }
 extern "C" int kalle_llama_decode_step(const kalle_llama_layer* layers, int n_layers, const float* x, float* out, int H,
@@ -934,18 +1035,19 @@ extern "C" int kalle_llama_decode_step(const kalle_llama_layer* layers, int n_la
                                       workspace, stream);
 }
 
-// ---- batched decoding (R rows per step) ----------------------------------------------------------------------------------------
-extern "C" int kalle_gemm_rows_fused(const void* x, int64_t ldx, int prologue, const float* gamma, float eps, void* xhat,
-                                     const void* W, int64_t ldw, void* y, int64_t ldy, int y_dtype, void* y2, int nsplit,
-                                     const int64_t* y2_off, const float* residual, int64_t ldres, const int32_t* active, int R,
-                                     int N, int K, void* stream) {
-    if (!x || !W || !y || R < 1 || R > KALLE_DECODE_MAX_ROWS || N <= 0 || K <= 0 || (K & 7) || (ldw & 7) || K > 32768)
+// ---- the R-row GEMM entry points -------------------------------------------------------------------------------------------------
+// the argument check and the RowsArgs of both weight formats, then the launch.  kalign: 8 (bf16) or 16 (e4m3) weights per 16 bytes.
+static int gemm_rows_entry(const Proj& P, int kalign, const void* x, int64_t ldx, int prologue, const float* gamma, float eps,
+                           void* xhat, void* y, int64_t ldy, int y_dtype, void* y2, int nsplit, const int64_t* y2_off,
+                           const float* residual, int64_t ldres, const int32_t* active, int R, int N, int K, void* stream) {
+    if (!x || !P.w || !y || R < 1 || R > KALLE_DECODE_MAX_ROWS || N <= 0 || K <= 0 || (K & (kalign - 1)) || (P.ld & (kalign - 1)) ||
+        K > 32768)
         return KALLE_ERR_ARG;
     if (y_dtype != KALLE_F32 && y_dtype != KALLE_BF16) return KALLE_ERR_ARG;
     if (prologue != PRO_BF16 && prologue != PRO_RMS && prologue != PRO_SWIGLU) return KALLE_ERR_ARG;
     if (prologue == PRO_RMS ? (!gamma || (ldx & 3)) : (ldx & 7)) return KALLE_ERR_ARG;
     if (prologue != PRO_BF16 && !xhat) return KALLE_ERR_ARG;
-    if (ldx < (prologue == PRO_SWIGLU ? 2 * (int64_t)K : K) || ldw < K || ldy < 0 || ldres < 0) return KALLE_ERR_ARG;
+    if (ldx < (prologue == PRO_SWIGLU ? 2 * (int64_t)K : K) || P.ld < K || ldy < 0 || ldres < 0) return KALLE_ERR_ARG;
     if (nsplit < 0 || nsplit > N || (nsplit < N && (!y2 || !y2_off))) return KALLE_ERR_ARG;
     RowsArgs a{};
     a.R = R;
@@ -954,8 +1056,16 @@ extern "C" int kalle_gemm_rows_fused(const void* x, int64_t ldx, int prologue, c
         a.y2_off[r] = nsplit < N ? y2_off[r] : 0;
     }
     if (!a.active) return KALLE_OK;
-    return gemm_rows_run(x, ldx, prologue, gamma, eps, static_cast<bf16_t*>(xhat), K, W, ldw, y, ldy, y_dtype == KALLE_F32, y2,
-                         nsplit, residual, ldres, a, N, K, static_cast<hipStream_t>(stream));
+    return proj_launch(P, x, ldx, prologue, gamma, eps, static_cast<bf16_t*>(xhat), K, y, ldy, y_dtype == KALLE_F32, y2, nsplit,
+                       residual, ldres, &a, N, K, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int kalle_gemm_rows_fused(const void* x, int64_t ldx, int prologue, const float* gamma, float eps, void* xhat,
+                                     const void* W, int64_t ldw, void* y, int64_t ldy, int y_dtype, void* y2, int nsplit,
+                                     const int64_t* y2_off, const float* residual, int64_t ldres, const int32_t* active, int R,
+                                     int N, int K, void* stream) {
+    return gemm_rows_entry({W, ldw, nullptr}, 8, x, ldx, prologue, gamma, eps, xhat, y, ldy, y_dtype, y2, nsplit, y2_off, residual,
+                           ldres, active, R, N, K, stream);
 }
 
 extern "C" int kalle_gemm_rows_bf16(const void* x, int64_t ldx, const void* W, int64_t ldw, void* y, int64_t ldy, int y_dtype,
@@ -964,74 +1074,13 @@ extern "C" int kalle_gemm_rows_bf16(const void* x, int64_t ldx, const void* W, i
                                  ldres, nullptr, R, N, K, stream);
 }
 
-extern "C" int kalle_llama_decode_ws_bytes_rows(int R, int H, int Hkv, int inner, int head_dim) {
-    if (R < 1 || R > KALLE_DECODE_MAX_ROWS || H <= 0 || Hkv <= 0 || inner <= 0 || (head_dim != 64 && head_dim != 128))
-        return KALLE_ERR_ARG;
-    if ((int64_t)H * head_dim > 32768 || inner > 32768) return KALLE_ERR_ARG;
-    const int64_t D = (int64_t)H * head_dim, xw = D > inner ? D : inner;
-    // x2 | x3 fp32, lse fp32 (padded), q | ao | hf | xn bf16: each [R][...]
-    return (int)(2 * R * D * 4 + (((int64_t)R * H * 4 + 63) & ~63) + 2 * R * D * 2 + 2 * R * (int64_t)inner * 2 + R * xw * 2);
-}
-
-extern "C" int kalle_llama_decode_step_rows(const kalle_llama_layer* layers, int n_layers, const float* x, float* out, int R,
-                                            int H, int Hkv, int inner, int head_dim, float eps, const int32_t* t0,
-                                            int cache_rows, const float* rope_cos, const float* rope_sin, void* workspace,
-                                            void* stream) {
-    kalle_set_attn_plan(0);
-    if (!layers || n_layers <= 0 || !x || !out || !workspace || !rope_cos || !rope_sin || !t0) return KALLE_ERR_ARG;
-    if (R < 1 || R > KALLE_DECODE_MAX_ROWS) return KALLE_ERR_ARG;
-    if (H <= 0 || Hkv <= 0 || H % Hkv || inner <= 0 || (inner & 7) || cache_rows <= 0) return KALLE_ERR_ARG;
-    if (head_dim != 64 && head_dim != 128) return KALLE_ERR_ARG;
-    if ((int64_t)H * head_dim > 32768 || inner > 32768) return KALLE_ERR_ARG;
-    const int D = H * head_dim, kvw = 2 * Hkv * head_dim, xw = D > inner ? D : inner;
-    RowsArgs a{};
-    a.R = R;
-    int32_t nk[KALLE_DECODE_MAX_ROWS];
-    for (int r = 0; r < R; ++r) {
-        if (t0[r] >= cache_rows || t0[r] >= 15360) return KALLE_ERR_ARG;      // (the attention's LDS score array: nk <= 15360)
-        nk[r] = t0[r] < 0 ? 0 : t0[r] + 1;
-        if (t0[r] >= 0) a.active |= 1u << r;
-        a.y2_off[r] = t0[r] < 0 ? 0 : ((int64_t)r * cache_rows + t0[r]) * kvw;
-    }
-    for (int l = 0; l < n_layers; ++l) {
-        const kalle_llama_layer& L = layers[l];
-        if (!L.input_norm || !L.wqkv || !L.wo || !L.post_norm || !L.wug || !L.wdown || !L.kv_cache) return KALLE_ERR_ARG;
-    }
-    if (!a.active) return KALLE_OK;
-    RowsArgs plain = a;                                      // (no second destination)
-    for (int r = 0; r < R; ++r) plain.y2_off[r] = 0;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(workspace);
-    float* xa = reinterpret_cast<float*>(ws);               // x2 [R][D]
-    float* xb = xa + (int64_t)R * D;                        // x3 [R][D]
-    float* lse = xb + (int64_t)R * D;                       // [R][H]
-    bf16_t* q = reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(lse) + ((R * H * 4 + 63) & ~63));
-    bf16_t* ao = q + (int64_t)R * D;
-    bf16_t* hf = ao + (int64_t)R * D;
-    bf16_t* xn = hf + (int64_t)R * 2 * inner;
-    const float* xin = x;
-    for (int l = 0; l < n_layers; ++l) {
-        const kalle_llama_layer& L = layers[l];
-        // q -> scratch, k | v -> cache row t0[r] of sequence r (un-rotated: the attention kernel rotates by row index)
-        int rc = gemm_rows_run(xin, D, PRO_RMS, L.input_norm, eps, xn, xw, L.wqkv, D, q, D, false, L.kv_cache, D, nullptr, 0, a,
-                               D + kvw, D, st);
-        if (rc != KALLE_OK) return rc;
-        rc = kalle_attention_decode_rows(q, D, 0, L.kv_cache, kvw, 0, L.kv_cache, kvw, Hkv * head_dim, (int64_t)cache_rows * kvw, ao,
-                                         D, lse, rope_cos, rope_sin, head_dim, nk, R, H, Hkv, head_dim, stream);
-        if (rc != KALLE_OK) return rc;
-        if ((rc = gemm_rows_run(ao, D, PRO_BF16, nullptr, 0.f, nullptr, 0, L.wo, D, xa, D, true, xa, D, xin, D, plain, D, D, st)) !=
-            KALLE_OK)
-            return rc;
-        if ((rc = gemm_rows_run(xa, D, PRO_RMS, L.post_norm, eps, xn, xw, L.wug, D, hf, 2 * inner, false, hf, 2 * inner, nullptr, 0,
-                                plain, 2 * inner, D, st)) != KALLE_OK)
-            return rc;
-        float* xo = l + 1 == n_layers ? out : xb;
-        if ((rc = gemm_rows_run(hf, 2 * inner, PRO_SWIGLU, nullptr, 0.f, xn, xw, L.wdown, inner, xo, D, true, xo, D, xa, D, plain,
-                                D, inner, st)) != KALLE_OK)
-            return rc;
-        xin = xo;
-    }
-    return KALLE_OK;
+extern "C" int kalle_gemm_rows_fused_e4m3(const void* x, int64_t ldx, int prologue, const float* gamma, float eps, void* xhat,
+                                          const void* W8, int64_t ldq, const float* scale, void* y, int64_t ldy, int y_dtype,
+                                          void* y2, int nsplit, const int64_t* y2_off, const float* residual, int64_t ldres,
+                                          const int32_t* active, int R, int N, int K, void* stream) {
+    if (!scale) return KALLE_ERR_ARG;
+    return gemm_rows_entry({W8, ldq, scale}, 16, x, ldx, prologue, gamma, eps, xhat, y, ldy, y_dtype, y2, nsplit, y2_off, residual,
+                           ldres, active, R, N, K, stream);
 }
 
 // ---- weight-only e4m3 decoding -----------------------------------------------------------------------------------------------
@@ -1043,16 +1092,6 @@ extern "C" int kalle_quantize_rows_e4m3(const void* W, int64_t ldw, void* W8, in
     return kalle_check_launch();
 }
 
-extern "C" int kalle_gemv_e4m3(const void* x, const void* W8, int64_t ldq, const float* scale, void* y, int y_dtype,
-                               const float* residual, int N, int K, void* stream) {
-    if (!x || !W8 || !scale || !y || N <= 0 || K <= 0 || (K & 15) || (ldq & 15) || ldq < K || K > 32768) return KALLE_ERR_ARG;
-    if (y_dtype != KALLE_F32 && y_dtype != KALLE_BF16) return KALLE_ERR_ARG;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (y_dtype == KALLE_F32) gemv_e4m3_launch<true, PRO_BF16>(x, nullptr, 0.f, W8, ldq, scale, y, y, N, residual, N, K, st);
-    else gemv_e4m3_launch<false, PRO_BF16>(x, nullptr, 0.f, W8, ldq, scale, y, y, N, residual, N, K, st);
-    return kalle_check_launch();
-}
-
 extern "C" int kalle_gemv_fused_e4m3(const void* x, int prologue, const float* gamma, float eps, const void* W8, int64_t ldq,
                                      const float* scale, void* y, int y_dtype, void* y2, int nsplit, const float* residual,
                                      int N, int K, void* stream) {
@@ -1061,141 +1100,13 @@ extern "C" int kalle_gemv_fused_e4m3(const void* x, int prologue, const float* g
     if (prologue != PRO_BF16 && prologue != PRO_RMS && prologue != PRO_SWIGLU) return KALLE_ERR_ARG;
     if (prologue == PRO_RMS && !gamma) return KALLE_ERR_ARG;
     if (nsplit < 0 || nsplit > N || (nsplit < N && !y2)) return KALLE_ERR_ARG;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool f = y_dtype == KALLE_F32;
-    if (nsplit == N) y2 = y;
-#define KALLE_GEMV8(F, P) gemv_e4m3_launch<F, P>(x, gamma, eps, W8, ldq, scale, y, y2, nsplit, residual, N, K, st)
-    if (prologue == PRO_BF16) { if (f) KALLE_GEMV8(true, PRO_BF16); else KALLE_GEMV8(false, PRO_BF16); }
-    else if (prologue == PRO_RMS) { if (f) KALLE_GEMV8(true, PRO_RMS); else KALLE_GEMV8(false, PRO_RMS); }
-    else { if (f) KALLE_GEMV8(true, PRO_SWIGLU); else KALLE_GEMV8(false, PRO_SWIGLU); }
-#undef KALLE_GEMV8
-    return kalle_check_launch();
+    return proj_launch({W8, ldq, scale}, x, 0, prologue, gamma, eps, nullptr, 0, y, 0, y_dtype == KALLE_F32, nsplit == N ? y : y2,
+                       nsplit, residual, 0, nullptr, N, K, static_cast<hipStream_t>(stream));
 }
 
-extern "C" int kalle_gemm_rows_fused_e4m3(const void* x, int64_t ldx, int prologue, const float* gamma, float eps, void* xhat,
-                                          const void* W8, int64_t ldq, const float* scale, void* y, int64_t ldy, int y_dtype,
-                                          void* y2, int nsplit, const int64_t* y2_off, const float* residual, int64_t ldres,
-                                          const int32_t* active, int R, int N, int K, void* stream) {
-    if (!x || !W8 || !scale || !y || R < 1 || R > KALLE_DECODE_MAX_ROWS || N <= 0 || K <= 0 || (K & 15) || (ldq & 15) || K > 32768)
-        return KALLE_ERR_ARG;
-    if (y_dtype != KALLE_F32 && y_dtype != KALLE_BF16) return KALLE_ERR_ARG;
-    if (prologue != PRO_BF16 && prologue != PRO_RMS && prologue != PRO_SWIGLU) return KALLE_ERR_ARG;
-    if (prologue == PRO_RMS ? (!gamma || (ldx & 3)) : (ldx & 7)) return KALLE_ERR_ARG;
-    if (prologue != PRO_BF16 && !xhat) return KALLE_ERR_ARG;
-    if (ldx < (prologue == PRO_SWIGLU ? 2 * (int64_t)K : K) || ldq < K || ldy < 0 || ldres < 0) return KALLE_ERR_ARG;
-    if (nsplit < 0 || nsplit > N || (nsplit < N && (!y2 || !y2_off))) return KALLE_ERR_ARG;
-    RowsArgs a{};
-    a.R = R;
-    for (int r = 0; r < R; ++r) {
-        if (!active || active[r]) a.active |= 1u << r;
-        a.y2_off[r] = nsplit < N ? y2_off[r] : 0;
-    }
-    if (!a.active) return KALLE_OK;
-    return gemm_rows_e4m3_run(x, ldx, prologue, gamma, eps, static_cast<bf16_t*>(xhat), K, W8, ldq, scale, y, ldy,
-                              y_dtype == KALLE_F32, y2, nsplit, residual, ldres, a, N, K, static_cast<hipStream_t>(stream));
-}
-
-static inline bool layer_w8_complete(const kalle_llama_layer_w8& L) {
-    return L.input_norm && L.wqkv && L.sqkv && L.wo && L.so && L.post_norm && L.wug && L.sug && L.wdown && L.sdown && L.kv_cache;
-}
-
-extern "C" int kalle_llama_decode_step_w8(const kalle_llama_layer_w8* layers, int n_layers, const float* x, float* out, int H,
-                                          int Hkv, int inner, int head_dim, float eps, int t0, int cache_rows,
-                                          const float* rope_cos, const float* rope_sin, void* workspace, void* stream) {
-    kalle_set_attn_plan(0);
-    if (!layers || n_layers <= 0 || !x || !out || !workspace || !rope_cos || !rope_sin) return KALLE_ERR_ARG;
-    if (H <= 0 || Hkv <= 0 || H % Hkv || inner <= 0 || (inner & 15) || t0 < 0 || t0 >= cache_rows) return KALLE_ERR_ARG;
-    if (head_dim != 64 && head_dim != 128) return KALLE_ERR_ARG;                // (so D % 16 == 0)
-    if ((int64_t)H * head_dim > 32768 || inner > 32768) return KALLE_ERR_ARG;
-    for (int l = 0; l < n_layers; ++l)                       // (every layer before the first launch)
-        if (!layer_w8_complete(layers[l])) return KALLE_ERR_ARG;
-    const int D = H * head_dim, kvw = 2 * Hkv * head_dim;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(workspace);                // (the layout of kalle_llama_decode_step_hd)
-    float* xa = reinterpret_cast<float*>(ws);
-    float* xb = xa + D;
-    float* lse = xb + D;
-    bf16_t* q = reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(lse) + ((H * 4 + 63) & ~63));
-    bf16_t* ao = q + D;
-    bf16_t* hf = ao + D;
-    const float* xin = x;
-    for (int l = 0; l < n_layers; ++l) {
-        const kalle_llama_layer_w8& L = layers[l];
-        bf16_t* kv_row = static_cast<bf16_t*>(L.kv_cache) + (int64_t)t0 * kvw;
-        gemv_e4m3_launch<false, PRO_RMS>(xin, L.input_norm, eps, L.wqkv, D, L.sqkv, q, kv_row, D, nullptr, D + kvw, D, st);
-        int rc = kalle_check_launch();
-        if (rc != KALLE_OK) return rc;
-        rc = kalle_attention_decode_hd(q, D, 0, L.kv_cache, kvw, 0, L.kv_cache, kvw, Hkv * head_dim, ao, D, lse, rope_cos, rope_sin,
-                                       head_dim, nullptr, 1, H, Hkv, t0 + 1, head_dim, stream);
-        if (rc != KALLE_OK) return rc;
-        gemv_e4m3_launch<true, PRO_BF16>(ao, nullptr, 0.f, L.wo, D, L.so, xa, xa, D, xin, D, D, st);
-        if ((rc = kalle_check_launch()) != KALLE_OK) return rc;
-        gemv_e4m3_launch<false, PRO_RMS>(xa, L.post_norm, eps, L.wug, D, L.sug, hf, hf, 2 * inner, nullptr, 2 * inner, D, st);
-        if ((rc = kalle_check_launch()) != KALLE_OK) return rc;
-        float* xo = l + 1 == n_layers ? out : xb;
-        gemv_e4m3_launch<true, PRO_SWIGLU>(hf, nullptr, 0.f, L.wdown, inner, L.sdown, xo, xo, D, xa, D, inner, st);
-        if ((rc = kalle_check_launch()) != KALLE_OK) return rc;
-        xin = xo;
-    }
-    return KALLE_OK;
-}
-
-extern "C" int kalle_llama_decode_step_rows_w8(const kalle_llama_layer_w8* layers, int n_layers, const float* x, float* out,
-                                               int R, int H, int Hkv, int inner, int head_dim, float eps, const int32_t* t0,
-                                               int cache_rows, const float* rope_cos, const float* rope_sin, void* workspace,
-                                               void* stream) {
-    kalle_set_attn_plan(0);
-    if (!layers || n_layers <= 0 || !x || !out || !workspace || !rope_cos || !rope_sin || !t0) return KALLE_ERR_ARG;
-    if (R < 1 || R > KALLE_DECODE_MAX_ROWS) return KALLE_ERR_ARG;
-    if (H <= 0 || Hkv <= 0 || H % Hkv || inner <= 0 || (inner & 15) || cache_rows <= 0) return KALLE_ERR_ARG;
-    if (head_dim != 64 && head_dim != 128) return KALLE_ERR_ARG;                // (so D % 16 == 0)
-    if ((int64_t)H * head_dim > 32768 || inner > 32768) return KALLE_ERR_ARG;
-    const int D = H * head_dim, kvw = 2 * Hkv * head_dim, xw = D > inner ? D : inner;
-    RowsArgs a{};
-    a.R = R;
-    int32_t nk[KALLE_DECODE_MAX_ROWS];
-    for (int r = 0; r < R; ++r) {
-        if (t0[r] >= cache_rows || t0[r] >= 15360) return KALLE_ERR_ARG;
-        nk[r] = t0[r] < 0 ? 0 : t0[r] + 1;
-        if (t0[r] >= 0) a.active |= 1u << r;
-        a.y2_off[r] = t0[r] < 0 ? 0 : ((int64_t)r * cache_rows + t0[r]) * kvw;
-    }
-    for (int l = 0; l < n_layers; ++l)
-        if (!layer_w8_complete(layers[l])) return KALLE_ERR_ARG;
-    if (!a.active) return KALLE_OK;
-    RowsArgs plain = a;                                      // (no second destination)
-    for (int r = 0; r < R; ++r) plain.y2_off[r] = 0;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(workspace);                // (the layout of kalle_llama_decode_step_rows)
-    float* xa = reinterpret_cast<float*>(ws);
-    float* xb = xa + (int64_t)R * D;
-    float* lse = xb + (int64_t)R * D;
-    bf16_t* q = reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(lse) + ((R * H * 4 + 63) & ~63));
-    bf16_t* ao = q + (int64_t)R * D;
-    bf16_t* hf = ao + (int64_t)R * D;
-    bf16_t* xn = hf + (int64_t)R * 2 * inner;
-    const float* xin = x;
-    for (int l = 0; l < n_layers; ++l) {
-        const kalle_llama_layer_w8& L = layers[l];
-        int rc = gemm_rows_e4m3_run(xin, D, PRO_RMS, L.input_norm, eps, xn, xw, L.wqkv, D, L.sqkv, q, D, false, L.kv_cache, D,
-                                    nullptr, 0, a, D + kvw, D, st);
-        if (rc != KALLE_OK) return rc;
-        rc = kalle_attention_decode_rows(q, D, 0, L.kv_cache, kvw, 0, L.kv_cache, kvw, Hkv * head_dim, (int64_t)cache_rows * kvw, ao,
-                                         D, lse, rope_cos, rope_sin, head_dim, nk, R, H, Hkv, head_dim, stream);
-        if (rc != KALLE_OK) return rc;
-        if ((rc = gemm_rows_e4m3_run(ao, D, PRO_BF16, nullptr, 0.f, nullptr, 0, L.wo, D, L.so, xa, D, true, xa, D, xin, D, plain,
-                                     D, D, st)) != KALLE_OK)
-            return rc;
-        if ((rc = gemm_rows_e4m3_run(xa, D, PRO_RMS, L.post_norm, eps, xn, xw, L.wug, D, L.sug, hf, 2 * inner, false, hf,
-                                     2 * inner, nullptr, 0, plain, 2 * inner, D, st)) != KALLE_OK)
-            return rc;
-        float* xo = l + 1 == n_layers ? out : xb;
-        if ((rc = gemm_rows_e4m3_run(hf, 2 * inner, PRO_SWIGLU, nullptr, 0.f, xn, xw, L.wdown, inner, L.sdown, xo, D, true, xo,
-                                     D, xa, D, plain, D, inner, st)) != KALLE_OK)
-            return rc;
-        xin = xo;
-    }
-    return KALLE_OK;
+extern "C" int kalle_gemv_e4m3(const void* x, const void* W8, int64_t ldq, const float* scale, void* y, int y_dtype,
+                               const float* residual, int N, int K, void* stream) {
+    return kalle_gemv_fused_e4m3(x, PRO_BF16, nullptr, 0.f, W8, ldq, scale, y, y_dtype, nullptr, N, residual, N, K, stream);
 }
 
 extern "C" int kalle_peak_normalize_int16(const void* x, int dtype, float* peak, int16_t* out, int64_t n, void* stream) {

@@ -67,7 +67,7 @@ def e4m3_of(p):
 
 def layer_params_w8(layer):
     """layer_params with the four projections as e4m3 codes + scales (made lazily, per layer): the fields of
-    ops.llama_decode_plan_w8 in order, without the cache"""
+    ops.W8_FIELDS in order, without the cache"""
     p = layer_params(layer)
     out = [p.g1]
     for w in (layer.self_attn.qkv_proj.weight, layer.self_attn.o_proj.weight):

@@ -294,24 +294,17 @@ class LlamaModel(nn.Module):
         """the cache's plan for the current decode weight format; rebuilt when the format changed or (quantised) a weight did"""
         fmt = self._decode_fmt
         plan = cache.get("plan")
-        if fmt is None:
-            if plan is None or plan.get("fmt") is not None:
+        # (bf16 plans hold the weights themselves: nothing to key)
+        key = None if fmt is None else (ops.WEIGHTS_EPOCH,) + tuple(p._version for p in self._decode_weights(plan is None))
+        if plan is None or plan.get("fmt") != fmt or plan["wkey"] != key:
+            if fmt is None:
                 ps = [LO.layer_params(layer) for layer in self.layers]
                 ts = [(p.g1, p.wqkv, p.wo, p.g2, p.wug, p.wdown, kv) for p, kv in zip(ps, cache["kv"])]
-                H, Hkv, inner, hd = ps[0].H, ps[0].Hkv, ps[0].wug.shape[0] // 2, ps[0].hd
-                plan = (ops.llama_decode_plan(ts, H, Hkv, inner, device, head_dim=hd) if rows is None else
-                        ops.llama_decode_plan_rows(ts, rows, H, Hkv, inner, device, head_dim=hd))
-                plan["eps"] = ps[0].eps
-                cache["plan"] = plan
-            return plan
-        key = (ops.WEIGHTS_EPOCH,) + tuple(p._version for p in self._decode_weights(plan is None))
-        if plan is None or plan.get("fmt") != fmt or plan["wkey"] != key:
-            pts = [LO.layer_params_w8(layer) for layer in self.layers]
-            ts = [t + (kv,) for (_, t), kv in zip(pts, cache["kv"])]
-            p0 = pts[0][0]
-            H, Hkv, inner, hd = p0.H, p0.Hkv, self.cfg["intermediate_size"], p0.hd
-            plan = (ops.llama_decode_plan_w8(ts, H, Hkv, inner, device, head_dim=hd) if rows is None else
-                    ops.llama_decode_plan_rows_w8(ts, rows, H, Hkv, inner, device, head_dim=hd))
+            else:
+                ps, qs = zip(*(LO.layer_params_w8(layer) for layer in self.layers))
+                ts = [q + (kv,) for q, kv in zip(qs, cache["kv"])]
+            p0 = ps[0]
+            plan = ops.llama_decode_plan(ts, p0.H, p0.Hkv, p0.wug.shape[0] // 2, device, head_dim=p0.hd, rows=rows)
             plan["eps"], plan["wkey"] = p0.eps, key
             cache["plan"] = plan
         return plan
@@ -367,8 +360,7 @@ class LlamaModel(nn.Module):
         if n == 1:
             # one generated frame: the whole stack is sequenced by kalle_llama_decode_step (one host call)
             plan = self._decode_plan(cache, x.device)
-            step = ops.llama_decode_step if plan.get("fmt") is None else ops.llama_decode_step_w8
-            x = step(plan, x.view(Dm), t0, cache["kv"][0].shape[0], cache["rope"], plan["eps"])
+            x = ops.llama_decode_step(plan, x.view(Dm), t0, cache["kv"][0].shape[0], cache["rope"], plan["eps"])
         else:
             for layer, kv in zip(self.layers, cache["kv"]):
                 x = LO.layer_fwd_cached(LO.layer_params(layer), x, kv, t0, cache["rope"])
@@ -415,8 +407,7 @@ class LlamaModel(nn.Module):
             raise ValueError("KV cache too short")
         x = Fn._to_f32(inputs_embeds.contiguous()).view(R, Dm)
         plan = self._decode_plan(cache, x.device, rows=R)
-        step = ops.llama_decode_step_rows if plan.get("fmt") is None else ops.llama_decode_step_rows_w8
-        x = step(plan, x, t0, rows, cache["rope"], plan["eps"])
+        x = ops.llama_decode_step(plan, x, t0, rows, cache["rope"], plan["eps"])
         cache["len"] = [t + 1 if a else t for t, a in zip(cache["len"], active)]
         return self.norm(x.view(R, 1, Dm))
 

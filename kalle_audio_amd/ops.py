@@ -632,50 +632,37 @@ def gauss_kl_bwd(pred, label, mask_a, mask_b, sums, grad_a, grad_b, std):
     return dpred
 
 
-def llama_decode_plan(layer_tensors, H, Hkv, inner, device, head_dim=64):
-    """layer_tensors: per layer (input_norm fp32, wqkv bf16, wo bf16, post_norm fp32, wug bf16, wdown bf16, kv_cache bf16).
-    Returns the host-side descriptor array + workspace of kalle_llama_decode_step (keeps the tensors alive)."""
-    lib = _lib.load()
-    arr = (_lib.LlamaLayer * len(layer_tensors))()
-    for d, ts in zip(arr, layer_tensors):
-        for t in ts:
-            assert t.is_contiguous() and t.device == torch.device(device)
-        d.input_norm, d.wqkv, d.wo, d.post_norm, d.wug, d.wdown, d.kv_cache = (t.data_ptr() for t in ts)
-    nbytes = lib.kalle_llama_decode_ws_bytes_hd(H, Hkv, inner, head_dim)
-    check(min(nbytes, 0), "kalle_llama_decode_ws_bytes_hd")
-    ws = torch.empty(nbytes, device=device, dtype=torch.uint8)
-    return {"layers": arr, "n": len(layer_tensors), "keep": layer_tensors, "ws": ws, "H": H, "Hkv": Hkv, "inner": inner,
-            "head_dim": head_dim}
-
-
-def llama_decode_step(plan, x, t0, cache_rows, rope, eps):
-    """x fp32 [D] -> fp32 [D]: every decoder layer at position t0 against the KV caches of `plan` (one host call)"""
-    lib = _lib.load()
-    out = torch.empty_like(x)
-    check(lib.kalle_llama_decode_step_hd(ctypes.cast(plan["layers"], ctypes.c_void_p), plan["n"], _p(x), _p(out), plan["H"],
-                                         plan["Hkv"], plan["inner"], plan.get("head_dim", 64), eps, t0, cache_rows,
-                                         _p(rope[0]), _p(rope[1]), _p(plan["ws"]), _stream()), "kalle_llama_decode_step_hd")
-    return out
-
-
-# ---- batched decoding: R <= DECODE_MAX_ROWS sequences per step (include/kalle_hip.h) ----------------------------------------
+# ---- KV-cached decoding (include/kalle_hip.h): one row or R <= DECODE_MAX_ROWS sequences per step, bf16 weights or uint8 OCP
+# e4m3fn codes [N, K] + one fp32 scale per output row
 DECODE_MAX_ROWS = 16
+BF16_FIELDS = ("input_norm", "wqkv", "wo", "post_norm", "wug", "wdown", "kv_cache")
+W8_FIELDS = ("input_norm", "wqkv", "sqkv", "wo", "so", "post_norm", "wug", "sug", "wdown", "sdown", "kv_cache")
+_DECODE_STEP = {(False, False): "kalle_llama_decode_step_hd", (False, True): "kalle_llama_decode_step_w8",      # (R-row, e4m3)
+                (True, False): "kalle_llama_decode_step_rows", (True, True): "kalle_llama_decode_step_rows_w8"}
 
 
 def _i32(vals):
     return (ctypes.c_int32 * len(vals))(*[int(v) for v in vals])
 
 
+def _proj_args(x, w, wdtype, scale, residual, yshape):
+    """the assertions the GEMV / skinny-GEMM wrappers share: x bf16 [.., K] against w [N, K] (+ scale fp32 [N]), residual fp32"""
+    assert w.dim() == 2 and w.stride(1) == 1 and w.dtype == wdtype and x.shape[-1] == w.shape[1]
+    assert x.dtype == torch.bfloat16 and x.stride(-1) == 1
+    if scale is not None:
+        assert scale.dtype == torch.float32 and scale.shape == (w.shape[0],) and scale.is_contiguous()
+    if residual is not None:
+        assert residual.dtype == torch.float32 and residual.shape == yshape and residual.stride(-1) == 1
+
+
 def gemm_rows(x, w, *, residual=None, out_dtype=torch.float32):
     """Y[r] = W . x[r] (+ residual[r]) for the R <= 16 rows of x (bf16 [R, K], rows may be strided); W bf16 [N, K] is read once
     for all rows: kalle_gemm_rows_bf16"""
     lib = _lib.load()
-    assert x.dim() == 2 and w.dim() == 2 and x.stride(1) == 1 and w.stride(1) == 1 and x.shape[1] == w.shape[1]
-    assert x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16
+    assert x.dim() == 2
     R, K = x.shape
     y = torch.empty((R, w.shape[0]), device=x.device, dtype=out_dtype)
-    if residual is not None:
-        assert residual.dtype == torch.float32 and residual.shape == y.shape and residual.stride(1) == 1
+    _proj_args(x, w, torch.bfloat16, None, residual, y.shape)
     check(lib.kalle_gemm_rows_bf16(_p(x), x.stride(0), _p(w), w.stride(0), _p(y), y.stride(0), _dt(y), _p(residual),
                                    residual.stride(0) if residual is not None else 0, R, w.shape[0], K, _stream()),
           "kalle_gemm_rows_bf16")
@@ -697,42 +684,6 @@ def attention_decode_rows(q, k, v, nk, *, ldq, q_off, ldk, k_off, ldv, v_off, kv
     return out, lse
 
 
-def llama_decode_plan_rows(layer_tensors, R, H, Hkv, inner, device, head_dim=64):
-    """llama_decode_plan for R rows: kv_cache of a layer is bf16 [R, cache_rows, 2*Hkv*head_dim]"""
-    lib = _lib.load()
-    arr = (_lib.LlamaLayer * len(layer_tensors))()
-    for d, ts in zip(arr, layer_tensors):
-        for t in ts:
-            assert t.is_contiguous() and t.device == torch.device(device)
-        assert ts[6].dim() == 3 and ts[6].shape[0] == R
-        d.input_norm, d.wqkv, d.wo, d.post_norm, d.wug, d.wdown, d.kv_cache = (t.data_ptr() for t in ts)
-    nbytes = lib.kalle_llama_decode_ws_bytes_rows(R, H, Hkv, inner, head_dim)
-    check(min(nbytes, 0), "kalle_llama_decode_ws_bytes_rows")
-    ws = torch.empty(nbytes, device=device, dtype=torch.uint8)
-    return {"layers": arr, "n": len(layer_tensors), "keep": layer_tensors, "ws": ws, "R": R, "H": H, "Hkv": Hkv, "inner": inner,
-            "head_dim": head_dim}
-
-
-def llama_decode_step_rows(plan, x, t0, cache_rows, rope, eps):
-    """x fp32 [R, D] -> fp32 [R, D]: every decoder layer for row r at position t0[r] (host ints; negative = inactive row) against
-    the KV caches of `plan` (one host call).  The result is the plan's own buffer, reused by the next step: an inactive row keeps
-    what its last active step left there (zeros before the first)"""
-    lib = _lib.load()
-    assert x.shape[0] == plan["R"] == len(t0) and x.is_contiguous() and x.dtype == torch.float32
-    out = plan.get("out")
-    if out is None:
-        out = plan["out"] = torch.zeros_like(x)
-    check(lib.kalle_llama_decode_step_rows(ctypes.cast(plan["layers"], ctypes.c_void_p), plan["n"], _p(x), _p(out), plan["R"],
-                                           plan["H"], plan["Hkv"], plan["inner"], plan["head_dim"], eps,
-                                           ctypes.cast(_i32(t0), ctypes.c_void_p), cache_rows, _p(rope[0]), _p(rope[1]),
-                                           _p(plan["ws"]), _stream()), "kalle_llama_decode_step_rows")
-    return out
-
-
-# ---- weight-only e4m3 decoding (include/kalle_hip.h): uint8 OCP e4m3fn codes [N, K] + one fp32 scale per output row -----------
-W8_FIELDS = ("input_norm", "wqkv", "sqkv", "wo", "so", "post_norm", "wug", "sug", "wdown", "sdown", "kv_cache")
-
-
 def quantize_rows_e4m3(w):
     """w bf16 [N, K] (rows may be strided, K % 16 == 0) -> (w8 uint8 [N, K], scale fp32 [N]): kalle_quantize_rows_e4m3"""
     lib = _lib.load()
@@ -744,21 +695,13 @@ def quantize_rows_e4m3(w):
     return w8, scale
 
 
-def _w8_args(x, w8, scale):
-    assert w8.dim() == 2 and w8.stride(1) == 1 and w8.dtype == torch.uint8 and x.shape[-1] == w8.shape[1]
-    assert scale.dtype == torch.float32 and scale.shape == (w8.shape[0],) and scale.is_contiguous()
-    assert x.dtype == torch.bfloat16 and x.stride(-1) == 1
-
-
 def gemv_e4m3(x, w8, scale, *, residual=None, out_dtype=torch.float32):
     """y = scale * (e4m3(w8) . x) (+ residual) for one bf16 row x [K]: kalle_gemv_e4m3"""
     lib = _lib.load()
     assert x.dim() == 1
-    _w8_args(x, w8, scale)
     N, K = w8.shape
     y = torch.empty((N,), device=x.device, dtype=out_dtype)
-    if residual is not None:
-        assert residual.dtype == torch.float32 and residual.shape == y.shape and residual.is_contiguous()
+    _proj_args(x, w8, torch.uint8, scale, residual, y.shape)
     check(lib.kalle_gemv_e4m3(_p(x), _p(w8), w8.stride(0), _p(scale), _p(y), _dt(y), _p(residual), N, K, _stream()),
           "kalle_gemv_e4m3")
     return y
@@ -769,12 +712,10 @@ def gemm_rows_e4m3(x, w8, scale, *, residual=None, out_dtype=torch.float32):
     kalle_gemm_rows_fused_e4m3 without a prologue"""
     lib = _lib.load()
     assert x.dim() == 2
-    _w8_args(x, w8, scale)
     R, K = x.shape
     N = w8.shape[0]
     y = torch.empty((R, N), device=x.device, dtype=out_dtype)
-    if residual is not None:
-        assert residual.dtype == torch.float32 and residual.shape == y.shape and residual.stride(1) == 1
+    _proj_args(x, w8, torch.uint8, scale, residual, y.shape)
     check(lib.kalle_gemm_rows_fused_e4m3(_p(x), x.stride(0), 0, None, 0.0, None, _p(w8), w8.stride(0), _p(scale), _p(y),
                                          y.stride(0), _dt(y), None, N, None, _p(residual),
                                          residual.stride(0) if residual is not None else 0, None, R, N, K, _stream()),
@@ -782,63 +723,57 @@ def gemm_rows_e4m3(x, w8, scale, *, residual=None, out_dtype=torch.float32):
     return y
 
 
-def _w8_plan(layer_tensors, device, rows=None):
-    arr = (_lib.LlamaLayerW8 * len(layer_tensors))()
+def llama_decode_plan(layer_tensors, H, Hkv, inner, device, head_dim=64, rows=None):
+    """The host-side descriptor array + workspace of the decode step (keeps the tensors alive).  layer_tensors: per layer the
+    tensors of BF16_FIELDS (input_norm fp32, wqkv bf16, wo bf16, post_norm fp32, wug bf16, wdown bf16, kv_cache bf16) or of
+    W8_FIELDS (each weight uint8 and followed by its fp32 scale, the pairs as quantize_rows_e4m3 returns them); the tuple length
+    tells which.  rows = R: the R-row step, kv_cache of a layer is bf16 [R, cache_rows, 2*Hkv*head_dim]."""
+    lib = _lib.load()
+    nf = len(layer_tensors[0])
+    assert nf in (len(BF16_FIELDS), len(W8_FIELDS)), f"a layer is {len(BF16_FIELDS)} (bf16) or {len(W8_FIELDS)} (e4m3) tensors"
+    w8 = nf == len(W8_FIELDS)
+    fields, desc = (W8_FIELDS, _lib.LlamaLayerW8) if w8 else (BF16_FIELDS, _lib.LlamaLayer)
+    arr = (desc * len(layer_tensors))()
     for d, ts in zip(arr, layer_tensors):
-        assert len(ts) == len(W8_FIELDS)
-        for t in ts:
+        assert len(ts) == nf
+        for f, t in zip(fields, ts):
             assert t.is_contiguous() and t.device == torch.device(device)
+            setattr(d, f, t.data_ptr())
         if rows is not None:
             assert ts[-1].dim() == 3 and ts[-1].shape[0] == rows
-        for f, t in zip(W8_FIELDS, ts):
-            setattr(d, f, t.data_ptr())
-    return arr
+    if rows is None:
+        nbytes, what = lib.kalle_llama_decode_ws_bytes_hd(H, Hkv, inner, head_dim), "kalle_llama_decode_ws_bytes_hd"
+    else:
+        nbytes, what = lib.kalle_llama_decode_ws_bytes_rows(rows, H, Hkv, inner, head_dim), "kalle_llama_decode_ws_bytes_rows"
+    check(min(nbytes, 0), what)
+    plan = {"layers": arr, "n": len(layer_tensors), "keep": layer_tensors, "ws": torch.empty(nbytes, device=device, dtype=torch.uint8),
+            "H": H, "Hkv": Hkv, "inner": inner, "head_dim": head_dim,
+            "step": _DECODE_STEP[rows is not None, w8]}
+    if rows is not None:
+        plan["R"] = rows
+    if w8:
+        plan["fmt"] = "e4m3"
+    return plan
 
 
-def llama_decode_plan_w8(layer_tensors, H, Hkv, inner, device, head_dim=64):
-    """llama_decode_plan on e4m3 weights.  layer_tensors: per layer (input_norm fp32, wqkv uint8, sqkv fp32, wo uint8, so fp32,
-    post_norm fp32, wug uint8, sug fp32, wdown uint8, sdown fp32, kv_cache bf16), the pairs as quantize_rows_e4m3 returns them"""
+def llama_decode_step(plan, x, t0, cache_rows, rope, eps):
+    """every decoder layer at the new position against the KV caches of `plan`, one host call (the entry point is the plan's).
+    One-row plan: x fp32 [D], t0 an int -> a fresh fp32 [D].  R-row plan: x fp32 [R, D], t0 R host ints (negative = inactive
+    row) -> fp32 [R, D], the plan's own buffer, reused by the next step: an inactive row keeps what its last active step left
+    there (zeros before the first)"""
     lib = _lib.load()
-    arr = _w8_plan(layer_tensors, device)
-    nbytes = lib.kalle_llama_decode_ws_bytes_hd(H, Hkv, inner, head_dim)
-    check(min(nbytes, 0), "kalle_llama_decode_ws_bytes_hd")
-    ws = torch.empty(nbytes, device=device, dtype=torch.uint8)
-    return {"layers": arr, "n": len(layer_tensors), "keep": layer_tensors, "ws": ws, "H": H, "Hkv": Hkv, "inner": inner,
-            "head_dim": head_dim, "fmt": "e4m3"}
-
-
-def llama_decode_step_w8(plan, x, t0, cache_rows, rope, eps):
-    """llama_decode_step against a plan of llama_decode_plan_w8: kalle_llama_decode_step_w8"""
-    lib = _lib.load()
-    out = torch.empty_like(x)
-    check(lib.kalle_llama_decode_step_w8(ctypes.cast(plan["layers"], ctypes.c_void_p), plan["n"], _p(x), _p(out), plan["H"],
-                                         plan["Hkv"], plan["inner"], plan["head_dim"], eps, t0, cache_rows, _p(rope[0]),
-                                         _p(rope[1]), _p(plan["ws"]), _stream()), "kalle_llama_decode_step_w8")
-    return out
-
-
-def llama_decode_plan_rows_w8(layer_tensors, R, H, Hkv, inner, device, head_dim=64):
-    """llama_decode_plan_w8 for R rows: kv_cache of a layer is bf16 [R, cache_rows, 2*Hkv*head_dim]"""
-    lib = _lib.load()
-    arr = _w8_plan(layer_tensors, device, rows=R)
-    nbytes = lib.kalle_llama_decode_ws_bytes_rows(R, H, Hkv, inner, head_dim)
-    check(min(nbytes, 0), "kalle_llama_decode_ws_bytes_rows")
-    ws = torch.empty(nbytes, device=device, dtype=torch.uint8)
-    return {"layers": arr, "n": len(layer_tensors), "keep": layer_tensors, "ws": ws, "R": R, "H": H, "Hkv": Hkv, "inner": inner,
-            "head_dim": head_dim, "fmt": "e4m3"}
-
-
-def llama_decode_step_rows_w8(plan, x, t0, cache_rows, rope, eps):
-    """llama_decode_step_rows against a plan of llama_decode_plan_rows_w8: kalle_llama_decode_step_rows_w8"""
-    lib = _lib.load()
-    assert x.shape[0] == plan["R"] == len(t0) and x.is_contiguous() and x.dtype == torch.float32
-    out = plan.get("out")
-    if out is None:
-        out = plan["out"] = torch.zeros_like(x)
-    check(lib.kalle_llama_decode_step_rows_w8(ctypes.cast(plan["layers"], ctypes.c_void_p), plan["n"], _p(x), _p(out), plan["R"],
-                                              plan["H"], plan["Hkv"], plan["inner"], plan["head_dim"], eps,
-                                              ctypes.cast(_i32(t0), ctypes.c_void_p), cache_rows, _p(rope[0]), _p(rope[1]),
-                                              _p(plan["ws"]), _stream()), "kalle_llama_decode_step_rows_w8")
+    R = plan.get("R")
+    if R is None:
+        out, rows, pos = torch.empty_like(x), (), t0
+    else:
+        assert x.shape[0] == R == len(t0) and x.is_contiguous() and x.dtype == torch.float32
+        out = plan.get("out")
+        if out is None:
+            out = plan["out"] = torch.zeros_like(x)
+        rows, pos = (R,), ctypes.cast(_i32(t0), ctypes.c_void_p)
+    check(getattr(lib, plan["step"])(ctypes.cast(plan["layers"], ctypes.c_void_p), plan["n"], _p(x), _p(out), *rows, plan["H"],
+                                     plan["Hkv"], plan["inner"], plan["head_dim"], eps, pos, cache_rows, _p(rope[0]),
+                                     _p(rope[1]), _p(plan["ws"]), _stream()), plan["step"])
     return out
 
 

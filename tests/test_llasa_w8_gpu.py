@@ -127,8 +127,8 @@ def test_module_step_is_the_ops_step_on_the_ops_quantiser(dev, tmp_path, hd):
         kvs = [k.clone() for k in cache["kv"]]
         got = model.forward_cached(x[:, 5:].contiguous(), cache)
         ts, p = tensors(kvs)
-        plan = ops.llama_decode_plan_w8(ts, p.H, p.Hkv, model.cfg["intermediate_size"], dev, head_dim=hd)
-        want = model.norm(ops.llama_decode_step_w8(plan, x[0, 5].float().contiguous(), 5, 16, cache["rope"], p.eps).view(1, 1, D))
+        plan = ops.llama_decode_plan(ts, p.H, p.Hkv, model.cfg["intermediate_size"], dev, head_dim=hd)
+        want = model.norm(ops.llama_decode_step(plan, x[0, 5].float().contiguous(), 5, 16, cache["rope"], p.eps).view(1, 1, D))
         assert torch.equal(got, want)
         for a, b in zip(cache["kv"], kvs):
             assert torch.equal(a, b) and torch.isfinite(a[5]).all() and a[5].abs().sum() > 0
@@ -140,8 +140,8 @@ def test_module_step_is_the_ops_step_on_the_ops_quantiser(dev, tmp_path, hd):
         xb = torch.randn(3, 1, D, device=dev)
         got = model.forward_cached_batch(xb, bc, active=[True, False, True])
         ts, p = tensors(kvs)
-        plan = ops.llama_decode_plan_rows_w8(ts, 3, p.H, p.Hkv, model.cfg["intermediate_size"], dev, head_dim=hd)
-        want = model.norm(ops.llama_decode_step_rows_w8(plan, xb.view(3, D).float().contiguous(), [5, -1, 3], 16, bc["rope"], p.eps).view(3, 1, D))
+        plan = ops.llama_decode_plan(ts, p.H, p.Hkv, model.cfg["intermediate_size"], dev, head_dim=hd, rows=3)
+        want = model.norm(ops.llama_decode_step(plan, xb.view(3, D).float().contiguous(), [5, -1, 3], 16, bc["rope"], p.eps).view(3, 1, D))
         assert torch.equal(got, want)
         for a, b in zip(bc["kv"], kvs):
             assert torch.equal(a, b)
