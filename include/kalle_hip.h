@@ -359,8 +359,11 @@ int kalle_attention_bwd(const void* q, int64_t ldq, int q_off, const void* k, in
  * transformer.py:730: the DiT's rot is 32 at dh 32 - the whole head - and 64 at dh 128; rot 128 at dh 128 is a Llama decoder
  * with 128-wide heads, `AutoModelForCausalLM.from_pretrained(config['llm_model_name_or_path'])` at model_sigmaVAE.py:17-29 with a
  * Llama-3.2-3B / 3.1-8B checkpoint: tables [Npos][64]).
- * Anything else (head_dim not in {32, 64, 128}, rot > head_dim) returns KALLE_ERR_ARG.  head_dim 64 is exactly
- * kalle_attention_fwd / _bwd (which forward here); at 32 and 128 the backward is the two-pass kernel pair at every shape. */
+ * Anything else returns KALLE_ERR_ARG: a head dim or a rot without an instantiation (attn_head_dim_exists / attn_rot_exists in
+ * csrc/attention.hip: head_dim not in {32, 64, 128}, rot not in {0, 32, 64, 128} or > head_dim), the null, size, alignment and
+ * table checks of plan_attention there, causal with Nk < Nq.  head_dim 64 is exactly kalle_attention_fwd / _bwd (which forward
+ * here); which kernel family a shape gets is the list of predicates next to attn_fold_tail in csrc/attention.hip, reported by
+ * kalle_attn_last_plan and, with no device, by the _plan queries below. */
 int kalle_attention_fwd_hd(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off,
                            const void* v, int64_t ldv, int v_off, void* out, int64_t ldo, float* lse,
                            const float* rope_cos, const float* rope_sin, int rot, const uint8_t* key_mask, int causal,
@@ -373,13 +376,15 @@ int kalle_attention_bwd_hd(const void* q, int64_t ldq, int q_off, const void* k,
 /* Decoding against a KV cache: ONE query per batch row, the LAST position (rotary position Nk - 1, sees every key), against Nk
  * cached keys (model_sigmaVAE.py:122-146 re-runs `self.base_model.model(inputs_embeds=...)` over the prefix for every frame; with a
  * cache only this row is new).  q: [B][ldq], out: [B][ldo], lse: [B][H] or NULL, k / v / key_mask / tables as above.
- *   head_dim 64:  exactly kalle_attention_fwd with causal != 0 and Nq == 1 (attn_decode_kernel<rot>, rot in {0, 32, 64}), bit for bit
+ * It is kalle_attention_fwd_hd with causal = 1 and Nq = 1, and one family more (attn_fwd_decode128 in csrc/attention.hip):
+ *   head_dim 64:  exactly that call, bit for bit (attn_decode_kernel<rot>, rot in {0, 32, 64})
  *   head_dim 128: rot = 128 only (attn_decode128_kernel: vector-ALU scoring with two lanes per key, block softmax over the scores
  *                 in LDS, P V with 16 lanes per key row; bf16 rounding of the rotated q / k and of the probabilities as in the tiled
  *                 kernel, so the two agree to the rounding of fp32 sums)
- *   Nk > 15360 (the scores no longer fit in LDS): the tiled kernel of kalle_attention_fwd_hd at either head dim.
- * Anything else - head_dim 32 or any other, at head_dim 128 a rot other than 128, and whatever kalle_attention_fwd_hd refuses -
- * returns KALLE_ERR_ARG and launches nothing. */
+ *   Nk > KALLE_ATTN_DECODE_MAX_KEYS (the scores no longer fit in LDS): the tiled kernel of kalle_attention_fwd_hd at either head dim.
+ * Anything else - head_dim 32 or any other, at head_dim 128 a rot other than 128 (at every Nk), and whatever
+ * kalle_attention_fwd_hd refuses - returns KALLE_ERR_ARG and launches nothing. */
+#define KALLE_ATTN_DECODE_MAX_KEYS 15360      /* keys whose fp32 scores the single-query kernels hold in LDS (60 KiB) */
 int kalle_attention_decode_hd(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off,
                               const void* v, int64_t ldv, int v_off, void* out, int64_t ldo, float* lse,
                               const float* rope_cos, const float* rope_sin, int rot, const uint8_t* key_mask,
@@ -392,9 +397,10 @@ int kalle_attention_decode_hd(const void* q, int64_t ldq, int q_off, const void*
  * never read.  The kernels are the per-row launch forms of attn_decode_kernel<rot> (head_dim 64, rot 64 or 0) and
  * attn_decode128_kernel<128> (head_dim 128, rot 128): the same statements, so the same arithmetic and rounding points; the LDS
  * score array is sized by max(nk).
- * KALLE_ERR_ARG, nothing launched: R outside 1 .. KALLE_DECODE_MAX_ROWS, max(nk) > 15360 (there is no tiled fallback with per-row
- * lengths), kv_row_stride not a multiple of 8, rot 32, and whatever kalle_attention_decode_hd refuses.  Every row inactive:
- * KALLE_OK, nothing launched (plan word 0). */
+ * KALLE_ERR_ARG, nothing launched: R outside 1 .. KALLE_DECODE_MAX_ROWS, max(nk) > KALLE_ATTN_DECODE_MAX_KEYS (there is no tiled
+ * fallback with per-row lengths), kv_row_stride negative or not a multiple of 8, rot 32 (attn_rot_exists), and whatever
+ * kalle_attention_decode_hd refuses at Nk = max(max(nk), 1).  Every row inactive: KALLE_OK, nothing launched (plan word 0) -
+ * checked like any other call first. */
 #define KALLE_DECODE_MAX_ROWS 16
 int kalle_attention_decode_rows(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off,
                                 const void* v, int64_t ldv, int v_off, int64_t kv_row_stride, void* out, int64_t ldo,
@@ -402,18 +408,47 @@ int kalle_attention_decode_rows(const void* q, int64_t ldq, int q_off, const voi
                                 int R, int H, int Hkv, int head_dim, void* stream);
 /* which kernel family the calling thread's most recent kalle_attention_fwd / _bwd (_hd) / kalle_attention_decode_hd /
  * kalle_attention_decode_rows launched; 0 when that call returned before launching anything.
- *   bits 0-3   family: 1 fwd_tiled (attn_fwd_kernel), 2 fwd_decode (attn_decode_kernel: head dim 64, Nq == 1, Nk <= 15360),
- *              3 bwd_two_pass (attn_bwd_kernel, dQ + delta then dK / dV), 4 bwd_fused (attn_bwd_fused_kernel: head dim 64, not
- *              causal, H == Hkv, Nq, Nk <= 128), 5 bwd_fused_gqa (attn_bwd_fused_gqa_kernel: head dim 64, not causal, rot 0,
- *              Nq <= 128, Nk - 128 <= min(16, 128 - Nq)), 6 fwd_decode_128 (attn_decode128_kernel: kalle_attention_decode_hd at
- *              head dim 128, Nk <= 15360; a forward family: bit 4 is 0), 7 fwd_decode_rows (attn_decode_rows_kernel /
- *              attn_decode128_rows_kernel: kalle_attention_decode_rows; a forward family, head dim and ROT in their fields)
+ *   bits 0-3   family; the condition of each is ONE predicate in csrc/attention.hip (next to attn_fold_tail), named here:
+ *              1 fwd_tiled (attn_fwd_kernel: every forward that is neither 2 nor 6), 2 fwd_decode (attn_decode_kernel;
+ *              attn_fwd_decode: head dim 64, Nq == 1, Nk <= KALLE_ATTN_DECODE_MAX_KEYS, causal or not), 3 bwd_two_pass
+ *              (attn_bwd_kernel, dQ + delta then dK / dV: every backward that is neither 4 nor 5, so all of head dims 32 and 128),
+ *              4 bwd_fused (attn_bwd_fused_kernel; attn_bwd_fused: head dim 64, not causal, H == Hkv, Nq, Nk <= 128), 5 bwd_fused_gqa
+ *              (attn_bwd_fused_gqa_kernel; attn_bwd_fused_gqa, asked after 4: head dim 64, not causal, rot 0, Nq <= 128,
+ *              max(Nk - 128, 0) <= min(16, 128 - Nq)), 6 fwd_decode_128 (attn_decode128_kernel; attn_fwd_decode128:
+ *              kalle_attention_decode_hd at head dim 128, Nk <= KALLE_ATTN_DECODE_MAX_KEYS; a forward family: bit 4 is 0),
+ *              7 fwd_decode_rows (attn_decode_rows_kernel / attn_decode128_rows_kernel: kalle_attention_decode_rows; a forward
+ *              family, head dim and ROT in their fields)
  *   bit 4      direction: 0 forward, 1 backward
  *   bits 8-15  head dim (32 / 64 / 128)
  *   bit 16     family 1: the keys 128 .. Nk - 1 were folded into the first block (Nk in (128, 160], rot 0, not causal)
  *   bits 17-24 families 2, 6 and 7: the ROT instantiation (0 / 32 / 64; 128 for family 6 and for 7 at head dim 128, which is why the field has 8 bits - every
  *              word of families 1-5 keeps the value it had with a 7-bit field) */
 int kalle_attn_last_plan(void);
+/* The planner of the four entry points as pure host queries, one per entry point: its arguments without `stream`, then `plan`.
+ * Pointers are tested for null and never read (nk is: a host array by contract); the same checks and return codes as the
+ * entry point.  On KALLE_OK plan[0 .. 11] =
+ *   [0] the word kalle_attn_last_plan would hold after the call   [1] the number of launches: 0 (kalle_attention_decode_rows with
+ *   every row inactive; word 0), 1, or 2 (family 3: dQ + delta, then dK / dV)
+ *   [2 .. 6] the first launch: grid x, y, z, block threads, dynamic LDS bytes   [7 .. 11] the second likewise; 0 where there is none
+ * otherwise plan is left as found (a NULL plan is KALLE_ERR_ARG).  They launch nothing, need no device and do not change
+ * kalle_attn_last_plan. */
+int kalle_attention_fwd_plan(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off,
+                             const void* v, int64_t ldv, int v_off, void* out, int64_t ldo, float* lse,
+                             const float* rope_cos, const float* rope_sin, int rot, const uint8_t* key_mask, int causal,
+                             int B, int H, int Hkv, int Nq, int Nk, int head_dim, int* plan);
+int kalle_attention_bwd_plan(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off,
+                             const void* v, int64_t ldv, int v_off, const void* out, const void* dout, int64_t ldo,
+                             const float* lse, float* delta, void* dq, void* dk, void* dv,
+                             const float* rope_cos, const float* rope_sin, int rot, const uint8_t* key_mask, int causal,
+                             int B, int H, int Hkv, int Nq, int Nk, int head_dim, int* plan);
+int kalle_attention_decode_plan(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off,
+                                const void* v, int64_t ldv, int v_off, void* out, int64_t ldo, float* lse,
+                                const float* rope_cos, const float* rope_sin, int rot, const uint8_t* key_mask,
+                                int B, int H, int Hkv, int Nk, int head_dim, int* plan);
+int kalle_attention_decode_rows_plan(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off,
+                                     const void* v, int64_t ldv, int v_off, int64_t kv_row_stride, void* out, int64_t ldo,
+                                     float* lse, const float* rope_cos, const float* rope_sin, int rot, const int32_t* nk,
+                                     int R, int H, int Hkv, int head_dim, int* plan);
 
 /* ------------------------------------------------------------------------------------------------
  * Optimizer: fused Adam / AdamW over a flat fp32 master buffer, also emitting the bf16 compute copy.
@@ -629,7 +664,7 @@ int kalle_gemm_rows_fused(const void* x, int64_t ldx, int prologue, const float*
  * not its out row.  kv_cache of a layer: bf16 [R][cache_rows][2*Hkv*head_dim]; only row t0[r] of sequence r is written.
  * rope tables: [>= max(t0)+1][head_dim/2].  Per layer (8 launches): RMSNorm pre-pass -> q|k|v skinny GEMM (k|v into the caches)
  * -> kalle_attention_decode_rows (nk = t0 + 1) -> o_proj + residual -> RMSNorm pre-pass -> up|gate -> SwiGLU pre-pass -> down +
- * residual.  Limits: those of the _hd step, 1 <= R <= 16, t0[r] < cache_rows, max(t0) < 15360; anything else returns
+ * residual.  Limits: those of the _hd step, 1 <= R <= 16, t0[r] < cache_rows, max(t0) < KALLE_ATTN_DECODE_MAX_KEYS; anything else returns
  * KALLE_ERR_ARG before the first launch and leaves no attention plan.  Every launch is checked where it is made.  Every row
  * inactive: KALLE_OK, nothing launched.
  * Workspace (kalle_llama_decode_ws_bytes_rows bytes, 64-byte aligned), the regions of the one-row step, each [R][...] row-major,

@@ -20,6 +20,9 @@
 #include "common.h"
 #include "../../include/kalle_hip.h"
 
+#include <cstddef>
+#include <cstring>
+
 namespace {
 
 // Per-head-dim constants.  STRIDE: bytes per LDS row, DH bf16 + 32 B pad - the pad keeps both the ds_read_b128 row fragments
@@ -276,6 +279,33 @@ struct AttnParams {
 // word the host reports
 __host__ __device__ __forceinline__ bool attn_fold_tail(const AttnParams& p) {
     return !p.causal && p.rot == 0 && p.Nk > 128 && p.Nk <= 160;
+}
+// ---- the dispatch rule (host): every family's condition, once, in the order plan_attention (end of file) asks them; the
+// families and their numbers are those of kalle_attn_last_plan (kalle_hip.h)
+enum AttnEntry { ENTRY_FWD, ENTRY_BWD, ENTRY_DECODE, ENTRY_ROWS };   // kalle_attention_fwd_hd, _bwd_hd, _decode_hd, _decode_rows
+enum { PLAN_FWD_TILED = 1, PLAN_FWD_DECODE = 2, PLAN_BWD_TWO_PASS = 3, PLAN_BWD_FUSED = 4, PLAN_BWD_FUSED_GQA = 5,
+       PLAN_FWD_DECODE_128 = 6, PLAN_FWD_DECODE_ROWS = 7 };
+// the single-query kernels keep every key's score in LDS (4 B each, 60 KiB): past it a one-row call is tiled, a rows call refused
+inline bool attn_decode_fits(int Nk) { return Nk <= KALLE_ATTN_DECODE_MAX_KEYS; }
+inline bool attn_head_dim_exists(AttnEntry e, int dh) { return dh == 64 || dh == 128 || (dh == 32 && e <= ENTRY_BWD); }
+// ROT instantiations: the tile kernels and attn_decode_kernel up to the head dim; kalle_attention_decode_hd at head dim 128 asks
+// for attn_decode128_kernel<128> at every Nk; the rows kernels exist at 0 and 64 (head dim 64) and 128 (head dim 128)
+inline bool attn_rot_exists(AttnEntry e, int dh, int rot) {
+    if (rot != 0 && rot != 32 && rot != 64 && rot != 128) return false;
+    if (e == ENTRY_ROWS) return dh == 128 ? rot == 128 : rot == 0 || rot == 64;
+    return e == ENTRY_DECODE && dh == 128 ? rot == 128 : rot <= dh;
+}
+// attn_decode_kernel: one query at head dim 64 (kalle_attention_decode_hd is that call with causal = 1)
+inline bool attn_fwd_decode(const AttnParams& p, int dh) { return dh == 64 && p.Nq == 1 && attn_decode_fits(p.Nk); }
+// attn_decode128_kernel: kalle_attention_decode_hd alone (kalle_attention_fwd_hd stays tiled at head dim 128 and Nq == 1)
+inline bool attn_fwd_decode128(AttnEntry e, const AttnParams& p, int dh) { return e == ENTRY_DECODE && dh == 128 && attn_decode_fits(p.Nk); }
+// one block of queries and keys, one kv head per query head (the DiT's self-attention): everything in one kernel
+inline bool attn_bwd_fused(const AttnParams& p, int dh) { return dh == 64 && !p.causal && p.Nq <= 128 && p.Nk <= 128 && p.H == p.Hkv; }
+// the DiT's cross-attention: several query heads per kv head and / or a few keys beyond one block (they take query-row slots of
+// the block: tail <= min(16, 128 - Nq)), no rotary
+inline bool attn_bwd_fused_gqa(const AttnParams& p, int dh) {
+    const int tail = p.Nk > 128 ? p.Nk - 128 : 0;
+    return dh == 64 && !p.causal && p.rot == 0 && p.Nq <= 128 && tail <= 16 && tail <= 128 - p.Nq;
 }
 __device__ __forceinline__ void attn_stamp(const AttnParams& p, int tid, int idx) {
     if (p.stamps && tid == 0)
@@ -1331,16 +1361,6 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_fused_gqa_kernel(AttnParams p
     }
 }
 
-bool check_common(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off, const void* v,
-                  int64_t ldv, int v_off, int64_t ldo, int rot, int B, int H, int Hkv, int Nq, int Nk) {
-    if (!q || !k || !v || B <= 0 || H <= 0 || Hkv <= 0 || Nq <= 0 || Nk <= 0) return false;
-    if (H % Hkv) return false;
-    if ((ldq & 7) || (ldk & 7) || (ldv & 7) || (ldo & 7) || (q_off & 7) || (k_off & 7) || (v_off & 7)) return false;
-    if (rot != 0 && rot != 32 && rot != 64 && rot != 128) return false;     // (rot <= head dim: check_head_dim)
-    if (H > 65535 || B > 65535) return false;
-    return true;
-}
-
 // ---- single-query attention: decoding against a KV cache (Nq == 1) -------------------------------------------
 // The tiled kernel would spend a 128-query MFMA tile on one query.  Here a workgroup owns one (head, batch): every
 // thread scores one key at a time on the vector ALUs (64-dim dot against the rotated query kept in LDS, rotary applied
@@ -1604,7 +1624,7 @@ __global__ __launch_bounds__(256) void attn_decode_rows_kernel(AttnRowsParams rp
 
 // ---- single-query attention at head dim 128 (Llama decoders with 128-wide heads, rotary over the whole head) ------------------
 // Same shape as attn_decode_kernel: a workgroup per (head, batch), scores on the vector ALUs, block softmax over the scores in
-// LDS (Nk * 4 bytes: the same 15360-key ceiling), then P.V; bf16 rounding at the same points as the tiled kernel (rotated q,
+// LDS (Nk * 4 bytes: the same ceiling, attn_decode_fits), then P.V; bf16 rounding at the same points as the tiled kernel (rotated q,
 // rotated k, probabilities).  What differs is who owns a key.  A thread per key would hold 128 fp32 key values + 128 of q through
 // the rotary and the dot product: past the 256-VGPR ceiling once addresses and the table values are counted, so it spills.  Here
 // TWO adjacent lanes share a key and the workgroup scores DECODE128_KB = 128 keys per pass: lane i of the pair owns dims
@@ -1874,86 +1894,199 @@ __global__ __launch_bounds__(256) void attn_decode128_rows_kernel(AttnRowsParams
     attn_decode128_body<ROT>(rp.p, b, Nk, Nk - 1, rp.p.k + b * rp.kv_row_stride, rp.p.v + b * rp.kv_row_stride);
 }
 
+// ================================================================================================ host: plan, launch, query
 // kalle_attn_last_plan (encoding: include/kalle_hip.h)
 thread_local int g_attn_plan = 0;
-enum { PLAN_FWD_TILED = 1, PLAN_FWD_DECODE = 2, PLAN_BWD_TWO_PASS = 3, PLAN_BWD_FUSED = 4, PLAN_BWD_FUSED_GQA = 5,
-       PLAN_FWD_DECODE_128 = 6, PLAN_FWD_DECODE_ROWS = 7 };
+inline void set_attn_plan(int plan) { g_attn_plan = plan; }
 constexpr int attn_plan(int family, int head_dim, bool fold_tail = false, int decode_rot = 0) {
     return family | (family >= PLAN_BWD_TWO_PASS && family <= PLAN_BWD_FUSED_GQA ? 1 << 4 : 0) | head_dim << 8 |
            (fold_tail ? 1 << 16 : 0) | decode_rot << 17;
+}
+unsigned long long* g_attn_stamps = nullptr;      // diagnostics only
+
+// the arguments of an entry point as given (kalle_hip.h); decode and rows have no causal / Nq (the planner sets 1 / 1), rows
+// has B = R and no Nk / key_mask
+struct AttnArgs {
+    const void* q; int64_t ldq; int q_off; const void* k; int64_t ldk; int k_off; const void* v; int64_t ldv; int v_off;
+    const void* out; int64_t ldo; const float* lse; const float* cosT; const float* sinT; int rot; const uint8_t* mask;
+    int causal, B, H, Hkv, Nq, Nk, head_dim;
+    const void* dout; float* delta; void* dq; void* dk; void* dv;      // backward
+    int64_t kv_row_stride; const int32_t* nk;                          // rows
+};
+// what a call launches: plan_attention fills it from the arguments alone, launch_attention executes it, the queries report it
+struct AttnLaunch { int grid[3], block, lds; };
+struct AttnPlan {       // (word, n, l: the twelve ints a query hands out, in that order)
+    int word;           // kalle_attn_last_plan after the call
+    int n;              // launches: 0 (every row of a rows call inactive), 1, or 2 (two-pass backward: dQ + delta, then dK / dV)
+    AttnLaunch l[2];
+    int kernel;         // ATTN_KERNEL(family, head dim | ROT): the case of launch_attention's switch
+    bool allow_lds;     // the tile kernels: kalle_allow_lds before the launch (the single-query kernels stay below 64 KiB)
+};
+// the tile kernels are instantiated per head dim, the single-query kernels per ROT
+constexpr int ATTN_KERNEL(int family, int dh_or_rot) { return family << 8 | dh_or_rot; }
+
+// dynamic LDS of the tile kernels, from the constants their templates use
+constexpr int hd_tile(int dh) { return dh == 32 ? Hd<32>::TILE : dh == 64 ? Hd<64>::TILE : Hd<128>::TILE; }
+constexpr int lds_fwd_tiled(int dh) { return 3 * hd_tile(dh) + 160 * 4 + 2 * 32 * (hd_tile(dh) / 128); }   // Q | K | V, key bias [128 + 32], 2 x 32 tail rows
+constexpr int lds_bwd_two_pass(int dh) { return 2 * hd_tile(dh) + 256 * 4; }
+constexpr int LDS_BWD_FUSED = 4 * AT_TILE;
+
+// the one filler of the kernels' parameter block (a: after the planner's `causal = Nq = 1` for decode and rows)
+__forceinline__ void fill_params(const AttnArgs& a, AttnParams& p) {
+    p = AttnParams{};
+    p.q = static_cast<const bf16_t*>(a.q); p.ldq = a.ldq; p.q_off = a.q_off;
+    p.k = static_cast<const bf16_t*>(a.k); p.ldk = a.ldk; p.k_off = a.k_off;
+    p.v = static_cast<const bf16_t*>(a.v); p.ldv = a.ldv; p.v_off = a.v_off;
+    p.out = static_cast<bf16_t*>(const_cast<void*>(a.out)); p.ldo = a.ldo; p.lse = const_cast<float*>(a.lse);   // (the backward only reads them)
+    p.cosT = a.cosT; p.sinT = a.sinT; p.rot = a.rot; p.mask = a.mask;
+    p.B = a.B; p.H = a.H; p.Hkv = a.Hkv; p.Nq = a.Nq; p.Nk = a.Nk; p.causal = a.causal;
+    p.qpos = a.causal ? a.Nk - a.Nq : 0;
+    p.dout = static_cast<const bf16_t*>(a.dout); p.delta = a.delta;
+    p.dq = static_cast<bf16_t*>(a.dq); p.dk = static_cast<bf16_t*>(a.dk); p.dv = static_cast<bf16_t*>(a.dv);
+    p.stamps = g_attn_stamps;
+}
+
+__forceinline__ void set_launch(AttnPlan& g, int gx, int gy, int gz, int block, int lds) { g.l[g.n++] = AttnLaunch{{gx, gy, gz}, block, lds}; }
+
+// Pure: no HIP call, nothing global read but g_attn_stamps (fill_params), no pointer read but a.nk (a host array by contract).
+// Returns the entry point's return code; on KALLE_OK `rp` (rp.p alone but for rows) and `g` are what launch_attention needs.
+// (Inlined into the entry points, where the entry kind is a constant and the argument struct never exists in memory: as a
+// call it cost each of them 20 ns.)
+__forceinline__ int plan_attention(AttnEntry e, AttnArgs a, AttnRowsParams& rp, AttnPlan& g) {
+    g = AttnPlan{};
+    const bool bwd = e == ENTRY_BWD, rows = e == ENTRY_ROWS;
+    int max_nk = 0;
+    if (e == ENTRY_DECODE || rows) a.causal = a.Nq = 1;        // one query per row, at the last position
+    if (rows) {                                                 // B = R rows with their own key counts and caches
+        if (!a.nk || a.B < 1 || a.B > DECODE_MAX_ROWS) return KALLE_ERR_ARG;
+        for (int r = 0; r < a.B; ++r) max_nk = a.nk[r] > max_nk ? a.nk[r] : max_nk;
+        if (!attn_decode_fits(max_nk) || (a.kv_row_stride & 7) || a.kv_row_stride < 0) return KALLE_ERR_ARG;   // (no tiled fallback per row)
+        a.Nk = max_nk > 0 ? max_nk : 1;
+    }
+    if (!attn_head_dim_exists(e, a.head_dim) || !attn_rot_exists(e, a.head_dim, a.rot)) return KALLE_ERR_ARG;
+    if (!a.out || (bwd && (!a.dout || !a.lse || !a.delta || !a.dq || !a.dk || !a.dv))) return KALLE_ERR_ARG;
+    if (!a.q || !a.k || !a.v || a.B <= 0 || a.H <= 0 || a.Hkv <= 0 || a.Nq <= 0 || a.Nk <= 0) return KALLE_ERR_ARG;
+    if (a.H % a.Hkv || a.H > 65535 || a.B > 65535) return KALLE_ERR_ARG;
+    if ((a.ldq & 7) || (a.ldk & 7) || (a.ldv & 7) || (a.ldo & 7) || (a.q_off & 7) || (a.k_off & 7) || (a.v_off & 7)) return KALLE_ERR_ARG;
+    if (a.rot && (!a.cosT || !a.sinT)) return KALLE_ERR_ARG;
+    if (a.causal && a.Nk < a.Nq) return KALLE_ERR_ARG;
+    if (rows && max_nk <= 0) return KALLE_OK;                   // every row inactive: nothing to launch, word 0
+
+    AttnParams& p = rp.p;
+    fill_params(a, p);
+    const int dh = a.head_dim;
+    int family;
+    if (rows) family = PLAN_FWD_DECODE_ROWS;
+    else if (bwd) family = attn_bwd_fused(p, dh) ? PLAN_BWD_FUSED : attn_bwd_fused_gqa(p, dh) ? PLAN_BWD_FUSED_GQA : PLAN_BWD_TWO_PASS;
+    else if (attn_fwd_decode128(e, p, dh)) family = PLAN_FWD_DECODE_128;
+    else family = attn_fwd_decode(p, dh) ? PLAN_FWD_DECODE : PLAN_FWD_TILED;
+
+    switch (family) {
+    case PLAN_FWD_TILED: set_launch(g, (p.Nq + 127) / 128, p.H, p.B, 512, lds_fwd_tiled(dh)); break;
+    case PLAN_BWD_TWO_PASS:                                     // dQ first: it also produces delta, which the dK / dV kernel streams
+        set_launch(g, (p.Nq + 127) / 128, p.H, p.B, 512, lds_bwd_two_pass(dh));
+        set_launch(g, (p.Nk + 127) / 128, p.Hkv, p.B, 512, lds_bwd_two_pass(dh));
+        break;
+    case PLAN_BWD_FUSED: set_launch(g, 1, p.H, p.B, 512, LDS_BWD_FUSED); break;
+    case PLAN_BWD_FUSED_GQA: set_launch(g, 1, p.Hkv, p.B, 512, LDS_BWD_FUSED); break;
+    default:                                                    // the single-query kernels: a workgroup per (head, row), [Nk] fp32 scores
+        set_launch(g, p.H, p.B, 1, 256, a.Nk * 4);
+        if (family != PLAN_FWD_DECODE) p.stamps = nullptr;      // (as ever: attn_decode128_kernel and the rows kernels get none)
+    }
+    if (rows) {                                                 // the key counts travel per row: p.Nk / p.qpos / p.mask are not used
+        p.Nk = p.qpos = 0;
+        rp.kv_row_stride = a.kv_row_stride;
+        for (int r = 0; r < DECODE_MAX_ROWS; ++r) rp.nk[r] = r < a.B ? a.nk[r] : 0;
+    }
+    const bool single = family == PLAN_FWD_DECODE || family >= PLAN_FWD_DECODE_128;
+    g.allow_lds = !single;
+    g.kernel = ATTN_KERNEL(family, single ? a.rot : dh);
+    g.word = attn_plan(family, dh, family == PLAN_FWD_TILED && attn_fold_tail(p), single ? a.rot : 0);
+    return KALLE_OK;
+}
+
+// one launch of a plan; the "more than 64 KiB of LDS allowed" flag of a kernel lives here, once per kernel
+template <auto Kernel, class P>
+void launch_one(const AttnPlan& g, int i, hipStream_t st, const P& p) {
+    if (g.allow_lds) {
+        static std::atomic<uint64_t> lds_ok{0};
+        kalle_allow_lds(reinterpret_cast<const void*>(Kernel), g.l[i].lds, lds_ok);
+    }
+    KALLE_LAUNCH(Kernel, dim3(g.l[i].grid[0], g.l[i].grid[1], g.l[i].grid[2]), dim3(g.l[i].block), g.l[i].lds, st, p);
+}
+
+int launch_attention(const AttnPlan& g, const AttnRowsParams& rp, hipStream_t st) {
+    const AttnParams& p = rp.p;
+    if (g.n == 0) return KALLE_OK;
+    switch (g.kernel) {
+    case ATTN_KERNEL(PLAN_FWD_TILED, 32): launch_one<attn_fwd_kernel<1, 32>>(g, 0, st, p); break;
+    case ATTN_KERNEL(PLAN_FWD_TILED, 64): launch_one<attn_fwd_kernel<1, 64>>(g, 0, st, p); break;
+    case ATTN_KERNEL(PLAN_FWD_TILED, 128): launch_one<attn_fwd_kernel<1, 128>>(g, 0, st, p); break;
+    case ATTN_KERNEL(PLAN_FWD_DECODE, 0): launch_one<attn_decode_kernel<0>>(g, 0, st, p); break;
+    case ATTN_KERNEL(PLAN_FWD_DECODE, 32): launch_one<attn_decode_kernel<32>>(g, 0, st, p); break;
+    case ATTN_KERNEL(PLAN_FWD_DECODE, 64): launch_one<attn_decode_kernel<64>>(g, 0, st, p); break;
+    case ATTN_KERNEL(PLAN_FWD_DECODE_128, 128): launch_one<attn_decode128_kernel<128>>(g, 0, st, p); break;
+    case ATTN_KERNEL(PLAN_FWD_DECODE_ROWS, 0): launch_one<attn_decode_rows_kernel<0>>(g, 0, st, rp); break;
+    case ATTN_KERNEL(PLAN_FWD_DECODE_ROWS, 64): launch_one<attn_decode_rows_kernel<64>>(g, 0, st, rp); break;
+    case ATTN_KERNEL(PLAN_FWD_DECODE_ROWS, 128): launch_one<attn_decode128_rows_kernel<128>>(g, 0, st, rp); break;
+    case ATTN_KERNEL(PLAN_BWD_TWO_PASS, 32):
+        launch_one<attn_bwd_kernel<false, 1, 32>>(g, 0, st, p); launch_one<attn_bwd_kernel<true, 1, 32>>(g, 1, st, p); break;
+    case ATTN_KERNEL(PLAN_BWD_TWO_PASS, 64):
+        launch_one<attn_bwd_kernel<false, 1, 64>>(g, 0, st, p); launch_one<attn_bwd_kernel<true, 1, 64>>(g, 1, st, p); break;
+    case ATTN_KERNEL(PLAN_BWD_TWO_PASS, 128):
+        launch_one<attn_bwd_kernel<false, 1, 128>>(g, 0, st, p); launch_one<attn_bwd_kernel<true, 1, 128>>(g, 1, st, p); break;
+    case ATTN_KERNEL(PLAN_BWD_FUSED, 64): launch_one<attn_bwd_fused_kernel>(g, 0, st, p); break;
+    case ATTN_KERNEL(PLAN_BWD_FUSED_GQA, 64): launch_one<attn_bwd_fused_gqa_kernel>(g, 0, st, p); break;
+    default: return KALLE_ERR_UNSUPPORTED;                      // a plan without a kernel: not reachable from plan_attention
+    }
+    set_attn_plan(g.word);
+    return kalle_check_launch();
+}
+
+// an entry point: reset the plan word, plan, return on refusal, launch
+__forceinline__ int attention_call(AttnEntry e, const AttnArgs& a, void* stream) {
+    set_attn_plan(0);
+    AttnRowsParams rp;
+    AttnPlan g;
+    const int rc = plan_attention(e, a, rp, g);
+    return rc != KALLE_OK ? rc : launch_attention(g, rp, static_cast<hipStream_t>(stream));
+}
+// its host query (layout of `out`: kalle_hip.h)
+int attention_query(AttnEntry e, const AttnArgs& a, int* out) {
+    AttnRowsParams rp;
+    AttnPlan g;
+    const int rc = out ? plan_attention(e, a, rp, g) : KALLE_ERR_ARG;
+    static_assert(offsetof(AttnPlan, kernel) == 12 * sizeof(int), "word, n, 2 x (grid x, y, z, block, LDS)");
+    if (rc == KALLE_OK) memcpy(out, &g, 12 * sizeof(int));
+    return rc;
 }
 }  // namespace
 
 extern "C" int kalle_attn_last_plan(void) { return g_attn_plan; }
 // library-internal, as kalle_set_conv_plan: not part of the ABI, not exported
-extern "C" __attribute__((visibility("hidden"))) void kalle_set_attn_plan(int plan) { g_attn_plan = plan; }
-
-static unsigned long long* g_attn_stamps = nullptr;      // diagnostics only
+extern "C" __attribute__((visibility("hidden"))) void kalle_set_attn_plan(int plan) { set_attn_plan(plan); }
 extern "C" int kalle_attn_debug_stamps(void* buf) { g_attn_stamps = static_cast<unsigned long long*>(buf); return KALLE_OK; }
 
-// head dims other than 64 (DH 32 / 128): the tiled kernels, Nq == 1 included (kalle_attention_decode_hd is the way to the
-// single-query kernel at DH 128)
-template <int DH>
-static int attention_fwd_dh(const AttnParams& p, hipStream_t st) {
-    constexpr int lds = 3 * Hd<DH>::TILE + 160 * 4 + 2 * 32 * Hd<DH>::STRIDE;   // Q | K | V, key bias [128 + 32], tail tiles
-    static std::atomic<uint64_t> lds_ok{0};
-    kalle_allow_lds(reinterpret_cast<const void*>(attn_fwd_kernel<1, DH>), lds, lds_ok);
-    KALLE_LAUNCH((attn_fwd_kernel<1, DH>), dim3((p.Nq + 127) / 128, p.H, p.B), dim3(512), lds, st, p);
-    kalle_set_attn_plan(attn_plan(PLAN_FWD_TILED, DH, attn_fold_tail(p)));
-    return kalle_check_launch();
-}
-template <int DH>
-static int attention_bwd_dh(const AttnParams& p, hipStream_t st) {
-    constexpr int lds = 2 * Hd<DH>::TILE + 256 * 4;
-    static std::atomic<uint64_t> lds_ok_kv{0}, lds_ok_q{0};
-    kalle_allow_lds(reinterpret_cast<const void*>(attn_bwd_kernel<true, 1, DH>), lds, lds_ok_kv);
-    kalle_allow_lds(reinterpret_cast<const void*>(attn_bwd_kernel<false, 1, DH>), lds, lds_ok_q);
-    KALLE_LAUNCH((attn_bwd_kernel<false, 1, DH>), dim3((p.Nq + 127) / 128, p.H, p.B), dim3(512), lds, st, p);   // dQ + delta first
-    KALLE_LAUNCH((attn_bwd_kernel<true, 1, DH>), dim3((p.Nk + 127) / 128, p.Hkv, p.B), dim3(512), lds, st, p);
-    kalle_set_attn_plan(attn_plan(PLAN_BWD_TWO_PASS, DH));
-    return kalle_check_launch();
-}
-static bool check_head_dim(int head_dim, int rot) {
-    return (head_dim == 32 || head_dim == 64 || head_dim == 128) && rot <= head_dim;
-}
+#define FWD_ARGS {q, ldq, q_off, k, ldk, k_off, v, ldv, v_off, out, ldo, lse, rope_cos, rope_sin, rot, key_mask, causal, B, H, Hkv, Nq, Nk, head_dim}
+#define BWD_ARGS {q, ldq, q_off, k, ldk, k_off, v, ldv, v_off, out, ldo, lse, rope_cos, rope_sin, rot, key_mask, causal, B, H, Hkv, Nq, Nk, head_dim, \
+                  dout, delta, dq, dk, dv}
+// one query per batch row at the LAST position against Nk cached keys
+#define DECODE_ARGS {q, ldq, q_off, k, ldk, k_off, v, ldv, v_off, out, ldo, lse, rope_cos, rope_sin, rot, key_mask, 1, B, H, Hkv, 1, Nk, head_dim}
+// one query per row with per-row key counts and caches (batched generation)
+#define ROWS_ARGS {q, ldq, q_off, k, ldk, k_off, v, ldv, v_off, out, ldo, lse, rope_cos, rope_sin, rot, nullptr, 1, R, H, Hkv, 1, 0, head_dim, \
+                   nullptr, nullptr, nullptr, nullptr, nullptr, kv_row_stride, nk}
 
 extern "C" int kalle_attention_fwd_hd(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off,
                                       const void* v, int64_t ldv, int v_off, void* out, int64_t ldo, float* lse,
                                       const float* rope_cos, const float* rope_sin, int rot, const uint8_t* key_mask,
                                       int causal, int B, int H, int Hkv, int Nq, int Nk, int head_dim, void* stream) {
-    kalle_set_attn_plan(0);
-    if (!out || !check_common(q, ldq, q_off, k, ldk, k_off, v, ldv, v_off, ldo, rot, B, H, Hkv, Nq, Nk) ||
-        !check_head_dim(head_dim, rot))
-        return KALLE_ERR_ARG;
-    if (rot && (!rope_cos || !rope_sin)) return KALLE_ERR_ARG;
-    AttnParams p{};
-    p.q = static_cast<const bf16_t*>(q); p.ldq = ldq; p.q_off = q_off;
-    p.k = static_cast<const bf16_t*>(k); p.ldk = ldk; p.k_off = k_off;
-    p.v = static_cast<const bf16_t*>(v); p.ldv = ldv; p.v_off = v_off;
-    p.out = static_cast<bf16_t*>(out); p.ldo = ldo; p.lse = lse;
-    p.cosT = rope_cos; p.sinT = rope_sin; p.rot = rot; p.mask = key_mask;
-    p.B = B; p.H = H; p.Hkv = Hkv; p.Nq = Nq; p.Nk = Nk; p.causal = causal;
-    p.stamps = g_attn_stamps;
-    if (causal && Nk < Nq) return KALLE_ERR_ARG;
-    p.qpos = causal ? Nk - Nq : 0;
-    if (head_dim == 32) return attention_fwd_dh<32>(p, static_cast<hipStream_t>(stream));
-    if (head_dim == 128) return attention_fwd_dh<128>(p, static_cast<hipStream_t>(stream));
-    if (Nq == 1 && Nk <= 15360) {   // decoding against a KV cache: scores of all keys fit in LDS (60 KB)
-        const dim3 grid(H, B), block(256);
-        hipStream_t st = static_cast<hipStream_t>(stream);
-        if (rot == 64) KALLE_LAUNCH(attn_decode_kernel<64>, grid, block, (size_t)Nk * 4, st, p);
-        else if (rot == 32) KALLE_LAUNCH(attn_decode_kernel<32>, grid, block, (size_t)Nk * 4, st, p);
-        else KALLE_LAUNCH(attn_decode_kernel<0>, grid, block, (size_t)Nk * 4, st, p);
-        kalle_set_attn_plan(attn_plan(PLAN_FWD_DECODE, 64, false, rot));
-        return kalle_check_launch();
-    }
-    constexpr int lds = 3 * AT_TILE + 160 * 4 + 2 * 32 * AT_STRIDE;     // Q | K | V tiles, key bias [128 + 32], folded tail tiles
-    static std::atomic<uint64_t> lds_ok{0};
-    kalle_allow_lds(reinterpret_cast<const void*>(attn_fwd_kernel<1>), lds, lds_ok);
-    dim3 grid((Nq + 127) / 128, H, B), block(512);
-    KALLE_LAUNCH(attn_fwd_kernel<1>, grid, block, lds, static_cast<hipStream_t>(stream), p);
-    kalle_set_attn_plan(attn_plan(PLAN_FWD_TILED, 64, attn_fold_tail(p)));
-    return kalle_check_launch();
+    return attention_call(ENTRY_FWD, FWD_ARGS, stream);
+}
+extern "C" int kalle_attention_fwd_plan(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off,
+                                        const void* v, int64_t ldv, int v_off, void* out, int64_t ldo, float* lse,
+                                        const float* rope_cos, const float* rope_sin, int rot, const uint8_t* key_mask,
+                                        int causal, int B, int H, int Hkv, int Nq, int Nk, int head_dim, int* plan) {
+    return attention_query(ENTRY_FWD, FWD_ARGS, plan);
 }
 
 extern "C" int kalle_attention_bwd_hd(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off,
@@ -1961,118 +2094,40 @@ extern "C" int kalle_attention_bwd_hd(const void* q, int64_t ldq, int q_off, con
                                       int64_t ldo, const float* lse, float* delta, void* dq, void* dk, void* dv,
                                       const float* rope_cos, const float* rope_sin, int rot, const uint8_t* key_mask,
                                       int causal, int B, int H, int Hkv, int Nq, int Nk, int head_dim, void* stream) {
-    kalle_set_attn_plan(0);
-    if (!out || !dout || !lse || !delta || !dq || !dk || !dv ||
-        !check_common(q, ldq, q_off, k, ldk, k_off, v, ldv, v_off, ldo, rot, B, H, Hkv, Nq, Nk) ||
-        !check_head_dim(head_dim, rot))
-        return KALLE_ERR_ARG;
-    if (rot && (!rope_cos || !rope_sin)) return KALLE_ERR_ARG;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    AttnParams p{};
-    p.q = static_cast<const bf16_t*>(q); p.ldq = ldq; p.q_off = q_off;
-    p.k = static_cast<const bf16_t*>(k); p.ldk = ldk; p.k_off = k_off;
-    p.v = static_cast<const bf16_t*>(v); p.ldv = ldv; p.v_off = v_off;
-    p.out = static_cast<bf16_t*>(const_cast<void*>(out)); p.ldo = ldo; p.lse = const_cast<float*>(lse);   // (read only here)
-    p.cosT = rope_cos; p.sinT = rope_sin; p.rot = rot; p.mask = key_mask;
-    p.B = B; p.H = H; p.Hkv = Hkv; p.Nq = Nq; p.Nk = Nk; p.causal = causal;
-    if (causal && Nk < Nq) return KALLE_ERR_ARG;
-    p.qpos = causal ? Nk - Nq : 0;
-    p.dout = static_cast<const bf16_t*>(dout); p.delta = delta;
-    p.dq = static_cast<bf16_t*>(dq); p.dk = static_cast<bf16_t*>(dk); p.dv = static_cast<bf16_t*>(dv);
-    p.stamps = g_attn_stamps;
-    if (head_dim == 32) return attention_bwd_dh<32>(p, st);
-    if (head_dim == 128) return attention_bwd_dh<128>(p, st);
-
-    // one block of queries and keys, one kv head per query head (the DiT's self-attention): everything in one kernel
-    if (!causal && Nq <= 128 && Nk <= 128 && H == Hkv) {
-        constexpr int flds = 4 * AT_TILE;
-        static std::atomic<uint64_t> lds_ok_f{0};
-        kalle_allow_lds(reinterpret_cast<const void*>(attn_bwd_fused_kernel), flds, lds_ok_f);
-        KALLE_LAUNCH(attn_bwd_fused_kernel, dim3(1, H, B), dim3(512), flds, st, p);
-        kalle_set_attn_plan(attn_plan(PLAN_BWD_FUSED, 64));
-        return kalle_check_launch();
-    }
-    // cross-attention of the DiT: several query heads per kv head and / or a few keys beyond one block, no rotary
-    const int tail = Nk > 128 ? Nk - 128 : 0;
-    if (!causal && rot == 0 && Nq <= 128 && tail <= 16 && tail <= 128 - Nq) {
-        constexpr int flds = 4 * AT_TILE;
-        static std::atomic<uint64_t> lds_ok_g{0};
-        kalle_allow_lds(reinterpret_cast<const void*>(attn_bwd_fused_gqa_kernel), flds, lds_ok_g);
-        KALLE_LAUNCH(attn_bwd_fused_gqa_kernel, dim3(1, Hkv, B), dim3(512), flds, st, p);
-        kalle_set_attn_plan(attn_plan(PLAN_BWD_FUSED_GQA, 64));
-        return kalle_check_launch();
-    }
-    constexpr int lds = 2 * AT_TILE + 256 * 4;
-    static std::atomic<uint64_t> lds_ok_kv{0}, lds_ok_q{0};
-    kalle_allow_lds(reinterpret_cast<const void*>(attn_bwd_kernel<true, 1>), lds, lds_ok_kv);
-    kalle_allow_lds(reinterpret_cast<const void*>(attn_bwd_kernel<false, 1>), lds, lds_ok_q);
-    // dQ first: it also produces delta, which the dK/dV kernel streams
-    KALLE_LAUNCH((attn_bwd_kernel<false, 1>), dim3((Nq + 127) / 128, H, B), dim3(512), lds, st, p);
-    KALLE_LAUNCH((attn_bwd_kernel<true, 1>), dim3((Nk + 127) / 128, Hkv, B), dim3(512), lds, st, p);
-    kalle_set_attn_plan(attn_plan(PLAN_BWD_TWO_PASS, 64));
-    return kalle_check_launch();
+    return attention_call(ENTRY_BWD, BWD_ARGS, stream);
+}
+extern "C" int kalle_attention_bwd_plan(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off,
+                                        const void* v, int64_t ldv, int v_off, const void* out, const void* dout,
+                                        int64_t ldo, const float* lse, float* delta, void* dq, void* dk, void* dv,
+                                        const float* rope_cos, const float* rope_sin, int rot, const uint8_t* key_mask,
+                                        int causal, int B, int H, int Hkv, int Nq, int Nk, int head_dim, int* plan) {
+    return attention_query(ENTRY_BWD, BWD_ARGS, plan);
 }
 
-// one query per batch row at the LAST position against Nk cached keys: the single-query kernels by head dim
 extern "C" int kalle_attention_decode_hd(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off,
                                          const void* v, int64_t ldv, int v_off, void* out, int64_t ldo, float* lse,
                                          const float* rope_cos, const float* rope_sin, int rot, const uint8_t* key_mask,
                                          int B, int H, int Hkv, int Nk, int head_dim, void* stream) {
-    kalle_set_attn_plan(0);
-    if (head_dim != 64 && head_dim != 128) return KALLE_ERR_ARG;
-    if (head_dim == 128 && rot != 128) return KALLE_ERR_ARG;              // attn_decode128_kernel<128> is the one instantiation
-    // head dim 64: attn_decode_kernel<ROT> as kalle_attention_fwd launches it at Nq == 1; beyond the LDS score array: tiled
-    if (head_dim == 64 || Nk > 15360)
-        return kalle_attention_fwd_hd(q, ldq, q_off, k, ldk, k_off, v, ldv, v_off, out, ldo, lse, rope_cos, rope_sin, rot, key_mask,
-                                      1, B, H, Hkv, 1, Nk, head_dim, stream);
-    if (!out || !check_common(q, ldq, q_off, k, ldk, k_off, v, ldv, v_off, ldo, rot, B, H, Hkv, 1, Nk)) return KALLE_ERR_ARG;
-    if (!rope_cos || !rope_sin) return KALLE_ERR_ARG;
-    AttnParams p{};
-    p.q = static_cast<const bf16_t*>(q); p.ldq = ldq; p.q_off = q_off;
-    p.k = static_cast<const bf16_t*>(k); p.ldk = ldk; p.k_off = k_off;
-    p.v = static_cast<const bf16_t*>(v); p.ldv = ldv; p.v_off = v_off;
-    p.out = static_cast<bf16_t*>(out); p.ldo = ldo; p.lse = lse;
-    p.cosT = rope_cos; p.sinT = rope_sin; p.rot = rot; p.mask = key_mask;
-    p.B = B; p.H = H; p.Hkv = Hkv; p.Nq = 1; p.Nk = Nk; p.causal = 1;
-    p.qpos = Nk - 1;
-    KALLE_LAUNCH(attn_decode128_kernel<128>, dim3(H, B), dim3(256), (size_t)Nk * 4, static_cast<hipStream_t>(stream), p);
-    kalle_set_attn_plan(attn_plan(PLAN_FWD_DECODE_128, 128, false, 128));
-    return kalle_check_launch();
+    return attention_call(ENTRY_DECODE, DECODE_ARGS, stream);
+}
+extern "C" int kalle_attention_decode_plan(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off,
+                                           const void* v, int64_t ldv, int v_off, void* out, int64_t ldo, float* lse,
+                                           const float* rope_cos, const float* rope_sin, int rot, const uint8_t* key_mask,
+                                           int B, int H, int Hkv, int Nk, int head_dim, int* plan) {
+    return attention_query(ENTRY_DECODE, DECODE_ARGS, plan);
 }
 
-// one query per row with per-row key counts and caches (batched generation): the per-row launch forms of the two kernels above
 extern "C" int kalle_attention_decode_rows(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off,
                                            const void* v, int64_t ldv, int v_off, int64_t kv_row_stride, void* out, int64_t ldo,
                                            float* lse, const float* rope_cos, const float* rope_sin, int rot, const int32_t* nk,
                                            int R, int H, int Hkv, int head_dim, void* stream) {
-    kalle_set_attn_plan(0);
-    if (!nk || R < 1 || R > DECODE_MAX_ROWS) return KALLE_ERR_ARG;
-    if (head_dim != 64 && head_dim != 128) return KALLE_ERR_ARG;
-    if (head_dim == 128 ? rot != 128 : (rot != 0 && rot != 64)) return KALLE_ERR_ARG;       // the instantiations below
-    int max_nk = 0;
-    for (int r = 0; r < R; ++r) max_nk = nk[r] > max_nk ? nk[r] : max_nk;
-    if (max_nk > 15360 || (kv_row_stride & 7) || kv_row_stride < 0) return KALLE_ERR_ARG;  // (scores in LDS; no tiled fallback per row)
-    if (!out || !check_common(q, ldq, q_off, k, ldk, k_off, v, ldv, v_off, ldo, rot, R, H, Hkv, 1, max_nk > 0 ? max_nk : 1))
-        return KALLE_ERR_ARG;
-    if (rot && (!rope_cos || !rope_sin)) return KALLE_ERR_ARG;
-    if (max_nk <= 0) return KALLE_OK;                                                       // every row inactive: nothing to launch
-    AttnRowsParams rp{};
-    AttnParams& p = rp.p;
-    p.q = static_cast<const bf16_t*>(q); p.ldq = ldq; p.q_off = q_off;
-    p.k = static_cast<const bf16_t*>(k); p.ldk = ldk; p.k_off = k_off;
-    p.v = static_cast<const bf16_t*>(v); p.ldv = ldv; p.v_off = v_off;
-    p.out = static_cast<bf16_t*>(out); p.ldo = ldo; p.lse = lse;
-    p.cosT = rope_cos; p.sinT = rope_sin; p.rot = rot;
-    p.B = R; p.H = H; p.Hkv = Hkv; p.Nq = 1; p.causal = 1;
-    rp.kv_row_stride = kv_row_stride;
-    for (int r = 0; r < R; ++r) rp.nk[r] = nk[r];
-    const dim3 grid(H, R), block(256);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (head_dim == 128) KALLE_LAUNCH(attn_decode128_rows_kernel<128>, grid, block, (size_t)max_nk * 4, st, rp);
-    else if (rot == 64) KALLE_LAUNCH(attn_decode_rows_kernel<64>, grid, block, (size_t)max_nk * 4, st, rp);
-    else KALLE_LAUNCH(attn_decode_rows_kernel<0>, grid, block, (size_t)max_nk * 4, st, rp);
-    kalle_set_attn_plan(attn_plan(PLAN_FWD_DECODE_ROWS, head_dim, false, rot));
-    return kalle_check_launch();
+    return attention_call(ENTRY_ROWS, ROWS_ARGS, stream);
+}
+extern "C" int kalle_attention_decode_rows_plan(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off,
+                                                const void* v, int64_t ldv, int v_off, int64_t kv_row_stride, void* out, int64_t ldo,
+                                                float* lse, const float* rope_cos, const float* rope_sin, int rot, const int32_t* nk,
+                                                int R, int H, int Hkv, int head_dim, int* plan) {
+    return attention_query(ENTRY_ROWS, ROWS_ARGS, plan);
 }
 
 // the head-dim-64 entry points of the C ABI (bound by signature from ctypes): unchanged, forwarders

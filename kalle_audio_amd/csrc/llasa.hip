@@ -928,8 +928,8 @@ int decode_step(const kalle_llama_layer* lb, const kalle_llama_layer_w8* l8, int
     a.R = R;
     int32_t nk[KALLE_DECODE_MAX_ROWS];
     for (int r = 0; r < R; ++r) {
-        // (batched: the attention's LDS score array holds nk <= 15360 keys; the one-row attention falls back to the tiled kernel)
-        if (t0[r] >= cache_rows || (batched ? t0[r] >= 15360 : t0[r] < 0)) return KALLE_ERR_ARG;
+        // (batched: the attention's LDS score array holds nk <= KALLE_ATTN_DECODE_MAX_KEYS keys; the one-row attention falls back to the tiled kernel)
+        if (t0[r] >= cache_rows || (batched ? t0[r] >= KALLE_ATTN_DECODE_MAX_KEYS : t0[r] < 0)) return KALLE_ERR_ARG;
         nk[r] = t0[r] < 0 ? 0 : t0[r] + 1;
         if (t0[r] >= 0) a.active |= 1u << r;
         a.y2_off[r] = t0[r] < 0 ? 0 : ((int64_t)r * cache_rows + t0[r]) * kvw;

@@ -444,21 +444,16 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, param_bf16, *, lr, beta1=0.9, be
 # ------------------------------------------------------------------------------------------------ attention
 def attention_fwd(q, k, v, *, ldq, q_off, ldk, k_off, ldv, v_off, B, H, Hkv, Nq, Nk, rope=None, key_mask=None,
                   causal=False, dh=64):
-    """q/k/v: base tensors (bf16) of the projection outputs; see kalle_attention_fwd (_hd for head dims dh = 32, 128).
+    """q/k/v: base tensors (bf16) of the projection outputs; see kalle_attention_fwd_hd (dh = 32, 64 or 128).
     Returns (out [B,Nq,H*dh], lse)."""
     lib = _lib.load()
     out = torch.empty((B, Nq, H * dh), device=q.device, dtype=torch.bfloat16)
     lse = torch.empty((B, H, Nq), device=q.device, dtype=torch.float32)
     cos, sin, rot = (rope[0], rope[1], rope[0].shape[-1] * 2) if rope is not None else (None, None, 0)
     m8 = key_mask.to(torch.uint8).contiguous() if key_mask is not None else None
-    if dh == 64:
-        check(lib.kalle_attention_fwd(_p(q), ldq, q_off, _p(k), ldk, k_off, _p(v), ldv, v_off, _p(out), H * 64, _p(lse),
-                                      _p(cos), _p(sin), rot, _p(m8), int(causal), B, H, Hkv, Nq, Nk, _stream()),
-              "kalle_attention_fwd")
-    else:
-        check(lib.kalle_attention_fwd_hd(_p(q), ldq, q_off, _p(k), ldk, k_off, _p(v), ldv, v_off, _p(out), H * dh, _p(lse),
-                                         _p(cos), _p(sin), rot, _p(m8), int(causal), B, H, Hkv, Nq, Nk, dh, _stream()),
-              "kalle_attention_fwd_hd")
+    check(lib.kalle_attention_fwd_hd(_p(q), ldq, q_off, _p(k), ldk, k_off, _p(v), ldv, v_off, _p(out), H * dh, _p(lse),
+                                     _p(cos), _p(sin), rot, _p(m8), int(causal), B, H, Hkv, Nq, Nk, dh, _stream()),
+          "kalle_attention_fwd_hd")
     return out, lse
 
 
@@ -481,20 +476,43 @@ def attn_last_plan():
     return _lib.load().kalle_attn_last_plan()
 
 
+def attention_plan(entry, *, H, Hkv, B=1, Nq=1, Nk=1, dh=64, rot=0, causal=False, key_mask=False, nk=None, kv_row_stride=None):
+    """kalle_attention_fwd_plan / _bwd_plan / _decode_plan / _decode_rows_plan (entry "fwd", "bwd", "decode", "rows") for a call
+    given by its shape, with placeholder pointers in dense layouts (q [H dh], k | v [2 Hkv dh] rows; the planner tests pointers for
+    null only) and tables exactly when rot != 0; rows: nk host ints, kv_row_stride None = (max(nk) + 1) rows.  Returns (return
+    code, dict(word = what kalle_attn_last_plan would hold after the call, family, launches = [dict(grid, block, lds)]), or None
+    where the entry point refuses the call); host code only, no device needed"""
+    lib = _lib.load()
+    tab = 16 if rot else None
+    head = (16, H * dh, 0, 16, 2 * Hkv * dh, 0, 16, 2 * Hkv * dh, Hkv * dh)
+    tail = (tab, tab, rot, 16 if key_mask else None)
+    plan = (ctypes.c_int32 * 12)()
+    if entry == "fwd":
+        rc = lib.kalle_attention_fwd_plan(*head, 16, H * dh, 16, *tail, int(causal), B, H, Hkv, Nq, Nk, dh, plan)
+    elif entry == "bwd":
+        rc = lib.kalle_attention_bwd_plan(*head, 16, 16, H * dh, 16, 16, 16, 16, 16, *tail, int(causal), B, H, Hkv, Nq, Nk, dh, plan)
+    elif entry == "decode":
+        rc = lib.kalle_attention_decode_plan(*head, 16, H * dh, 16, *tail, B, H, Hkv, Nk, dh, plan)
+    else:
+        assert entry == "rows", entry
+        stride = (max(max(nk), 0) + 1) * 2 * Hkv * dh if kv_row_stride is None else kv_row_stride
+        rc = lib.kalle_attention_decode_rows_plan(*head, stride, 16, H * dh, 16, tab, tab, rot, ctypes.cast(_i32(nk), ctypes.c_void_p),
+                                                  len(nk), H, Hkv, dh, plan)
+    if rc != 0:
+        return rc, None
+    return rc, dict(word=plan[0], family=plan[0] & 15,
+                    launches=[dict(grid=tuple(plan[2 + 5 * i:5 + 5 * i]), block=plan[5 + 5 * i], lds=plan[6 + 5 * i]) for i in range(plan[1])])
+
+
 def attention_bwd(q, k, v, out, dout, lse, dq, dk, dv, *, ldq, q_off, ldk, k_off, ldv, v_off, B, H, Hkv, Nq, Nk,
                   rope=None, key_mask=None, causal=False, dh=64):
     lib = _lib.load()
     delta = torch.empty((B, H, Nq), device=q.device, dtype=torch.float32)
     cos, sin, rot = (rope[0], rope[1], rope[0].shape[-1] * 2) if rope is not None else (None, None, 0)
     m8 = key_mask.to(torch.uint8).contiguous() if key_mask is not None else None
-    if dh == 64:
-        check(lib.kalle_attention_bwd(_p(q), ldq, q_off, _p(k), ldk, k_off, _p(v), ldv, v_off, _p(out), _p(dout), H * 64,
-                                      _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), _p(cos), _p(sin), rot, _p(m8),
-                                      int(causal), B, H, Hkv, Nq, Nk, _stream()), "kalle_attention_bwd")
-    else:
-        check(lib.kalle_attention_bwd_hd(_p(q), ldq, q_off, _p(k), ldk, k_off, _p(v), ldv, v_off, _p(out), _p(dout), H * dh,
-                                         _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), _p(cos), _p(sin), rot, _p(m8),
-                                         int(causal), B, H, Hkv, Nq, Nk, dh, _stream()), "kalle_attention_bwd_hd")
+    check(lib.kalle_attention_bwd_hd(_p(q), ldq, q_off, _p(k), ldk, k_off, _p(v), ldv, v_off, _p(out), _p(dout), H * dh,
+                                     _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), _p(cos), _p(sin), rot, _p(m8),
+                                     int(causal), B, H, Hkv, Nq, Nk, dh, _stream()), "kalle_attention_bwd_hd")
 
 
 def head_norm_fwd(x, ldx, x_off, rows, heads, mode, gamma=None, beta=None, dh=64):

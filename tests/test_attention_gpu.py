@@ -35,6 +35,15 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import kernel_refs as kr  # noqa: E402
 from gpu_checks import NAN, U, Guard, check, clean as _clean, guarded as _guarded  # noqa: E402
 
+
+def asked(lib, entry, call_args):
+    """the word the host query of `entry` names for a call about to be made with `call_args` (those in front of `stream`): every
+    case asserts that it is the word kalle_attn_last_plan() holds after the call (attn_cases imports this file: imported here)"""
+    import attn_cases as ac
+    rc, out = ac.query(lib, entry, call_args)
+    assert rc == 0, (entry, rc)
+    return out[0]
+
 pytestmark = pytest.mark.gpu
 
 ERR_ARG = -1
@@ -238,12 +247,14 @@ def run_case(kl, c, seed=None, wrong=None, inputs=None):
     og = Guard(B * Nq, H * dh, ldo, torch.bfloat16, col0=8)
     lbuf, lse = _guarded(torch.full((B, H, Nq), NAN, device="cuda"))
     op = og.buf.data_ptr() + 16
-    rc = lib.kalle_attention_fwd_hd(P(qb), ldq, q_off, P(kb), ldk, k_off, P(vb), ldv, v_off, op, ldo, P(lse), P(cos), P(sin), rot,
-                                    P(m8), int(causal), B, H, Hkv, Nq, Nk, dh, st)
+    fa = (P(qb), ldq, q_off, P(kb), ldk, k_off, P(vb), ldv, v_off, op, ldo, P(lse), P(cos), P(sin), rot, P(m8), int(causal), B, H, Hkv, Nq, Nk, dh)
+    word = asked(lib, "fwd", fa)
+    rc = lib.kalle_attention_fwd_hd(*fa, st)
     plan = lib.kalle_attn_last_plan()
     torch.cuda.synchronize()
     assert rc == 0, (what, rc)
     assert plan == c["fwd"], (what, hex(plan), hex(c["fwd"]))
+    assert word == plan, (what, "the query named", hex(word))
     PLANS_SEEN.add(plan)
     u_out, u_lse = kr.attention_fwd_units(p, qh, kh, v, ref, rlse, H, Hkv, dh)
     out = og.v.reshape(B, Nq, H * dh)
@@ -263,13 +274,15 @@ def run_case(kl, c, seed=None, wrong=None, inputs=None):
     dqg = Guard(B * Nq, H * dh, ldq, torch.bfloat16, col0=q_off)
     dkg = Guard(B * Nk, Hkv * dh, ldk, torch.bfloat16, col0=k_off)
     dvg = Guard(B * Nk, Hkv * dh, ldv, torch.bfloat16, col0=v_off)
-    rc = lib.kalle_attention_bwd_hd(P(qb), ldq, q_off, P(kb), ldk, k_off, P(vb), ldv, v_off, oo.buf.data_ptr() + 16, do.buf.data_ptr() + 16, ldo,
-                                    P(lse_in), P(delta), P(dqg.buf), P(dkg.buf), P(dvg.buf), P(cos), P(sin), rot, P(m8), int(causal),
-                                    B, H, Hkv, Nq, Nk, dh, st)
+    ba = (P(qb), ldq, q_off, P(kb), ldk, k_off, P(vb), ldv, v_off, oo.buf.data_ptr() + 16, do.buf.data_ptr() + 16, ldo,
+          P(lse_in), P(delta), P(dqg.buf), P(dkg.buf), P(dvg.buf), P(cos), P(sin), rot, P(m8), int(causal), B, H, Hkv, Nq, Nk, dh)
+    word = asked(lib, "bwd", ba)
+    rc = lib.kalle_attention_bwd_hd(*ba, st)
     plan = lib.kalle_attn_last_plan()
     torch.cuda.synchronize()
     assert rc == 0, (what, rc)
     assert plan == c["bwd"], (what, hex(plan), hex(c["bwd"]))
+    assert word == plan, (what, "the query named", hex(word))
     PLANS_SEEN.add(plan)
     rdq, rdk, rdv, rdelta, mags = kr.attention_bwd_ref(q, k, v, dout, *args, round_points=True, out=out_b.double(), masked_rows_zero=True,
                                                        wrong=wrong_kw(wrong, c) if wrong else None)
@@ -292,10 +305,9 @@ def run_case(kl, c, seed=None, wrong=None, inputs=None):
 
 
 # ================================================================================================ forward + backward, head dim 64
-# Shapes found by reading the dispatch of kalle_attention_fwd_hd / _bwd_hd:
-#   forward: Nq == 1 -> decode; else tiled, fold_tail iff Nk in (128, 160], rot 0, not causal
-#   backward: fused iff !causal, Nq, Nk <= 128, H == Hkv; else fused_gqa iff !causal, rot 0, Nq <= 128, tail = max(Nk - 128, 0)
-#             <= min(16, 128 - Nq); else two_pass
+# Which family a shape gets is the list of predicates next to attn_fold_tail in csrc/attention.hip; that every case below reaches
+# the word it names is known without a GPU: tests/test_attn_plan_cpu.py asks the host queries for every case of this file
+# (tests/attn_cases.py) and compares with a table recorded before the predicates existed.
 T64, TF, TP = tiled(), tiled(fold=True), two_pass()
 CASES_64 = [
     # ---- tiled forward at the edge lengths (backward: whatever the shape dispatches to)

@@ -30,6 +30,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import attn_cases as ac  # noqa: E402
 import decode_cases as dc  # noqa: E402
 import kernel_refs as kr  # noqa: E402
 from gpu_checks import NAN, U, Guard, _exact, check, clean as _clean, guarded as _guarded  # noqa: E402
@@ -211,6 +212,7 @@ def run_case(lib, ops, name):
     torch.cuda.synchronize()
     assert rc == 0, (name, rc, lib.kalle_last_error())
     assert ops.attn_last_plan() == DECODE_PLAN, hex(ops.attn_last_plan())
+    assert ac.step_word(lib, 64, c["H"], c["Hkv"], c["t0"]) == ops.attn_last_plan()       # (what the host query names for the step's attention call)
     assert torch.isfinite(s.out).all(), (name, "NaN rows above t0 leaked into the output")
     for stage, got, ref, tol in stages(s, L, s.x, s.out):
         check(got, ref, tol, f"{name} {stage}")

@@ -16,6 +16,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import attn_cases as ac  # noqa: E402
 import decode_cases as dc  # noqa: E402
 import decode_rows_cases as rc  # noqa: E402
 import kernel_refs as kr  # noqa: E402
@@ -197,8 +198,10 @@ class Attn:
             self.cos, self.sin = cos.cuda(), sin.cuda()
         self.obuf, self.out = _guarded(torch.full((R, D), NAN, device="cuda", dtype=BF))
         self.lbuf, self.lse = _guarded(torch.full((R, H), NAN, device="cuda"))
-        self.rc = lib.kalle_attention_decode_rows(P(self.q), D, 0, P(self.cache), kvw, 0, P(self.cache), kvw, Hkv * hd, self.rows * kvw,
-                                                  P(self.out), D, P(self.lse), P(self.cos), P(self.sin), rot, iarr(nk), R, H, Hkv, hd, None)
+        a = (P(self.q), D, 0, P(self.cache), kvw, 0, P(self.cache), kvw, Hkv * hd, self.rows * kvw,
+             P(self.out), D, P(self.lse), P(self.cos), P(self.sin), rot, iarr(nk), R, H, Hkv, hd)
+        self.asked = ac.query(lib, "rows", a)              # (return code, plan ints) of the host query, before the call
+        self.rc = lib.kalle_attention_decode_rows(*a, None)
         torch.cuda.synchronize()
 
     def ref(self, r, keys=None):
@@ -223,6 +226,7 @@ def test_attention_rows(kl, hd, rot, nk):
     what = f"attention rows hd {hd} rot {rot} nk {nk}"
     assert a.rc == 0, (what, a.rc, lib.kalle_last_error())
     assert ops.attn_last_plan() == rows_plan(hd, rot), hex(ops.attn_last_plan())
+    assert a.asked[0] == 0 and a.asked[1][0] == ops.attn_last_plan(), a.asked
     H, Hkv = a.H, a.Hkv
     for r, n in enumerate(nk):
         if n <= 0:
@@ -254,6 +258,7 @@ def test_attention_rows_refusals(kl):
     ops, lib = kl
     a = Attn(lib, 64, 64, (1, 2, 3))
     assert ops.attn_last_plan() == rows_plan(64, 64)
+    assert a.asked[0] == 0 and a.asked[1][0] == ops.attn_last_plan(), a.asked
     H, Hkv, hd = a.H, a.Hkv, 64
     out = torch.full_like(a.out, NAN)
 
@@ -407,6 +412,7 @@ def step_runs(kl):
         s = Setup(lib, c)
         assert s.step() == 0, (name, lib.kalle_last_error())
         assert ops.attn_last_plan() == rows_plan(c["hd"], c["hd"]), hex(ops.attn_last_plan())
+        assert ac.step_word(lib, c["hd"], c["H"], c["Hkv"], c["t0"], c["rows"]) == ops.attn_last_plan()
         runs[name] = s
     return runs
 

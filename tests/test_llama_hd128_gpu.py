@@ -23,6 +23,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(HERE, "golden"))
+import attn_cases as ac  # noqa: E402
 import decode_cases as dc  # noqa: E402
 import golden_util as gu  # noqa: E402
 import kernel_refs as kr  # noqa: E402
@@ -92,17 +93,21 @@ def run_case(kl, c, seed=None, wrong=None, inputs=None, entry="fwd_hd"):
     og = Guard(B * Nq, H * dh, ldo, torch.bfloat16, col0=8)
     lbuf, lse = _guarded(torch.full((B, H, Nq), NAN, device="cuda"))
     op = og.buf.data_ptr() + 16
+    head = (P(qb), ldq, q_off, P(kb), ldk, k_off, P(vb), ldv, v_off, op, ldo, P(lse), P(cos), P(sin), rot, P(m8))
     if entry == "decode":
         assert Nq == 1 and causal
-        rc = lib.kalle_attention_decode_hd(P(qb), ldq, q_off, P(kb), ldk, k_off, P(vb), ldv, v_off, op, ldo, P(lse), P(cos), P(sin), rot,
-                                           P(m8), B, H, Hkv, Nk, dh, st)
+        fa = head + (B, H, Hkv, Nk, dh)
+        word = ta.asked(lib, "decode", fa)
+        rc = lib.kalle_attention_decode_hd(*fa, st)
     else:
-        rc = lib.kalle_attention_fwd_hd(P(qb), ldq, q_off, P(kb), ldk, k_off, P(vb), ldv, v_off, op, ldo, P(lse), P(cos), P(sin), rot,
-                                        P(m8), int(causal), B, H, Hkv, Nq, Nk, dh, st)
+        fa = head + (int(causal), B, H, Hkv, Nq, Nk, dh)
+        word = ta.asked(lib, "fwd", fa)
+        rc = lib.kalle_attention_fwd_hd(*fa, st)
     plan = lib.kalle_attn_last_plan()
     torch.cuda.synchronize()
     assert rc == 0, (what, rc)
     assert plan == c["fwd"], (what, hex(plan), hex(c["fwd"]))
+    assert word == plan, (what, "the query named", hex(word))
     PLANS_SEEN.add(plan)
     u_out, u_lse = kr.attention_fwd_units(p, qh, kh, v, ref, rlse, H, Hkv, dh)
     out = og.v.reshape(B, Nq, H * dh)
@@ -122,13 +127,15 @@ def run_case(kl, c, seed=None, wrong=None, inputs=None, entry="fwd_hd"):
     dqg = Guard(B * Nq, H * dh, ldq, torch.bfloat16, col0=q_off)
     dkg = Guard(B * Nk, Hkv * dh, ldk, torch.bfloat16, col0=k_off)
     dvg = Guard(B * Nk, Hkv * dh, ldv, torch.bfloat16, col0=v_off)
-    rc = lib.kalle_attention_bwd_hd(P(qb), ldq, q_off, P(kb), ldk, k_off, P(vb), ldv, v_off, oo.buf.data_ptr() + 16, do.buf.data_ptr() + 16, ldo,
-                                    P(lse_in), P(delta), P(dqg.buf), P(dkg.buf), P(dvg.buf), P(cos), P(sin), rot, P(m8), int(causal),
-                                    B, H, Hkv, Nq, Nk, dh, st)
+    ba = (P(qb), ldq, q_off, P(kb), ldk, k_off, P(vb), ldv, v_off, oo.buf.data_ptr() + 16, do.buf.data_ptr() + 16, ldo,
+          P(lse_in), P(delta), P(dqg.buf), P(dkg.buf), P(dvg.buf), P(cos), P(sin), rot, P(m8), int(causal), B, H, Hkv, Nq, Nk, dh)
+    word = ta.asked(lib, "bwd", ba)
+    rc = lib.kalle_attention_bwd_hd(*ba, st)
     plan = lib.kalle_attn_last_plan()
     torch.cuda.synchronize()
     assert rc == 0, (what, rc)
     assert plan == c["bwd"], (what, hex(plan), hex(c["bwd"]))
+    assert word == plan, (what, "the query named", hex(word))
     PLANS_SEEN.add(plan)
     rdq, rdk, rdv, rdelta, mags = kr.attention_bwd_ref(q, k, v, dout, *args, round_points=True, out=out_b.double(), masked_rows_zero=True,
                                                        wrong=wrong_kw(wrong, c) if wrong else None)
@@ -206,10 +213,12 @@ def test_decode_hd_at_head_dim_64_is_attention_fwd_bit_for_bit(kl, rot):
         og = Guard(B, 4 * 64, 4 * 64 + 16, torch.bfloat16, col0=8)
         lbuf, lse = _guarded(torch.full((B, 4, 1), NAN, device="cuda"))
         head = (P(qb), ldq, q_off, P(kb), ldk, k_off, P(kb), ldv, v_off, og.buf.data_ptr() + 16, 4 * 64 + 16, P(lse), P(cos), P(sin), rot, P(m8))
+        word = ta.asked(lib, "decode", head + (B, 4, 2, 257, 64)) if new else ta.asked(lib, "fwd", head + (1, B, 4, 2, 1, 257, 64))
         rc = lib.kalle_attention_decode_hd(*head, B, 4, 2, 257, 64, st) if new else lib.kalle_attention_fwd(*head, 1, B, 4, 2, 1, 257, st)
         plan = lib.kalle_attn_last_plan()
         torch.cuda.synchronize()
         assert rc == 0 and plan == lc128.decode64(rot), (rc, hex(plan))
+        assert word == plan, ("the query named", hex(word))
         og.clean("out")
         _clean(lbuf, lse, "lse")
         assert torch.isfinite(og.v).all() and torch.isfinite(lse).all()
@@ -355,6 +364,7 @@ def test_decode_step_at_head_dim_128_stage_by_stage(kl, name):
     torch.cuda.synchronize()
     assert rc == 0, (name, rc, lib.kalle_last_error())
     assert ops.attn_last_plan() == lc128.decode128(), hex(ops.attn_last_plan())
+    assert ac.step_word(lib, HD, c["H"], c["Hkv"], c["t0"]) == ops.attn_last_plan()
     PLANS_SEEN.add(ops.attn_last_plan())
     assert torch.isfinite(s.out).all(), (name, "NaN rows above t0 leaked into the output")
     for stage, got, ref, tol in stages(s, L, s.x, s.out):
@@ -415,6 +425,7 @@ def test_old_decode_step_equals_the_hd_form_at_64(kl, name):
     rc = lib.kalle_llama_decode_step_hd(ctypes.c_void_p(ctypes.addressof(b.arr)), 1, P(b.x), P(b.out), c["H"], c["Hkv"], c["inner"], 64,
                                         ctypes.c_float(dc.EPS), c["t0"], c["rows"], P(b.cos), P(b.sin), P(b.ws), None)
     assert rc == 0 and ops.attn_last_plan() == td.DECODE_PLAN
+    assert ac.step_word(lib, 64, c["H"], c["Hkv"], c["t0"]) == ops.attn_last_plan()
     PLANS_SEEN.add(ops.attn_last_plan())
     torch.cuda.synchronize()
     assert torch.isfinite(a.out).all()
