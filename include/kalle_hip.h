@@ -736,6 +736,42 @@ int kalle_llama_decode_step_w8(const kalle_llama_layer_w8* layers, int n_layers,
 int kalle_llama_decode_step_rows_w8(const kalle_llama_layer_w8* layers, int n_layers, const float* x, float* out, int R, int H,
                                     int Hkv, int inner, int head_dim, float eps, const int32_t* t0, int cache_rows,
                                     const float* rope_cos, const float* rope_sin, void* workspace, void* stream);
+/* ---- the per-frame head of KV-cached generation (model_sigmaVAE.py:123-146): everything between two decode steps, one call ----
+ * For each active row r of the R rows, from h = the UN-NORMED residual stream (`out` of kalle_llama_decode_step*, or the last
+ * position of a prefill before model.norm), fp32 [R][ldh >= D]:
+ *   xn     = bf16(rmsnorm(h[r]; norm, eps))                                    (LlamaRMSNorm, the rounding of kalle_rmsnorm_fwd)
+ *   h1     = W1 . xn + b1                            fp32 [dl]                 distribution_linear[0]
+ *   a      = bf16(gelu(h1))                                                    the exact GELU of kalle_gelu_fwd (one device function)
+ *   mean   = W2 . a + b2                             fp32 [R][dl]              distribution_linear[2]
+ *   latent = mean + std * noise[r]                   fp32 [R][dl]              sample(), noise fp32 [R][ldn >= dl]
+ *   kl[r]  = (1/dl) sum_j [ log(e/std) + (std^2 + (mean_j - 1)^2) / (2 e^2) - 1/2 ]     KL(N(mean, std) || N(1, e)) / dl (:135-139)
+ *   x_next = Wa . bf16(latent) + ba                  fp32 [R][D]               audio_linear: the next decode step's input
+ * bf16 roundings at exactly the three marked points (those of a host path whose Linear casts its input to bf16); all else fp32.
+ * Four launches: the RMSNorm pre-pass and the R-row GEMM of kalle_gemm_rows_fused for W1 (bias = residual at row stride 0), one
+ * kernel with a workgroup per active row for GELU, W2, the sample and the KL (its terms summed in a fixed order), the R-row GEMM
+ * for Wa.  No atomics, no workgroup waits on another: two calls on the same input give the same bits, and an active row's bits
+ * do not depend on which other rows are active.  active: HOST int32 [R], 0 = row r is INACTIVE - nothing of it is read or
+ * written, in the outputs or the workspace; NULL = every row active (as in kalle_gemm_rows_fused).  Every row inactive:
+ * KALLE_OK, nothing launched.
+ * Limits: 1 <= R <= KALLE_DECODE_MAX_ROWS; D % 8 == 0, 8 <= D <= 32768; dl % 8 == 0, 8 <= dl <= 512 (one workgroup streams the
+ * dl x dl matrix per row: 512 KiB at the bound); std > 0; ldh % 4 == 0, ldh >= D; ldn >= dl; ldw* % 8 == 0 and not below the
+ * row they hold.  Anything else, or a NULL argument or descriptor field other than active / stream, returns KALLE_ERR_ARG
+ * before the first HIP call.  Every launch is checked where it is made.
+ * Workspace (kalle_llasa_head_ws_bytes(R, D, dl) bytes, 64-byte aligned, caller-owned; KALLE_ERR_ARG outside the limits), in
+ * this order, each region padded to a multiple of 64 bytes, rows dense:
+ *   xn bf16 [R][D] | h1 fp32 [R][dl] | a bf16 [R][dl] | lat bf16 [R][dl] (= bf16(latent))
+ * They are published so that every stage can be checked from its own inputs. */
+typedef struct kalle_llasa_head {
+    const float* norm;                 /* final RMSNorm weight, fp32 [D] */
+    const void* w1; const float* b1;   /* distribution_linear[0]: bf16 [dl][ldw1 >= D], fp32 [dl] */
+    const void* w2; const float* b2;   /* distribution_linear[2]: bf16 [dl][ldw2 >= dl], fp32 [dl] */
+    const void* wa; const float* ba;   /* audio_linear:           bf16 [D][ldwa >= dl],  fp32 [D]  */
+    int64_t ldw1, ldw2, ldwa;
+} kalle_llasa_head;
+int kalle_llasa_head_ws_bytes(int R, int D, int dl);
+int kalle_llasa_frame_head_rows(const kalle_llasa_head* head, const float* h, int64_t ldh, const float* noise, int64_t ldn,
+                                float std, float eps, float* mean, float* latent, float* kl, float* x_next,
+                                const int32_t* active, int R, int D, int dl, void* workspace, void* stream);
 /* waveform -> int16 PCM as the inference scripts write it (infer_0723.py:293): out = int16(clamp(x / max|x|, -1, 1) * 32767);
  * peak: one fp32 of device scratch that receives max|x|; x fp32 or bf16 */
 int kalle_peak_normalize_int16(const void* x, int dtype, float* peak, int16_t* out, int64_t n, void* stream);

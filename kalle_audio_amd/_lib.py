@@ -72,6 +72,13 @@ class LlamaLayerW8(ctypes.Structure):
                 ("kv_cache", ctypes.c_void_p)]
 
 
+class LlasaHead(ctypes.Structure):
+    """Mirror of `kalle_llasa_head`: final norm, distribution_linear[0] / [2] and audio_linear (bf16 weights, fp32 biases)."""
+    _fields_ = [("norm", ctypes.c_void_p), ("w1", ctypes.c_void_p), ("b1", ctypes.c_void_p), ("w2", ctypes.c_void_p),
+                ("b2", ctypes.c_void_p), ("wa", ctypes.c_void_p), ("ba", ctypes.c_void_p), ("ldw1", ctypes.c_int64),
+                ("ldw2", ctypes.c_int64), ("ldwa", ctypes.c_int64)]
+
+
 class WgradProblem(ctypes.Structure):
     """Mirror of `kalle_wgrad_problem`."""
     _fields_ = [("dy", ctypes.c_void_p), ("lddy", ctypes.c_int64), ("x", ctypes.c_void_p), ("ldx", ctypes.c_int64),

@@ -713,11 +713,16 @@ __global__ __launch_bounds__(256) void embed_mix_bwd_kernel(const float* __restr
 }
 
 // exact GELU (nn.GELU() default, model_sigmaVAE.py:46): 0.5 x (1 + erf(x / sqrt 2))
+__device__ __forceinline__ float gelu_exact(float v) {
+    const float h = 0.5f * v;
+    return h * (1.f + erff(v * 0.70710678118654752f));
+}
+
 template <bool F32>
 __global__ __launch_bounds__(256) void gelu_fwd_kernel(const void* __restrict__ x, void* __restrict__ y, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const float v = F32 ? static_cast<const float*>(x)[i] : bf16_to_f32(static_cast<const bf16_t*>(x)[i]);
-        const float o = 0.5f * v * (1.f + erff(v * 0.70710678118654752f));
+        const float o = gelu_exact(v);
         if constexpr (F32) static_cast<float*>(y)[i] = o;
         else static_cast<bf16_t*>(y)[i] = f32_to_bf16(o);
     }
@@ -733,6 +738,87 @@ __global__ __launch_bounds__(256) void gelu_bwd_kernel(const void* __restrict__ 
         const float o = g * (cdf + v * pdf);
         if constexpr (F32) static_cast<float*>(dx)[i] = o;
         else static_cast<bf16_t*>(dx)[i] = f32_to_bf16(o);
+    }
+}
+
+// ---- the middle of the per-frame head of KV-cached generation (model_sigmaVAE.py:127-146, kalle_llasa_frame_head_rows) ---------
+// One workgroup per active row r:  a = bf16(gelu(h1[r])),  mean = W2 . a + b2,  latent = mean + std * noise[r],
+// lat = bf16(latent),  kl[r] = (1/dl) sum_j [c0 + (std^2 + (mean_j - 1)^2) c1 - 1/2]  with c0 = log(e / std), c1 = 1 / (2 e^2).
+// A weight row is dl / 8 <= 64 chunks of 16 bytes: G lanes (the power of two >= dl / 8) own a row and lane c of the group its
+// chunk c, so a lane multiplies every row it meets by the SAME eight activations - they are computed once, into registers, and
+// need no LDS.  The 256 / G groups walk the rows 256 / G at a time, PF rows per step, the loads of the next step issued before
+// the FMAs of this one.  The KL terms meet in LDS and wave 0 sums them in a fixed order.  No atomics, nothing another
+// workgroup writes is read: a row's bits depend on that row alone.
+__global__ __launch_bounds__(256) void llasa_head_kernel(const float* __restrict__ h1, const bf16_t* __restrict__ W2, int64_t ldw2,
+                                                         const float* __restrict__ b2, const float* __restrict__ noise,
+                                                         int64_t ldn, float std, float c0, float c1, bf16_t* __restrict__ a_out,
+                                                         float* __restrict__ mean, float* __restrict__ latent,
+                                                         bf16_t* __restrict__ lat, float* __restrict__ kl, int dl, int lgG,
+                                                         unsigned active) {
+    __shared__ float term[512];
+    const int r = blockIdx.x;
+    if (!(active >> r & 1)) return;
+    constexpr int PF = 8;
+    const int G = 1 << lgG, ngrp = 256 >> lgG, nc = dl >> 3;
+    const int c = threadIdx.x & (G - 1), grp = threadIdx.x >> lgG;
+    const bool in = c < nc;
+    auto load = [&](int base, i32x4* w) {
+#pragma unroll
+        for (int p = 0; p < PF; ++p) {
+            const int j = base + p * ngrp + grp;
+            w[p] = i32x4{0, 0, 0, 0};
+            if (in) w[p] = *reinterpret_cast<const i32x4*>(W2 + (int64_t)(j < dl ? j : dl - 1) * ldw2 + 8 * c);
+        }
+    };
+    i32x4 w[PF];
+    load(0, w);                                   // (the weight stream does not wait for the activations)
+    float x[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (in) {
+        const float* hr = h1 + (int64_t)r * dl + 8 * c;
+        const f32x4 lo = *reinterpret_cast<const f32x4*>(hr), hi = *reinterpret_cast<const f32x4*>(hr + 4);
+        i32x4 o;
+        o[0] = (int)pack_bf16x2(gelu_exact(lo[0]), gelu_exact(lo[1]));
+        o[1] = (int)pack_bf16x2(gelu_exact(lo[2]), gelu_exact(lo[3]));
+        o[2] = (int)pack_bf16x2(gelu_exact(hi[0]), gelu_exact(hi[1]));
+        o[3] = (int)pack_bf16x2(gelu_exact(hi[2]), gelu_exact(hi[3]));
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { x[2 * e] = bf16lo((uint32_t)o[e]); x[2 * e + 1] = bf16hi((uint32_t)o[e]); }
+        if (grp == 0) *reinterpret_cast<i32x4*>(a_out + (int64_t)r * dl + 8 * c) = o;
+    }
+    const float s2 = std * std;
+    for (int base = 0; base < dl; base += ngrp * PF) {          // (uniform over the workgroup: every lane takes every shuffle)
+        i32x4 wn[PF];
+        const bool more = base + ngrp * PF < dl;
+        if (more) load(base + ngrp * PF, wn);
+#pragma unroll
+        for (int p = 0; p < PF; ++p) {
+            float s = 0.f;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) s += bf16lo((uint32_t)w[p][e]) * x[2 * e] + bf16hi((uint32_t)w[p][e]) * x[2 * e + 1];
+            for (int o = G >> 1; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+            const int j = base + p * ngrp + grp;
+            if (c == 0 && j < dl) {
+                const int64_t at = (int64_t)r * dl + j;
+                const float m = s + b2[j];
+                const float z = m + std * noise[r * ldn + j];
+                mean[at] = m;
+                latent[at] = z;
+                lat[at] = f32_to_bf16(z);
+                const float d = m - 1.f;
+                term[j] = c0 + (s2 + d * d) * c1 - 0.5f;
+            }
+        }
+        if (more) {
+#pragma unroll
+            for (int p = 0; p < PF; ++p) w[p] = wn[p];
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        float s = 0.f;
+        for (int j = threadIdx.x; j < dl; j += 64) s += term[j];
+        s = wave_sum(s);
+        if (threadIdx.x == 0) kl[r] = s / (float)dl;
     }
 }
 
@@ -1081,6 +1167,75 @@ extern "C" int kalle_gemm_rows_fused_e4m3(const void* x, int64_t ldx, int prolog
     if (!scale) return KALLE_ERR_ARG;
     return gemm_rows_entry({W8, ldq, scale}, 16, x, ldx, prologue, gamma, eps, xhat, y, ldy, y_dtype, y2, nsplit, y2_off, residual,
                            ldres, active, R, N, K, stream);
+}
+
+// ---- the per-frame head of KV-cached generation: final norm, distribution_linear, sampling, stop KL, audio_linear ----------------
+namespace {
+
+// The workspace the header publishes, carved in its order, each region padded to 64 bytes.
+struct HeadWs {                  // byte offsets
+    int64_t xn, h1, a, lat;      // bf16 [R][D] | fp32 [R][dl] | bf16 [R][dl] | bf16 [R][dl]
+    int64_t end;
+};
+
+inline HeadWs head_ws(int R, int D, int dl) {
+    auto pad = [](int64_t b) { return (b + 63) & ~(int64_t)63; };
+    HeadWs w;
+    w.xn = 0;
+    w.h1 = w.xn + pad((int64_t)R * D * 2);
+    w.a = w.h1 + pad((int64_t)R * dl * 4);
+    w.lat = w.a + pad((int64_t)R * dl * 2);
+    w.end = w.lat + pad((int64_t)R * dl * 2);
+    return w;
+}
+
+inline bool head_dims_ok(int R, int D, int dl) {
+    return R >= 1 && R <= KALLE_DECODE_MAX_ROWS && D >= 8 && !(D & 7) && D <= 32768 && dl >= 8 && !(dl & 7) && dl <= 512;
+}
+
+}  // namespace
+
+extern "C" int kalle_llasa_head_ws_bytes(int R, int D, int dl) {
+    if (!head_dims_ok(R, D, dl)) return KALLE_ERR_ARG;
+    return (int)head_ws(R, D, dl).end;
+}
+
+extern "C" int kalle_llasa_frame_head_rows(const kalle_llasa_head* head, const float* h, int64_t ldh, const float* noise,
+                                           int64_t ldn, float std, float eps, float* mean, float* latent, float* kl,
+                                           float* x_next, const int32_t* active, int R, int D, int dl, void* workspace,
+                                           void* stream) {
+    if (!head || !h || !noise || !mean || !latent || !kl || !x_next || !workspace) return KALLE_ERR_ARG;
+    if (!head->norm || !head->w1 || !head->b1 || !head->w2 || !head->b2 || !head->wa || !head->ba) return KALLE_ERR_ARG;
+    if (!head_dims_ok(R, D, dl) || !(std > 0.f)) return KALLE_ERR_ARG;
+    if ((ldh & 3) || ldh < D || ldn < dl) return KALLE_ERR_ARG;
+    if ((head->ldw1 & 7) || head->ldw1 < D || (head->ldw2 & 7) || head->ldw2 < dl || (head->ldwa & 7) || head->ldwa < dl)
+        return KALLE_ERR_ARG;
+    RowsArgs a{};
+    a.R = R;
+    for (int r = 0; r < R; ++r)
+        if (!active || active[r]) a.active |= 1u << r;
+    if (!a.active) return KALLE_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const HeadWs o = head_ws(R, D, dl);
+    char* ws = static_cast<char*>(workspace);
+    bf16_t* xn = reinterpret_cast<bf16_t*>(ws + o.xn);       // bf16(rmsnorm(h))
+    float* h1 = reinterpret_cast<float*>(ws + o.h1);         // W1 . xn + b1
+    bf16_t* ga = reinterpret_cast<bf16_t*>(ws + o.a);        // bf16(gelu(h1))
+    bf16_t* lat = reinterpret_cast<bf16_t*>(ws + o.lat);     // bf16(latent)
+    // (every launch is checked where it is made, as in decode_step; a bias is the residual at row stride 0)
+    int rc = proj_launch({head->w1, head->ldw1, nullptr}, h, ldh, PRO_RMS, head->norm, eps, xn, D, h1, dl, true, h1, dl, head->b1, 0,
+                         &a, dl, D, st);
+    if (rc != KALLE_OK) return rc;
+    int lg = 0;
+    while ((8 << lg) < dl) ++lg;                             // G = 1 << lg lanes per weight row, the power of two >= dl / 8
+    const float c0 = (float)(1.0 - log((double)std));        // log(e / std)
+    const float c1 = (float)(0.5 / (M_E * M_E));             // 1 / (2 e^2)
+    KALLE_LAUNCH(llasa_head_kernel, dim3(R), dim3(256), 0, st, h1, static_cast<const bf16_t*>(head->w2), head->ldw2, head->b2, noise,
+                 ldn, std, c0, c1, ga, mean, latent, lat, kl, dl, lg, a.active);
+    rc = kalle_check_launch();
+    if (rc != KALLE_OK) return rc;
+    return proj_launch({head->wa, head->ldwa, nullptr}, lat, dl, PRO_BF16, nullptr, 0.f, nullptr, 0, x_next, D, true, x_next, D,
+                       head->ba, 0, &a, D, dl, st);
 }
 
 // ---- weight-only e4m3 decoding -----------------------------------------------------------------------------------------------

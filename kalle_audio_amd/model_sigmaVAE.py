@@ -349,8 +349,9 @@ class LlamaModel(nn.Module):
                 "rope": LO.rope_tables(max_len, self._inv_freq, device)}
 
     @torch.no_grad()
-    def forward_cached(self, inputs_embeds, cache):
-        """appends the positions of `inputs_embeds` [1, n, D] to the cache and returns their last hidden states"""
+    def forward_cached(self, inputs_embeds, cache, final_norm=True):
+        """appends the positions of `inputs_embeds` [1, n, D] to the cache and returns their last hidden states
+        (final_norm=False: the residual stream before `self.norm`, what kalle_llasa_frame_head_rows takes)"""
         _need_gpu(inputs_embeds)
         _, n, Dm = inputs_embeds.shape
         t0 = cache["len"]
@@ -365,7 +366,7 @@ class LlamaModel(nn.Module):
             for layer, kv in zip(self.layers, cache["kv"]):
                 x = LO.layer_fwd_cached(LO.layer_params(layer), x, kv, t0, cache["rope"])
         cache["len"] = t0 + n
-        return self.norm(x.view(1, n, Dm))
+        return self.norm(x.view(1, n, Dm)) if final_norm else x.view(1, n, Dm)
 
     # ---- inference with a KV cache, R sequences of different lengths per step -------------------------------------------------
     def init_cache_batch(self, R, max_len, device):
@@ -377,9 +378,9 @@ class LlamaModel(nn.Module):
                 "rope": LO.rope_tables(max_len, self._inv_freq, device)}
 
     @torch.no_grad()
-    def prefill_row(self, inputs_embeds, cache, r):
+    def prefill_row(self, inputs_embeds, cache, r, final_norm=True):
         """appends the positions of `inputs_embeds` [1, n, D] to row r of a batch cache (the layers of forward_cached on that
-        row's slice) and returns their last hidden states"""
+        row's slice) and returns their last hidden states (final_norm=False: before `self.norm`)"""
         _need_gpu(inputs_embeds)
         _, n, Dm = inputs_embeds.shape
         t0 = cache["len"][r]
@@ -389,13 +390,14 @@ class LlamaModel(nn.Module):
         for layer, kv in zip(self.layers, cache["kv"]):
             x = LO.layer_fwd_cached(LO.layer_params(layer), x, kv[r], t0, cache["rope"])
         cache["len"][r] = t0 + n
-        return self.norm(x.view(1, n, Dm))
+        return self.norm(x.view(1, n, Dm)) if final_norm else x.view(1, n, Dm)
 
     @torch.no_grad()
-    def forward_cached_batch(self, inputs_embeds, cache, active=None):
+    def forward_cached_batch(self, inputs_embeds, cache, active=None, final_norm=True):
         """one new position for every active row: appends `inputs_embeds` [R, 1, D] row by row to the caches and returns the last
         hidden states [R, 1, D].  active: R host booleans (default: all); an inactive row's cache and length stay as they are
-        and its output row is that of its last active step (zero before the first).  The whole stack is sequenced by kalle_llama_decode_step_rows (one host call)."""
+        and its output row is that of its last active step (zero before the first).  The whole stack is sequenced by kalle_llama_decode_step_rows (one host call).
+        final_norm=False: the residual stream before `self.norm` (the step's own buffer, rewritten by the next step)."""
         _need_gpu(inputs_embeds)
         R, n, Dm = inputs_embeds.shape
         if n != 1 or R != len(cache["len"]):
@@ -409,7 +411,7 @@ class LlamaModel(nn.Module):
         plan = self._decode_plan(cache, x.device, rows=R)
         x = ops.llama_decode_step(plan, x, t0, rows, cache["rope"], plan["eps"])
         cache["len"] = [t + 1 if a else t for t, a in zip(cache["len"], active)]
-        return self.norm(x.view(R, 1, Dm))
+        return self.norm(x.view(R, 1, Dm)) if final_norm else x.view(R, 1, Dm)
 
 
 class LlamaForCausalLM(nn.Module):
@@ -529,11 +531,26 @@ class Llasa(nn.Module):
 
     @torch.no_grad()
     def infer(self, input_ids, audio_latents, end_disp_kl_thres=0.5, max_length=200, sample=False, use_cfg=None,
-              flow=None, use_cache=True):
+              flow=None, use_cache=True, device_head=False, noise=None, stop_lag=0):
         """model_sigmaVAE.py:106-148: frame-by-frame generation, stopping when KL(N(mean, std) || N(1, e)) / dim drops
         below the threshold.  The reference re-runs the decoder over the whole prefix for every frame (O(T^2) GEMM work);
         with use_cache (default) the prompt is prefilled once and every frame is one single-position pass against a KV
-        cache - same arithmetic per position.  use_cache=False reproduces the reference's schedule."""
+        cache - same arithmetic per position.  use_cache=False reproduces the reference's schedule.
+        device_head=True (extension, opt-in): everything between two decode steps - final norm, distribution_linear, the
+        sample, the stop KL, audio_linear - is one call of kalle_llasa_frame_head_rows, so a frame is two host calls and one
+        4-byte read-back; `sample()` and the head modules' forward are not called.  noise: the N(0, 1) draws, fp32,
+        broadcastable to [max_length, 1, latent_dim] (default: one torch.randn((1, 1, latent_dim)) per frame, the shape and order
+        `sample()` draws in, so a seeded run consumes the generator as the host path does).  stop_lag=1: frame i + 1 is enqueued
+        before frame i's KL is read, so the read-back no longer drains the device; the returned tensor is the same, bit for bit,
+        but the frame after the stop has run (and been discarded): the cache holds one extra position and, with noise=None, one
+        extra draw has been taken from the generator."""
+        if device_head:
+            if not use_cache:
+                raise NotImplementedError("device_head=True generates against a KV cache; use_cache=False runs on the host path "
+                                          "(device_head=False)")
+            return self._generate_device_head([(input_ids, audio_latents)], end_disp_kl_thres, max_length, noise, stop_lag)[0]
+        if noise is not None or stop_lag:
+            raise ValueError("noise= and stop_lag= belong to device_head=True")
         ids = input_ids.unsqueeze(0)
         text_embed = self.base_model.model.embed_tokens(ids)
         parts = [text_embed]
@@ -567,21 +584,34 @@ class Llasa(nn.Module):
     infer_batch_rows = ops.DECODE_MAX_ROWS      # sequences decoded per step by infer_batch (the kernels take up to DECODE_MAX_ROWS)
 
     @torch.no_grad()
-    def infer_batch(self, prompts, end_disp_kl_thres=0.5, max_length=200):
+    def infer_batch(self, prompts, end_disp_kl_thres=0.5, max_length=200, device_head=False, noise=None, stop_lag=0):
         """`infer` (KV-cached) for a list of (input_ids, audio_latents or None): the utterances of a group are generated together,
         one decoder pass per frame for all of them, so the decoder weights are read once per frame instead of once per frame
         and utterance.  Returns a list with what `infer` returns for each prompt.  The prompts are prefilled one by one (they
         differ in length); a row that meets `infer`'s stop rule leaves the batch (its cache is not touched again) while the
-        others go on.  Lists longer than `infer_batch_rows` are processed in groups; one prompt is `infer` itself."""
+        others go on.  Lists longer than `infer_batch_rows` are processed in groups; one prompt is `infer` itself.
+        device_head / noise / stop_lag: as in `infer`, noise broadcastable to [max_length, len(prompts), latent_dim] and drawn,
+        when absent, as one torch.randn((R, 1, latent_dim)) per frame for the R rows of a group; with stop_lag=1 a stopped
+        row's cache holds one extra position."""
         prompts = list(prompts)
         if not prompts:
             return []
+        if not device_head and (noise is not None or stop_lag):
+            raise ValueError("noise= and stop_lag= belong to device_head=True")
+        if device_head and noise is not None:
+            dl = self.distribution_linear[2].weight.shape[0]
+            noise = noise.to(F32).expand(max_length, len(prompts), dl)
         if len(prompts) == 1:
-            return [self.infer(prompts[0][0], prompts[0][1], end_disp_kl_thres=end_disp_kl_thres, max_length=max_length)]
+            return [self.infer(prompts[0][0], prompts[0][1], end_disp_kl_thres=end_disp_kl_thres, max_length=max_length,
+                               device_head=device_head, noise=noise, stop_lag=stop_lag)]
         G = max(1, min(int(self.infer_batch_rows), ops.DECODE_MAX_ROWS))
         if len(prompts) > G:
             return [o for i in range(0, len(prompts), G)
-                    for o in self.infer_batch(prompts[i:i + G], end_disp_kl_thres=end_disp_kl_thres, max_length=max_length)]
+                    for o in self.infer_batch(prompts[i:i + G], end_disp_kl_thres=end_disp_kl_thres, max_length=max_length,
+                                              device_head=device_head, noise=None if noise is None else noise[:, i:i + G],
+                                              stop_lag=stop_lag)]
+        if device_head:
+            return self._generate_device_head(prompts, end_disp_kl_thres, max_length, noise, stop_lag)
         model = self.base_model.model
         embeds = []
         for ids, lat in prompts:
@@ -613,6 +643,80 @@ class Llasa(nn.Module):
                 break
             step_in = self.audio_linear(audio_latent)
         return [torch.stack(f[:-1], dim=1).squeeze(1).squeeze(2).transpose(1, 2) for f in final]
+
+    def _generate_device_head(self, prompts, thres, max_length, noise, stop_lag):
+        """`infer` (one prompt: the one-row decode step) / one group of `infer_batch` (the R-row step) with the per-frame head on the
+        device: a frame is the decode step plus ops.llasa_frame_head, its KL goes to slot i of a device buffer, from there to
+        pinned host memory without blocking, followed by an event.  stop_lag = how many frames are enqueued ahead of the
+        event the host waits for (0 or 1)."""
+        if stop_lag not in (0, 1):
+            raise NotImplementedError(f"stop_lag is 0 or 1, got {stop_lag!r}")
+        model = self.base_model.model
+        dlin, alin = self.distribution_linear, self.audio_linear
+        dl = dlin[2].weight.shape[0]
+        if dl % 8 or not 8 <= dl <= ops.HEAD_MAX_LATENT:
+            raise NotImplementedError(f"device_head=True takes a latent_dim that is a multiple of 8 in 8 .. {ops.HEAD_MAX_LATENT}, "
+                                      f"got {dl}; the host path (device_head=False) has no such limit")
+        std = self.std
+        if not (isinstance(std, (int, float)) or (torch.is_tensor(std) and std.numel() == 1)) or not float(std) > 0:
+            raise NotImplementedError("device_head=True takes the fixed scalar std of init_sigmaVAE; any other std runs on the "
+                                      "host path (device_head=False)")
+        std = float(std)
+        embeds = []
+        for ids, lat in prompts:
+            parts = [model.embed_tokens(ids.unsqueeze(0))]
+            if lat is not None:
+                parts.append(alin(lat))
+            embeds.append(torch.cat(parts, dim=1))
+        R, dev = len(embeds), embeds[0].device
+        Dm = embeds[0].shape[2]
+        if noise is not None:
+            noise = noise.to(device=dev, dtype=F32).expand(max_length, R, dl)
+        one = R == 1
+        room = max(e.shape[1] for e in embeds) + max_length
+        cache = model.init_cache(room, dev) if one else model.init_cache_batch(R, room, dev)
+        plan = ops.llasa_head_plan(model.norm.weight, dlin[0].weight, dlin[0].bias, dlin[2].weight, dlin[2].bias, alin.weight,
+                                   alin.bias, R, model.norm.variance_epsilon, dev, frames=max_length)
+        kl_host = torch.empty((max_length, R), dtype=F32, pin_memory=True)
+        events = [None] * max_length
+        active, count = [True] * R, [0] * R
+
+        def enqueue(i):
+            if i == 0:      # prefill: the last position's un-normed residual stream of every prompt
+                if one:
+                    h = model.forward_cached(embeds[0], cache, final_norm=False)[0, -1:, :]
+                else:
+                    h = torch.cat([model.prefill_row(emb, cache, r, final_norm=False)[:, -1, :] for r, emb in enumerate(embeds)])
+            elif one:
+                h = model.forward_cached(plan["x_next"].view(1, 1, Dm), cache, final_norm=False).view(1, Dm)
+            else:
+                h = model.forward_cached_batch(plan["x_next"].view(R, 1, Dm), cache, active, final_norm=False).view(R, Dm)
+            nz = torch.randn((R, 1, dl), device=dev, dtype=F32).view(R, dl) if noise is None else noise[i].contiguous()
+            ops.llasa_frame_head(plan, h, nz, std, None if one else active, frame=i)
+            kl_host[i].copy_(plan["kl"][i], non_blocking=True)
+            events[i] = torch.cuda.Event()
+            events[i].record()
+
+        def resolve(i):     # the one host wait of frame i
+            events[i].synchronize()
+            kl = kl_host[i].tolist()
+            for r in range(R):
+                if active[r]:
+                    count[r] = i + 1
+                    if kl[r] < thres and i > 3:
+                        active[r] = False
+
+        if stop_lag:
+            enqueue(0)
+        for i in range(max_length):
+            if not stop_lag:
+                enqueue(i)
+            elif i + 1 < max_length:
+                enqueue(i + 1)          # (ahead of frame i's event; discarded if frame i turns out to stop every row)
+            resolve(i)
+            if not any(active):
+                break
+        return [plan["latent"][:count[r] - 1, r, :].clone().unsqueeze(0).transpose(1, 2) for r in range(R)]
 
     def init_sigmaVAE(self):
         self.std = torch.tensor(0.5)

@@ -795,6 +795,55 @@ def llama_decode_step(plan, x, t0, cache_rows, rope, eps):
     return out
 
 
+# ---- the per-frame head of KV-cached generation (kalle_llasa_frame_head_rows): final norm, distribution_linear, sample, stop KL,
+# audio_linear in one host call
+HEAD_FIELDS = ("norm", "w1", "b1", "w2", "b2", "wa", "ba")
+HEAD_MAX_LATENT = 512
+
+
+def llasa_head_plan(norm, w1, b1, w2, b2, wa, ba, R, eps, device, frames=1):
+    """The descriptor, workspace and output buffers of the frame head for R rows.  The seven arguments are the PARAMETERS (final
+    RMSNorm weight [D], distribution_linear[0] weight [dl, D] / bias, distribution_linear[2] weight [dl, dl] / bias, audio_linear
+    weight [D, dl] / bias): every call reads the weights' bf16 compute copies through dit_ops.bf16_of, so a changed weight is
+    picked up at the next frame.  frames: how many frames of `latent` [frames, R, dl] and `kl` [frames, R] the plan keeps (the head
+    writes frame i into slot i); `mean` [R, dl] and `x_next` [R, D] are rewritten by every call."""
+    lib = _lib.load()
+    dl, D = w1.shape
+    assert tuple(w2.shape) == (dl, dl) and tuple(wa.shape) == (D, dl) and norm.shape[0] == D
+    nbytes = lib.kalle_llasa_head_ws_bytes(R, D, dl)
+    check(min(nbytes, 0), "kalle_llasa_head_ws_bytes")
+    f32 = dict(device=device, dtype=torch.float32)
+    return {"params": (norm, w1, b1, w2, b2, wa, ba), "desc": _lib.LlasaHead(), "keep": None, "R": R, "D": D, "dl": dl,
+            "eps": float(eps), "frames": frames, "ws": torch.empty(nbytes, device=device, dtype=torch.uint8),
+            "mean": torch.zeros((R, dl), **f32), "latent": torch.zeros((frames, R, dl), **f32),
+            "kl": torch.zeros((frames, R), **f32), "x_next": torch.zeros((R, D), **f32)}
+
+
+def llasa_frame_head(plan, h, noise, std, active=None, frame=0):
+    """one frame's head, one host call.  h: the UN-NORMED residual stream, fp32 [R, D] (rows may be strided); noise fp32 [R, dl]
+    (rows may be strided); active: R host booleans (None: all) - an inactive row's outputs are not touched.  Returns
+    (mean [R, dl], latent [R, dl], kl [R], x_next [R, D]): views of the plan's buffers, latent and kl those of slot `frame`."""
+    from .dit_ops import bf16_of, f32_of
+    lib = _lib.load()
+    R, D, dl = plan["R"], plan["D"], plan["dl"]
+    assert h.dtype == torch.float32 and tuple(h.shape) == (R, D) and h.stride(1) == 1
+    assert noise.dtype == torch.float32 and tuple(noise.shape) == (R, dl) and noise.stride(1) == 1
+    assert 0 <= frame < plan["frames"]
+    desc = plan["desc"]
+    keep = [bf16_of(p) if f[0] == "w" else f32_of(p) for f, p in zip(HEAD_FIELDS, plan["params"])]
+    for f, t in zip(HEAD_FIELDS, keep):
+        assert t.is_contiguous() and t.device == h.device
+        setattr(desc, f, t.data_ptr())
+    desc.ldw1, desc.ldw2, desc.ldwa = D, dl, dl
+    plan["keep"] = keep
+    act = None if active is None else ctypes.cast(_i32([1 if a else 0 for a in active]), ctypes.c_void_p)
+    latent, kl = plan["latent"][frame], plan["kl"][frame]
+    check(lib.kalle_llasa_frame_head_rows(ctypes.addressof(desc), _p(h), h.stride(0), _p(noise), noise.stride(0), float(std),
+                                          plan["eps"], _p(plan["mean"]), _p(latent), _p(kl), _p(plan["x_next"]), act, R, D, dl,
+                                          _p(plan["ws"]), _stream()), "kalle_llasa_frame_head_rows")
+    return plan["mean"], latent, kl, plan["x_next"]
+
+
 def gauss_kl2_fwd(pred, label_mean, label_std, mask_a, mask_b, std_mult=1.25):
     """two-Gaussian KL (model.py:84-100); label_std None -> label_mean is the raw mean | scale label [rows, 2 dim]"""
     lib = _lib.load()

@@ -4,7 +4,10 @@ random weights, synthetic batch: text prefix + audio frames per sample.   python
 The decoder shape is an option (defaults: Llama-3.2-1B): --hidden --layers --heads --kv-heads --head-dim --inner, e.g. the
 Llama-3.2-3B shape  --hidden 3072 --layers 28 --heads 24 --kv-heads 8 --head-dim 128 --inner 8192
 --infer-only: KV-cached generation only; --infer-batch R: also Llasa.infer_batch on R prompts (aggregate and per-row frames/s)
---decode-weights e4m3: the --infer-only and --infer-batch lines with Llasa.quantize_decoder("e4m3") (weight-only FP8 decode steps)"""
+--decode-weights e4m3: the --infer-only and --infer-batch lines with Llasa.quantize_decoder("e4m3") (weight-only FP8 decode steps)
+--device-head: after the host-head lines, the same KV-cached generation with device_head=True (the per-frame head as one call of
+kalle_llasa_frame_head_rows) in the same process, each line with its ratio to the host-head line; --stop-lag N (0 or 1): one more
+set of lines with stop_lag=N"""
 import json, os, sys, tempfile, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from kalle_audio_amd.model_sigmaVAE import Llasa
@@ -27,6 +30,18 @@ if "--decode-weights" in sys.argv:
     _i = sys.argv.index("--decode-weights")
     DECODE_WEIGHTS = sys.argv[_i + 1]
     del sys.argv[_i:_i + 2]
+HEADS = [("host head", {})]                  # (label, keywords of infer / infer_batch); --device-head / --stop-lag N add to it
+if "--device-head" in sys.argv:
+    sys.argv.remove("--device-head")
+    HEADS.append(("device head", dict(device_head=True)))
+if "--stop-lag" in sys.argv:
+    _i = sys.argv.index("--stop-lag")
+    _lag = int(sys.argv[_i + 1])
+    del sys.argv[_i:_i + 2]
+    if len(HEADS) < 2:
+        sys.exit("--stop-lag belongs to --device-head")
+    if _lag:
+        HEADS.append((f"device head, stop_lag={_lag}", dict(device_head=True, stop_lag=_lag)))
 HID, NLAYER = SHAPE["--hidden"], SHAPE["--layers"]
 _pos = [a for a in sys.argv[1:] if not a.startswith("--")]
 B = int(_pos[0]) if len(_pos) > 0 else 8
@@ -92,17 +107,19 @@ if "--infer" in sys.argv or INFER_ONLY:
         print(f"decode weights: {DECODE_WEIGHTS} (use_cache=True lines; quantised at the first step, inside the warm-up call)")
     pid = torch.randint(0, 128264, (64,), device=dev)
     for use_cache, nfr in ((True, 200),) if INFER_ONLY else ((True, 200), (False, 200)):
-        m.infer(pid, None, end_disp_kl_thres=-1.0, max_length=4, use_cache=use_cache)
-        for rep in range(3 if INFER_ONLY else 1):          # (--infer-only: three repeats, for a min and a max)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            out = m.infer(pid, None, end_disp_kl_thres=-1.0, max_length=nfr, use_cache=use_cache)
-            torch.cuda.synchronize()
-            dt = time.perf_counter() - t0
-            print(f"infer use_cache={use_cache}: {nfr} frames in {dt*1e3:.0f} ms = {nfr/dt:.1f} frames/s "
-                  f"({nfr/dt/12.5:.2f} x real time at 12.5 Hz), out {tuple(out.shape)}")
-        if use_cache:
-            one_fps = nfr / dt
+        for label, kw in HEADS if use_cache else HEADS[:1]:
+            m.infer(pid, None, end_disp_kl_thres=-1.0, max_length=4, use_cache=use_cache, **kw)
+            for rep in range(3 if INFER_ONLY else 1):          # (--infer-only: three repeats, for a min and a max)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                out = m.infer(pid, None, end_disp_kl_thres=-1.0, max_length=nfr, use_cache=use_cache, **kw)
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t0
+                tag = "" if not kw else f" [{label}: {nfr/dt/one_fps:.3f} x the host head's last repeat]"
+                print(f"infer use_cache={use_cache}: {nfr} frames in {dt*1e3:.0f} ms = {nfr/dt:.1f} frames/s "
+                      f"({nfr/dt/12.5:.2f} x real time at 12.5 Hz), out {tuple(out.shape)}{tag}")
+            if use_cache and not kw:
+                one_fps = nfr / dt
 
 if INFER_BATCH:
     # the same generation for R utterances at once (Llasa.infer_batch): prompts of 64, 56, 48, ... tokens, 200 frames each
@@ -110,14 +127,18 @@ if INFER_BATCH:
     m.infer_batch_rows = max(m.infer_batch_rows, INFER_BATCH)
     nfr = 200
     prompts = [(torch.randint(0, 128264, (64 - 8 * (r % 4),), device=dev), None) for r in range(INFER_BATCH)]
-    m.infer_batch(prompts, end_disp_kl_thres=-1.0, max_length=4)
-    for rep in range(3):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        outs = m.infer_batch(prompts, end_disp_kl_thres=-1.0, max_length=nfr)
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
-        R = len(outs)
-        print(f"infer_batch R={R} (repeat {rep}): {nfr} frames x {R} rows in {dt*1e3:.0f} ms = {dt/nfr*1e3:.3f} ms/step incl. prefill, "
-              f"{R*nfr/dt:.1f} frames/s aggregate, {nfr/dt:.1f} frames/s per row, "
-              f"{R*nfr/dt/one_fps:.2f} x {R} sequential infer calls ({one_fps:.1f} frames/s), out {tuple(outs[0].shape)}")
+    for label, kw in HEADS:
+        m.infer_batch(prompts, end_disp_kl_thres=-1.0, max_length=4, **kw)
+        for rep in range(3):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            outs = m.infer_batch(prompts, end_disp_kl_thres=-1.0, max_length=nfr, **kw)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            R = len(outs)
+            tag = "" if not kw else f" [{label}: {host_dt/dt:.3f} x the host head's last repeat]"
+            print(f"infer_batch R={R} (repeat {rep}): {nfr} frames x {R} rows in {dt*1e3:.0f} ms = {dt/nfr*1e3:.3f} ms/step incl. prefill, "
+                  f"{R*nfr/dt:.1f} frames/s aggregate, {nfr/dt:.1f} frames/s per row, "
+                  f"{R*nfr/dt/one_fps:.2f} x {R} sequential infer calls ({one_fps:.1f} frames/s), out {tuple(outs[0].shape)}{tag}")
+        if not kw:
+            host_dt = dt
