@@ -239,7 +239,8 @@ class DataParallelTrainer:
             pre = n + "."
             blk._kalle_grad_sinks = {k[len(pre):]: self.flat.grad_view(k) for k in self.flat.names if k.startswith(pre)}
             blk._kalle_grad_accumulate = False
-            blk._kalle_bucket_key = pre
+            # (a block whose parameters are all frozen owns no bucket: nothing of it is cleared, reduced or stepped)
+            blk._kalle_bucket_key = pre if pre in self.flat.bucket_range else None
             blk._kalle_on_backward_done = self._on_block_done
         # consecutive blocks of one transformer know each other: the LayerNorm backward that produces a block's output gradient
         # also adds its column sums into that block's FF-out bias sink (functional.TransformerBlockFn.backward)
@@ -361,6 +362,8 @@ class DataParallelTrainer:
         if not self._sharded_active():
             return
         for _, blk in self.blocks:
+            if blk._kalle_bucket_key is None:
+                continue
             s0, s1, b1, c, o0 = self._shard_range(blk._kalle_bucket_key)
             if c:
                 for buf in (self.exp_avg, self.exp_avg_sq):
@@ -368,9 +371,9 @@ class DataParallelTrainer:
 
     def _on_block_done(self, blk):
         """called (from autograd's backward) right after a block's backward kernels were queued"""
-        if not self._boundary():
-            return
         key = blk._kalle_bucket_key
+        if key is None or not self._boundary():
+            return
         if self._sharded_active():
             ev = None
             if self.flat.grad.is_cuda:
@@ -494,7 +497,7 @@ class DataParallelTrainer:
             else:
                 if grouped:
                     for _, blk in self.blocks:
-                        a, b = self.flat.small_range[blk._kalle_bucket_key]
+                        a, b = self.flat.small_range.get(blk._kalle_bucket_key, (0, 0))
                         if b > a:
                             self.flat.grad[a:b].zero_()
                 for key in ("_rest", "_vae"):

@@ -6,6 +6,10 @@ reference file:line it follows.  It is pinned against golden vectors produced by
 the build container (tests/golden/make_golden.py, make_golden_r02.py -> tests/golden/*.npz; checked in
 tests/test_oracle_golden.py).
 
+The functions preserve the dtype they are given: fp32 state and inputs give the pinned fp32 results bit for bit, an fp64 state
+dict with fp64 inputs runs in fp64 throughout (tables built with arange().float() stay fp32 and are promoted) - the reference of
+the per-slice gradient checks (tests/grad_slices.py), which also patch `linear`, `_attn_operands` and `_softmax` to emulate bf16.
+
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this module.  The product path
 (kalle_audio_amd/*) never does: it runs hand-written HIP kernels and fails loudly without them.
 
@@ -22,6 +26,12 @@ import torch.nn.functional as F
 
 
 # ---------------------------------------------------------------------------------------------- small pieces
+def _stat(x):
+    """the dtype statistics and rotations run in: fp32 for fp32 / bf16 inputs (the reference's `.float()`), fp64 stays fp64 -
+    an fp64 state dict and fp64 inputs run every function of this file in fp64 (the gradient yardstick of tests/grad_slices.py)"""
+    return x if x.dtype == torch.float64 else x.float()
+
+
 def layer_norm(x, gamma, beta=None, eps=1e-5):
     """transformer.py:173-192: F.layer_norm over the last dim with gamma and an (optional) beta buffer."""
     mu = x.mean(-1, keepdim=True)
@@ -32,8 +42,8 @@ def layer_norm(x, gamma, beta=None, eps=1e-5):
 
 def rms_norm(x, scale, eps=1e-6):
     """blocks.py:268-272 (RMSNorm 285-299): x * scale * rsqrt(mean(x^2)+eps), statistics in fp32."""
-    ms = (x.float() ** 2).mean(-1, keepdim=True)
-    return x * (scale.float() * torch.rsqrt(ms + eps)).to(x.dtype)
+    ms = (_stat(x) ** 2).mean(-1, keepdim=True)
+    return x * (_stat(scale) * torch.rsqrt(ms + eps)).to(x.dtype)
 
 
 def snake_beta(x, alpha, beta, logscale=True):
@@ -74,6 +84,17 @@ def linear(x, w, b=None):
     return y + b if b is not None else y
 
 
+def _attn_operands(q, k, v):
+    """the tensors an attention core consumes, after the rotary embedding and before grouped keys are repeated: a seam (identity)
+    where tests/grad_slices.py puts the roundings of a bf16 attention kernel"""
+    return q, k, v
+
+
+def _softmax(dots):
+    """softmax over the keys; the second seam of tests/grad_slices.py (bf16 P, bf16 dS)"""
+    return dots.softmax(-1)
+
+
 def _sub(sd, prefix):
     pl = len(prefix)
     return {k[pl:]: v for k, v in sd.items() if k.startswith(prefix)}
@@ -107,11 +128,12 @@ def attention(sd, x, context=None, mask=None, context_mask=None, rotary=None, di
         q = q / q.norm(dim=-1, keepdim=True).clamp_min(1e-12)
         k = k / k.norm(dim=-1, keepdim=True).clamp_min(1e-12)
     if rotary is not None and context is None:       # 430-444: self-attention only
-        q = apply_rotary(q.float(), rotary)
-        k = apply_rotary(k.float(), rotary)
+        q = apply_rotary(_stat(q), rotary)
+        k = apply_rotary(_stat(k), rotary)
     in_mask = context_mask                            # 446-462
     if in_mask is None and context is None:
         in_mask = mask
+    q, k, v = _attn_operands(q, k, v)
     if h != kv_h:                                     # 505-508 repeat_interleave
         k = k.repeat_interleave(h // kv_h, 1)
         v = v.repeat_interleave(h // kv_h, 1)
@@ -121,7 +143,7 @@ def attention(sd, x, context=None, mask=None, context_mask=None, rotary=None, di
     if causal and dots.shape[-2] > 1:                 # 468-469: a single query is never masked
         i, j = dots.shape[-2:]
         dots = dots.masked_fill(torch.ones(i, j, dtype=torch.bool).triu(j - i + 1), -torch.finfo(dots.dtype).max)
-    attn = dots.softmax(-1)
+    attn = _softmax(dots)
     out = (attn @ v).transpose(1, 2).reshape(B, N, D)
     out = linear(out, sd["to_out.weight"])
     if mask is not None:                              # 543-545 zero padded query rows
@@ -199,7 +221,7 @@ def scaled_sinusoidal_embedding(scale, n, dim, theta=10000.0):
 
 
 def continuous_transformer(sd, x, depth, mask=None, prepend_embeds=None, prepend_mask=None, global_cond=None,
-                           context=None, context_mask=None, dim_heads=64, rotary=True, causal=False):
+                           context=None, context_mask=None, dim_heads=64, rotary=True, causal=False, qk_l2=False):
     """transformer.py:758-812: project_in, prepend (+mask cat 776-787), rotary over the full length, the optional position
     embedding added to the sequence (796-797: ScaledSinusoidalEmbedding when the state has pos_emb.scale,
     AbsolutePositionalEmbedding 45-65 = emb.weight[arange(n)] * dim^-0.5 when it has pos_emb.emb.weight), blocks,
@@ -224,7 +246,7 @@ def continuous_transformer(sd, x, depth, mask=None, prepend_embeds=None, prepend
     # (pinned by tests/golden/training_step.npz, whose steps run with mask_padding=True)
     for i in range(depth):
         x = transformer_block(_sub(sd, f"layers.{i}."), x, context=context, global_cond=global_cond, mask=None,
-                              context_mask=context_mask, rotary=rot, dim_heads=dim_heads, causal=causal)
+                              context_mask=context_mask, rotary=rot, dim_heads=dim_heads, causal=causal, qk_l2=qk_l2)
     if "project_out.weight" in sd:
         x = linear(x, sd["project_out.weight"])
     return x
@@ -239,7 +261,8 @@ def _mlp2(sd, pre, x, bias):
 def dit_inner(sd, cfg, x, t, mask=None, cross_attn_cond=None, cross_attn_cond_mask=None, global_embed=None,
               prepend_cond=None, prepend_cond_mask=None):
     """dit.py:135-229 (_forward), continuous_transformer branch. cfg: dict(depth, num_heads, embed_dim,
-    global_cond_type)."""
+    global_cond_type; optional causal, qk_l2: ContinuousTransformer(causal=True) / attn_kwargs qk_norm="l2" handed through **kwargs,
+    dit.py:115-125 - qk_norm="ln" and the conformer show in the state dict)."""
     D = cfg["embed_dim"]
     dh = D // cfg["num_heads"]
     if cross_attn_cond is not None:
@@ -265,7 +288,8 @@ def dit_inner(sd, cfg, x, t, mask=None, cross_attn_cond=None, cross_attn_cond_ma
     x = x.transpose(1, 2)                                        # b c t -> b t c
     out = continuous_transformer(_sub(sd, "transformer."), x, cfg["depth"], mask=mask, prepend_embeds=prepend_inputs,
                                  prepend_mask=prepend_mask, global_cond=global_embed if gtype == "adaLN" else None,
-                                 context=cross_attn_cond, context_mask=cross_attn_cond_mask, dim_heads=dh)
+                                 context=cross_attn_cond, context_mask=cross_attn_cond_mask, dim_heads=dh,
+                                 causal=cfg.get("causal", False), qk_l2=cfg.get("qk_l2", False))
     out = out.transpose(1, 2)[:, :, plen:]
     return F.conv1d(out, sd["postprocess_conv.weight"]) + out   # dit.py:224
 
@@ -473,19 +497,20 @@ def block_shapes(D, dim_heads=64, dim_context=None, global_cond_dim=None, prefix
 
 
 def continuous_transformer_shapes(D, depth, dim_in=None, dim_out=None, dim_context=None, global_cond_dim=None,
-                                  prefix=""):
+                                  prefix="", dim_heads=64, qk_ln=False, conformer=False):
     s = []
     if dim_in is not None:
         s.append((prefix + "project_in.weight", (D, dim_in)))
     if dim_out is not None:
         s.append((prefix + "project_out.weight", (dim_out, D)))
     for i in range(depth):
-        s += block_shapes(D, dim_context=dim_context, global_cond_dim=global_cond_dim, prefix=f"{prefix}layers.{i}.")
+        s += block_shapes(D, dim_heads=dim_heads, dim_context=dim_context, global_cond_dim=global_cond_dim,
+                          prefix=f"{prefix}layers.{i}.", qk_ln=qk_ln, conformer=conformer)
     return s
 
 
 def dit_shapes(io_channels, embed_dim, depth, cond_token_dim=0, global_cond_dim=0, prepend_cond_dim=0,
-               global_cond_type="prepend", project_cond_tokens=True):
+               global_cond_type="prepend", project_cond_tokens=True, dim_heads=64, qk_ln=False, conformer=False):
     """dit.py:14-133 parameter inventory (continuous_transformer branch)."""
     D = embed_dim
     s = [("timestep_features.weight", (128, 1)), ("to_timestep_embed.0.weight", (D, 256)),
@@ -501,7 +526,7 @@ def dit_shapes(io_channels, embed_dim, depth, cond_token_dim=0, global_cond_dim=
     s += continuous_transformer_shapes(D, depth, dim_in=io_channels, dim_out=io_channels,
                                        dim_context=ce if cond_token_dim > 0 else None,
                                        global_cond_dim=D if global_cond_type == "adaLN" else None,
-                                       prefix="transformer.")
+                                       prefix="transformer.", dim_heads=dim_heads, qk_ln=qk_ln, conformer=conformer)
     s += [("preprocess_conv.weight", (io_channels, io_channels, 1)),
           ("postprocess_conv.weight", (io_channels, io_channels, 1))]
     return s
@@ -769,22 +794,22 @@ def llama_layer(sd, x, cos, sin, allow, H, Hkv, eps):
     B, L, D = x.shape
     hd = D // H
     h = llama_rms_norm(x, sd["input_layernorm.weight"], eps)
-    q = (h @ sd["self_attn.q_proj.weight"].T).view(B, L, H, hd).transpose(1, 2)
-    k = (h @ sd["self_attn.k_proj.weight"].T).view(B, L, Hkv, hd).transpose(1, 2)
-    v = (h @ sd["self_attn.v_proj.weight"].T).view(B, L, Hkv, hd).transpose(1, 2)
+    q = linear(h, sd["self_attn.q_proj.weight"]).view(B, L, H, hd).transpose(1, 2)
+    k = linear(h, sd["self_attn.k_proj.weight"]).view(B, L, Hkv, hd).transpose(1, 2)
+    v = linear(h, sd["self_attn.v_proj.weight"]).view(B, L, Hkv, hd).transpose(1, 2)
 
     def rope(t):
         return t * cos + torch.cat([-t[..., hd // 2:], t[..., :hd // 2]], -1) * sin
-    q, k = rope(q), rope(k)
+    q, k, v = _attn_operands(rope(q), rope(k), v)
     k = k.repeat_interleave(H // Hkv, 1)
     v = v.repeat_interleave(H // Hkv, 1)
     dots = (q @ k.transpose(-1, -2)) * hd ** -0.5
     dots = dots.masked_fill(~allow, torch.finfo(dots.dtype).min)
-    a = (dots.softmax(-1) @ v).transpose(1, 2).reshape(B, L, D)
-    x = x + a @ sd["self_attn.o_proj.weight"].T
+    a = (_softmax(dots) @ v).transpose(1, 2).reshape(B, L, D)
+    x = x + linear(a, sd["self_attn.o_proj.weight"])
     h = llama_rms_norm(x, sd["post_attention_layernorm.weight"], eps)
-    m = F.silu(h @ sd["mlp.gate_proj.weight"].T) * (h @ sd["mlp.up_proj.weight"].T)
-    return x + m @ sd["mlp.down_proj.weight"].T
+    m = F.silu(linear(h, sd["mlp.gate_proj.weight"])) * linear(h, sd["mlp.up_proj.weight"])
+    return x + linear(m, sd["mlp.down_proj.weight"])
 
 
 def llama_model(sd, cfg, inputs_embeds, attention_mask):
@@ -807,11 +832,11 @@ def llasa_forward(sd, cfg, batch, eps, std=0.5):
     m = _sub(sd, "base_model.model.")
     text = m["embed_tokens.weight"][batch["input_ids"]]
     lat = batch["audio_latents"] + std * eps                                        # sample(), dist_type 'fix'
-    audio = lat @ sd["audio_linear.weight"].T + sd["audio_linear.bias"]
+    audio = linear(lat, sd["audio_linear.weight"], sd["audio_linear.bias"])
     x = audio * batch["audio_mask"].unsqueeze(-1) + text * batch["ids_mask"].unsqueeze(-1)
     hidden = llama_model(m, cfg["llama"], x, batch["ids_mask"] + batch["audio_mask"])
-    h = hidden @ sd["distribution_linear.0.weight"].T + sd["distribution_linear.0.bias"]
-    pred = F.gelu(h) @ sd["distribution_linear.2.weight"].T + sd["distribution_linear.2.bias"]
+    h = linear(hidden, sd["distribution_linear.0.weight"], sd["distribution_linear.0.bias"])
+    pred = linear(F.gelu(h), sd["distribution_linear.2.weight"], sd["distribution_linear.2.bias"])
     kl = ((pred - batch["audio_distribution_l"]) ** 2 / (2 * std * std)).sum(2) / lat.shape[-1]
     tm, em = batch["target_mask"], batch["end_mask"]
     return {"audio_loss": (kl * tm).sum() / tm.sum(), "end_loss": (kl * em).sum() / em.sum(), "pre_mean": pred,
@@ -827,11 +852,11 @@ def llasa_model_forward(sd, cfg, batch, mean_stdev_fn):
     m = _sub(sd, "base_model.model.")
     text = m["embed_tokens.weight"][batch["input_ids"]]
     lat = batch["audio_latents"]
-    audio = lat @ sd["audio_linear.weight"].T + sd["audio_linear.bias"]
+    audio = linear(lat, sd["audio_linear.weight"], sd["audio_linear.bias"])
     x = audio * batch["audio_mask"].unsqueeze(-1) + text * batch["ids_mask"].unsqueeze(-1)
     hidden = llama_model(m, cfg["llama"], x, batch["ids_mask"] + batch["audio_mask"])
-    h = hidden @ sd["distribution_linear.0.weight"].T + sd["distribution_linear.0.bias"]
-    pred = F.gelu(h) @ sd["distribution_linear.2.weight"].T + sd["distribution_linear.2.bias"]
+    h = linear(hidden, sd["distribution_linear.0.weight"], sd["distribution_linear.0.bias"])
+    pred = linear(F.gelu(h), sd["distribution_linear.2.weight"], sd["distribution_linear.2.bias"])
     mean1, std1 = mean_stdev_fn(batch["audio_distribution_l"].transpose(1, 2))
     mean1, std1 = mean1.transpose(1, 2), std1.transpose(1, 2) * 1.25                   # model.py:85-87
     mean2, logs2 = pred.chunk(2, dim=2)
