@@ -772,6 +772,39 @@ int kalle_llasa_head_ws_bytes(int R, int D, int dl);
 int kalle_llasa_frame_head_rows(const kalle_llasa_head* head, const float* h, int64_t ldh, const float* noise, int64_t ldn,
                                 float std, float eps, float* mean, float* latent, float* kl, float* x_next,
                                 const int32_t* active, int R, int D, int dl, void* workspace, void* stream);
+/* ---- the same for the head that predicts its scale (model.py:109-150; infer_0828_sigma.py:319-323): mean || log-scale ----------
+ * The descriptor is kalle_llasa_head with d2 = 2 * lat output rows in distribution_linear:
+ *   w1 bf16 [d2][ldw1 >= D], b1 fp32 [d2];  w2 bf16 [d2][ldw2 >= d2], b2 fp32 [d2];  wa bf16 [D][ldwa >= lat], ba fp32 [D].
+ * For each active row r of the R rows, from h = the UN-NORMED residual stream, fp32 [R][ldh >= D]:
+ *   xn     = bf16(rmsnorm(h[r]; norm, eps))                                    (as above)
+ *   h1     = W1 . xn + b1                            fp32 [d2]                 distribution_linear[0]
+ *   a      = bf16(gelu(h1))                                                    the exact GELU of kalle_gelu_fwd (one device function)
+ *   disp   = W2 . a + b2                             fp32 [R][d2]              distribution_linear[2]: mean = disp[:lat],
+ *                                                                              logs = disp[lat:] - what `infer` stacks and returns
+ *   s      = exp(logs)                               fp32 [R][lat]             (expf of this build)
+ *   latent = mean + s * noise[r]                     fp32 [R][lat]             noise fp32 [R][ldn >= lat]
+ *   kl[r]  = (1/lat) sum_j [ (1 - logs_j) + (s_j^2 + (mean_j - 1)^2) / (2 e^2) - 1/2 ]   KL(N(mean, s) || N(1, e)) / lat (:133-136)
+ *   x_next = Wa . bf16(latent) + ba                  fp32 [R][D]               audio_linear: the next decode step's input
+ * bf16 roundings at exactly the three marked points; all else fp32.  There is no std argument.
+ * Four launches, as above: the RMSNorm pre-pass and the R-row GEMM for W1, one kernel with a workgroup per active row for GELU,
+ * W2, exp, the sample and the KL, the R-row GEMM for Wa.  In the middle kernel rows j and j + lat of the W2 walk are finished
+ * by different lanes (at d2 = 512 in different passes), so disp goes through LDS and a second phase after a barrier computes
+ * s, latent, bf16(latent) and the KL terms, which one wave sums in a fixed order.  No atomics, no workgroup reads what another
+ * writes: two calls on the same input give the same bits, and an active row's bits do not depend on which other rows are
+ * active.  active: HOST int32 [R] as above - nothing of an inactive row is read or written, in the outputs or the workspace;
+ * NULL = every row active.  Every row inactive: KALLE_OK, nothing launched.
+ * Limits: 1 <= R <= KALLE_DECODE_MAX_ROWS; D % 8 == 0, 8 <= D <= 32768; lat % 8 == 0, 8 <= lat <= 256 (d2 <= 512: one workgroup
+ * streams the d2 x d2 matrix per row, 512 KiB at the bound); ldh % 4 == 0, ldh >= D; ldn >= lat; ldw* % 8 == 0 and not below
+ * the row they hold (D, d2, lat).  Anything else, or a NULL argument or descriptor field other than active / stream, returns
+ * KALLE_ERR_ARG before the first HIP call.  Every launch is checked where it is made.
+ * Workspace (kalle_llasa_head2_ws_bytes(R, D, lat) bytes, 64-byte aligned, caller-owned; KALLE_ERR_ARG outside the limits), in
+ * this order, each region padded to a multiple of 64 bytes, rows dense:
+ *   xn bf16 [R][D] | h1 fp32 [R][d2] | a bf16 [R][d2] | s fp32 [R][lat] | lat bf16 [R][lat] (= bf16(latent))
+ * They are published so that every stage can be checked from its own inputs. */
+int kalle_llasa_head2_ws_bytes(int R, int D, int lat);
+int kalle_llasa_frame_head2_rows(const kalle_llasa_head* head, const float* h, int64_t ldh, const float* noise, int64_t ldn,
+                                 float eps, float* disp, float* latent, float* kl, float* x_next, const int32_t* active, int R,
+                                 int D, int lat, void* workspace, void* stream);
 /* waveform -> int16 PCM as the inference scripts write it (infer_0723.py:293): out = int16(clamp(x / max|x|, -1, 1) * 32767);
  * peak: one fp32 of device scratch that receives max|x|; x fp32 or bf16 */
 int kalle_peak_normalize_int16(const void* x, int dtype, float* peak, int16_t* out, int64_t n, void* stream);

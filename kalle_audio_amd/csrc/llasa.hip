@@ -822,6 +822,97 @@ __global__ __launch_bounds__(256) void llasa_head_kernel(const float* __restrict
     }
 }
 
+// ---- the same stage for the head that predicts its scale (model.py:109-150, kalle_llasa_frame_head2_rows) -------------------------
+// One workgroup per active row r, d2 = 2 lat:  a = bf16(gelu(h1[r])),  disp = W2 . a + b2  (mean = disp[:lat], logs = disp[lat:]),
+// s = exp(logs),  latent = mean + s * noise[r],  lat = bf16(latent),
+// kl[r] = (1/lat) sum_j [(1 - logs_j) + (s_j^2 + (mean_j - 1)^2) c1 - 1/2]  with c1 = 1 / (2 e^2).
+// Phase 1 is the W2 walk of llasa_head_kernel over d2 rows (written out again, so that kernel's summation order and bits stay as
+// they are): rows j and j + lat are finished by different lane groups and, at d2 = 512, in different passes, so the finished
+// row goes to global `disp` and to LDS.  Phase 2, after a barrier: thread j < lat reads mean_j and logs_j from LDS and computes
+// everything that needs both; the KL terms meet in LDS and wave 0 sums them in a fixed order.  No atomics, nothing another
+// workgroup writes is read: a row's bits depend on that row alone.
+__global__ __launch_bounds__(256) void llasa_head2_kernel(const float* __restrict__ h1, const bf16_t* __restrict__ W2, int64_t ldw2,
+                                                          const float* __restrict__ b2, const float* __restrict__ noise,
+                                                          int64_t ldn, float c1, bf16_t* __restrict__ a_out,
+                                                          float* __restrict__ disp, float* __restrict__ s_out,
+                                                          float* __restrict__ latent, bf16_t* __restrict__ lat,
+                                                          float* __restrict__ kl, int dl, int lgG, unsigned active) {
+    __shared__ float dsp[512];
+    __shared__ float term[256];
+    const int r = blockIdx.x;
+    if (!(active >> r & 1)) return;
+    constexpr int PF = 8;
+    const int d2 = 2 * dl;
+    const int G = 1 << lgG, ngrp = 256 >> lgG, nc = d2 >> 3;
+    const int c = threadIdx.x & (G - 1), grp = threadIdx.x >> lgG;
+    const bool in = c < nc;
+    auto load = [&](int base, i32x4* w) {
+#pragma unroll
+        for (int p = 0; p < PF; ++p) {
+            const int j = base + p * ngrp + grp;
+            w[p] = i32x4{0, 0, 0, 0};
+            if (in) w[p] = *reinterpret_cast<const i32x4*>(W2 + (int64_t)(j < d2 ? j : d2 - 1) * ldw2 + 8 * c);
+        }
+    };
+    i32x4 w[PF];
+    load(0, w);                                   // (the weight stream does not wait for the activations)
+    float x[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (in) {
+        const float* hr = h1 + (int64_t)r * d2 + 8 * c;
+        const f32x4 lo = *reinterpret_cast<const f32x4*>(hr), hi = *reinterpret_cast<const f32x4*>(hr + 4);
+        i32x4 o;
+        o[0] = (int)pack_bf16x2(gelu_exact(lo[0]), gelu_exact(lo[1]));
+        o[1] = (int)pack_bf16x2(gelu_exact(lo[2]), gelu_exact(lo[3]));
+        o[2] = (int)pack_bf16x2(gelu_exact(hi[0]), gelu_exact(hi[1]));
+        o[3] = (int)pack_bf16x2(gelu_exact(hi[2]), gelu_exact(hi[3]));
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { x[2 * e] = bf16lo((uint32_t)o[e]); x[2 * e + 1] = bf16hi((uint32_t)o[e]); }
+        if (grp == 0) *reinterpret_cast<i32x4*>(a_out + (int64_t)r * d2 + 8 * c) = o;
+    }
+    for (int base = 0; base < d2; base += ngrp * PF) {          // (uniform over the workgroup: every lane takes every shuffle)
+        i32x4 wn[PF];
+        const bool more = base + ngrp * PF < d2;
+        if (more) load(base + ngrp * PF, wn);
+#pragma unroll
+        for (int p = 0; p < PF; ++p) {
+            float s = 0.f;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) s += bf16lo((uint32_t)w[p][e]) * x[2 * e] + bf16hi((uint32_t)w[p][e]) * x[2 * e + 1];
+            for (int o = G >> 1; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+            const int j = base + p * ngrp + grp;
+            if (c == 0 && j < d2) {
+                const float v = s + b2[j];
+                disp[(int64_t)r * d2 + j] = v;
+                dsp[j] = v;
+            }
+        }
+        if (more) {
+#pragma unroll
+            for (int p = 0; p < PF; ++p) w[p] = wn[p];
+        }
+    }
+    __syncthreads();
+    const int j = threadIdx.x;                    // lat <= 256: one thread per latent element
+    if (j < dl) {
+        const float m = dsp[j], lg = dsp[j + dl];
+        const float sc = expf(lg);
+        const float z = m + sc * noise[r * ldn + j];
+        const int64_t at = (int64_t)r * dl + j;
+        s_out[at] = sc;
+        latent[at] = z;
+        lat[at] = f32_to_bf16(z);
+        const float d = m - 1.f;
+        term[j] = (1.f - lg) + (sc * sc + d * d) * c1 - 0.5f;
+    }
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        float s = 0.f;
+        for (int t = threadIdx.x; t < dl; t += 64) s += term[t];
+        s = wave_sum(s);
+        if (threadIdx.x == 0) kl[r] = s / (float)dl;
+    }
+}
+
 // KL( N(pred, s) || N(label, s) ) = (pred - label)^2 / (2 s^2), summed over the latent dim / dim, then the two masked
 // sums over rows (model_sigmaVAE.py:85-95).  One wave per row; sums[0..3] += {kl*ma, ma, kl*mb, mb}.
 __global__ __launch_bounds__(256) void gauss_kl_fwd_kernel(const float* __restrict__ pred, const float* __restrict__ label,
@@ -1236,6 +1327,75 @@ extern "C" int kalle_llasa_frame_head_rows(const kalle_llasa_head* head, const f
     if (rc != KALLE_OK) return rc;
     return proj_launch({head->wa, head->ldwa, nullptr}, lat, dl, PRO_BF16, nullptr, 0.f, nullptr, 0, x_next, D, true, x_next, D,
                        head->ba, 0, &a, D, dl, st);
+}
+
+// ---- the same for the head that predicts mean || log-scale (model.py:109-150) ---------------------------------------------------
+namespace {
+
+struct Head2Ws {                    // byte offsets
+    int64_t xn, h1, a, s, lat;      // bf16 [R][D] | fp32 [R][d2] | bf16 [R][d2] | fp32 [R][lat] | bf16 [R][lat]
+    int64_t end;
+};
+
+inline Head2Ws head2_ws(int R, int D, int lat) {
+    auto pad = [](int64_t b) { return (b + 63) & ~(int64_t)63; };
+    const int64_t d2 = 2 * (int64_t)lat;
+    Head2Ws w;
+    w.xn = 0;
+    w.h1 = w.xn + pad((int64_t)R * D * 2);
+    w.a = w.h1 + pad(R * d2 * 4);
+    w.s = w.a + pad(R * d2 * 2);
+    w.lat = w.s + pad((int64_t)R * lat * 4);
+    w.end = w.lat + pad((int64_t)R * lat * 2);
+    return w;
+}
+
+inline bool head2_dims_ok(int R, int D, int lat) {
+    return R >= 1 && R <= KALLE_DECODE_MAX_ROWS && D >= 8 && !(D & 7) && D <= 32768 && lat >= 8 && !(lat & 7) && lat <= 256;
+}
+
+}  // namespace
+
+extern "C" int kalle_llasa_head2_ws_bytes(int R, int D, int lat) {
+    if (!head2_dims_ok(R, D, lat)) return KALLE_ERR_ARG;
+    return (int)head2_ws(R, D, lat).end;
+}
+
+extern "C" int kalle_llasa_frame_head2_rows(const kalle_llasa_head* head, const float* h, int64_t ldh, const float* noise,
+                                            int64_t ldn, float eps, float* disp, float* latent, float* kl, float* x_next,
+                                            const int32_t* active, int R, int D, int lat, void* workspace, void* stream) {
+    if (!head || !h || !noise || !disp || !latent || !kl || !x_next || !workspace) return KALLE_ERR_ARG;
+    if (!head->norm || !head->w1 || !head->b1 || !head->w2 || !head->b2 || !head->wa || !head->ba) return KALLE_ERR_ARG;
+    if (!head2_dims_ok(R, D, lat)) return KALLE_ERR_ARG;
+    const int d2 = 2 * lat;
+    if ((ldh & 3) || ldh < D || ldn < lat) return KALLE_ERR_ARG;
+    if ((head->ldw1 & 7) || head->ldw1 < D || (head->ldw2 & 7) || head->ldw2 < d2 || (head->ldwa & 7) || head->ldwa < lat)
+        return KALLE_ERR_ARG;
+    RowsArgs a{};
+    a.R = R;
+    for (int r = 0; r < R; ++r)
+        if (!active || active[r]) a.active |= 1u << r;
+    if (!a.active) return KALLE_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const Head2Ws o = head2_ws(R, D, lat);
+    char* ws = static_cast<char*>(workspace);
+    bf16_t* xn = reinterpret_cast<bf16_t*>(ws + o.xn);       // bf16(rmsnorm(h))
+    float* h1 = reinterpret_cast<float*>(ws + o.h1);         // W1 . xn + b1
+    bf16_t* ga = reinterpret_cast<bf16_t*>(ws + o.a);        // bf16(gelu(h1))
+    float* sc = reinterpret_cast<float*>(ws + o.s);          // exp(logs)
+    bf16_t* lb = reinterpret_cast<bf16_t*>(ws + o.lat);      // bf16(latent)
+    int rc = proj_launch({head->w1, head->ldw1, nullptr}, h, ldh, PRO_RMS, head->norm, eps, xn, D, h1, d2, true, h1, d2, head->b1, 0,
+                         &a, d2, D, st);
+    if (rc != KALLE_OK) return rc;
+    int lg = 0;
+    while ((8 << lg) < d2) ++lg;                             // G = 1 << lg lanes per weight row, the power of two >= d2 / 8
+    const float c1 = (float)(0.5 / (M_E * M_E));             // 1 / (2 e^2)
+    KALLE_LAUNCH(llasa_head2_kernel, dim3(R), dim3(256), 0, st, h1, static_cast<const bf16_t*>(head->w2), head->ldw2, head->b2, noise,
+                 ldn, c1, ga, disp, sc, latent, lb, kl, lat, lg, a.active);
+    rc = kalle_check_launch();
+    if (rc != KALLE_OK) return rc;
+    return proj_launch({head->wa, head->ldwa, nullptr}, lb, lat, PRO_BF16, nullptr, 0.f, nullptr, 0, x_next, D, true, x_next, D,
+                       head->ba, 0, &a, D, lat, st);
 }
 
 // ---- weight-only e4m3 decoding -----------------------------------------------------------------------------------------------

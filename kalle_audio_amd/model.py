@@ -18,7 +18,8 @@ from torch import nn
 from . import functional as Fn
 from . import ops
 from .dit_ops import F32
-from .model_sigmaVAE import GELU, EmbedMixFn, Linear, LlamaForCausalLM, _need_gpu
+from .model_sigmaVAE import (GELU, EmbedMixFn, Linear, LlamaForCausalLM, _need_gpu, device_head_limits, generate_batch,
+                             generate_device_head)
 
 get_mean_stdev_from_stableaudio2_latents = None      # injectable stand-in for the missing twj_utils function (see above)
 LABEL_STD_MULT = 1.25                                # model.py:87
@@ -91,11 +92,22 @@ class Llasa(nn.Module):
 
     @torch.no_grad()
     def infer(self, input_ids, audio_latents, end_disp_kl_thres=0.5, max_length=1000, sample=False, use_cfg=None,
-              flow=None, use_cache=True):
+              flow=None, use_cache=True, device_head=False, noise=None, stop_lag=0):
         """model.py:109-150: frame-by-frame generation; every frame is drawn from N(mean, exp(log_scale)) and generation
         stops when KL(N(mean, s) || N(1, e)) / dim < threshold (and i > 3).  Returns [1, 2*lat, T'] (mean || log-scale rows,
         as the reference stacks `last_disp`).  use_cache: prefill once, then one position per frame against a KV cache
-        (same arithmetic per position); use_cache=False re-runs the whole prefix per frame as the reference does."""
+        (same arithmetic per position); use_cache=False re-runs the whole prefix per frame as the reference does.
+        device_head / noise / stop_lag (extensions, opt-in): as documented on model_sigmaVAE.Llasa.infer - everything between
+        two decode steps is one call of kalle_llasa_frame_head2_rows, `noise` is the N(0, 1) draws, fp32, broadcastable to
+        [max_length, 1, latent_dim] (default: one torch.randn((1, 1, latent_dim)) per frame, the shape and order the host path
+        draws in), stop_lag=1 enqueues frame i + 1 before frame i's KL is read and returns the same bits."""
+        if device_head:
+            if not use_cache:
+                raise NotImplementedError("device_head=True generates against a KV cache; use_cache=False runs on the host path "
+                                          "(device_head=False)")
+            return self._generate_device_head([(input_ids, audio_latents)], end_disp_kl_thres, max_length, noise, stop_lag)[0]
+        if noise is not None or stop_lag:
+            raise ValueError("noise= and stop_lag= belong to device_head=True")
         ids = input_ids.unsqueeze(0)
         parts = [self.base_model.model.embed_tokens(ids)]
         if audio_latents is not None:
@@ -105,17 +117,10 @@ class Llasa(nn.Module):
         model = self.base_model.model
         cache = model.init_cache(input_embed.shape[1] + max_length, input_embed.device) if use_cache else None
         step_in = input_embed
-        e = float(torch.e)
         for i in range(max_length):
             hidden = model.forward_cached(step_in, cache) if use_cache else model(inputs_embeds=input_embed)[0]
-            last_disp = self.distribution_linear(hidden[:, -1:, :].contiguous())
-            lat = last_disp.shape[-1] // 2
-            mean, logs = last_disp[..., :lat].float(), last_disp[..., lat:].float()
-            s = torch.exp(logs)
-            audio_latent = ops.axpby(mean.contiguous(), (torch.randn_like(mean) * s).contiguous(), 1.0, 1.0)
+            last_disp, audio_latent, kl = self._host_frame(hidden[:, -1:, :])
             final.append(last_disp)
-            # KL(N(m, s) || N(1, e)) = log(e / s) + (s^2 + (m - 1)^2) / (2 e^2) - 1/2    (model.py:133-136)
-            kl = ((1.0 - logs) + (s * s + (mean - 1.0) ** 2) / (2 * e * e) - 0.5).sum(2) / lat
             if kl.item() < end_disp_kl_thres and i > 3:
                 break
             step_in = self.audio_linear(audio_latent)
@@ -123,3 +128,43 @@ class Llasa(nn.Module):
                 input_embed = torch.cat((input_embed, step_in), dim=1)
         out = torch.stack(final[:-1], dim=1).squeeze(1).squeeze(2)
         return out.transpose(1, 2)
+
+    def _host_frame(self, hidden):
+        """the head of one frame on the host for the rows of hidden [R, 1, D]: (last_disp [R, 1, 2 lat], the sampled latent
+        [R, 1, lat], kl [R, 1]); one torch.randn_like per call, so R rows draw [R, 1, lat] at once"""
+        e = float(torch.e)
+        last_disp = self.distribution_linear(hidden.contiguous())
+        lat = last_disp.shape[-1] // 2
+        mean, logs = last_disp[..., :lat].float(), last_disp[..., lat:].float()
+        s = torch.exp(logs)
+        audio_latent = ops.axpby(mean.contiguous(), (torch.randn_like(mean) * s).contiguous(), 1.0, 1.0)
+        # KL(N(m, s) || N(1, e)) = log(e / s) + (s^2 + (m - 1)^2) / (2 e^2) - 1/2    (model.py:133-136)
+        kl = ((1.0 - logs) + (s * s + (mean - 1.0) ** 2) / (2 * e * e) - 0.5).sum(2) / lat
+        return last_disp, audio_latent, kl
+
+    infer_batch_rows = ops.DECODE_MAX_ROWS      # sequences decoded per step by infer_batch (the kernels take up to DECODE_MAX_ROWS)
+
+    @torch.no_grad()
+    def infer_batch(self, prompts, end_disp_kl_thres=0.5, max_length=1000, device_head=False, noise=None, stop_lag=0):
+        """`infer` (KV-cached) for a list of (input_ids, audio_latents or None), as model_sigmaVAE.Llasa.infer_batch: the
+        utterances of a group (up to `infer_batch_rows`) share one decoder pass per frame, a row that meets the stop rule leaves
+        the batch while the others go on, longer lists run in groups, one prompt is `infer` itself.  Returns a list with what
+        `infer` returns for each prompt.  device_head / noise / stop_lag: as in `infer`, noise broadcastable to
+        [max_length, len(prompts), latent_dim] and drawn, when absent, as one torch.randn((R, 1, latent_dim)) per frame."""
+        return generate_batch(self, prompts, end_disp_kl_thres, max_length, device_head, noise, stop_lag,
+                              self.audio_linear.weight.shape[1])
+
+    def _generate_device_head(self, prompts, thres, max_length, noise, stop_lag):
+        """generate_device_head with the mean || log-scale head (ops.llasa_frame_head2); returns the stacked `disp` rows"""
+        dlin, alin, model = self.distribution_linear, self.audio_linear, self.base_model.model
+        lat = alin.weight.shape[1]
+        device_head_limits(stop_lag, lat, ops.HEAD2_MAX_LATENT)
+
+        def plan_of(R, dev, frames):
+            return ops.llasa_head2_plan(model.norm.weight, dlin[0].weight, dlin[0].bias, dlin[2].weight, dlin[2].bias, alin.weight,
+                                        alin.bias, R, model.norm.variance_epsilon, dev, frames=frames)
+
+        def head(plan, h, nz, active, frame):
+            ops.llasa_frame_head2(plan, h, nz, active, frame=frame)
+
+        return generate_device_head(self, prompts, thres, max_length, noise, stop_lag, lat, plan_of, head, "disp")

@@ -488,6 +488,135 @@ def _read_hf_weights(path):
     return None
 
 
+def device_head_limits(stop_lag, lat, max_lat):
+    """the refusals both task models share before a device-head generation starts"""
+    if stop_lag not in (0, 1):
+        raise NotImplementedError(f"stop_lag is 0 or 1, got {stop_lag!r}; the host path (device_head=False) takes neither")
+    if lat % 8 or not 8 <= lat <= max_lat:
+        raise NotImplementedError(f"device_head=True takes a latent_dim that is a multiple of 8 in 8 .. {max_lat}, "
+                                  f"got {lat}; the host path (device_head=False) has no such limit")
+
+
+def _prompt_embeds(owner, prompts):
+    model = owner.base_model.model
+    embeds = []
+    for ids, lat in prompts:
+        parts = [model.embed_tokens(ids.unsqueeze(0))]
+        if lat is not None:
+            parts.append(owner.audio_linear(lat))
+        embeds.append(torch.cat(parts, dim=1))
+    return embeds
+
+
+def generate_batch(owner, prompts, thres, max_length, device_head, noise, stop_lag, lat):
+    """`infer_batch` of both task models: the checks, one prompt = `owner.infer`, lists longer than `owner.infer_batch_rows` in
+    groups, a group through owner._generate_device_head or through generate_host_batch with owner._host_frame"""
+    prompts = list(prompts)
+    if not prompts:
+        return []
+    if not device_head and (noise is not None or stop_lag):
+        raise ValueError("noise= and stop_lag= belong to device_head=True")
+    if device_head and noise is not None:
+        noise = noise.to(F32).expand(max_length, len(prompts), lat)
+    if len(prompts) == 1:
+        return [owner.infer(prompts[0][0], prompts[0][1], end_disp_kl_thres=thres, max_length=max_length,
+                            device_head=device_head, noise=noise, stop_lag=stop_lag)]
+    G = max(1, min(int(owner.infer_batch_rows), ops.DECODE_MAX_ROWS))
+    if len(prompts) > G:
+        return [o for i in range(0, len(prompts), G)
+                for o in generate_batch(owner, prompts[i:i + G], thres, max_length, device_head,
+                                        None if noise is None else noise[:, i:i + G], stop_lag, lat)]
+    if device_head:
+        return owner._generate_device_head(prompts, thres, max_length, noise, stop_lag)
+    return generate_host_batch(owner, prompts, thres, max_length, owner._host_frame)
+
+
+def generate_host_batch(owner, prompts, thres, max_length, frame):
+    """One group of `infer_batch` with the head on the host, for both task models (model_sigmaVAE.Llasa, model.Llasa).
+    frame(hidden [R, 1, D]) -> (kept [R, 1, w], audio_latent [R, 1, lat], kl [R, 1]): `kept` is what the caller's `infer`
+    stacks per frame (the sampled latent / mean || log-scale), `audio_latent` feeds audio_linear, `kl` is the stop quantity."""
+    model = owner.base_model.model
+    embeds = _prompt_embeds(owner, prompts)
+    R = len(embeds)
+    cache = model.init_cache_batch(R, max(e.shape[1] for e in embeds) + max_length, embeds[0].device)
+    final = [[] for _ in range(R)]
+    active = [True] * R
+    for i in range(max_length):
+        if i == 0:      # prefill: the last position's hidden state of every prompt
+            hidden = torch.cat([model.prefill_row(emb, cache, r)[:, -1:, :] for r, emb in enumerate(embeds)], dim=0)
+        else:
+            hidden = model.forward_cached_batch(step_in, cache, active)
+        kept, audio_latent, kl = frame(hidden)
+        kl = kl.view(R).tolist()                                                     # the one host read of the frame
+        for r in range(R):
+            if active[r]:
+                final[r].append(kept[r:r + 1])
+                if kl[r] < thres and i > 3:
+                    active[r] = False
+        if not any(active):
+            break
+        step_in = owner.audio_linear(audio_latent)
+    return [torch.stack(f[:-1], dim=1).squeeze(1).squeeze(2).transpose(1, 2) for f in final]
+
+
+def generate_device_head(owner, prompts, thres, max_length, noise, stop_lag, lat, plan_of, head, kept):
+    """`infer` (one prompt: the one-row decode step) / one group of `infer_batch` (the R-row step) with the per-frame head on the
+    device, for both task models: a frame is the decode step plus head(plan, h, noise, active, frame) - ops.llasa_frame_head or
+    ops.llasa_frame_head2 on the plan of plan_of(R, device, frames) - its KL goes to slot i of a device buffer, from there to
+    pinned host memory without blocking, followed by an event.  stop_lag = how many frames are enqueued ahead of the event the
+    host waits for (0 or 1).  kept: the plan's [frames, R, w] buffer a row's result is cut from ("latent" / "disp")."""
+    model = owner.base_model.model
+    embeds = _prompt_embeds(owner, prompts)
+    R, dev = len(embeds), embeds[0].device
+    Dm = embeds[0].shape[2]
+    if noise is not None:
+        noise = noise.to(device=dev, dtype=F32).expand(max_length, R, lat)
+    one = R == 1
+    room = max(e.shape[1] for e in embeds) + max_length
+    cache = model.init_cache(room, dev) if one else model.init_cache_batch(R, room, dev)
+    plan = plan_of(R, dev, max_length)
+    kl_host = torch.empty((max_length, R), dtype=F32, pin_memory=True)
+    events = [None] * max_length
+    active, count = [True] * R, [0] * R
+
+    def enqueue(i):
+        if i == 0:      # prefill: the last position's un-normed residual stream of every prompt
+            if one:
+                h = model.forward_cached(embeds[0], cache, final_norm=False)[0, -1:, :]
+            else:
+                h = torch.cat([model.prefill_row(emb, cache, r, final_norm=False)[:, -1, :] for r, emb in enumerate(embeds)])
+        elif one:
+            h = model.forward_cached(plan["x_next"].view(1, 1, Dm), cache, final_norm=False).view(1, Dm)
+        else:
+            h = model.forward_cached_batch(plan["x_next"].view(R, 1, Dm), cache, active, final_norm=False).view(R, Dm)
+        nz = torch.randn((R, 1, lat), device=dev, dtype=F32).view(R, lat) if noise is None else noise[i].contiguous()
+        head(plan, h, nz, None if one else active, i)
+        kl_host[i].copy_(plan["kl"][i], non_blocking=True)
+        events[i] = torch.cuda.Event()
+        events[i].record()
+
+    def resolve(i):     # the one host wait of frame i
+        events[i].synchronize()
+        kl = kl_host[i].tolist()
+        for r in range(R):
+            if active[r]:
+                count[r] = i + 1
+                if kl[r] < thres and i > 3:
+                    active[r] = False
+
+    if stop_lag:
+        enqueue(0)
+    for i in range(max_length):
+        if not stop_lag:
+            enqueue(i)
+        elif i + 1 < max_length:
+            enqueue(i + 1)          # (ahead of frame i's event; discarded if frame i turns out to stop every row)
+        resolve(i)
+        if not any(active):
+            break
+    return [plan[kept][:count[r] - 1, r, :].clone().unsqueeze(0).transpose(1, 2) for r in range(R)]
+
+
 class Llasa(nn.Module):
     """model_sigmaVAE.py:8-183"""
 
@@ -593,130 +722,37 @@ class Llasa(nn.Module):
         device_head / noise / stop_lag: as in `infer`, noise broadcastable to [max_length, len(prompts), latent_dim] and drawn,
         when absent, as one torch.randn((R, 1, latent_dim)) per frame for the R rows of a group; with stop_lag=1 a stopped
         row's cache holds one extra position."""
-        prompts = list(prompts)
-        if not prompts:
-            return []
-        if not device_head and (noise is not None or stop_lag):
-            raise ValueError("noise= and stop_lag= belong to device_head=True")
-        if device_head and noise is not None:
-            dl = self.distribution_linear[2].weight.shape[0]
-            noise = noise.to(F32).expand(max_length, len(prompts), dl)
-        if len(prompts) == 1:
-            return [self.infer(prompts[0][0], prompts[0][1], end_disp_kl_thres=end_disp_kl_thres, max_length=max_length,
-                               device_head=device_head, noise=noise, stop_lag=stop_lag)]
-        G = max(1, min(int(self.infer_batch_rows), ops.DECODE_MAX_ROWS))
-        if len(prompts) > G:
-            return [o for i in range(0, len(prompts), G)
-                    for o in self.infer_batch(prompts[i:i + G], end_disp_kl_thres=end_disp_kl_thres, max_length=max_length,
-                                              device_head=device_head, noise=None if noise is None else noise[:, i:i + G],
-                                              stop_lag=stop_lag)]
-        if device_head:
-            return self._generate_device_head(prompts, end_disp_kl_thres, max_length, noise, stop_lag)
-        model = self.base_model.model
-        embeds = []
-        for ids, lat in prompts:
-            parts = [model.embed_tokens(ids.unsqueeze(0))]
-            if lat is not None:
-                parts.append(self.audio_linear(lat))
-            embeds.append(torch.cat(parts, dim=1))
-        R = len(embeds)
-        cache = model.init_cache_batch(R, max(e.shape[1] for e in embeds) + max_length, embeds[0].device)
-        hidden = None
-        final = [[] for _ in range(R)]
-        active = [True] * R
+        return generate_batch(self, prompts, end_disp_kl_thres, max_length, device_head, noise, stop_lag,
+                              self.distribution_linear[2].weight.shape[0])
+
+    def _host_frame(self, hidden):
+        """the head of one frame on the host for the rows of hidden [R, 1, D]: (what `infer_batch` stacks, the sampled latent
+        [R, 1, d] - here the same tensor - and kl [R, 1])"""
         s, e = float(self.std), float(torch.e)
-        for i in range(max_length):
-            if i == 0:      # prefill: the last position's hidden state of every prompt
-                hidden = torch.cat([model.prefill_row(emb, cache, r)[:, -1:, :] for r, emb in enumerate(embeds)], dim=0)
-            else:
-                hidden = model.forward_cached_batch(step_in, cache, active)
-            mean2 = self.distribution_linear(hidden.contiguous())                    # [R, 1, d]: every row at once
-            audio_latent = self.sample(mean2)
-            kl = (torch.log(torch.tensor(e / s)) + (s * s + (mean2.float() - 1.0) ** 2) / (2 * e * e) - 0.5).sum(2)
-            kl = (kl / mean2.shape[2]).view(R).tolist()                              # the one host read of the frame
-            for r in range(R):
-                if active[r]:
-                    final[r].append(audio_latent[r:r + 1])
-                    if kl[r] < end_disp_kl_thres and i > 3:
-                        active[r] = False
-            if not any(active):
-                break
-            step_in = self.audio_linear(audio_latent)
-        return [torch.stack(f[:-1], dim=1).squeeze(1).squeeze(2).transpose(1, 2) for f in final]
+        mean2 = self.distribution_linear(hidden.contiguous())                    # [R, 1, d]: every row at once
+        audio_latent = self.sample(mean2)
+        kl = (torch.log(torch.tensor(e / s)) + (s * s + (mean2.float() - 1.0) ** 2) / (2 * e * e) - 0.5).sum(2)
+        return audio_latent, audio_latent, kl / mean2.shape[2]
 
     def _generate_device_head(self, prompts, thres, max_length, noise, stop_lag):
-        """`infer` (one prompt: the one-row decode step) / one group of `infer_batch` (the R-row step) with the per-frame head on the
-        device: a frame is the decode step plus ops.llasa_frame_head, its KL goes to slot i of a device buffer, from there to
-        pinned host memory without blocking, followed by an event.  stop_lag = how many frames are enqueued ahead of the
-        event the host waits for (0 or 1)."""
-        if stop_lag not in (0, 1):
-            raise NotImplementedError(f"stop_lag is 0 or 1, got {stop_lag!r}")
-        model = self.base_model.model
-        dlin, alin = self.distribution_linear, self.audio_linear
+        """generate_device_head with the fixed-std head (ops.llasa_frame_head); returns the sampled latents"""
+        dlin, alin, model = self.distribution_linear, self.audio_linear, self.base_model.model
         dl = dlin[2].weight.shape[0]
-        if dl % 8 or not 8 <= dl <= ops.HEAD_MAX_LATENT:
-            raise NotImplementedError(f"device_head=True takes a latent_dim that is a multiple of 8 in 8 .. {ops.HEAD_MAX_LATENT}, "
-                                      f"got {dl}; the host path (device_head=False) has no such limit")
+        device_head_limits(stop_lag, dl, ops.HEAD_MAX_LATENT)
         std = self.std
         if not (isinstance(std, (int, float)) or (torch.is_tensor(std) and std.numel() == 1)) or not float(std) > 0:
             raise NotImplementedError("device_head=True takes the fixed scalar std of init_sigmaVAE; any other std runs on the "
                                       "host path (device_head=False)")
         std = float(std)
-        embeds = []
-        for ids, lat in prompts:
-            parts = [model.embed_tokens(ids.unsqueeze(0))]
-            if lat is not None:
-                parts.append(alin(lat))
-            embeds.append(torch.cat(parts, dim=1))
-        R, dev = len(embeds), embeds[0].device
-        Dm = embeds[0].shape[2]
-        if noise is not None:
-            noise = noise.to(device=dev, dtype=F32).expand(max_length, R, dl)
-        one = R == 1
-        room = max(e.shape[1] for e in embeds) + max_length
-        cache = model.init_cache(room, dev) if one else model.init_cache_batch(R, room, dev)
-        plan = ops.llasa_head_plan(model.norm.weight, dlin[0].weight, dlin[0].bias, dlin[2].weight, dlin[2].bias, alin.weight,
-                                   alin.bias, R, model.norm.variance_epsilon, dev, frames=max_length)
-        kl_host = torch.empty((max_length, R), dtype=F32, pin_memory=True)
-        events = [None] * max_length
-        active, count = [True] * R, [0] * R
 
-        def enqueue(i):
-            if i == 0:      # prefill: the last position's un-normed residual stream of every prompt
-                if one:
-                    h = model.forward_cached(embeds[0], cache, final_norm=False)[0, -1:, :]
-                else:
-                    h = torch.cat([model.prefill_row(emb, cache, r, final_norm=False)[:, -1, :] for r, emb in enumerate(embeds)])
-            elif one:
-                h = model.forward_cached(plan["x_next"].view(1, 1, Dm), cache, final_norm=False).view(1, Dm)
-            else:
-                h = model.forward_cached_batch(plan["x_next"].view(R, 1, Dm), cache, active, final_norm=False).view(R, Dm)
-            nz = torch.randn((R, 1, dl), device=dev, dtype=F32).view(R, dl) if noise is None else noise[i].contiguous()
-            ops.llasa_frame_head(plan, h, nz, std, None if one else active, frame=i)
-            kl_host[i].copy_(plan["kl"][i], non_blocking=True)
-            events[i] = torch.cuda.Event()
-            events[i].record()
+        def plan_of(R, dev, frames):
+            return ops.llasa_head_plan(model.norm.weight, dlin[0].weight, dlin[0].bias, dlin[2].weight, dlin[2].bias, alin.weight,
+                                       alin.bias, R, model.norm.variance_epsilon, dev, frames=frames)
 
-        def resolve(i):     # the one host wait of frame i
-            events[i].synchronize()
-            kl = kl_host[i].tolist()
-            for r in range(R):
-                if active[r]:
-                    count[r] = i + 1
-                    if kl[r] < thres and i > 3:
-                        active[r] = False
+        def head(plan, h, nz, active, frame):
+            ops.llasa_frame_head(plan, h, nz, std, active, frame=frame)
 
-        if stop_lag:
-            enqueue(0)
-        for i in range(max_length):
-            if not stop_lag:
-                enqueue(i)
-            elif i + 1 < max_length:
-                enqueue(i + 1)          # (ahead of frame i's event; discarded if frame i turns out to stop every row)
-            resolve(i)
-            if not any(active):
-                break
-        return [plan["latent"][:count[r] - 1, r, :].clone().unsqueeze(0).transpose(1, 2) for r in range(R)]
+        return generate_device_head(self, prompts, thres, max_length, noise, stop_lag, dl, plan_of, head, "latent")
 
     def init_sigmaVAE(self):
         self.std = torch.tensor(0.5)

@@ -844,6 +844,53 @@ def llasa_frame_head(plan, h, noise, std, active=None, frame=0):
     return plan["mean"], latent, kl, plan["x_next"]
 
 
+# ---- the same for the head that predicts mean || log-scale (kalle_llasa_frame_head2_rows; model.Llasa)
+HEAD2_MAX_LATENT = 256
+
+
+def llasa_head2_plan(norm, w1, b1, w2, b2, wa, ba, R, eps, device, frames=1):
+    """llasa_head_plan for the mean || log-scale head: distribution_linear[0] weight [2 lat, D], distribution_linear[2] weight
+    [2 lat, 2 lat], audio_linear weight [D, lat].  The plan keeps `disp` [frames, R, 2 lat] (mean || log-scale, what `infer`
+    returns), `latent` [frames, R, lat] and `kl` [frames, R] (the head writes frame i into slot i); `x_next` [R, D] is
+    rewritten by every call.  The weights are read through dit_ops.bf16_of / f32_of at every call."""
+    lib = _lib.load()
+    d2, D = w1.shape
+    lat = d2 // 2
+    assert d2 == 2 * lat and tuple(w2.shape) == (d2, d2) and tuple(wa.shape) == (D, lat) and norm.shape[0] == D
+    nbytes = lib.kalle_llasa_head2_ws_bytes(R, D, lat)
+    check(min(nbytes, 0), "kalle_llasa_head2_ws_bytes")
+    f32 = dict(device=device, dtype=torch.float32)
+    return {"params": (norm, w1, b1, w2, b2, wa, ba), "desc": _lib.LlasaHead(), "keep": None, "R": R, "D": D, "lat": lat,
+            "eps": float(eps), "frames": frames, "ws": torch.empty(nbytes, device=device, dtype=torch.uint8),
+            "disp": torch.zeros((frames, R, d2), **f32), "latent": torch.zeros((frames, R, lat), **f32),
+            "kl": torch.zeros((frames, R), **f32), "x_next": torch.zeros((R, D), **f32)}
+
+
+def llasa_frame_head2(plan, h, noise, active=None, frame=0):
+    """one frame's head, one host call.  h: the UN-NORMED residual stream, fp32 [R, D] (rows may be strided); noise fp32 [R, lat]
+    (rows may be strided); active: R host booleans (None: all) - an inactive row's outputs are not touched.  Returns
+    (disp [R, 2 lat], latent [R, lat], kl [R], x_next [R, D]): views of the plan's buffers, the first three those of slot `frame`."""
+    from .dit_ops import bf16_of, f32_of
+    lib = _lib.load()
+    R, D, lat = plan["R"], plan["D"], plan["lat"]
+    assert h.dtype == torch.float32 and tuple(h.shape) == (R, D) and h.stride(1) == 1
+    assert noise.dtype == torch.float32 and tuple(noise.shape) == (R, lat) and noise.stride(1) == 1
+    assert 0 <= frame < plan["frames"]
+    desc = plan["desc"]
+    keep = [bf16_of(p) if f[0] == "w" else f32_of(p) for f, p in zip(HEAD_FIELDS, plan["params"])]
+    for f, t in zip(HEAD_FIELDS, keep):
+        assert t.is_contiguous() and t.device == h.device
+        setattr(desc, f, t.data_ptr())
+    desc.ldw1, desc.ldw2, desc.ldwa = D, 2 * lat, lat
+    plan["keep"] = keep
+    act = None if active is None else ctypes.cast(_i32([1 if a else 0 for a in active]), ctypes.c_void_p)
+    disp, latent, kl = plan["disp"][frame], plan["latent"][frame], plan["kl"][frame]
+    check(lib.kalle_llasa_frame_head2_rows(ctypes.addressof(desc), _p(h), h.stride(0), _p(noise), noise.stride(0), plan["eps"],
+                                           _p(disp), _p(latent), _p(kl), _p(plan["x_next"]), act, R, D, lat, _p(plan["ws"]),
+                                           _stream()), "kalle_llasa_frame_head2_rows")
+    return disp, latent, kl, plan["x_next"]
+
+
 def gauss_kl2_fwd(pred, label_mean, label_std, mask_a, mask_b, std_mult=1.25):
     """two-Gaussian KL (model.py:84-100); label_std None -> label_mean is the raw mean | scale label [rows, 2 dim]"""
     lib = _lib.load()

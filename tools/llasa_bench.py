@@ -7,11 +7,20 @@ Llama-3.2-3B shape  --hidden 3072 --layers 28 --heads 24 --kv-heads 8 --head-dim
 --decode-weights e4m3: the --infer-only and --infer-batch lines with Llasa.quantize_decoder("e4m3") (weight-only FP8 decode steps)
 --device-head: after the host-head lines, the same KV-cached generation with device_head=True (the per-frame head as one call of
 kalle_llasa_frame_head_rows) in the same process, each line with its ratio to the host-head line; --stop-lag N (0 or 1): one more
-set of lines with stop_lag=N"""
+set of lines with stop_lag=N
+--scale-head: the generation lines for model.Llasa (the mean || log-scale head of train.py / configs/twj_0828.yaml; its device
+head is kalle_llasa_frame_head2_rows) in place of model_sigmaVAE.Llasa; implies --infer-only"""
 import json, os, sys, tempfile, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from kalle_audio_amd.model_sigmaVAE import Llasa
 from kalle_audio_amd.engine import DataParallelTrainer
+SCALE_HEAD = "--scale-head" in sys.argv      # model.Llasa (predicted scale) in place of model_sigmaVAE.Llasa (fixed std)
+if SCALE_HEAD:
+    sys.argv.remove("--scale-head")
+    from kalle_audio_amd.model import Llasa
+    if "--infer-only" not in sys.argv:
+        sys.argv.append("--infer-only")
+else:
+    from kalle_audio_amd.model_sigmaVAE import Llasa
 SHAPE = {"--hidden": 2048, "--layers": 16, "--heads": 32, "--kv-heads": 8, "--head-dim": 64, "--inner": 8192}
 for _o in SHAPE:
     if _o in sys.argv:
@@ -102,6 +111,8 @@ if not INFER_ONLY:
 if "--infer" in sys.argv or INFER_ONLY:
     # frame-by-frame generation (Llasa.infer): 64 prompt tokens, 200 frames, KV cache vs the reference's full re-forward
     m.eval()
+    if SCALE_HEAD:
+        print("model.Llasa: the head predicts mean || log-scale (latent 64, audio_proj_dim = hidden)")
     if DECODE_WEIGHTS:
         m.quantize_decoder(DECODE_WEIGHTS)
         print(f"decode weights: {DECODE_WEIGHTS} (use_cache=True lines; quantised at the first step, inside the warm-up call)")
