@@ -406,8 +406,42 @@ int kalle_attention_decode_rows(const void* q, int64_t ldq, int q_off, const voi
                                 const void* v, int64_t ldv, int v_off, int64_t kv_row_stride, void* out, int64_t ldo,
                                 float* lse, const float* rope_cos, const float* rope_sin, int rot, const int32_t* nk,
                                 int R, int H, int Hkv, int head_dim, void* stream);
+/* Packed ragged batches (training on right-padded batches without the padding; the reference's flash_attention_2 path unpads and
+ * calls variable-length attention whenever an attention_mask is given, model_sigmaVAE.py:18-22): nseq sequences share one buffer
+ * of total_rows rows.  Sequence b owns the packed rows row0[b] .. row0[b] + len[b] - 1; there is no B / Nq / Nk block structure,
+ * the row index of q / k / v / out / dout / dq / dk / dv IS the packed row, everything else (ld, column offset, head h at
+ * off + h*dh, GQA as h / (H/Hkv)) is addressed as in kalle_attention_fwd_hd / _bwd_hd.
+ *   Per sequence b the result is exactly kalle_attention_fwd_hd / _bwd_hd with B = 1, causal = 1, Nq = Nk = len[b],
+ *   key_mask = NULL on that sequence's rows (the same kernel statements on a rebased parameter block: bit for bit);
+ *   the rotary position of a row is row - row0[b] (tables [>= max_len][rot/2]).
+ *   lse / delta: sequence b's block is [H][len[b]] at float offset H * row0[b]; the whole buffer is H * total_rows floats.
+ * Sequences lie in increasing row order and do not overlap; rows between them and after the last one belong to nobody: such
+ * rows of q / k / v / dout are never read, such rows of out / lse / delta / dq / dk / dv stay as found.
+ * row0 / len are passed twice: as HOST int32 arrays (row0_host / len_host: read by the planner, as nk of
+ * kalle_attention_decode_rows is) and as DEVICE int32 arrays (row0_dev / len_dev: read by the kernels).  The library allocates
+ * nothing and copies nothing.  The host arrays are checked; THAT THE DEVICE ARRAYS HOLD THE SAME VALUES IS THE CALLER'S
+ * CONTRACT (the kernels index the buffers by them).  max_len >= max(len) sizes the grid: forward (ceil(max_len/128), H, nseq),
+ * backward that and then (ceil(max_len/128), Hkv, nseq); a workgroup whose block lies past its sequence leaves at once.
+ * Supported: head_dim 64 with rot in {0, 64}, head_dim 128 with rot in {0, 64, 128}, GQA.  KALLE_ERR_ARG before any launch:
+ * any other head_dim (32 included) or rot, nseq outside 1 .. 65535, a len[b] <= 0, overlapping or unordered sequences,
+ * row0[b] + len[b] > total_rows, max_len < max(len), a NULL array, and the null / alignment / table checks of
+ * kalle_attention_fwd_hd / _bwd_hd. */
+int kalle_attention_fwd_varlen(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off,
+                               const void* v, int64_t ldv, int v_off, void* out, int64_t ldo, float* lse,
+                               const float* rope_cos, const float* rope_sin, int rot,
+                               int nseq, const int32_t* row0_host, const int32_t* len_host,
+                               const int32_t* row0_dev, const int32_t* len_dev, int total_rows, int max_len,
+                               int H, int Hkv, int head_dim, void* stream);
+int kalle_attention_bwd_varlen(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off,
+                               const void* v, int64_t ldv, int v_off, const void* out, const void* dout, int64_t ldo,
+                               const float* lse, float* delta, void* dq, void* dk, void* dv,
+                               const float* rope_cos, const float* rope_sin, int rot,
+                               int nseq, const int32_t* row0_host, const int32_t* len_host,
+                               const int32_t* row0_dev, const int32_t* len_dev, int total_rows, int max_len,
+                               int H, int Hkv, int head_dim, void* stream);
 /* which kernel family the calling thread's most recent kalle_attention_fwd / _bwd (_hd) / kalle_attention_decode_hd /
- * kalle_attention_decode_rows launched; 0 when that call returned before launching anything.
+ * kalle_attention_decode_rows / kalle_attention_fwd_varlen / _bwd_varlen launched; 0 when that call returned before launching
+ * anything.
  *   bits 0-3   family; the condition of each is ONE predicate in csrc/attention.hip (next to attn_fold_tail), named here:
  *              1 fwd_tiled (attn_fwd_kernel: every forward that is neither 2 nor 6), 2 fwd_decode (attn_decode_kernel;
  *              attn_fwd_decode: head dim 64, Nq == 1, Nk <= KALLE_ATTN_DECODE_MAX_KEYS, causal or not), 3 bwd_two_pass
@@ -417,14 +451,16 @@ int kalle_attention_decode_rows(const void* q, int64_t ldq, int q_off, const voi
  *              max(Nk - 128, 0) <= min(16, 128 - Nq)), 6 fwd_decode_128 (attn_decode128_kernel; attn_fwd_decode128:
  *              kalle_attention_decode_hd at head dim 128, Nk <= KALLE_ATTN_DECODE_MAX_KEYS; a forward family: bit 4 is 0),
  *              7 fwd_decode_rows (attn_decode_rows_kernel / attn_decode128_rows_kernel: kalle_attention_decode_rows; a forward
- *              family, head dim and ROT in their fields)
+ *              family, head dim and ROT in their fields), 8 fwd_varlen (attn_fwd_kernel<1, dh, VARLEN>: kalle_attention_fwd_varlen),
+ *              9 bwd_varlen (attn_bwd_kernel<KV, 1, dh, VARLEN>, dQ + delta then dK / dV: kalle_attention_bwd_varlen; bit 4 is 1):
+ *              words 8 | dh << 8 and 9 | 16 | dh << 8
  *   bit 4      direction: 0 forward, 1 backward
  *   bits 8-15  head dim (32 / 64 / 128)
  *   bit 16     family 1: the keys 128 .. Nk - 1 were folded into the first block (Nk in (128, 160], rot 0, not causal)
  *   bits 17-24 families 2, 6 and 7: the ROT instantiation (0 / 32 / 64; 128 for family 6 and for 7 at head dim 128, which is why the field has 8 bits - every
  *              word of families 1-5 keeps the value it had with a 7-bit field) */
 int kalle_attn_last_plan(void);
-/* The planner of the four entry points as pure host queries, one per entry point: its arguments without `stream`, then `plan`.
+/* The planner of the entry points as pure host queries, one per entry point: its arguments without `stream`, then `plan`.
  * Pointers are tested for null and never read (nk is: a host array by contract); the same checks and return codes as the
  * entry point.  On KALLE_OK plan[0 .. 11] =
  *   [0] the word kalle_attn_last_plan would hold after the call   [1] the number of launches: 0 (kalle_attention_decode_rows with
@@ -449,6 +485,21 @@ int kalle_attention_decode_rows_plan(const void* q, int64_t ldq, int q_off, cons
                                      const void* v, int64_t ldv, int v_off, int64_t kv_row_stride, void* out, int64_t ldo,
                                      float* lse, const float* rope_cos, const float* rope_sin, int rot, const int32_t* nk,
                                      int R, int H, int Hkv, int head_dim, int* plan);
+/* (the varlen entry points likewise: row0_host / len_host are read, row0_dev / len_dev tested for null only; 2 launches for the
+ * backward) */
+int kalle_attention_fwd_varlen_plan(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off,
+                                    const void* v, int64_t ldv, int v_off, void* out, int64_t ldo, float* lse,
+                                    const float* rope_cos, const float* rope_sin, int rot,
+                                    int nseq, const int32_t* row0_host, const int32_t* len_host,
+                                    const int32_t* row0_dev, const int32_t* len_dev, int total_rows, int max_len,
+                                    int H, int Hkv, int head_dim, int* plan);
+int kalle_attention_bwd_varlen_plan(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off,
+                                    const void* v, int64_t ldv, int v_off, const void* out, const void* dout, int64_t ldo,
+                                    const float* lse, float* delta, void* dq, void* dk, void* dv,
+                                    const float* rope_cos, const float* rope_sin, int rot,
+                                    int nseq, const int32_t* row0_host, const int32_t* len_host,
+                                    const int32_t* row0_dev, const int32_t* len_dev, int total_rows, int max_len,
+                                    int H, int Hkv, int head_dim, int* plan);
 
 /* ------------------------------------------------------------------------------------------------
  * Optimizer: fused Adam / AdamW over a flat fp32 master buffer, also emitting the bf16 compute copy.

@@ -275,6 +275,27 @@ struct AttnParams {
     bf16_t* dq; bf16_t* dk; bf16_t* dv;
     unsigned long long* stamps;   // diagnostics (kalle_attn_debug_stamps): [workgroup][8] s_memrealtime stamps of wave 0, or NULL
 };
+// Packed ragged batches (kalle_attention_fwd_varlen / _bwd_varlen): sequence b = blockIdx.z owns the packed rows row0[b] ..
+// row0[b] + len[b] - 1 of every operand (device int32 arrays; Nq = Nk = max_len, B = nseq as planned).  The VARLEN
+// instantiations of attn_fwd_kernel / attn_bwd_kernel take the dense block plus the two arrays; a workgroup turns its copy into
+// the dense causal call on its sequence alone - pointers advanced by row0[b] rows, lse / delta by H * row0[b] floats (the
+// sequence's [H][len[b]] block), Nq = Nk = len[b], batch index 0 - and runs the dense kernel's statements on it: rotary positions
+// restart at 0 because the tables are not advanced.  attn_varlen_rebase returns the sequence's 128-row blocks.
+struct AttnVarlenParams : AttnParams { const int32_t* row0; const int32_t* len; };
+template <bool VARLEN> using AttnKernelParams = std::conditional_t<VARLEN, AttnVarlenParams, AttnParams>;
+template <bool BWD>
+__device__ __forceinline__ int attn_varlen_rebase(AttnVarlenParams& p) {
+    const int64_t r0 = p.row0[blockIdx.z];
+    const int n = p.len[blockIdx.z];
+    p.q += r0 * p.ldq; p.k += r0 * p.ldk; p.v += r0 * p.ldv; p.out += r0 * p.ldo;
+    if (p.lse) p.lse += r0 * p.H;
+    if constexpr (BWD) {
+        p.dout += r0 * p.ldo; p.delta += r0 * p.H;
+        p.dq += r0 * p.ldq; p.dk += r0 * p.ldk; p.dv += r0 * p.ldv;
+    }
+    p.B = 1; p.Nq = p.Nk = n;
+    return (n + 127) / 128;
+}
 // the forward's folded tail (attn_fwd_kernel<1>; the host launches no other QT): the one rule, for the kernel and for the plan
 // word the host reports
 __host__ __device__ __forceinline__ bool attn_fold_tail(const AttnParams& p) {
@@ -282,9 +303,10 @@ __host__ __device__ __forceinline__ bool attn_fold_tail(const AttnParams& p) {
 }
 // ---- the dispatch rule (host): every family's condition, once, in the order plan_attention (end of file) asks them; the
 // families and their numbers are those of kalle_attn_last_plan (kalle_hip.h)
-enum AttnEntry { ENTRY_FWD, ENTRY_BWD, ENTRY_DECODE, ENTRY_ROWS };   // kalle_attention_fwd_hd, _bwd_hd, _decode_hd, _decode_rows
+enum AttnEntry { ENTRY_FWD, ENTRY_BWD, ENTRY_DECODE, ENTRY_ROWS,      // kalle_attention_fwd_hd, _bwd_hd, _decode_hd, _decode_rows
+                 ENTRY_FWD_VARLEN, ENTRY_BWD_VARLEN };                  // kalle_attention_fwd_varlen, _bwd_varlen
 enum { PLAN_FWD_TILED = 1, PLAN_FWD_DECODE = 2, PLAN_BWD_TWO_PASS = 3, PLAN_BWD_FUSED = 4, PLAN_BWD_FUSED_GQA = 5,
-       PLAN_FWD_DECODE_128 = 6, PLAN_FWD_DECODE_ROWS = 7 };
+       PLAN_FWD_DECODE_128 = 6, PLAN_FWD_DECODE_ROWS = 7, PLAN_FWD_VARLEN = 8, PLAN_BWD_VARLEN = 9 };
 // the single-query kernels keep every key's score in LDS (4 B each, 60 KiB): past it a one-row call is tiled, a rows call refused
 inline bool attn_decode_fits(int Nk) { return Nk <= KALLE_ATTN_DECODE_MAX_KEYS; }
 inline bool attn_head_dim_exists(AttnEntry e, int dh) { return dh == 64 || dh == 128 || (dh == 32 && e <= ENTRY_BWD); }
@@ -293,6 +315,7 @@ inline bool attn_head_dim_exists(AttnEntry e, int dh) { return dh == 64 || dh ==
 inline bool attn_rot_exists(AttnEntry e, int dh, int rot) {
     if (rot != 0 && rot != 32 && rot != 64 && rot != 128) return false;
     if (e == ENTRY_ROWS) return dh == 128 ? rot == 128 : rot == 0 || rot == 64;
+    if (e >= ENTRY_FWD_VARLEN) return rot == 0 || rot == 64 || rot == dh;       // (head dims 64 and 128 only: attn_head_dim_exists)
     return e == ENTRY_DECODE && dh == 128 ? rot == 128 : rot <= dh;
 }
 // attn_decode_kernel: one query at head dim 64 (kalle_attention_decode_hd is that call with causal = 1)
@@ -352,8 +375,15 @@ __device__ __forceinline__ void store_row64(bf16_t* row, const f32x4& v0, const 
 
 
 // DH = 128: the Q | K | V tiles (3 x 36 KiB) leave room for one workgroup per CU, so its 8 waves may take 256 VGPRs each.
-template <int QT, int DH = 64>
-__global__ __launch_bounds__(128 / (16 * QT) * 64, DH == 128 ? 2 : QT == 1 ? 4 : 2) void attn_fwd_kernel(AttnParams p) {
+// VARLEN (kalle_attention_fwd_varlen; grid (ceil(max_len / 128), H, nseq)): p becomes the block of sequence blockIdx.z, see
+// AttnVarlenParams.  The other instantiations compile to what they were without the parameter.
+template <int QT, int DH = 64, bool VARLEN = false>
+__global__ __launch_bounds__(128 / (16 * QT) * 64, DH == 128 ? 2 : QT == 1 ? 4 : 2) void attn_fwd_kernel(AttnKernelParams<VARLEN> p) {
+    int nblk = 0;           // VARLEN: the 128-row blocks of this workgroup's sequence, in place of gridDim.x
+    if constexpr (VARLEN) {
+        nblk = attn_varlen_rebase<false>(p);
+        if ((int)blockIdx.x >= nblk) return;                    // past its sequence: before any load or barrier
+    }
     constexpr int NT = 128 / (16 * QT) * 64;
     constexpr int STRIDE = Hd<DH>::STRIDE, TILE = Hd<DH>::TILE, KS = DH / 32, DT = DH / 16;
     constexpr float SCALE = Hd<DH>::SCALE, SCALE_LOG2E = Hd<DH>::SCALE_LOG2E;
@@ -368,7 +398,8 @@ __global__ __launch_bounds__(128 / (16 * QT) * 64, DH == 128 ? 2 : QT == 1 ? 4 :
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 4, li = lane & 15;
     // causal: the last query block streams the most key blocks - dispatch the heavy workgroups first
-    const int b = blockIdx.z, h = blockIdx.y, q0 = (p.causal ? (int)(gridDim.x - 1 - blockIdx.x) : (int)blockIdx.x) * 128;
+    const int b = VARLEN ? 0 : (int)blockIdx.z, h = blockIdx.y;
+    const int q0 = (p.causal ? (int)((VARLEN ? nblk : gridDim.x) - 1 - blockIdx.x) : (int)blockIdx.x) * 128;
     // The DiT's cross-attention has 130 context tokens: the 2 keys beyond the first block used to cost a second pass through
     // the staging code - barrier, global loads with nothing to hide their latency, barrier - 16 us of a 111-us call.  A tail of
     // up to 32 keys (no rotary, no causal mask) is fetched WITH the first block into its own small tiles instead and multiplied
@@ -577,8 +608,14 @@ __global__ __launch_bounds__(128 / (16 * QT) * 64, DH == 128 ? 2 : QT == 1 ? 4 :
 // In both, the owner's fragments sit in registers (B operand, "column" index on the lane) and the streamed tensors
 // are LDS images read as row fragments (A operand) and as transposed fragments.
 // DH = 128: twice the owner fragments and accumulators of DH = 64 - up to 256 VGPRs (one workgroup per CU) instead of spilling.
-template <bool KV, int OT, int DH = 64>
-__global__ __launch_bounds__(128 / (16 * OT) * 64, DH == 128 ? 2 : OT == 1 ? 4 : 2) void attn_bwd_kernel(AttnParams p) {
+// VARLEN (kalle_attention_bwd_varlen; grids (ceil(max_len / 128), H | Hkv, nseq)): as in attn_fwd_kernel.
+template <bool KV, int OT, int DH = 64, bool VARLEN = false>
+__global__ __launch_bounds__(128 / (16 * OT) * 64, DH == 128 ? 2 : OT == 1 ? 4 : 2) void attn_bwd_kernel(AttnKernelParams<VARLEN> p) {
+    int nblk = 0;
+    if constexpr (VARLEN) {
+        nblk = attn_varlen_rebase<true>(p);
+        if ((int)blockIdx.x >= nblk) return;
+    }
     constexpr int NT = 128 / (16 * OT) * 64;
     constexpr int STRIDE = Hd<DH>::STRIDE, TILE = Hd<DH>::TILE, KS = DH / 32, DT = DH / 16;
     constexpr float SM_SCALE = Hd<DH>::SCALE, SM_SCALE_LOG2E = Hd<DH>::SCALE_LOG2E;
@@ -590,10 +627,10 @@ __global__ __launch_bounds__(128 / (16 * OT) * 64, DH == 128 ? 2 : OT == 1 ? 4 :
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 4, li = lane & 15;
-    const int b = blockIdx.z;
+    const int b = VARLEN ? 0 : (int)blockIdx.z;
     const int group = p.H / p.Hkv;
     // owner block start (dQ kernel with causal masking: heavy query blocks - the last ones - first)
-    const int o0 = (!KV && p.causal ? (int)(gridDim.x - 1 - blockIdx.x) : (int)blockIdx.x) * 128;
+    const int o0 = (!KV && p.causal ? (int)((VARLEN ? nblk : gridDim.x) - 1 - blockIdx.x) : (int)blockIdx.x) * 128;
     const int hown = blockIdx.y;      // kv head (KV) or q head (!KV)
     const int hk = KV ? hown : hown / group;
 
@@ -1899,7 +1936,7 @@ __global__ __launch_bounds__(256) void attn_decode128_rows_kernel(AttnRowsParams
 thread_local int g_attn_plan = 0;
 inline void set_attn_plan(int plan) { g_attn_plan = plan; }
 constexpr int attn_plan(int family, int head_dim, bool fold_tail = false, int decode_rot = 0) {
-    return family | (family >= PLAN_BWD_TWO_PASS && family <= PLAN_BWD_FUSED_GQA ? 1 << 4 : 0) | head_dim << 8 |
+    return family | ((family >= PLAN_BWD_TWO_PASS && family <= PLAN_BWD_FUSED_GQA) || family == PLAN_BWD_VARLEN ? 1 << 4 : 0) | head_dim << 8 |
            (fold_tail ? 1 << 16 : 0) | decode_rot << 17;
 }
 unsigned long long* g_attn_stamps = nullptr;      // diagnostics only
@@ -1912,6 +1949,8 @@ struct AttnArgs {
     int causal, B, H, Hkv, Nq, Nk, head_dim;
     const void* dout; float* delta; void* dq; void* dk; void* dv;      // backward
     int64_t kv_row_stride; const int32_t* nk;                          // rows
+    int nseq; const int32_t* row0_host; const int32_t* len_host;       // varlen: the sequences, as host arrays (read by plan_varlen)
+    const int32_t* row0_dev; const int32_t* len_dev; int total_rows, max_len;   // ... and as device arrays (read by the kernels)
 };
 // what a call launches: plan_attention fills it from the arguments alone, launch_attention executes it, the queries report it
 struct AttnLaunch { int grid[3], block, lds; };
@@ -1921,6 +1960,7 @@ struct AttnPlan {       // (word, n, l: the twelve ints a query hands out, in th
     AttnLaunch l[2];
     int kernel;         // ATTN_KERNEL(family, head dim | ROT): the case of launch_attention's switch
     bool allow_lds;     // the tile kernels: kalle_allow_lds before the launch (the single-query kernels stay below 64 KiB)
+    const int32_t* row0; const int32_t* len;      // the varlen families: the device arrays of AttnVarlenParams
 };
 // the tile kernels are instantiated per head dim, the single-query kernels per ROT
 constexpr int ATTN_KERNEL(int family, int dh_or_rot) { return family << 8 | dh_or_rot; }
@@ -1948,14 +1988,29 @@ __forceinline__ void fill_params(const AttnArgs& a, AttnParams& p) {
 
 __forceinline__ void set_launch(AttnPlan& g, int gx, int gy, int gz, int block, int lds) { g.l[g.n++] = AttnLaunch{{gx, gy, gz}, block, lds}; }
 
+// The sequences of a varlen call, from the host arrays alone: 1 .. 65535 of them, each with at least one row, in increasing row
+// order without overlap, inside the buffers, none longer than max_len.  (That the device arrays hold the same values is the
+// caller's contract: kalle_hip.h.)
+inline int plan_varlen(const AttnArgs& a) {
+    if (!a.row0_host || !a.len_host || !a.row0_dev || !a.len_dev || a.nseq < 1 || a.nseq > 65535) return KALLE_ERR_ARG;
+    int64_t end = 0;
+    for (int b = 0; b < a.nseq; ++b) {
+        const int64_t r0 = a.row0_host[b], n = a.len_host[b];
+        if (n <= 0 || n > a.max_len || r0 < end || r0 + n > a.total_rows) return KALLE_ERR_ARG;
+        end = r0 + n;
+    }
+    return KALLE_OK;
+}
+
 // Pure: no HIP call, nothing global read but g_attn_stamps (fill_params), no pointer read but a.nk (a host array by contract).
 // Returns the entry point's return code; on KALLE_OK `rp` (rp.p alone but for rows) and `g` are what launch_attention needs.
 // (Inlined into the entry points, where the entry kind is a constant and the argument struct never exists in memory: as a
 // call it cost each of them 20 ns.)
 __forceinline__ int plan_attention(AttnEntry e, AttnArgs a, AttnRowsParams& rp, AttnPlan& g) {
     g = AttnPlan{};
-    const bool bwd = e == ENTRY_BWD, rows = e == ENTRY_ROWS;
+    const bool varlen = e >= ENTRY_FWD_VARLEN, bwd = e == ENTRY_BWD || e == ENTRY_BWD_VARLEN, rows = e == ENTRY_ROWS;
     int max_nk = 0;
+    if (varlen && plan_varlen(a) != KALLE_OK) return KALLE_ERR_ARG;   // (a: causal, B = nseq, Nq = Nk = max_len, no key mask)
     if (e == ENTRY_DECODE || rows) a.causal = a.Nq = 1;        // one query per row, at the last position
     if (rows) {                                                 // B = R rows with their own key counts and caches
         if (!a.nk || a.B < 1 || a.B > DECODE_MAX_ROWS) return KALLE_ERR_ARG;
@@ -1977,13 +2032,14 @@ __forceinline__ int plan_attention(AttnEntry e, AttnArgs a, AttnRowsParams& rp, 
     const int dh = a.head_dim;
     int family;
     if (rows) family = PLAN_FWD_DECODE_ROWS;
+    else if (varlen) family = bwd ? PLAN_BWD_VARLEN : PLAN_FWD_VARLEN;
     else if (bwd) family = attn_bwd_fused(p, dh) ? PLAN_BWD_FUSED : attn_bwd_fused_gqa(p, dh) ? PLAN_BWD_FUSED_GQA : PLAN_BWD_TWO_PASS;
     else if (attn_fwd_decode128(e, p, dh)) family = PLAN_FWD_DECODE_128;
     else family = attn_fwd_decode(p, dh) ? PLAN_FWD_DECODE : PLAN_FWD_TILED;
 
     switch (family) {
-    case PLAN_FWD_TILED: set_launch(g, (p.Nq + 127) / 128, p.H, p.B, 512, lds_fwd_tiled(dh)); break;
-    case PLAN_BWD_TWO_PASS:                                     // dQ first: it also produces delta, which the dK / dV kernel streams
+    case PLAN_FWD_TILED: case PLAN_FWD_VARLEN: set_launch(g, (p.Nq + 127) / 128, p.H, p.B, 512, lds_fwd_tiled(dh)); break;
+    case PLAN_BWD_TWO_PASS: case PLAN_BWD_VARLEN:                               // dQ first: it also produces delta, which the dK / dV kernel streams
         set_launch(g, (p.Nq + 127) / 128, p.H, p.B, 512, lds_bwd_two_pass(dh));
         set_launch(g, (p.Nk + 127) / 128, p.Hkv, p.B, 512, lds_bwd_two_pass(dh));
         break;
@@ -1998,7 +2054,8 @@ __forceinline__ int plan_attention(AttnEntry e, AttnArgs a, AttnRowsParams& rp, 
         rp.kv_row_stride = a.kv_row_stride;
         for (int r = 0; r < DECODE_MAX_ROWS; ++r) rp.nk[r] = r < a.B ? a.nk[r] : 0;
     }
-    const bool single = family == PLAN_FWD_DECODE || family >= PLAN_FWD_DECODE_128;
+    if (varlen) { p.stamps = nullptr; g.row0 = a.row0_dev; g.len = a.len_dev; }
+    const bool single = family == PLAN_FWD_DECODE || (family >= PLAN_FWD_DECODE_128 && family <= PLAN_FWD_DECODE_ROWS);
     g.allow_lds = !single;
     g.kernel = ATTN_KERNEL(family, single ? a.rot : dh);
     g.word = attn_plan(family, dh, family == PLAN_FWD_TILED && attn_fold_tail(p), single ? a.rot : 0);
@@ -2015,6 +2072,11 @@ void launch_one(const AttnPlan& g, int i, hipStream_t st, const P& p) {
     KALLE_LAUNCH(Kernel, dim3(g.l[i].grid[0], g.l[i].grid[1], g.l[i].grid[2]), dim3(g.l[i].block), g.l[i].lds, st, p);
 }
 
+inline AttnVarlenParams varlen_params(const AttnParams& p, const AttnPlan& g) {
+    AttnVarlenParams vp;
+    static_cast<AttnParams&>(vp) = p; vp.row0 = g.row0; vp.len = g.len;
+    return vp;
+}
 int launch_attention(const AttnPlan& g, const AttnRowsParams& rp, hipStream_t st) {
     const AttnParams& p = rp.p;
     if (g.n == 0) return KALLE_OK;
@@ -2035,6 +2097,14 @@ int launch_attention(const AttnPlan& g, const AttnRowsParams& rp, hipStream_t st
         launch_one<attn_bwd_kernel<false, 1, 64>>(g, 0, st, p); launch_one<attn_bwd_kernel<true, 1, 64>>(g, 1, st, p); break;
     case ATTN_KERNEL(PLAN_BWD_TWO_PASS, 128):
         launch_one<attn_bwd_kernel<false, 1, 128>>(g, 0, st, p); launch_one<attn_bwd_kernel<true, 1, 128>>(g, 1, st, p); break;
+    case ATTN_KERNEL(PLAN_FWD_VARLEN, 64): launch_one<attn_fwd_kernel<1, 64, true>>(g, 0, st, varlen_params(p, g)); break;
+    case ATTN_KERNEL(PLAN_FWD_VARLEN, 128): launch_one<attn_fwd_kernel<1, 128, true>>(g, 0, st, varlen_params(p, g)); break;
+    case ATTN_KERNEL(PLAN_BWD_VARLEN, 64):
+        launch_one<attn_bwd_kernel<false, 1, 64, true>>(g, 0, st, varlen_params(p, g));
+        launch_one<attn_bwd_kernel<true, 1, 64, true>>(g, 1, st, varlen_params(p, g)); break;
+    case ATTN_KERNEL(PLAN_BWD_VARLEN, 128):
+        launch_one<attn_bwd_kernel<false, 1, 128, true>>(g, 0, st, varlen_params(p, g));
+        launch_one<attn_bwd_kernel<true, 1, 128, true>>(g, 1, st, varlen_params(p, g)); break;
     case ATTN_KERNEL(PLAN_BWD_FUSED, 64): launch_one<attn_bwd_fused_kernel>(g, 0, st, p); break;
     case ATTN_KERNEL(PLAN_BWD_FUSED_GQA, 64): launch_one<attn_bwd_fused_gqa_kernel>(g, 0, st, p); break;
     default: return KALLE_ERR_UNSUPPORTED;                      // a plan without a kernel: not reachable from plan_attention
@@ -2102,6 +2172,41 @@ extern "C" int kalle_attention_bwd_plan(const void* q, int64_t ldq, int q_off, c
                                         const float* rope_cos, const float* rope_sin, int rot, const uint8_t* key_mask,
                                         int causal, int B, int H, int Hkv, int Nq, int Nk, int head_dim, int* plan) {
     return attention_query(ENTRY_BWD, BWD_ARGS, plan);
+}
+
+// packed ragged batches: causal, no key mask, Nq = Nk = max_len and B = nseq for the planner
+#define VARLEN_TAIL nseq, row0_host, len_host, row0_dev, len_dev, total_rows, max_len
+#define FWD_VARLEN_ARGS {q, ldq, q_off, k, ldk, k_off, v, ldv, v_off, out, ldo, lse, rope_cos, rope_sin, rot, nullptr, 1, nseq, H, Hkv, \
+                         max_len, max_len, head_dim, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, VARLEN_TAIL}
+#define BWD_VARLEN_ARGS {q, ldq, q_off, k, ldk, k_off, v, ldv, v_off, out, ldo, lse, rope_cos, rope_sin, rot, nullptr, 1, nseq, H, Hkv, \
+                         max_len, max_len, head_dim, dout, delta, dq, dk, dv, 0, nullptr, VARLEN_TAIL}
+#define VARLEN_SEQS int nseq, const int32_t* row0_host, const int32_t* len_host, const int32_t* row0_dev, const int32_t* len_dev, \
+                    int total_rows, int max_len
+extern "C" int kalle_attention_fwd_varlen(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off,
+                                          const void* v, int64_t ldv, int v_off, void* out, int64_t ldo, float* lse,
+                                          const float* rope_cos, const float* rope_sin, int rot, VARLEN_SEQS,
+                                          int H, int Hkv, int head_dim, void* stream) {
+    return attention_call(ENTRY_FWD_VARLEN, FWD_VARLEN_ARGS, stream);
+}
+extern "C" int kalle_attention_fwd_varlen_plan(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off,
+                                               const void* v, int64_t ldv, int v_off, void* out, int64_t ldo, float* lse,
+                                               const float* rope_cos, const float* rope_sin, int rot, VARLEN_SEQS,
+                                               int H, int Hkv, int head_dim, int* plan) {
+    return attention_query(ENTRY_FWD_VARLEN, FWD_VARLEN_ARGS, plan);
+}
+extern "C" int kalle_attention_bwd_varlen(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off,
+                                          const void* v, int64_t ldv, int v_off, const void* out, const void* dout,
+                                          int64_t ldo, const float* lse, float* delta, void* dq, void* dk, void* dv,
+                                          const float* rope_cos, const float* rope_sin, int rot, VARLEN_SEQS,
+                                          int H, int Hkv, int head_dim, void* stream) {
+    return attention_call(ENTRY_BWD_VARLEN, BWD_VARLEN_ARGS, stream);
+}
+extern "C" int kalle_attention_bwd_varlen_plan(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off,
+                                               const void* v, int64_t ldv, int v_off, const void* out, const void* dout,
+                                               int64_t ldo, const float* lse, float* delta, void* dq, void* dk, void* dv,
+                                               const float* rope_cos, const float* rope_sin, int rot, VARLEN_SEQS,
+                                               int H, int Hkv, int head_dim, int* plan) {
+    return attention_query(ENTRY_BWD_VARLEN, BWD_VARLEN_ARGS, plan);
 }
 
 extern "C" int kalle_attention_decode_hd(const void* q, int64_t ldq, int q_off, const void* k, int64_t ldk, int k_off,

@@ -40,6 +40,28 @@ def rope_tables(L, inv, device):
     return fr.cos().contiguous().to(device), fr.sin().contiguous().to(device)
 
 
+PACK_GRANULE = 8      # packed row counts are rounded up to it: kalle_gemm_wgrad_group and the trainer's grouped rule need it
+
+
+def packed_lengths(mask):
+    """The sequence lengths of a right-padded batch from its 0 / 1 mask [B, L] (host values: a CPU tensor, an array or nested
+    lists; nonzero = live): every row must be a run of live positions from 0 followed by padding only, with at least one live
+    position.  Anything else - left padding, a hole, an empty row - is a ValueError naming the row: a packed sequence is causal
+    and whole, so such a mask cannot be honoured and is not silently replaced."""
+    m = torch.as_tensor(mask)
+    if m.dim() != 2:
+        raise ValueError(f"attention_mask must be [B, L]; got shape {tuple(m.shape)}")
+    live = (m != 0).cpu()
+    lens = live.sum(1)
+    want = torch.arange(live.shape[1])[None, :] < lens[:, None]
+    bad = ((live != want).any(1) | (lens == 0)).nonzero().view(-1).tolist()
+    if bad:
+        b = bad[0]
+        what = "has no live position" if int(lens[b]) == 0 else "is not a run of ones followed by zeros (left padding or a hole)"
+        raise ValueError(f"pack_sequences: attention_mask row {b} {what}; packed sequences must be right-padded")
+    return [int(n) for n in lens.tolist()]
+
+
 def layer_params(layer):
     p = SimpleNamespace()
     p.g1 = f32_of(layer.input_layernorm.weight)
@@ -82,15 +104,22 @@ PARAM_ORDER = ("input_layernorm.weight", "self_attn.qkv_proj.weight", "self_attn
                "post_attention_layernorm.weight", "mlp.up_gate_proj.weight", "mlp.down_proj.weight")
 
 
-def layer_fwd(p, x, B, L, rope, mask8):
-    """x: fp32 [B*L, D] residual stream -> (fp32 [B*L, D], saved)"""
+def layer_fwd(p, x, B, L, rope, mask8, seqs=None):
+    """x: fp32 [B*L, D] residual stream -> (fp32 [B*L, D], saved).  seqs (an ops.Packed): x is [total_rows, D] = B * L with
+    B = 1, the packed rows of a ragged batch, and the attention is the varlen one (no mask8: every sequence is causal and whole,
+    rotary positions restart per sequence); rows outside every sequence are zero and stay zero through every kernel of the layer."""
     H, Hkv, hd = p.H, p.Hkv, p.hd
     D = H * hd
     ld = (H + 2 * Hkv) * hd
     h1, rr1 = ops.rmsnorm_fwd(x, p.g1, eps=p.eps, out_dtype=BF16)
     qkv = ops.gemm(h1, p.wqkv)
-    ao, lse = ops.attention_fwd(qkv, qkv, qkv, ldq=ld, q_off=0, ldk=ld, k_off=D, ldv=ld, v_off=D + Hkv * hd, B=B, H=H,
-                                Hkv=Hkv, Nq=L, Nk=L, rope=rope, key_mask=mask8, causal=True, dh=hd)
+    if seqs is not None:
+        assert mask8 is None and B * L == seqs.total_rows
+        ao, lse = ops.attention_fwd_varlen(qkv, qkv, qkv, seqs, ldq=ld, q_off=0, ldk=ld, k_off=D, ldv=ld, v_off=D + Hkv * hd,
+                                           H=H, Hkv=Hkv, rope=rope, dh=hd)
+    else:
+        ao, lse = ops.attention_fwd(qkv, qkv, qkv, ldq=ld, q_off=0, ldk=ld, k_off=D, ldv=ld, v_off=D + Hkv * hd, B=B, H=H,
+                                    Hkv=Hkv, Nq=L, Nk=L, rope=rope, key_mask=mask8, causal=True, dh=hd)
     x2 = ops.gemm(ao.view(B * L, D), p.wo, out_dtype=F32, residual=x)
     h2, rr2 = ops.rmsnorm_fwd(x2, p.g2, eps=p.eps, out_dtype=BF16)
     inner = p.wug.shape[0] // 2
@@ -103,7 +132,7 @@ def layer_fwd(p, x, B, L, rope, mask8):
     return x3, (x, h1, rr1, qkv, ao, lse, x2, h2, rr2, hf, act)
 
 
-def layer_bwd(p, saved, g, B, L, rope, mask8, go=None, g_bf16=None, want_dx_bf16=False):
+def layer_bwd(p, saved, g, B, L, rope, mask8, go=None, g_bf16=None, want_dx_bf16=False, seqs=None):
     """g: fp32 [B*L, D] gradient of the layer output (g_bf16: its bf16 copy if the layer above left one).
     Returns (dx fp32, dx bf16 | None, go)."""
     go = (go or GradOut()).defer()          # the four weight gradients of the layer go out in one grouped launch
@@ -126,9 +155,13 @@ def layer_bwd(p, saved, g, B, L, rope, mask8, go=None, g_bf16=None, want_dx_bf16
     # ---- attention branch: x2 = x + o(attn)
     go.wgrad("self_attn.o_proj.weight", dxb2, ao.view(M, D))
     dao = dgrad(dxb2, p.wo)
-    dqkv = torch.empty_like(qkv)
-    ops.attention_bwd(qkv, qkv, qkv, ao, dao, lse, dqkv, dqkv, dqkv, ldq=ld, q_off=0, ldk=ld, k_off=D, ldv=ld,
-                      v_off=D + Hkv * hd, B=B, H=H, Hkv=Hkv, Nq=L, Nk=L, rope=rope, key_mask=mask8, causal=True, dh=hd)
+    if seqs is not None:
+        dqkv, _, _ = ops.attention_bwd_varlen(qkv, qkv, qkv, ao, dao, lse, seqs, ldq=ld, q_off=0, ldk=ld, k_off=D, ldv=ld,
+                                              v_off=D + Hkv * hd, H=H, Hkv=Hkv, rope=rope, dh=hd)
+    else:
+        dqkv = torch.empty_like(qkv)
+        ops.attention_bwd(qkv, qkv, qkv, ao, dao, lse, dqkv, dqkv, dqkv, ldq=ld, q_off=0, ldk=ld, k_off=D, ldv=ld,
+                          v_off=D + Hkv * hd, B=B, H=H, Hkv=Hkv, Nq=L, Nk=L, rope=rope, key_mask=mask8, causal=True, dh=hd)
     go.wgrad("self_attn.qkv_proj.weight", dqkv, h1)
     dh1 = dgrad(dqkv, p.wqkv)
     dxb = torch.empty((M, D), device=g.device, dtype=BF16) if want_dx_bf16 else None

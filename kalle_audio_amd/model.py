@@ -69,6 +69,12 @@ class Llasa(nn.Module):
         self.base_model.model.quantize_decode_weights(fmt)
         return self
 
+    def pack_sequences(self, enable=True):
+        """LlamaModel.pack_sequences on the decoder (opt-in), as model_sigmaVAE.Llasa.pack_sequences: `pre_mean` /
+        `pre_log_scale` at padded positions become what the head gives a zero hidden state"""
+        self.base_model.model.pack_sequences(enable)
+        return self
+
     def forward(self, input_ids, audio_latents, audio_distribution_l, ids_mask, audio_mask, target_mask, end_mask):
         _need_gpu(input_ids)
         f = lambda m: m.to(F32).contiguous()

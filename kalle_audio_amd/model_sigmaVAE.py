@@ -33,17 +33,19 @@ class LlamaLayerFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, layer, x, mask8, rope, *params):
+        """mask8: the key mask [B, L], None, or an ops.Packed - x is then [1, total_rows, Dm], the packed rows of a ragged batch"""
         B, L, Dm = x.shape
         p = LO.layer_params(layer)
-        y, sv = LO.layer_fwd(p, x.contiguous().view(B * L, Dm), B, L, rope, mask8)
-        ctx.layer, ctx.sv, ctx.aux, ctx.dims = layer, sv, (mask8, rope), (B, L, Dm)
-        layer._kalle_last_rows = B * L                  # (the trainer picks its gradient-clearing rule from it)
+        seqs, mask8 = (mask8, None) if isinstance(mask8, ops.Packed) else (None, mask8)
+        y, sv = LO.layer_fwd(p, x.contiguous().view(B * L, Dm), B, L, rope, mask8, seqs=seqs)
+        ctx.layer, ctx.sv, ctx.aux, ctx.dims = layer, sv, (mask8, rope, seqs), (B, L, Dm)
+        layer._kalle_last_rows = B * L                  # (the trainer picks its gradient-clearing rule from it; packed: total_rows)
         return y.view(B, L, Dm)
 
     @staticmethod
     def backward(ctx, g):
         layer, sv = ctx.layer, ctx.sv
-        mask8, rope = ctx.aux
+        mask8, rope, seqs = ctx.aux
         B, L, Dm = ctx.dims
         p = LO.layer_params(layer)
         gf = g.contiguous().view(B * L, Dm)
@@ -54,7 +56,8 @@ class LlamaLayerFn(torch.autograd.Function):
         g_bf16 = sh[1] if sh is not None and sh[0] == ("llama", layer.layer_idx + 1) and sh[1].shape == gf.shape else None
         if len(Fn._GRAD_SHADOW) > 8:
             Fn._GRAD_SHADOW.clear()
-        dx, dxb, go = LO.layer_bwd(p, sv, gf, B, L, rope, mask8, go=go, g_bf16=g_bf16, want_dx_bf16=layer.layer_idx > 0)
+        dx, dxb, go = LO.layer_bwd(p, sv, gf, B, L, rope, mask8, go=go, g_bf16=g_bf16, want_dx_bf16=layer.layer_idx > 0,
+                                   seqs=seqs)
         if dxb is not None:
             Fn._GRAD_SHADOW[dx.data_ptr()] = (("llama", layer.layer_idx), dxb)
         ctx.sv = None
@@ -62,6 +65,43 @@ class LlamaLayerFn(torch.autograd.Function):
         if hook is not None:
             hook(layer)
         return (None, dx.view(B, L, Dm), None, None) + tuple(go.grads.get(n) for n in LO.PARAM_ORDER)
+
+
+def _copy_sequences(src, dst, seqs, L, pack):
+    """pack: dst [total_rows, D] rows row0[b] .. + lens[b] <- src [B, L, D] rows (b, 0 .. lens[b]); not pack: the opposite copy.
+    One kalle_segment_copy launch per 64 sequences (a segment = one sequence's lens[b] * D contiguous elements)."""
+    D = src.shape[-1]
+    padded = [b * L * D for b in range(seqs.nseq)]
+    packed = [r * D for r in seqs.row0]
+    n = [m * D for m in seqs.lens]
+    so, do = (padded, packed) if pack else (packed, padded)
+    return ops.segment_copy(src, dst, so, do, n, 1, 1, src_strides=(0, 0, 0), dst_strides=(0, 0, 0))
+
+
+class PackRowsFn(torch.autograd.Function):
+    """[B, L, D] -> [1, total_rows, D]: the live rows of a right-padded batch, sequence after sequence; rows outside every
+    sequence (total_rows is a multiple of LO.PACK_GRANULE) are zero.  unpack=True is the opposite map, [1, total_rows, D] ->
+    [B, L, D] with zeros at padded positions; each is the other's backward."""
+
+    @staticmethod
+    def forward(ctx, x, seqs, B, L, unpack=False):
+        ctx.seqs, ctx.dims, ctx.unpack = seqs, (B, L), unpack
+        return PackRowsFn._run(x, seqs, B, L, not unpack)
+
+    @staticmethod
+    def _run(x, seqs, B, L, pack):
+        x = x.contiguous()
+        D = x.shape[-1]
+        if pack:
+            out = (torch.zeros if seqs.has_gaps else torch.empty)((1, seqs.total_rows, D), device=x.device, dtype=x.dtype)
+        else:
+            out = (torch.zeros if seqs.live_rows != B * L else torch.empty)((B, L, D), device=x.device, dtype=x.dtype)
+        return _copy_sequences(x, out, seqs, L, pack)
+
+    @staticmethod
+    def backward(ctx, g):
+        B, L = ctx.dims
+        return PackRowsFn._run(g, ctx.seqs, B, L, ctx.unpack), None, None, None, None
 
 
 class EmbedMixFn(torch.autograd.Function):
@@ -267,6 +307,7 @@ class LlamaModel(nn.Module):
         self._decode_fmt = None
 
     DECODE_WEIGHT_FORMATS = ("e4m3",)
+    _pack = False                   # pack_sequences()
 
     def quantize_decode_weights(self, fmt="e4m3"):
         """fmt "e4m3": the KV-cached single-position steps (forward_cached at n == 1, forward_cached_batch) read the four
@@ -334,11 +375,35 @@ class LlamaModel(nn.Module):
         _need_gpu(x)
         B, L, _ = x.shape
         x = Fn._to_f32(x.contiguous())
-        mask8 = Fn._mask8(attention_mask > 0) if attention_mask is not None else None
         rope = self._rope(L, x.device)
+        seqs = self._packed(attention_mask, B, L, x.device) if self._pack and attention_mask is not None else None
+        if seqs is not None:
+            # the live rows alone go through the layers and the final norm; padded positions come back as zeros
+            x = PackRowsFn.apply(x, seqs, B, L)
+            for layer in self.layers:
+                x = layer(x, seqs, rope)
+            return (PackRowsFn.apply(self.norm(x), seqs, B, L, True),)
+        mask8 = Fn._mask8(attention_mask > 0) if attention_mask is not None else None
         for layer in self.layers:
             x = layer(x, mask8, rope)
         return (self.norm(x),)
+
+    def pack_sequences(self, enable=True):
+        """Opt-in: forward() with an attention_mask runs the decoder on the live rows only - the rows of every sample packed
+        back to back into [1, total_rows, D] (total_rows = sum of the lengths rounded up to LO.PACK_GRANULE, the extra rows
+        zero), varlen causal attention per sequence with rotary positions restarting at 0, the result scattered back with zeros
+        at padded positions.  The mask must be right-padded (LO.packed_lengths: ValueError otherwise); reading the lengths costs
+        one device-to-host copy of the mask per call.  The KV-cached paths ignore the flag.  Off (the default): nothing changes."""
+        self._pack = bool(enable)
+        return self
+
+    def _packed(self, attention_mask, B, L, device):
+        """the ops.Packed of a right-padded mask, or None where packing gains nothing: no padding and a row count that is a
+        multiple of the granule already"""
+        lens = LO.packed_lengths((attention_mask > 0).cpu())
+        if sum(lens) == B * L and (B * L) % LO.PACK_GRANULE == 0:
+            return None
+        return ops.Packed.back_to_back(lens, device, granule=LO.PACK_GRANULE)
 
 
     # ---- inference with a KV cache (batch 1) ---------------------------------------------------------------------
@@ -638,6 +703,13 @@ class Llasa(nn.Module):
     def quantize_decoder(self, fmt="e4m3"):
         """LlamaModel.quantize_decode_weights on the decoder: `infer` and `infer_batch` then stream e4m3 weights per frame"""
         self.base_model.model.quantize_decode_weights(fmt)
+        return self
+
+    def pack_sequences(self, enable=True):
+        """LlamaModel.pack_sequences on the decoder (opt-in): `forward` then spends no decoder work on padded positions.  Its
+        signature, returned dict and losses stay; `pre_mean` at padded positions becomes what the head gives a zero hidden state
+        (undefined in the reference, and different from the padded mode here)."""
+        self.base_model.model.pack_sequences(enable)
         return self
 
     def forward(self, input_ids, audio_latents, audio_distribution_l, ids_mask, audio_mask, target_mask, end_mask,

@@ -476,9 +476,11 @@ def attn_last_plan():
     return _lib.load().kalle_attn_last_plan()
 
 
-def attention_plan(entry, *, H, Hkv, B=1, Nq=1, Nk=1, dh=64, rot=0, causal=False, key_mask=False, nk=None, kv_row_stride=None):
-    """kalle_attention_fwd_plan / _bwd_plan / _decode_plan / _decode_rows_plan (entry "fwd", "bwd", "decode", "rows") for a call
-    given by its shape, with placeholder pointers in dense layouts (q [H dh], k | v [2 Hkv dh] rows; the planner tests pointers for
+def attention_plan(entry, *, H, Hkv, B=1, Nq=1, Nk=1, dh=64, rot=0, causal=False, key_mask=False, nk=None, kv_row_stride=None,
+                   seqs=None):
+    """kalle_attention_fwd_plan / _bwd_plan / _decode_plan / _decode_rows_plan (entry "fwd", "bwd", "decode", "rows") and
+    kalle_attention_fwd_varlen_plan / _bwd_varlen_plan ("fwd_varlen", "bwd_varlen": seqs = a Packed, which may have been made
+    with device=None) for a call given by its shape, with placeholder pointers in dense layouts (q [H dh], k | v [2 Hkv dh] rows; the planner tests pointers for
     null only) and tables exactly when rot != 0; rows: nk host ints, kv_row_stride None = (max(nk) + 1) rows.  Returns (return
     code, dict(word = what kalle_attn_last_plan would hold after the call, family, launches = [dict(grid, block, lds)]), or None
     where the entry point refuses the call); host code only, no device needed"""
@@ -491,6 +493,10 @@ def attention_plan(entry, *, H, Hkv, B=1, Nq=1, Nk=1, dh=64, rot=0, causal=False
         rc = lib.kalle_attention_fwd_plan(*head, 16, H * dh, 16, *tail, int(causal), B, H, Hkv, Nq, Nk, dh, plan)
     elif entry == "bwd":
         rc = lib.kalle_attention_bwd_plan(*head, 16, 16, H * dh, 16, 16, 16, 16, 16, *tail, int(causal), B, H, Hkv, Nq, Nk, dh, plan)
+    elif entry == "fwd_varlen":
+        rc = lib.kalle_attention_fwd_varlen_plan(*head, 16, H * dh, 16, *tail[:3], *seqs._args(), H, Hkv, dh, plan)
+    elif entry == "bwd_varlen":
+        rc = lib.kalle_attention_bwd_varlen_plan(*head, 16, 16, H * dh, 16, 16, 16, 16, 16, *tail[:3], *seqs._args(), H, Hkv, dh, plan)
     elif entry == "decode":
         rc = lib.kalle_attention_decode_plan(*head, 16, H * dh, 16, *tail, B, H, Hkv, Nk, dh, plan)
     else:
@@ -502,6 +508,71 @@ def attention_plan(entry, *, H, Hkv, B=1, Nq=1, Nk=1, dh=64, rot=0, causal=False
         return rc, None
     return rc, dict(word=plan[0], family=plan[0] & 15,
                     launches=[dict(grid=tuple(plan[2 + 5 * i:5 + 5 * i]), block=plan[5 + 5 * i], lds=plan[6 + 5 * i]) for i in range(plan[1])])
+
+
+class Packed:
+    """The sequences of a packed ragged batch for kalle_attention_fwd_varlen / _bwd_varlen: sequence b owns the packed rows
+    row0[b] .. row0[b] + lens[b] - 1 of a buffer of total_rows rows (increasing, not overlapping; rows in between and behind
+    belong to nobody).  row0 / lens: host ints (the planner reads them); dev: the same values as ONE device int32 tensor
+    [2, nseq] (row0 | lens; the kernels read it) - made here from the host lists, so the two cannot disagree."""
+
+    def __init__(self, row0, lens, total_rows, device, max_len=None):
+        self.row0, self.lens = [int(r) for r in row0], [int(n) for n in lens]
+        assert len(self.row0) == len(self.lens) >= 1
+        self.nseq, self.total_rows = len(self.lens), int(total_rows)
+        self.max_len = int(max_len) if max_len is not None else max(self.lens)
+        self.live_rows = sum(self.lens)
+        self.has_gaps = self.live_rows != self.total_rows       # rows outside every sequence: outputs start as zeros
+        self.host = (_i32(self.row0), _i32(self.lens))
+        self.dev = torch.tensor([self.row0, self.lens], dtype=torch.int32).to(device) if device is not None else None
+
+    @classmethod
+    def back_to_back(cls, lens, device, granule=1):
+        """sequences packed back to back from row 0; total_rows = sum(lens) rounded up to a multiple of `granule`"""
+        lens = [int(n) for n in lens]
+        row0 = [sum(lens[:b]) for b in range(len(lens))]
+        return cls(row0, lens, -(-sum(lens) // granule) * granule, device)
+
+    def _args(self):
+        cast = ctypes.cast
+        d = self.dev
+        if d is not None and not d.is_cuda:
+            raise RuntimeError("kalle_audio_amd ops run on the GPU only (HIP kernels); got a CPU tensor")
+        dev = (ctypes.c_void_p(d.data_ptr()), ctypes.c_void_p(d.data_ptr() + 4 * self.nseq)) if d is not None else (16, 16)
+        return (self.nseq, cast(self.host[0], ctypes.c_void_p), cast(self.host[1], ctypes.c_void_p), *dev, self.total_rows,
+                self.max_len)
+
+
+def attention_fwd_varlen(q, k, v, seqs, *, ldq, q_off, ldk, k_off, ldv, v_off, H, Hkv, rope=None, dh=64):
+    """causal attention of every sequence of `seqs` (a Packed) inside packed buffers: kalle_attention_fwd_varlen.
+    Returns (out [total_rows, H*dh], lse [H * total_rows]: sequence b's [H][len] block at H * row0[b]); rows outside every
+    sequence are zeros in both (torch.zeros; without such rows torch.empty as attention_fwd)."""
+    lib = _lib.load()
+    new = torch.zeros if seqs.has_gaps else torch.empty
+    out = new((seqs.total_rows, H * dh), device=q.device, dtype=torch.bfloat16)
+    lse = new((H * seqs.total_rows,), device=q.device, dtype=torch.float32)
+    cos, sin, rot = (rope[0], rope[1], rope[0].shape[-1] * 2) if rope is not None else (None, None, 0)
+    check(lib.kalle_attention_fwd_varlen(_p(q), ldq, q_off, _p(k), ldk, k_off, _p(v), ldv, v_off, _p(out), H * dh, _p(lse),
+                                         _p(cos), _p(sin), rot, *seqs._args(), H, Hkv, dh, _stream()),
+          "kalle_attention_fwd_varlen")
+    return out, lse
+
+
+def attention_bwd_varlen(q, k, v, out, dout, lse, seqs, *, ldq, q_off, ldk, k_off, ldv, v_off, H, Hkv, rope=None, dh=64,
+                         dq=None, dk=None, dv=None):
+    """kalle_attention_bwd_varlen.  dq / dk / dv None: ONE new buffer shaped like q that receives all three (the fused qkv
+    layout: q, k and v are windows of one tensor), zeros where `seqs` has rows outside every sequence so that the GEMMs behind
+    read no uninitialised memory, torch.empty otherwise.  Returns (dq, dk, dv)."""
+    lib = _lib.load()
+    if dq is None:
+        assert dk is None and dv is None and q.data_ptr() == k.data_ptr() == v.data_ptr()
+        dq = dk = dv = (torch.zeros_like if seqs.has_gaps else torch.empty_like)(q)
+    delta = torch.empty((H * seqs.total_rows,), device=q.device, dtype=torch.float32)
+    cos, sin, rot = (rope[0], rope[1], rope[0].shape[-1] * 2) if rope is not None else (None, None, 0)
+    check(lib.kalle_attention_bwd_varlen(_p(q), ldq, q_off, _p(k), ldk, k_off, _p(v), ldv, v_off, _p(out), _p(dout), H * dh,
+                                         _p(lse), _p(delta), _p(dq), _p(dk), _p(dv), _p(cos), _p(sin), rot, *seqs._args(),
+                                         H, Hkv, dh, _stream()), "kalle_attention_bwd_varlen")
+    return dq, dk, dv
 
 
 def attention_bwd(q, k, v, out, dout, lse, dq, dk, dv, *, ldq, q_off, ldk, k_off, ldv, v_off, B, H, Hkv, Nq, Nk,

@@ -9,7 +9,13 @@ Llama-3.2-3B shape  --hidden 3072 --layers 28 --heads 24 --kv-heads 8 --head-dim
 kalle_llasa_frame_head_rows) in the same process, each line with its ratio to the host-head line; --stop-lag N (0 or 1): one more
 set of lines with stop_lag=N
 --scale-head: the generation lines for model.Llasa (the mean || log-scale head of train.py / configs/twj_0828.yaml; its device
-head is kalle_llasa_frame_head2_rows) in place of model_sigmaVAE.Llasa; implies --infer-only"""
+head is kalle_llasa_frame_head2_rows) in place of model_sigmaVAE.Llasa; implies --infer-only
+--ragged SEED [--pack]: the train step on a batch shaped like the reference's collate - sample 0 at full length L, the others
+with lengths drawn uniformly from [L/4, L], right-padded (about 35 % padding) - with Llasa.pack_sequences() when --pack is given;
+prints ms/step, LIVE tokens/s and the padding share
+--ragged SEED --ab [REPEATS]: the three arms in ONE process on the same batch, alternating, REPEATS (default 3) timed windows
+each: padded (the default path), packed (pack_sequences()), and the floor - a dense unpadded batch [1, total_rows] of the packed
+row count; and the time of the one host read of the lengths per packed step"""
 import json, os, sys, tempfile, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from kalle_audio_amd.engine import DataParallelTrainer
@@ -51,6 +57,22 @@ if "--stop-lag" in sys.argv:
         sys.exit("--stop-lag belongs to --device-head")
     if _lag:
         HEADS.append((f"device head, stop_lag={_lag}", dict(device_head=True, stop_lag=_lag)))
+RAGGED = None                                # --ragged SEED: a right-padded batch with lengths from [L/4, L]
+if "--ragged" in sys.argv:
+    _i = sys.argv.index("--ragged")
+    RAGGED = int(sys.argv[_i + 1])
+    del sys.argv[_i:_i + 2]
+PACK = "--pack" in sys.argv
+if PACK:
+    sys.argv.remove("--pack")
+AB = 0                                       # --ab [REPEATS]: padded / packed / dense floor in one process, alternating
+if "--ab" in sys.argv:
+    _i = sys.argv.index("--ab")
+    _n = sys.argv[_i + 1] if _i + 1 < len(sys.argv) and sys.argv[_i + 1].isdigit() else None
+    AB = int(_n) if _n else 3
+    del sys.argv[_i:_i + (2 if _n else 1)]
+if (PACK or AB) and RAGGED is None:
+    sys.exit("--pack and --ab belong to --ragged SEED")
 HID, NLAYER = SHAPE["--hidden"], SHAPE["--layers"]
 _pos = [a for a in sys.argv[1:] if not a.startswith("--")]
 B = int(_pos[0]) if len(_pos) > 0 else 8
@@ -86,11 +108,78 @@ target_mask = torch.zeros(B, L, device=dev); target_mask[:, 63:L - 1] = 1
 end_mask = torch.zeros(B, L, device=dev); end_mask[:, L - 1] = 1
 
 
-def step():
-    out = m(ids, lat, lbl, ids_mask, audio_mask, target_mask, end_mask)
+def ragged_batch(lens, width):
+    """masks of a collate-shaped batch: 64 text tokens (fewer for a short sample), audio frames up to the sample's length, padding"""
+    im, am, tm, em = (torch.zeros(len(lens), width) for _ in range(4))
+    for b, n in enumerate(lens):
+        nt = min(64, n // 2)
+        im[b, :nt] = 1
+        am[b, nt:n] = 1
+        tm[b, nt - 1:n - 1] = 1
+        em[b, n - 1] = 1
+    return tuple(t.to(dev) for t in (im, am, tm, em))
+
+
+LENS = None
+if RAGGED is not None:
+    g = torch.Generator().manual_seed(RAGGED)
+    LENS = [L] + [int(v) for v in torch.randint(L // 4, L + 1, (B - 1,), generator=g)]
+    ids_mask, audio_mask, target_mask, end_mask = ragged_batch(LENS, L)
+    LIVE = sum(LENS)
+    print(f"ragged batch (seed {RAGGED}): lengths {LENS}, {LIVE} live of {B * L} positions, padding share {1 - LIVE / (B * L):.3f}")
+
+
+def step(batch=None):
+    out = m(*(batch or (ids, lat, lbl, ids_mask, audio_mask, target_mask, end_mask)))
     tr.backward(out["audio_loss"] * 1.0 + out["end_loss"] * 1.0)
     return out
 
+
+def timed(batch, pack, n):
+    """ms per step over a window of n steps that ends in a device synchronise"""
+    m.pack_sequences(pack)
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    for _ in range(n):
+        o = step(batch)
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t) / n * 1e3, o
+
+
+if AB:
+    from kalle_audio_amd import llama_ops as LO
+    rows = -(-LIVE // LO.PACK_GRANULE) * LO.PACK_GRANULE
+    padded = (ids, lat, lbl, ids_mask, audio_mask, target_mask, end_mask)
+    # the floor: a dense batch without padding of the packed row count, B equal sequences (no more attention work than the ragged
+    # lengths need: sum of squares is least for equal lengths)
+    Bd, Ld = (B, rows // B) if rows % B == 0 else (1, rows)
+    dense = (torch.randint(0, 128264, (Bd, Ld), device=dev), torch.randn(Bd, Ld, 64, device=dev), torch.randn(Bd, Ld, 64, device=dev),
+             *ragged_batch([Ld] * Bd, Ld))
+    print(f"dense floor: B={Bd} L={Ld} ({rows} rows, no padding)")
+    arms = [("padded", padded, False), ("packed", padded, True), ("dense floor", dense, False)]
+    for name, batch, pack in arms:                    # warm every shape the timed windows use
+        timed(batch, pack, 2)
+    res = {name: [] for name, _, _ in arms}
+    for r in range(AB):
+        for name, batch, pack in (arms if r % 2 == 0 else arms[::-1]):      # alternate the order
+            ms, o = timed(batch, pack, steps)
+            res[name].append(ms)
+            print(f"repeat {r} {name:12s}: {ms:8.2f} ms/step  (loss {o['audio_loss'].item():.3f})")
+    mask = ids_mask + audio_mask
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(20):
+        LO.packed_lengths((mask > 0).cpu())
+    read_ms = (time.perf_counter() - t0) / 20 * 1e3
+    for name, _, _ in arms:
+        v = sorted(res[name])
+        n_live = rows if name == "dense floor" else LIVE
+        print(f"{name:12s} B={B} L={L}: median {v[len(v) // 2]:.2f} ms/step (min {v[0]:.2f}, max {v[-1]:.2f}), "
+              f"{n_live / v[len(v) // 2] * 1e3:.0f} live tokens/s, rows through the decoder {B * L if name == 'padded' else rows}")
+    print(f"padding share {1 - LIVE / (B * L):.3f}; packed rows {rows}; host read of the lengths (idle device): {read_ms:.3f} ms per step")
+    sys.exit(0)
+if PACK:
+    m.pack_sequences()
 
 for _ in range(0 if INFER_ONLY else 2):
     out = step()
@@ -103,7 +192,10 @@ dt = (time.perf_counter() - t0) / steps
 # algorithmic FLOPs: 6 * (non-embedding params) per token + attention 12 * L * D per token per layer (causal: half)
 nonemb = nparam - 128264 * HID
 fl = (6.0 * nonemb + NLAYER * 12.0 * L * HID * 0.5) * B * L
-if not INFER_ONLY:
+if not INFER_ONLY and RAGGED is not None:
+  print(f"Llasa ragged train step ({'packed' if PACK else 'padded'}) B={B} L={L}: {dt*1e3:.1f} ms/step, {LIVE/dt:.0f} live tokens/s, "
+        f"padding share {1 - LIVE / (B * L):.3f}, loss {out['audio_loss'].item():.3f}")
+elif not INFER_ONLY:
   print(f"Llasa {'Llama-3.2-1B-shape' if HID == 2048 and NLAYER == 16 else f'hidden-{HID}-x-{NLAYER}-layers'} train step B={B} L={L}: {dt*1e3:.1f} ms/step, {B*L/dt:.0f} tokens/s, "
         f"{B*L/12.5/dt:.0f} audio-s/s (12.5 Hz frames), {fl/dt/1e12:.0f} TFLOP/s algorithmic, params {nparam/1e9:.2f} B, "
         f"loss {out['audio_loss'].item():.3f}")
