@@ -417,11 +417,19 @@ def llasa_shapes(c):
     return names
 
 
-def llasa_inputs(c):
-    """(batch as numpy arrays, sampling noise as numpy)"""
+def llasa_inputs(c, seed=None):
+    """(batch as numpy arrays, sampling noise as numpy); seed: another micro-batch of the same shape (other ragged lengths)"""
+    seed = c["seed"] if seed is None else seed
     lc = llasa_config(c)
-    b = gu.llasa_batch_long(lc, c["seed"], B=c["B"], L=c["L"])
-    return b, gu.make_input("llasa_eps", tuple(b["audio_latents"].shape), c["seed"])
+    b = gu.llasa_batch_long(lc, seed, B=c["B"], L=c["L"])
+    return b, gu.make_input("llasa_eps", tuple(b["audio_latents"].shape), seed)
+
+
+def llasa_window(c, st, seeds, mode="f64", dtype=F64):
+    """llasa_reference summed over the micro-batches built from `seeds`: the parameter gradients the trainer's flat buffer holds
+    at the end of an accumulation window"""
+    runs = [llasa_reference(c, st, *llasa_inputs(c, s), mode, dtype) for s in seeds]
+    return {k: sum(g[k] for g in runs) for k in runs[0] if k in st}
 
 
 def llasa_reference(c, st, batch, eps, mode="f64", dtype=F64, bias_rows=None):
