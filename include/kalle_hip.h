@@ -727,6 +727,23 @@ int kalle_llama_decode_ws_bytes_rows(int R, int H, int Hkv, int inner, int head_
 int kalle_llama_decode_step_rows(const kalle_llama_layer* layers, int n_layers, const float* x, float* out, int R, int H,
                                  int Hkv, int inner, int head_dim, float eps, const int32_t* t0, int cache_rows,
                                  const float* rope_cos, const float* rope_sin, void* workspace, void* stream);
+/* Packed prefill into a batch cache: after the q|k|v GEMM over the packed rows of several prompts (kalle_attention_fwd_varlen's
+ * layout), the un-rotated k|v window of every sequence goes to that sequence's cache row, all sequences in ONE launch.
+ *   src   bf16 [total_rows][ld_src], the k|v window at column src_off (kvw = 2*Hkv*head_dim columns)
+ *   cache bf16 [R][cache_rows][kvw], row r at cache + r * cache_row_stride (elements)
+ * Sequence s < nseq (<= KALLE_DECODE_MAX_ROWS) owns packed rows row0[s] .. row0[s] + len[s] - 1; row j of it is copied, bit for
+ * bit, to cache[dst_row[s]][t0[s] + j][0 .. kvw).  Nothing else is written.  row0 / len / dst_row / t0 are HOST arrays [nseq] and
+ * travel in the kernel's parameter block.  A workgroup moves KALLE_KV_APPEND_ROWS rows of one sequence, 16 bytes per lane.
+ * KALLE_ERR_ARG before any launch (so the refusals need no device): a NULL pointer (stream excepted) or src / cache not 16-byte
+ * aligned; nseq outside 1 ..
+ * KALLE_DECODE_MAX_ROWS; R outside 1 .. KALLE_DECODE_MAX_ROWS; len <= 0, t0 < 0 or t0 + len > cache_rows; dst_row outside [0, R)
+ * or named twice; row0 < 0 or row0 + len > total_rows; sequences overlapping or not in increasing row order; kvw, ld_src,
+ * src_off or cache_row_stride <= 0 (src_off: < 0) or not a multiple of 8 elements; src_off + kvw > ld_src; cache_row_stride <
+ * cache_rows * kvw. */
+#define KALLE_KV_APPEND_ROWS 32
+int kalle_kv_append_varlen(const void* src, int64_t ld_src, int src_off, void* cache, int64_t cache_row_stride, int kvw,
+                           int nseq, const int32_t* row0_host, const int32_t* len_host, const int32_t* dst_row_host,
+                           const int32_t* t0_host, int total_rows, int R, int cache_rows, void* stream);
 /* ---- weight-only FP8 decoding: the decoder weights as OCP e4m3 codes with one fp32 scale per output row ------------------------
  * A decode step reads every decoder weight once, so a frame costs the bytes of the weights; this halves them.  Activations,
  * accumulation (fp32) and every bf16 rounding point of the steps above stay where they are.  Opt-in: nothing above changes.

@@ -1529,3 +1529,59 @@ extern "C" int kalle_gauss_kl2_bwd(const float* pred, const float* label_mean, c
     else KALLE_LAUNCH(gauss_kl2_bwd_kernel<1>, grid, block, 0, st, pred, label_mean, label_std, mask_a, mask_b, sums4, grad_a, grad_b, dpred, std_mult, rows, dim);
     return kalle_check_launch();
 }
+
+// ---- packed prefill: the k|v windows of several prompts' packed rows into their rows of a batch KV cache, one launch -----------
+// blockIdx.y = sequence, blockIdx.x = a chunk of KALLE_KV_APPEND_ROWS of its rows; a lane moves 16 bytes (8 bf16) at a time.
+namespace {
+struct KvAppendTab {
+    int row0[KALLE_DECODE_MAX_ROWS], len[KALLE_DECODE_MAX_ROWS], dst[KALLE_DECODE_MAX_ROWS], t0[KALLE_DECODE_MAX_ROWS];
+};
+__global__ __launch_bounds__(256) void kv_append_varlen_kernel(const bf16_t* __restrict__ src, int64_t ld_src, int src_off,
+                                                               bf16_t* __restrict__ cache, int64_t cache_row_stride, int kvw,
+                                                               KvAppendTab tab) {
+    const int s = blockIdx.y;
+    const int j0 = blockIdx.x * KALLE_KV_APPEND_ROWS;
+    const int len = tab.len[s];
+    if (j0 >= len) return;
+    const int nrows = len - j0 < KALLE_KV_APPEND_ROWS ? len - j0 : KALLE_KV_APPEND_ROWS;
+    const int vpr = kvw >> 3;                      // 16-byte units per row
+    const bf16_t* sp = src + (int64_t)(tab.row0[s] + j0) * ld_src + src_off;
+    bf16_t* dp = cache + (int64_t)tab.dst[s] * cache_row_stride + (int64_t)(tab.t0[s] + j0) * kvw;
+    for (int i = threadIdx.x; i < nrows * vpr; i += blockDim.x) {
+        const int r = i / vpr, c = (i - r * vpr) << 3;
+        *reinterpret_cast<i32x4*>(dp + (int64_t)r * kvw + c) = *reinterpret_cast<const i32x4*>(sp + (int64_t)r * ld_src + c);
+    }
+}
+}  // namespace
+
+extern "C" int kalle_kv_append_varlen(const void* src, int64_t ld_src, int src_off, void* cache, int64_t cache_row_stride,
+                                      int kvw, int nseq, const int32_t* row0_host, const int32_t* len_host,
+                                      const int32_t* dst_row_host, const int32_t* t0_host, int total_rows, int R, int cache_rows,
+                                      void* stream) {
+    if (!src || !cache || !row0_host || !len_host || !dst_row_host || !t0_host) return KALLE_ERR_ARG;
+    if (nseq < 1 || nseq > KALLE_DECODE_MAX_ROWS || R < 1 || R > KALLE_DECODE_MAX_ROWS || total_rows <= 0 || cache_rows <= 0)
+        return KALLE_ERR_ARG;
+    if (kvw <= 0 || (kvw & 7) || ld_src <= 0 || (ld_src & 7) || src_off < 0 || (src_off & 7) || cache_row_stride <= 0 ||
+        (cache_row_stride & 7))
+        return KALLE_ERR_ARG;
+    if ((int64_t)src_off + kvw > ld_src || cache_row_stride < (int64_t)cache_rows * kvw) return KALLE_ERR_ARG;
+    if ((((uintptr_t)src | (uintptr_t)cache) & 15) != 0) return KALLE_ERR_ARG;      // (16-byte loads and stores)
+    KvAppendTab tab{};
+    unsigned taken = 0;
+    int maxlen = 0;
+    int64_t next = 0;                              // the first packed row the next sequence may own
+    for (int s = 0; s < nseq; ++s) {
+        const int64_t r0 = row0_host[s], n = len_host[s], d = dst_row_host[s], t = t0_host[s];
+        if (n <= 0 || t < 0 || t + n > cache_rows) return KALLE_ERR_ARG;
+        if (d < 0 || d >= R || (taken >> d & 1u)) return KALLE_ERR_ARG;
+        if (r0 < next || r0 + n > total_rows) return KALLE_ERR_ARG;
+        taken |= 1u << d;
+        next = r0 + n;
+        tab.row0[s] = (int)r0; tab.len[s] = (int)n; tab.dst[s] = (int)d; tab.t0[s] = (int)t;
+        maxlen = (int)n > maxlen ? (int)n : maxlen;
+    }
+    const dim3 grid((maxlen + KALLE_KV_APPEND_ROWS - 1) / KALLE_KV_APPEND_ROWS, nseq), block(256);
+    KALLE_LAUNCH(kv_append_varlen_kernel, grid, block, 0, static_cast<hipStream_t>(stream), static_cast<const bf16_t*>(src),
+                 ld_src, src_off, static_cast<bf16_t*>(cache), cache_row_stride, kvw, tab);
+    return kalle_check_launch();
+}

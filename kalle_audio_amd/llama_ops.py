@@ -190,3 +190,26 @@ def layer_fwd_cached(p, x, kv_cache, t0, rope):
     hf = ops.gemm(h2, p.wug)
     act = ops.swiglu_fwd(hf)
     return ops.gemm(act, p.wdown, out_dtype=F32, residual=x2)
+
+
+def layer_fwd_cached_varlen(p, x, kv_cache, seqs, dst_rows, rope):
+    """layer_fwd_cached for the packed rows of several prompts that all start at position 0: x fp32 [total_rows, D] laid out by
+    seqs (an ops.Packed); kv_cache bf16 [R, Lmax, 2*Hkv*hd] is a layer's buffer of a batch cache and receives the un-rotated
+    k | v rows of sequence s at kv_cache[dst_rows[s], 0 .. lens[s]) in one launch; the attention is the varlen causal one straight
+    from the packed q|k|v buffer (rotary positions restart per sequence), as layer_fwd runs it with `seqs`.  Rows outside every
+    sequence are zero and stay zero.  Returns fp32 [total_rows, D]."""
+    H, Hkv, hd = p.H, p.Hkv, p.hd
+    D = H * hd
+    ld = (H + 2 * Hkv) * hd
+    n = x.shape[0]
+    assert n == seqs.total_rows
+    h1, _ = ops.rmsnorm_fwd(x, p.g1, eps=p.eps, out_dtype=BF16)
+    qkv = ops.gemm(h1, p.wqkv)
+    ops.kv_append_varlen(qkv, seqs, kv_cache, dst_rows, [0] * seqs.nseq, src_off=D)
+    ao, _ = ops.attention_fwd_varlen(qkv, qkv, qkv, seqs, ldq=ld, q_off=0, ldk=ld, k_off=D, ldv=ld, v_off=D + Hkv * hd, H=H,
+                                     Hkv=Hkv, rope=rope, dh=hd)
+    x2 = ops.gemm(ao.view(n, D), p.wo, out_dtype=F32, residual=x)
+    h2, _ = ops.rmsnorm_fwd(x2, p.g2, eps=p.eps, out_dtype=BF16)
+    hf = ops.gemm(h2, p.wug)
+    act = ops.swiglu_fwd(hf)
+    return ops.gemm(act, p.wdown, out_dtype=F32, residual=x2)

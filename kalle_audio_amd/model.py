@@ -19,7 +19,7 @@ from . import functional as Fn
 from . import ops
 from .dit_ops import F32
 from .model_sigmaVAE import (GELU, EmbedMixFn, Linear, LlamaForCausalLM, _need_gpu, device_head_limits, generate_batch,
-                             generate_device_head)
+                             generate_device_head, generate_refill)
 
 get_mean_stdev_from_stableaudio2_latents = None      # injectable stand-in for the missing twj_utils function (see above)
 LABEL_STD_MULT = 1.25                                # model.py:87
@@ -151,17 +151,22 @@ class Llasa(nn.Module):
     infer_batch_rows = ops.DECODE_MAX_ROWS      # sequences decoded per step by infer_batch (the kernels take up to DECODE_MAX_ROWS)
 
     @torch.no_grad()
-    def infer_batch(self, prompts, end_disp_kl_thres=0.5, max_length=1000, device_head=False, noise=None, stop_lag=0):
+    def infer_batch(self, prompts, end_disp_kl_thres=0.5, max_length=1000, device_head=False, noise=None, stop_lag=0,
+                    refill=False):
         """`infer` (KV-cached) for a list of (input_ids, audio_latents or None), as model_sigmaVAE.Llasa.infer_batch: the
         utterances of a group (up to `infer_batch_rows`) share one decoder pass per frame, a row that meets the stop rule leaves
         the batch while the others go on, longer lists run in groups, one prompt is `infer` itself.  Returns a list with what
         `infer` returns for each prompt.  device_head / noise / stop_lag: as in `infer`, noise broadcastable to
-        [max_length, len(prompts), latent_dim] and drawn, when absent, as one torch.randn((R, 1, latent_dim)) per frame."""
+        [max_length, len(prompts), latent_dim] and drawn, when absent, as one torch.randn((R, 1, latent_dim)) per frame.
+        max_length may be one int per prompt; refill=True (opt-in) keeps the rows full - a stopped row takes the next waiting
+        prompt, prompts admitted together are prefilled in one packed pass - exactly as documented on
+        model_sigmaVAE.Llasa.infer_batch (`self.last_refill_trace` holds the schedule that ran)."""
         return generate_batch(self, prompts, end_disp_kl_thres, max_length, device_head, noise, stop_lag,
-                              self.audio_linear.weight.shape[1])
+                              self.audio_linear.weight.shape[1], refill=refill)
 
-    def _generate_device_head(self, prompts, thres, max_length, noise, stop_lag):
-        """generate_device_head with the mean || log-scale head (ops.llasa_frame_head2); returns the stacked `disp` rows"""
+    def _generate_device_head(self, prompts, thres, max_length, noise, stop_lag, refill=False):
+        """generate_device_head (refill: generate_refill, max_length one cap per prompt) with the mean || log-scale head
+        (ops.llasa_frame_head2); returns the stacked `disp` rows"""
         dlin, alin, model = self.distribution_linear, self.audio_linear, self.base_model.model
         lat = alin.weight.shape[1]
         device_head_limits(stop_lag, lat, ops.HEAD2_MAX_LATENT)
@@ -173,4 +178,6 @@ class Llasa(nn.Module):
         def head(plan, h, nz, active, frame):
             ops.llasa_frame_head2(plan, h, nz, active, frame=frame)
 
+        if refill:
+            return generate_refill(self, prompts, thres, max_length, noise, stop_lag, lat, plan_of=plan_of, head=head, kept="disp")
         return generate_device_head(self, prompts, thres, max_length, noise, stop_lag, lat, plan_of, head, "disp")

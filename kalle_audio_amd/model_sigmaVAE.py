@@ -458,6 +458,42 @@ class LlamaModel(nn.Module):
         return self.norm(x.view(1, n, Dm)) if final_norm else x.view(1, n, Dm)
 
     @torch.no_grad()
+    def prefill_rows(self, embeds, cache, rows, final_norm=True):
+        """prefill_row for several prompts in ONE pass over the decoder weights: embeds, a list of [1, n_i, D], go through the
+        stack packed back to back (ops.Packed, LO.PACK_GRANULE; varlen causal attention, positions from 0) and their k | v rows
+        land in rows `rows` (distinct, each at length 0: a prompt does not continue a row) of the batch cache.  Sets
+        cache["len"][r] = n_i and returns [len(rows), 1, D], the LAST position's hidden state of every prompt (final_norm=False:
+        before `self.norm`).  One prompt is prefill_row.  The bf16 weights, also under quantize_decode_weights."""
+        rows = [int(r) for r in rows]
+        lens = [int(e.shape[1]) for e in embeds]
+        R, room = len(cache["len"]), cache["kv"][0].shape[1]
+        if not rows or len(rows) != len(embeds):
+            raise ValueError(f"prefill_rows takes one cache row per prompt, got {len(embeds)} prompts and rows {rows}")
+        if len(set(rows)) != len(rows) or min(rows) < 0 or max(rows) >= R:
+            raise ValueError(f"prefill_rows takes distinct rows of the cache's {R}, got {rows}")
+        busy = [r for r in rows if cache["len"][r] != 0]
+        if busy:
+            raise ValueError(f"prefill_rows starts at position 0: rows {busy} of the cache are not at length 0")
+        if min(lens) < 1 or max(lens) > room:
+            raise ValueError("KV cache too short" if max(lens) > room else "an empty prompt")
+        _need_gpu(embeds[0])
+        if len(rows) == 1:
+            return self.prefill_row(embeds[0], cache, rows[0], final_norm=final_norm)[:, -1:, :]
+        dev, Dm = embeds[0].device, embeds[0].shape[2]
+        seqs = ops.Packed.back_to_back(lens, dev, granule=LO.PACK_GRANULE)
+        parts = [Fn._to_f32(e.contiguous()).view(n, Dm) for e, n in zip(embeds, lens)]
+        if seqs.has_gaps:
+            parts.append(torch.zeros((seqs.total_rows - seqs.live_rows, Dm), device=dev, dtype=F32))
+        x = torch.cat(parts, dim=0)
+        for layer, kv in zip(self.layers, cache["kv"]):
+            x = LO.layer_fwd_cached_varlen(LO.layer_params(layer), x, kv, seqs, rows, cache["rope"])
+        last = torch.tensor([r0 + n - 1 for r0, n in zip(seqs.row0, lens)], device=dev)
+        x = x.index_select(0, last).view(len(rows), 1, Dm)
+        for r, n in zip(rows, lens):
+            cache["len"][r] = n
+        return self.norm(x) if final_norm else x
+
+    @torch.no_grad()
     def forward_cached_batch(self, inputs_embeds, cache, active=None, final_norm=True):
         """one new position for every active row: appends `inputs_embeds` [R, 1, D] row by row to the caches and returns the last
         hidden states [R, 1, D].  active: R host booleans (default: all); an inactive row's cache and length stay as they are
@@ -573,24 +609,114 @@ def _prompt_embeds(owner, prompts):
     return embeds
 
 
-def generate_batch(owner, prompts, thres, max_length, device_head, noise, stop_lag, lat):
+class RowSchedule:
+    """Which utterance runs in which row of the batch cache at which global step, when a row freed by a stopped utterance takes
+    the next waiting prompt (`infer_batch(refill=True)`).  Host bookkeeping only: prompts are admitted in list order, free rows
+    are taken in ascending row index.  A step s is `admit(s)` (the frame boundary), then one frame for every row of `live(s)`;
+    `release(row, frames)` frees a row once its utterance's stop is known - before `admit(s + 1)` when every step is resolved
+    before the next is enqueued, one `admit` later when the loop runs one step ahead (stop_lag=1)."""
+
+    def __init__(self, n_prompts, R):
+        if n_prompts < 0 or R < 1:
+            raise ValueError(f"RowSchedule takes n_prompts >= 0 and R >= 1, got {n_prompts}, {R}")
+        self.n, self.R = int(n_prompts), int(R)
+        self.rows, self.first = [None] * self.R, [0] * self.R       # the utterance in each row and the step of its frame 0
+        self.waiting = 0                                            # the next prompt of the list
+        self._trace = []
+
+    def admit(self, step):
+        """the (utterance, row) pairs to prefill at the frame boundary of `step`: frame 0 of each runs at that step"""
+        pairs = []
+        for r in range(self.R):
+            if self.rows[r] is None and self.waiting < self.n:
+                self.rows[r], self.first[r] = self.waiting, step
+                pairs.append((self.waiting, r))
+                self.waiting += 1
+        return pairs
+
+    def live(self, step):
+        """(row, utterance, frame) of every occupied row at `step`"""
+        return [(r, u, step - self.first[r]) for r, u in enumerate(self.rows) if u is not None]
+
+    def release(self, row, frames):
+        """the utterance in `row` stopped after `frames` frames (its last one included)"""
+        self._trace.append((self.rows[row], row, self.first[row], int(frames)))
+        self.rows[row] = None
+
+    @property
+    def done(self):
+        return self.waiting >= self.n and all(u is None for u in self.rows)
+
+    @property
+    def trace(self):
+        """(utterance, row, first_step, frames) of every released utterance, in list order"""
+        return sorted(self._trace)
+
+    @property
+    def steps(self):
+        """global steps up to the last frame of the last utterance (the discarded look-ahead frame of stop_lag=1 not counted)"""
+        return max((first + frames for _, _, first, frames in self._trace), default=0)
+
+
+def refill_steps(frames, R, stop_lag=0):
+    """What RowSchedule does for utterances that run frames[u] frames each, in closed form: (total steps, [(row, first_step)] per
+    utterance).  Utterance u starts at the first step >= its predecessor's start at which a row is free, in the lowest such row;
+    its row is free again frames[u] + stop_lag steps later.  `grouped_steps` is the count without refill."""
+    free_at = [0] * R
+    out, t, total = [], 0, 0
+    for n in frames:
+        t = max(t, min(free_at))
+        r = min(i for i in range(R) if free_at[i] <= t)
+        out.append((r, t))
+        free_at[r] = t + int(n) + stop_lag
+        total = max(total, t + int(n))
+    return total, out
+
+
+def grouped_steps(frames, R):
+    """decoder steps of `infer_batch` without refill: groups of R, each as long as its longest utterance"""
+    frames = list(frames)
+    return sum(max(frames[i:i + R]) for i in range(0, len(frames), R))
+
+
+def _frame_caps(max_length, n):
+    """max_length as one cap per prompt (a sequence of n ints), or None for the plain int"""
+    if not hasattr(max_length, "__iter__"):
+        return None
+    caps = [int(m) for m in max_length]
+    if len(caps) != n or min(caps) < 1:
+        raise ValueError(f"max_length is an int or one int >= 1 per prompt; got {len(caps)} values for {n} prompts")
+    return caps
+
+
+def generate_batch(owner, prompts, thres, max_length, device_head, noise, stop_lag, lat, refill=False):
     """`infer_batch` of both task models: the checks, one prompt = `owner.infer`, lists longer than `owner.infer_batch_rows` in
-    groups, a group through owner._generate_device_head or through generate_host_batch with owner._host_frame"""
+    groups, a group through owner._generate_device_head or through generate_host_batch with owner._host_frame; refill=True:
+    the whole list through generate_refill.  max_length: an int, or one frame cap per prompt."""
     prompts = list(prompts)
     if not prompts:
         return []
     if not device_head and (noise is not None or stop_lag):
         raise ValueError("noise= and stop_lag= belong to device_head=True")
+    caps = _frame_caps(max_length, len(prompts))
+    top = max_length if caps is None else max(caps)
     if device_head and noise is not None:
-        noise = noise.to(F32).expand(max_length, len(prompts), lat)
+        noise = noise.to(F32).expand(top, len(prompts), lat)
     if len(prompts) == 1:
-        return [owner.infer(prompts[0][0], prompts[0][1], end_disp_kl_thres=thres, max_length=max_length,
+        return [owner.infer(prompts[0][0], prompts[0][1], end_disp_kl_thres=thres, max_length=top,
                             device_head=device_head, noise=noise, stop_lag=stop_lag)]
+    if refill:
+        caps = [top] * len(prompts) if caps is None else caps
+        if device_head:
+            return owner._generate_device_head(prompts, thres, caps, noise, stop_lag, refill=True)
+        return generate_refill(owner, prompts, thres, caps, None, 0, lat, frame=owner._host_frame)
     G = max(1, min(int(owner.infer_batch_rows), ops.DECODE_MAX_ROWS))
     if len(prompts) > G:
+        part = lambda i: max_length if caps is None else caps[i:i + G]
+        cut = lambda i: noise[:, i:i + G] if caps is None else noise[:max(part(i)), i:i + G]
         return [o for i in range(0, len(prompts), G)
-                for o in generate_batch(owner, prompts[i:i + G], thres, max_length, device_head,
-                                        None if noise is None else noise[:, i:i + G], stop_lag, lat)]
+                for o in generate_batch(owner, prompts[i:i + G], thres, part(i), device_head,
+                                        None if noise is None else cut(i), stop_lag, lat)]
     if device_head:
         return owner._generate_device_head(prompts, thres, max_length, noise, stop_lag)
     return generate_host_batch(owner, prompts, thres, max_length, owner._host_frame)
@@ -603,6 +729,9 @@ def generate_host_batch(owner, prompts, thres, max_length, frame):
     model = owner.base_model.model
     embeds = _prompt_embeds(owner, prompts)
     R = len(embeds)
+    caps = _frame_caps(max_length, R)           # per-row caps: row r leaves after caps[r] frames (None: the loop's end is the cap)
+    max_length = max_length if caps is None else max(caps)
+    caps = caps or [max_length + 1] * R
     cache = model.init_cache_batch(R, max(e.shape[1] for e in embeds) + max_length, embeds[0].device)
     final = [[] for _ in range(R)]
     active = [True] * R
@@ -616,7 +745,7 @@ def generate_host_batch(owner, prompts, thres, max_length, frame):
         for r in range(R):
             if active[r]:
                 final[r].append(kept[r:r + 1])
-                if kl[r] < thres and i > 3:
+                if (kl[r] < thres and i > 3) or i + 1 >= caps[r]:
                     active[r] = False
         if not any(active):
             break
@@ -634,6 +763,9 @@ def generate_device_head(owner, prompts, thres, max_length, noise, stop_lag, lat
     embeds = _prompt_embeds(owner, prompts)
     R, dev = len(embeds), embeds[0].device
     Dm = embeds[0].shape[2]
+    caps = _frame_caps(max_length, R)           # per-row caps (None: the loop's end is the cap, as for generate_host_batch)
+    max_length = max_length if caps is None else max(caps)
+    caps = caps or [max_length + 1] * R
     if noise is not None:
         noise = noise.to(device=dev, dtype=F32).expand(max_length, R, lat)
     one = R == 1
@@ -666,7 +798,7 @@ def generate_device_head(owner, prompts, thres, max_length, noise, stop_lag, lat
         for r in range(R):
             if active[r]:
                 count[r] = i + 1
-                if kl[r] < thres and i > 3:
+                if (kl[r] < thres and i > 3) or i + 1 >= caps[r]:
                     active[r] = False
 
     if stop_lag:
@@ -680,6 +812,113 @@ def generate_device_head(owner, prompts, thres, max_length, noise, stop_lag, lat
         if not any(active):
             break
     return [plan[kept][:count[r] - 1, r, :].clone().unsqueeze(0).transpose(1, 2) for r in range(R)]
+
+
+def generate_refill(owner, prompts, thres, caps, noise, stop_lag, lat, frame=None, plan_of=None, head=None, kept=None):
+    """`infer_batch(refill=True)` of both task models and both heads: ONE batch cache of R = min(infer_batch_rows, DECODE_MAX_ROWS,
+    len(prompts)) rows for the whole list; a row whose utterance stops (the KL rule, or caps[u] frames) takes the next waiting
+    prompt at the next frame boundary (RowSchedule).  A global step is
+      the R-row decode step for the rows that continue (the rows being admitted are inactive in it),
+      LlamaModel.prefill_rows for the admitted prompts - one packed pass; their last hidden states are copied into the step's
+      hidden buffer, row by row - after their cache lengths were reset to 0 (the previous occupant's positions stay in the
+      buffer and are never read: every key count comes from cache["len"]),
+      one head call for every occupied row.
+    frame: the host head (generate_host_batch's), else plan_of / head / kept: the device head (generate_device_head's), whose
+    per-frame slots are a ring of max(caps) + stop_lag slots indexed by the global step (an utterance spans at most that many
+    consecutive steps, the look-ahead frame of stop_lag=1 included); a stopped row's frames are copied out when it stops.
+    noise [max(caps), len(prompts), lat]: utterance u's frame f reads noise[f, u] at whatever row and step it runs.
+    stop_lag=1: step s + 1 is enqueued before step s is resolved, so a stopped row has run one discarded frame and is refilled
+    one step later.  Leaves the schedule's trace in owner.last_refill_trace; returns the results in prompt order."""
+    model = owner.base_model.model
+    embeds = _prompt_embeds(owner, prompts)
+    N, dev, Dm = len(embeds), embeds[0].device, embeds[0].shape[2]
+    R = max(1, min(int(owner.infer_batch_rows), ops.DECODE_MAX_ROWS, N))
+    top = max(caps)
+    cache = model.init_cache_batch(R, max(e.shape[1] for e in embeds) + top, dev)
+    sched = RowSchedule(N, R)
+    results, live, host = [None] * N, {}, frame is not None
+    idle = torch.zeros((R, 1, Dm), device=dev, dtype=F32)       # the hidden buffer of a step without a decode step
+    if host:
+        final, pending, step_in = [[] for _ in range(N)], {}, [None]
+    else:
+        ring = top + stop_lag
+        plan = plan_of(R, dev, ring)
+        kl_host = torch.empty((ring, R), dtype=F32, pin_memory=True)
+        events = [None] * ring
+        if noise is not None:
+            noise = noise.to(device=dev, dtype=F32).expand(top, N, lat)
+
+    def enqueue(s):
+        admitted = sched.admit(s)
+        now = live[s] = sched.live(s)
+        if not now:
+            return
+        fresh = {r for _, r in admitted}
+        cont = [u is not None and r not in fresh for r, u in enumerate(sched.rows)]
+        if any(cont):
+            x_in = step_in[0] if host else plan["x_next"].view(R, 1, Dm)
+            h = model.forward_cached_batch(x_in, cache, cont, final_norm=host)
+        else:
+            h = idle
+        if admitted:
+            for _, r in admitted:
+                cache["len"][r] = 0
+            first = model.prefill_rows([embeds[u] for u, _ in admitted], cache, [r for _, r in admitted], final_norm=host)
+            for j, (_, r) in enumerate(admitted):
+                ops.copy_rows(first[j], h[r], 1, 1, Dm, 0, Dm, 0, Dm)
+        if host:
+            kept_t, audio_latent, kl = frame(h)
+            pending[s] = (kept_t, kl)
+            step_in[0] = owner.audio_linear(audio_latent)
+            return
+        if noise is None:
+            nz = torch.randn((R, 1, lat), device=dev, dtype=F32).view(R, lat)
+        else:       # (the discarded look-ahead frame of an utterance at its cap reads its last draw again)
+            fi, ui = [0] * R, [0] * R
+            for r, u, f in now:
+                fi[r], ui[r] = min(f, top - 1), u
+            nz = noise[fi, ui]
+        slot = s % ring
+        head(plan, h.view(R, Dm), nz, [u is not None for u in sched.rows], slot)
+        kl_host[slot].copy_(plan["kl"][slot], non_blocking=True)
+        events[slot] = torch.cuda.Event()
+        events[slot].record()
+
+    def resolve(s):     # the one host wait of step s
+        now = live.pop(s)
+        if not now:
+            return
+        if host:
+            kept_t, kl = pending.pop(s)
+            kl = kl.view(R).tolist()
+        else:
+            events[s % ring].synchronize()
+            kl = kl_host[s % ring].tolist()
+        for r, u, f in now:
+            if sched.rows[r] != u:          # (stop_lag=1: the look-ahead frame of an utterance that has stopped)
+                continue
+            if host:
+                final[u].append(kept_t[r:r + 1])
+            if (kl[r] < thres and f > 3) or f + 1 >= caps[u]:
+                if host:
+                    results[u] = torch.stack(final[u][:-1], dim=1).squeeze(1).squeeze(2).transpose(1, 2)
+                    final[u] = None
+                else:   # frames 0 .. f - 1 sit in the slots of steps s - f .. s - 1
+                    slots = torch.tensor([(s - f + j) % ring for j in range(f)], device=dev, dtype=torch.long)
+                    results[u] = plan[kept][:, r, :].index_select(0, slots).unsqueeze(0).transpose(1, 2)
+                sched.release(r, f + 1)
+
+    s = 0
+    if stop_lag:
+        enqueue(0)
+    while True:
+        enqueue(s + 1 if stop_lag else s)
+        resolve(s)
+        if sched.done:
+            break
+        s += 1
+    owner.last_refill_trace = sched.trace
+    return results
 
 
 class Llasa(nn.Module):
@@ -785,7 +1024,8 @@ class Llasa(nn.Module):
     infer_batch_rows = ops.DECODE_MAX_ROWS      # sequences decoded per step by infer_batch (the kernels take up to DECODE_MAX_ROWS)
 
     @torch.no_grad()
-    def infer_batch(self, prompts, end_disp_kl_thres=0.5, max_length=200, device_head=False, noise=None, stop_lag=0):
+    def infer_batch(self, prompts, end_disp_kl_thres=0.5, max_length=200, device_head=False, noise=None, stop_lag=0,
+                    refill=False):
         """`infer` (KV-cached) for a list of (input_ids, audio_latents or None): the utterances of a group are generated together,
         one decoder pass per frame for all of them, so the decoder weights are read once per frame instead of once per frame
         and utterance.  Returns a list with what `infer` returns for each prompt.  The prompts are prefilled one by one (they
@@ -793,9 +1033,20 @@ class Llasa(nn.Module):
         others go on.  Lists longer than `infer_batch_rows` are processed in groups; one prompt is `infer` itself.
         device_head / noise / stop_lag: as in `infer`, noise broadcastable to [max_length, len(prompts), latent_dim] and drawn,
         when absent, as one torch.randn((R, 1, latent_dim)) per frame for the R rows of a group; with stop_lag=1 a stopped
-        row's cache holds one extra position."""
+        row's cache holds one extra position.
+        max_length (extension): an int, or one int per prompt - utterance p leaves after max_length[p] frames and returns
+        max_length[p] - 1 of them, as the single cap does.
+        refill=True (extension, opt-in): the whole list shares ONE batch cache of min(infer_batch_rows, len(prompts)) rows; a row
+        whose utterance stops takes the next waiting prompt at the next frame boundary instead of idling until its group ends,
+        and the prompts admitted at one boundary are prefilled together in one packed pass (LlamaModel.prefill_rows).  Results
+        come back in prompt order, each what `infer` returns.  With explicit noise utterance p's frame f reads noise[f, p] at
+        whatever row and step it runs, so its result depends on its own prompt and noise only (up to rounding: the packed
+        prefill GEMMs may pick another plan at another row count).  With noise=None one torch.randn((R, 1, latent_dim)) is
+        drawn per global step, so WHICH utterance gets which draw differs from the grouped mode (and, under the host head, one
+        draw per step covers all R rows as before).  stop_lag=1: a stopped row is refilled one step later (its discarded extra
+        frame has run).  The schedule that ran is left in `self.last_refill_trace`: (utterance, row, first_step, frames)."""
         return generate_batch(self, prompts, end_disp_kl_thres, max_length, device_head, noise, stop_lag,
-                              self.distribution_linear[2].weight.shape[0])
+                              self.distribution_linear[2].weight.shape[0], refill=refill)
 
     def _host_frame(self, hidden):
         """the head of one frame on the host for the rows of hidden [R, 1, D]: (what `infer_batch` stacks, the sampled latent
@@ -806,8 +1057,9 @@ class Llasa(nn.Module):
         kl = (torch.log(torch.tensor(e / s)) + (s * s + (mean2.float() - 1.0) ** 2) / (2 * e * e) - 0.5).sum(2)
         return audio_latent, audio_latent, kl / mean2.shape[2]
 
-    def _generate_device_head(self, prompts, thres, max_length, noise, stop_lag):
-        """generate_device_head with the fixed-std head (ops.llasa_frame_head); returns the sampled latents"""
+    def _generate_device_head(self, prompts, thres, max_length, noise, stop_lag, refill=False):
+        """generate_device_head (refill: generate_refill, max_length one cap per prompt) with the fixed-std head
+        (ops.llasa_frame_head); returns the sampled latents"""
         dlin, alin, model = self.distribution_linear, self.audio_linear, self.base_model.model
         dl = dlin[2].weight.shape[0]
         device_head_limits(stop_lag, dl, ops.HEAD_MAX_LATENT)
@@ -824,6 +1076,8 @@ class Llasa(nn.Module):
         def head(plan, h, nz, active, frame):
             ops.llasa_frame_head(plan, h, nz, std, active, frame=frame)
 
+        if refill:
+            return generate_refill(self, prompts, thres, max_length, noise, stop_lag, dl, plan_of=plan_of, head=head, kept="latent")
         return generate_device_head(self, prompts, thres, max_length, noise, stop_lag, dl, plan_of, head, "latent")
 
     def init_sigmaVAE(self):

@@ -558,6 +558,23 @@ def attention_fwd_varlen(q, k, v, seqs, *, ldq, q_off, ldk, k_off, ldv, v_off, H
     return out, lse
 
 
+def kv_append_varlen(src, seqs, cache, dst_rows, t0, *, src_off):
+    """kalle_kv_append_varlen: the k|v window (columns src_off .. src_off + kvw of the packed bf16 buffer src [total_rows, ld]) of
+    every sequence of `seqs` (a Packed) goes to cache [R, cache_rows, kvw], sequence s to cache[dst_rows[s], t0[s] + j]; dst_rows /
+    t0: host ints, one per sequence.  One launch, nothing else written.  Returns cache."""
+    lib = _lib.load()
+    assert src.dtype == cache.dtype == torch.bfloat16 and src.dim() == 2 and src.stride(1) == 1 and src.shape[0] == seqs.total_rows
+    assert cache.dim() == 3 and cache.stride(2) == 1 and cache.stride(1) == cache.shape[2]
+    assert len(dst_rows) == len(t0) == seqs.nseq
+    R, cache_rows, kvw = cache.shape
+    cast = ctypes.cast
+    check(lib.kalle_kv_append_varlen(_p(src), src.stride(0), src_off, _p(cache), cache.stride(0), kvw, seqs.nseq,
+                                     cast(seqs.host[0], ctypes.c_void_p), cast(seqs.host[1], ctypes.c_void_p),
+                                     cast(_i32(dst_rows), ctypes.c_void_p), cast(_i32(t0), ctypes.c_void_p), seqs.total_rows, R,
+                                     cache_rows, _stream()), "kalle_kv_append_varlen")
+    return cache
+
+
 def attention_bwd_varlen(q, k, v, out, dout, lse, seqs, *, ldq, q_off, ldk, k_off, ldv, v_off, H, Hkv, rope=None, dh=64,
                          dq=None, dk=None, dv=None):
     """kalle_attention_bwd_varlen.  dq / dk / dv None: ONE new buffer shaped like q that receives all three (the fused qkv

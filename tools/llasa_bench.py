@@ -8,6 +8,11 @@ Llama-3.2-3B shape  --hidden 3072 --layers 28 --heads 24 --kv-heads 8 --head-dim
 --device-head: after the host-head lines, the same KV-cached generation with device_head=True (the per-frame head as one call of
 kalle_llasa_frame_head_rows) in the same process, each line with its ratio to the host-head line; --stop-lag N (0 or 1): one more
 set of lines with stop_lag=N
+--infer-batch R --refill [--utterances N]: INSTEAD of the lines above, N (default 64) prompts with per-prompt frame caps drawn in
+50 .. 250 (random.Random(0), printed; the stop threshold off) through infer_batch(refill=False) and infer_batch(refill=True) in one
+process, alternating, three repeats each, for every head selected: aggregate frames/s of both (min - max), the measured gain next
+to the step ratio refill_steps predicts for the list, then the time to the first frame of R prompts prefilled one by one
+(prefill_row) and packed (prefill_rows)
 --scale-head: the generation lines for model.Llasa (the mean || log-scale head of train.py / configs/twj_0828.yaml; its device
 head is kalle_llasa_frame_head2_rows) in place of model_sigmaVAE.Llasa; implies --infer-only
 --ragged SEED [--pack]: the train step on a batch shaped like the reference's collate - sample 0 at full length L, the others
@@ -57,6 +62,16 @@ if "--stop-lag" in sys.argv:
         sys.exit("--stop-lag belongs to --device-head")
     if _lag:
         HEADS.append((f"device head, stop_lag={_lag}", dict(device_head=True, stop_lag=_lag)))
+REFILL = "--refill" in sys.argv               # --infer-batch R --refill [--utterances N]: infer_batch(refill=True) against the groups
+if REFILL:
+    sys.argv.remove("--refill")
+    if not INFER_BATCH:
+        sys.exit("--refill belongs to --infer-batch R")
+UTTERANCES = 64
+if "--utterances" in sys.argv:
+    _i = sys.argv.index("--utterances")
+    UTTERANCES = int(sys.argv[_i + 1])
+    del sys.argv[_i:_i + 2]
 RAGGED = None                                # --ragged SEED: a right-padded batch with lengths from [L/4, L]
 if "--ragged" in sys.argv:
     _i = sys.argv.index("--ragged")
@@ -199,6 +214,72 @@ elif not INFER_ONLY:
   print(f"Llasa {'Llama-3.2-1B-shape' if HID == 2048 and NLAYER == 16 else f'hidden-{HID}-x-{NLAYER}-layers'} train step B={B} L={L}: {dt*1e3:.1f} ms/step, {B*L/dt:.0f} tokens/s, "
         f"{B*L/12.5/dt:.0f} audio-s/s (12.5 Hz frames), {fl/dt/1e12:.0f} TFLOP/s algorithmic, params {nparam/1e9:.2f} B, "
         f"loss {out['audio_loss'].item():.3f}")
+
+if REFILL:
+    # a ragged list through both modes of infer_batch in ONE process: UTTERANCES prompts of 64 / 56 / 48 / 40 tokens on R rows,
+    # per-prompt frame caps from a seeded draw in 50 .. 250 (the stop threshold off, so the caps alone decide the lengths)
+    import random
+    from kalle_audio_amd.model_sigmaVAE import grouped_steps, refill_steps
+    m.eval()
+    if DECODE_WEIGHTS:
+        m.quantize_decoder(DECODE_WEIGHTS)
+    R = m.infer_batch_rows = INFER_BATCH
+    rng = random.Random(0)
+    caps = [rng.randint(50, 250) for _ in range(UTTERANCES)]
+    prompts = [(torch.randint(0, 128264, (64 - 8 * (r % 4),), device=dev), None) for r in range(UTTERANCES)]
+    frames = sum(caps)
+    print(f"refill: {UTTERANCES} utterances on {R} rows, decode weights {DECODE_WEIGHTS or 'bf16'}, frame caps (random.Random(0), 50 .. 250): {caps}")
+    print(f"  {frames} frames; decoder steps predicted: grouped {grouped_steps(caps, R)}, refill {refill_steps(caps, R)[0]} "
+          f"(stop_lag=1: {refill_steps(caps, R, 1)[0]})")
+
+    def run(refill, kw):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        outs = m.infer_batch(prompts, end_disp_kl_thres=-1.0, max_length=caps, refill=refill, **kw)
+        torch.cuda.synchronize()
+        assert [o.shape[2] for o in outs] == [n - 1 for n in caps]
+        return time.perf_counter() - t
+
+    for label, kw in HEADS:
+        pred = grouped_steps(caps, R) / refill_steps(caps, R, kw.get("stop_lag", 0))[0]
+        for refill in (False, True):                      # warm every shape the timed runs use: one whole run of each mode
+            run(refill, kw)
+        dts = {False: [], True: []}
+        for rep in range(3):
+            for refill in ((False, True) if rep % 2 == 0 else (True, False)):      # alternate the order
+                dts[refill].append(run(refill, kw))
+        fps = {k: sorted(frames / dt for dt in v) for k, v in dts.items()}
+        print(f"refill [{label}]: grouped {fps[False][0]:.0f} - {fps[False][-1]:.0f} frames/s aggregate, refill {fps[True][0]:.0f} - "
+              f"{fps[True][-1]:.0f} frames/s aggregate (min - max of 3), measured gain x {min(dts[False]) / min(dts[True]):.3f} - "
+              f"x {max(dts[False]) / max(dts[True]):.3f} (best / worst runs), step ratio predicted x {pred:.3f}; "
+              f"grouped {min(dts[False]) * 1e3:.0f} ms, refill {min(dts[True]) * 1e3:.0f} ms")
+    # time to the first frame of R prompts: every prompt through the stack alone (prefill_row) against one packed pass (prefill_rows)
+    model = m.base_model.model
+    with torch.no_grad():
+        embeds = [model.embed_tokens(ids.unsqueeze(0)) for ids, _ in prompts[:R]]
+        room = max(e.shape[1] for e in embeds) + 8
+
+        def first_frame(packed):
+            cache = model.init_cache_batch(R, room, dev)
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            if packed:
+                h = model.prefill_rows(embeds, cache, list(range(R)))
+            else:
+                h = torch.cat([model.prefill_row(e, cache, r)[:, -1:, :] for r, e in enumerate(embeds)], dim=0)
+            m._host_frame(h)
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t) * 1e3
+
+        for packed in (False, True):
+            first_frame(packed)
+        ms = {False: [], True: []}
+        for rep in range(3):
+            for packed in ((False, True) if rep % 2 == 0 else (True, False)):
+                ms[packed].append(first_frame(packed))
+    print(f"time to the first frame, {R} prompts of {[e.shape[1] for e in embeds[:4]]} ... tokens (prefill + the host head): one by one "
+          f"{min(ms[False]):.2f} - {max(ms[False]):.2f} ms, packed {min(ms[True]):.2f} - {max(ms[True]):.2f} ms (min - max of 3)")
+    sys.exit(0)
 
 if "--infer" in sys.argv or INFER_ONLY:
     # frame-by-frame generation (Llasa.infer): 64 prompt tokens, 200 frames, KV cache vs the reference's full re-forward
