@@ -18,8 +18,8 @@ from torch import nn
 from . import functional as Fn
 from . import ops
 from .dit_ops import F32
-from .model_sigmaVAE import (GELU, EmbedMixFn, Linear, LlamaForCausalLM, _need_gpu, device_head_limits, generate_batch,
-                             generate_device_head, generate_refill)
+from .generation import DeviceHeadSpec, device_head_limits, generate, generate_batch, generate_one
+from .model_sigmaVAE import GELU, EmbedMixFn, Linear, LlamaForCausalLM, _need_gpu
 
 get_mean_stdev_from_stableaudio2_latents = None      # injectable stand-in for the missing twj_utils function (see above)
 LABEL_STD_MULT = 1.25                                # model.py:87
@@ -107,33 +107,8 @@ class Llasa(nn.Module):
         two decode steps is one call of kalle_llasa_frame_head2_rows, `noise` is the N(0, 1) draws, fp32, broadcastable to
         [max_length, 1, latent_dim] (default: one torch.randn((1, 1, latent_dim)) per frame, the shape and order the host path
         draws in), stop_lag=1 enqueues frame i + 1 before frame i's KL is read and returns the same bits."""
-        if device_head:
-            if not use_cache:
-                raise NotImplementedError("device_head=True generates against a KV cache; use_cache=False runs on the host path "
-                                          "(device_head=False)")
-            return self._generate_device_head([(input_ids, audio_latents)], end_disp_kl_thres, max_length, noise, stop_lag)[0]
-        if noise is not None or stop_lag:
-            raise ValueError("noise= and stop_lag= belong to device_head=True")
-        ids = input_ids.unsqueeze(0)
-        parts = [self.base_model.model.embed_tokens(ids)]
-        if audio_latents is not None:
-            parts.append(self.audio_linear(audio_latents))
-        input_embed = torch.cat(parts, dim=1)
-        final = []
-        model = self.base_model.model
-        cache = model.init_cache(input_embed.shape[1] + max_length, input_embed.device) if use_cache else None
-        step_in = input_embed
-        for i in range(max_length):
-            hidden = model.forward_cached(step_in, cache) if use_cache else model(inputs_embeds=input_embed)[0]
-            last_disp, audio_latent, kl = self._host_frame(hidden[:, -1:, :])
-            final.append(last_disp)
-            if kl.item() < end_disp_kl_thres and i > 3:
-                break
-            step_in = self.audio_linear(audio_latent)
-            if not use_cache:
-                input_embed = torch.cat((input_embed, step_in), dim=1)
-        out = torch.stack(final[:-1], dim=1).squeeze(1).squeeze(2)
-        return out.transpose(1, 2)
+        return generate_one(self, input_ids, audio_latents, end_disp_kl_thres, max_length, use_cache, device_head, noise,
+                            stop_lag)
 
     def _host_frame(self, hidden):
         """the head of one frame on the host for the rows of hidden [R, 1, D]: (last_disp [R, 1, 2 lat], the sampled latent
@@ -165,19 +140,8 @@ class Llasa(nn.Module):
                               self.audio_linear.weight.shape[1], refill=refill)
 
     def _generate_device_head(self, prompts, thres, max_length, noise, stop_lag, refill=False):
-        """generate_device_head (refill: generate_refill, max_length one cap per prompt) with the mean || log-scale head
-        (ops.llasa_frame_head2); returns the stacked `disp` rows"""
-        dlin, alin, model = self.distribution_linear, self.audio_linear, self.base_model.model
-        lat = alin.weight.shape[1]
+        """generation.generate with the mean || log-scale head (ops.llasa_frame_head2); returns the stacked `disp` rows"""
+        lat = self.audio_linear.weight.shape[1]
         device_head_limits(stop_lag, lat, ops.HEAD2_MAX_LATENT)
-
-        def plan_of(R, dev, frames):
-            return ops.llasa_head2_plan(model.norm.weight, dlin[0].weight, dlin[0].bias, dlin[2].weight, dlin[2].bias, alin.weight,
-                                        alin.bias, R, model.norm.variance_epsilon, dev, frames=frames)
-
-        def head(plan, h, nz, active, frame):
-            ops.llasa_frame_head2(plan, h, nz, active, frame=frame)
-
-        if refill:
-            return generate_refill(self, prompts, thres, max_length, noise, stop_lag, lat, plan_of=plan_of, head=head, kept="disp")
-        return generate_device_head(self, prompts, thres, max_length, noise, stop_lag, lat, plan_of, head, "disp")
+        spec = DeviceHeadSpec(ops.llasa_head2_plan, ops.llasa_frame_head2, (), "disp", lat)
+        return generate(self, prompts, thres, max_length, spec, noise, stop_lag, refill)

@@ -19,6 +19,8 @@ from . import functional as Fn
 from . import llama_ops as LO
 from . import ops
 from .dit_ops import BF16, F32, GradOut, bf16_of, f32_of
+from .generation import DeviceHeadSpec, device_head_limits, generate, generate_batch, generate_one
+from .generation import RowSchedule, grouped_steps, refill_steps  # noqa: F401  (documented under this module's name)
 
 
 def _need_gpu(t):
@@ -589,338 +591,6 @@ def _read_hf_weights(path):
     return None
 
 
-def device_head_limits(stop_lag, lat, max_lat):
-    """the refusals both task models share before a device-head generation starts"""
-    if stop_lag not in (0, 1):
-        raise NotImplementedError(f"stop_lag is 0 or 1, got {stop_lag!r}; the host path (device_head=False) takes neither")
-    if lat % 8 or not 8 <= lat <= max_lat:
-        raise NotImplementedError(f"device_head=True takes a latent_dim that is a multiple of 8 in 8 .. {max_lat}, "
-                                  f"got {lat}; the host path (device_head=False) has no such limit")
-
-
-def _prompt_embeds(owner, prompts):
-    model = owner.base_model.model
-    embeds = []
-    for ids, lat in prompts:
-        parts = [model.embed_tokens(ids.unsqueeze(0))]
-        if lat is not None:
-            parts.append(owner.audio_linear(lat))
-        embeds.append(torch.cat(parts, dim=1))
-    return embeds
-
-
-class RowSchedule:
-    """Which utterance runs in which row of the batch cache at which global step, when a row freed by a stopped utterance takes
-    the next waiting prompt (`infer_batch(refill=True)`).  Host bookkeeping only: prompts are admitted in list order, free rows
-    are taken in ascending row index.  A step s is `admit(s)` (the frame boundary), then one frame for every row of `live(s)`;
-    `release(row, frames)` frees a row once its utterance's stop is known - before `admit(s + 1)` when every step is resolved
-    before the next is enqueued, one `admit` later when the loop runs one step ahead (stop_lag=1)."""
-
-    def __init__(self, n_prompts, R):
-        if n_prompts < 0 or R < 1:
-            raise ValueError(f"RowSchedule takes n_prompts >= 0 and R >= 1, got {n_prompts}, {R}")
-        self.n, self.R = int(n_prompts), int(R)
-        self.rows, self.first = [None] * self.R, [0] * self.R       # the utterance in each row and the step of its frame 0
-        self.waiting = 0                                            # the next prompt of the list
-        self._trace = []
-
-    def admit(self, step):
-        """the (utterance, row) pairs to prefill at the frame boundary of `step`: frame 0 of each runs at that step"""
-        pairs = []
-        for r in range(self.R):
-            if self.rows[r] is None and self.waiting < self.n:
-                self.rows[r], self.first[r] = self.waiting, step
-                pairs.append((self.waiting, r))
-                self.waiting += 1
-        return pairs
-
-    def live(self, step):
-        """(row, utterance, frame) of every occupied row at `step`"""
-        return [(r, u, step - self.first[r]) for r, u in enumerate(self.rows) if u is not None]
-
-    def release(self, row, frames):
-        """the utterance in `row` stopped after `frames` frames (its last one included)"""
-        self._trace.append((self.rows[row], row, self.first[row], int(frames)))
-        self.rows[row] = None
-
-    @property
-    def done(self):
-        return self.waiting >= self.n and all(u is None for u in self.rows)
-
-    @property
-    def trace(self):
-        """(utterance, row, first_step, frames) of every released utterance, in list order"""
-        return sorted(self._trace)
-
-    @property
-    def steps(self):
-        """global steps up to the last frame of the last utterance (the discarded look-ahead frame of stop_lag=1 not counted)"""
-        return max((first + frames for _, _, first, frames in self._trace), default=0)
-
-
-def refill_steps(frames, R, stop_lag=0):
-    """What RowSchedule does for utterances that run frames[u] frames each, in closed form: (total steps, [(row, first_step)] per
-    utterance).  Utterance u starts at the first step >= its predecessor's start at which a row is free, in the lowest such row;
-    its row is free again frames[u] + stop_lag steps later.  `grouped_steps` is the count without refill."""
-    free_at = [0] * R
-    out, t, total = [], 0, 0
-    for n in frames:
-        t = max(t, min(free_at))
-        r = min(i for i in range(R) if free_at[i] <= t)
-        out.append((r, t))
-        free_at[r] = t + int(n) + stop_lag
-        total = max(total, t + int(n))
-    return total, out
-
-
-def grouped_steps(frames, R):
-    """decoder steps of `infer_batch` without refill: groups of R, each as long as its longest utterance"""
-    frames = list(frames)
-    return sum(max(frames[i:i + R]) for i in range(0, len(frames), R))
-
-
-def _frame_caps(max_length, n):
-    """max_length as one cap per prompt (a sequence of n ints), or None for the plain int"""
-    if not hasattr(max_length, "__iter__"):
-        return None
-    caps = [int(m) for m in max_length]
-    if len(caps) != n or min(caps) < 1:
-        raise ValueError(f"max_length is an int or one int >= 1 per prompt; got {len(caps)} values for {n} prompts")
-    return caps
-
-
-def generate_batch(owner, prompts, thres, max_length, device_head, noise, stop_lag, lat, refill=False):
-    """`infer_batch` of both task models: the checks, one prompt = `owner.infer`, lists longer than `owner.infer_batch_rows` in
-    groups, a group through owner._generate_device_head or through generate_host_batch with owner._host_frame; refill=True:
-    the whole list through generate_refill.  max_length: an int, or one frame cap per prompt."""
-    prompts = list(prompts)
-    if not prompts:
-        return []
-    if not device_head and (noise is not None or stop_lag):
-        raise ValueError("noise= and stop_lag= belong to device_head=True")
-    caps = _frame_caps(max_length, len(prompts))
-    top = max_length if caps is None else max(caps)
-    if device_head and noise is not None:
-        noise = noise.to(F32).expand(top, len(prompts), lat)
-    if len(prompts) == 1:
-        return [owner.infer(prompts[0][0], prompts[0][1], end_disp_kl_thres=thres, max_length=top,
-                            device_head=device_head, noise=noise, stop_lag=stop_lag)]
-    if refill:
-        caps = [top] * len(prompts) if caps is None else caps
-        if device_head:
-            return owner._generate_device_head(prompts, thres, caps, noise, stop_lag, refill=True)
-        return generate_refill(owner, prompts, thres, caps, None, 0, lat, frame=owner._host_frame)
-    G = max(1, min(int(owner.infer_batch_rows), ops.DECODE_MAX_ROWS))
-    if len(prompts) > G:
-        part = lambda i: max_length if caps is None else caps[i:i + G]
-        cut = lambda i: noise[:, i:i + G] if caps is None else noise[:max(part(i)), i:i + G]
-        return [o for i in range(0, len(prompts), G)
-                for o in generate_batch(owner, prompts[i:i + G], thres, part(i), device_head,
-                                        None if noise is None else cut(i), stop_lag, lat)]
-    if device_head:
-        return owner._generate_device_head(prompts, thres, max_length, noise, stop_lag)
-    return generate_host_batch(owner, prompts, thres, max_length, owner._host_frame)
-
-
-def generate_host_batch(owner, prompts, thres, max_length, frame):
-    """One group of `infer_batch` with the head on the host, for both task models (model_sigmaVAE.Llasa, model.Llasa).
-    frame(hidden [R, 1, D]) -> (kept [R, 1, w], audio_latent [R, 1, lat], kl [R, 1]): `kept` is what the caller's `infer`
-    stacks per frame (the sampled latent / mean || log-scale), `audio_latent` feeds audio_linear, `kl` is the stop quantity."""
-    model = owner.base_model.model
-    embeds = _prompt_embeds(owner, prompts)
-    R = len(embeds)
-    caps = _frame_caps(max_length, R)           # per-row caps: row r leaves after caps[r] frames (None: the loop's end is the cap)
-    max_length = max_length if caps is None else max(caps)
-    caps = caps or [max_length + 1] * R
-    cache = model.init_cache_batch(R, max(e.shape[1] for e in embeds) + max_length, embeds[0].device)
-    final = [[] for _ in range(R)]
-    active = [True] * R
-    for i in range(max_length):
-        if i == 0:      # prefill: the last position's hidden state of every prompt
-            hidden = torch.cat([model.prefill_row(emb, cache, r)[:, -1:, :] for r, emb in enumerate(embeds)], dim=0)
-        else:
-            hidden = model.forward_cached_batch(step_in, cache, active)
-        kept, audio_latent, kl = frame(hidden)
-        kl = kl.view(R).tolist()                                                     # the one host read of the frame
-        for r in range(R):
-            if active[r]:
-                final[r].append(kept[r:r + 1])
-                if (kl[r] < thres and i > 3) or i + 1 >= caps[r]:
-                    active[r] = False
-        if not any(active):
-            break
-        step_in = owner.audio_linear(audio_latent)
-    return [torch.stack(f[:-1], dim=1).squeeze(1).squeeze(2).transpose(1, 2) for f in final]
-
-
-def generate_device_head(owner, prompts, thres, max_length, noise, stop_lag, lat, plan_of, head, kept):
-    """`infer` (one prompt: the one-row decode step) / one group of `infer_batch` (the R-row step) with the per-frame head on the
-    device, for both task models: a frame is the decode step plus head(plan, h, noise, active, frame) - ops.llasa_frame_head or
-    ops.llasa_frame_head2 on the plan of plan_of(R, device, frames) - its KL goes to slot i of a device buffer, from there to
-    pinned host memory without blocking, followed by an event.  stop_lag = how many frames are enqueued ahead of the event the
-    host waits for (0 or 1).  kept: the plan's [frames, R, w] buffer a row's result is cut from ("latent" / "disp")."""
-    model = owner.base_model.model
-    embeds = _prompt_embeds(owner, prompts)
-    R, dev = len(embeds), embeds[0].device
-    Dm = embeds[0].shape[2]
-    caps = _frame_caps(max_length, R)           # per-row caps (None: the loop's end is the cap, as for generate_host_batch)
-    max_length = max_length if caps is None else max(caps)
-    caps = caps or [max_length + 1] * R
-    if noise is not None:
-        noise = noise.to(device=dev, dtype=F32).expand(max_length, R, lat)
-    one = R == 1
-    room = max(e.shape[1] for e in embeds) + max_length
-    cache = model.init_cache(room, dev) if one else model.init_cache_batch(R, room, dev)
-    plan = plan_of(R, dev, max_length)
-    kl_host = torch.empty((max_length, R), dtype=F32, pin_memory=True)
-    events = [None] * max_length
-    active, count = [True] * R, [0] * R
-
-    def enqueue(i):
-        if i == 0:      # prefill: the last position's un-normed residual stream of every prompt
-            if one:
-                h = model.forward_cached(embeds[0], cache, final_norm=False)[0, -1:, :]
-            else:
-                h = torch.cat([model.prefill_row(emb, cache, r, final_norm=False)[:, -1, :] for r, emb in enumerate(embeds)])
-        elif one:
-            h = model.forward_cached(plan["x_next"].view(1, 1, Dm), cache, final_norm=False).view(1, Dm)
-        else:
-            h = model.forward_cached_batch(plan["x_next"].view(R, 1, Dm), cache, active, final_norm=False).view(R, Dm)
-        nz = torch.randn((R, 1, lat), device=dev, dtype=F32).view(R, lat) if noise is None else noise[i].contiguous()
-        head(plan, h, nz, None if one else active, i)
-        kl_host[i].copy_(plan["kl"][i], non_blocking=True)
-        events[i] = torch.cuda.Event()
-        events[i].record()
-
-    def resolve(i):     # the one host wait of frame i
-        events[i].synchronize()
-        kl = kl_host[i].tolist()
-        for r in range(R):
-            if active[r]:
-                count[r] = i + 1
-                if (kl[r] < thres and i > 3) or i + 1 >= caps[r]:
-                    active[r] = False
-
-    if stop_lag:
-        enqueue(0)
-    for i in range(max_length):
-        if not stop_lag:
-            enqueue(i)
-        elif i + 1 < max_length:
-            enqueue(i + 1)          # (ahead of frame i's event; discarded if frame i turns out to stop every row)
-        resolve(i)
-        if not any(active):
-            break
-    return [plan[kept][:count[r] - 1, r, :].clone().unsqueeze(0).transpose(1, 2) for r in range(R)]
-
-
-def generate_refill(owner, prompts, thres, caps, noise, stop_lag, lat, frame=None, plan_of=None, head=None, kept=None):
-    """`infer_batch(refill=True)` of both task models and both heads: ONE batch cache of R = min(infer_batch_rows, DECODE_MAX_ROWS,
-    len(prompts)) rows for the whole list; a row whose utterance stops (the KL rule, or caps[u] frames) takes the next waiting
-    prompt at the next frame boundary (RowSchedule).  A global step is
-      the R-row decode step for the rows that continue (the rows being admitted are inactive in it),
-      LlamaModel.prefill_rows for the admitted prompts - one packed pass; their last hidden states are copied into the step's
-      hidden buffer, row by row - after their cache lengths were reset to 0 (the previous occupant's positions stay in the
-      buffer and are never read: every key count comes from cache["len"]),
-      one head call for every occupied row.
-    frame: the host head (generate_host_batch's), else plan_of / head / kept: the device head (generate_device_head's), whose
-    per-frame slots are a ring of max(caps) + stop_lag slots indexed by the global step (an utterance spans at most that many
-    consecutive steps, the look-ahead frame of stop_lag=1 included); a stopped row's frames are copied out when it stops.
-    noise [max(caps), len(prompts), lat]: utterance u's frame f reads noise[f, u] at whatever row and step it runs.
-    stop_lag=1: step s + 1 is enqueued before step s is resolved, so a stopped row has run one discarded frame and is refilled
-    one step later.  Leaves the schedule's trace in owner.last_refill_trace; returns the results in prompt order."""
-    model = owner.base_model.model
-    embeds = _prompt_embeds(owner, prompts)
-    N, dev, Dm = len(embeds), embeds[0].device, embeds[0].shape[2]
-    R = max(1, min(int(owner.infer_batch_rows), ops.DECODE_MAX_ROWS, N))
-    top = max(caps)
-    cache = model.init_cache_batch(R, max(e.shape[1] for e in embeds) + top, dev)
-    sched = RowSchedule(N, R)
-    results, live, host = [None] * N, {}, frame is not None
-    idle = torch.zeros((R, 1, Dm), device=dev, dtype=F32)       # the hidden buffer of a step without a decode step
-    if host:
-        final, pending, step_in = [[] for _ in range(N)], {}, [None]
-    else:
-        ring = top + stop_lag
-        plan = plan_of(R, dev, ring)
-        kl_host = torch.empty((ring, R), dtype=F32, pin_memory=True)
-        events = [None] * ring
-        if noise is not None:
-            noise = noise.to(device=dev, dtype=F32).expand(top, N, lat)
-
-    def enqueue(s):
-        admitted = sched.admit(s)
-        now = live[s] = sched.live(s)
-        if not now:
-            return
-        fresh = {r for _, r in admitted}
-        cont = [u is not None and r not in fresh for r, u in enumerate(sched.rows)]
-        if any(cont):
-            x_in = step_in[0] if host else plan["x_next"].view(R, 1, Dm)
-            h = model.forward_cached_batch(x_in, cache, cont, final_norm=host)
-        else:
-            h = idle
-        if admitted:
-            for _, r in admitted:
-                cache["len"][r] = 0
-            first = model.prefill_rows([embeds[u] for u, _ in admitted], cache, [r for _, r in admitted], final_norm=host)
-            for j, (_, r) in enumerate(admitted):
-                ops.copy_rows(first[j], h[r], 1, 1, Dm, 0, Dm, 0, Dm)
-        if host:
-            kept_t, audio_latent, kl = frame(h)
-            pending[s] = (kept_t, kl)
-            step_in[0] = owner.audio_linear(audio_latent)
-            return
-        if noise is None:
-            nz = torch.randn((R, 1, lat), device=dev, dtype=F32).view(R, lat)
-        else:       # (the discarded look-ahead frame of an utterance at its cap reads its last draw again)
-            fi, ui = [0] * R, [0] * R
-            for r, u, f in now:
-                fi[r], ui[r] = min(f, top - 1), u
-            nz = noise[fi, ui]
-        slot = s % ring
-        head(plan, h.view(R, Dm), nz, [u is not None for u in sched.rows], slot)
-        kl_host[slot].copy_(plan["kl"][slot], non_blocking=True)
-        events[slot] = torch.cuda.Event()
-        events[slot].record()
-
-    def resolve(s):     # the one host wait of step s
-        now = live.pop(s)
-        if not now:
-            return
-        if host:
-            kept_t, kl = pending.pop(s)
-            kl = kl.view(R).tolist()
-        else:
-            events[s % ring].synchronize()
-            kl = kl_host[s % ring].tolist()
-        for r, u, f in now:
-            if sched.rows[r] != u:          # (stop_lag=1: the look-ahead frame of an utterance that has stopped)
-                continue
-            if host:
-                final[u].append(kept_t[r:r + 1])
-            if (kl[r] < thres and f > 3) or f + 1 >= caps[u]:
-                if host:
-                    results[u] = torch.stack(final[u][:-1], dim=1).squeeze(1).squeeze(2).transpose(1, 2)
-                    final[u] = None
-                else:   # frames 0 .. f - 1 sit in the slots of steps s - f .. s - 1
-                    slots = torch.tensor([(s - f + j) % ring for j in range(f)], device=dev, dtype=torch.long)
-                    results[u] = plan[kept][:, r, :].index_select(0, slots).unsqueeze(0).transpose(1, 2)
-                sched.release(r, f + 1)
-
-    s = 0
-    if stop_lag:
-        enqueue(0)
-    while True:
-        enqueue(s + 1 if stop_lag else s)
-        resolve(s)
-        if sched.done:
-            break
-        s += 1
-    owner.last_refill_trace = sched.trace
-    return results
-
-
 class Llasa(nn.Module):
     """model_sigmaVAE.py:8-183"""
 
@@ -984,42 +654,8 @@ class Llasa(nn.Module):
         before frame i's KL is read, so the read-back no longer drains the device; the returned tensor is the same, bit for bit,
         but the frame after the stop has run (and been discarded): the cache holds one extra position and, with noise=None, one
         extra draw has been taken from the generator."""
-        if device_head:
-            if not use_cache:
-                raise NotImplementedError("device_head=True generates against a KV cache; use_cache=False runs on the host path "
-                                          "(device_head=False)")
-            return self._generate_device_head([(input_ids, audio_latents)], end_disp_kl_thres, max_length, noise, stop_lag)[0]
-        if noise is not None or stop_lag:
-            raise ValueError("noise= and stop_lag= belong to device_head=True")
-        ids = input_ids.unsqueeze(0)
-        text_embed = self.base_model.model.embed_tokens(ids)
-        parts = [text_embed]
-        if audio_latents is not None:
-            parts.append(self.audio_linear(audio_latents))
-        input_embed = torch.cat(parts, dim=1)
-        final = []
-        model = self.base_model.model
-        cache = model.init_cache(input_embed.shape[1] + max_length, input_embed.device) if use_cache else None
-        step_in = input_embed
-        for i in range(max_length):
-            if use_cache:
-                hidden = model.forward_cached(step_in, cache)
-            else:
-                hidden = model(inputs_embeds=input_embed)[0]
-            mean2 = self.distribution_linear(hidden[:, -1:, :].contiguous())
-            audio_latent = self.sample(mean2)
-            final.append(audio_latent)
-            # KL(N(m, s) || N(1, e)) = log(e/s) + (s^2 + (m-1)^2) / (2 e^2) - 1/2, summed over the latent dim / dim
-            s, e = float(self.std), float(torch.e)
-            kl = (torch.log(torch.tensor(e / s)) + (s * s + (mean2.float() - 1.0) ** 2) / (2 * e * e) - 0.5).sum(2)
-            kl = kl / mean2.shape[2]
-            if kl.item() < end_disp_kl_thres and i > 3:
-                break
-            step_in = self.audio_linear(audio_latent)
-            if not use_cache:
-                input_embed = torch.cat((input_embed, step_in), dim=1)
-        out = torch.stack(final[:-1], dim=1).squeeze(1).squeeze(2)
-        return out.transpose(1, 2)
+        return generate_one(self, input_ids, audio_latents, end_disp_kl_thres, max_length, use_cache, device_head, noise,
+                            stop_lag)
 
     infer_batch_rows = ops.DECODE_MAX_ROWS      # sequences decoded per step by infer_batch (the kernels take up to DECODE_MAX_ROWS)
 
@@ -1050,35 +686,25 @@ class Llasa(nn.Module):
 
     def _host_frame(self, hidden):
         """the head of one frame on the host for the rows of hidden [R, 1, D]: (what `infer_batch` stacks, the sampled latent
-        [R, 1, d] - here the same tensor - and kl [R, 1])"""
-        s, e = float(self.std), float(torch.e)
+        [R, 1, d] - here the same tensor - and kl [R, 1]).  `std` is read only after distribution_linear is
+        enqueued: on a model built on the device that read is a host wait, and the device would idle under the launches."""
         mean2 = self.distribution_linear(hidden.contiguous())                    # [R, 1, d]: every row at once
         audio_latent = self.sample(mean2)
-        kl = (torch.log(torch.tensor(e / s)) + (s * s + (mean2.float() - 1.0) ** 2) / (2 * e * e) - 0.5).sum(2)
+        # KL(N(m, s) || N(1, e)) = log(e/s) + (s^2 + (m-1)^2) / (2 e^2) - 1/2, summed over the latent dim / dim
+        s, e = float(self.std), float(torch.e)
+        kl =(torch.log(torch.tensor(e / s)) + (s * s + (mean2.float() - 1.0) ** 2) / (2 * e * e) - 0.5).sum(2)
         return audio_latent, audio_latent, kl / mean2.shape[2]
 
     def _generate_device_head(self, prompts, thres, max_length, noise, stop_lag, refill=False):
-        """generate_device_head (refill: generate_refill, max_length one cap per prompt) with the fixed-std head
-        (ops.llasa_frame_head); returns the sampled latents"""
-        dlin, alin, model = self.distribution_linear, self.audio_linear, self.base_model.model
-        dl = dlin[2].weight.shape[0]
+        """generation.generate with the fixed-std head (ops.llasa_frame_head); returns the sampled latents"""
+        dl = self.distribution_linear[2].weight.shape[0]
         device_head_limits(stop_lag, dl, ops.HEAD_MAX_LATENT)
         std = self.std
         if not (isinstance(std, (int, float)) or (torch.is_tensor(std) and std.numel() == 1)) or not float(std) > 0:
             raise NotImplementedError("device_head=True takes the fixed scalar std of init_sigmaVAE; any other std runs on the "
                                       "host path (device_head=False)")
-        std = float(std)
-
-        def plan_of(R, dev, frames):
-            return ops.llasa_head_plan(model.norm.weight, dlin[0].weight, dlin[0].bias, dlin[2].weight, dlin[2].bias, alin.weight,
-                                       alin.bias, R, model.norm.variance_epsilon, dev, frames=frames)
-
-        def head(plan, h, nz, active, frame):
-            ops.llasa_frame_head(plan, h, nz, std, active, frame=frame)
-
-        if refill:
-            return generate_refill(self, prompts, thres, max_length, noise, stop_lag, dl, plan_of=plan_of, head=head, kept="latent")
-        return generate_device_head(self, prompts, thres, max_length, noise, stop_lag, dl, plan_of, head, "latent")
+        spec = DeviceHeadSpec(ops.llasa_head_plan, ops.llasa_frame_head, (float(std),), "latent", dl)
+        return generate(self, prompts, thres, max_length, spec, noise, stop_lag, refill)
 
     def init_sigmaVAE(self):
         self.std = torch.tensor(0.5)

@@ -907,24 +907,31 @@ def llasa_head_plan(norm, w1, b1, w2, b2, wa, ba, R, eps, device, frames=1):
             "kl": torch.zeros((frames, R), **f32), "x_next": torch.zeros((R, D), **f32)}
 
 
-def llasa_frame_head(plan, h, noise, std, active=None, frame=0):
-    """one frame's head, one host call.  h: the UN-NORMED residual stream, fp32 [R, D] (rows may be strided); noise fp32 [R, dl]
-    (rows may be strided); active: R host booleans (None: all) - an inactive row's outputs are not touched.  Returns
-    (mean [R, dl], latent [R, dl], kl [R], x_next [R, D]): views of the plan's buffers, latent and kl those of slot `frame`."""
+def _head_call(plan, h, noise, lat, lds, active, frame):
+    """what llasa_frame_head and llasa_frame_head2 share: the argument checks, the descriptor filled from the parameters' compute
+    copies (kept alive in the plan until the next call) with the leading dimensions `lds` of w1 / w2 / wa, the active flags"""
     from .dit_ops import bf16_of, f32_of
-    lib = _lib.load()
-    R, D, dl = plan["R"], plan["D"], plan["dl"]
+    R, D = plan["R"], plan["D"]
     assert h.dtype == torch.float32 and tuple(h.shape) == (R, D) and h.stride(1) == 1
-    assert noise.dtype == torch.float32 and tuple(noise.shape) == (R, dl) and noise.stride(1) == 1
+    assert noise.dtype == torch.float32 and tuple(noise.shape) == (R, lat) and noise.stride(1) == 1
     assert 0 <= frame < plan["frames"]
     desc = plan["desc"]
     keep = [bf16_of(p) if f[0] == "w" else f32_of(p) for f, p in zip(HEAD_FIELDS, plan["params"])]
     for f, t in zip(HEAD_FIELDS, keep):
         assert t.is_contiguous() and t.device == h.device
         setattr(desc, f, t.data_ptr())
-    desc.ldw1, desc.ldw2, desc.ldwa = D, dl, dl
+    desc.ldw1, desc.ldw2, desc.ldwa = lds
     plan["keep"] = keep
-    act = None if active is None else ctypes.cast(_i32([1 if a else 0 for a in active]), ctypes.c_void_p)
+    return desc, None if active is None else ctypes.cast(_i32([1 if a else 0 for a in active]), ctypes.c_void_p)
+
+
+def llasa_frame_head(plan, h, noise, std, active=None, frame=0):
+    """one frame's head, one host call.  h: the UN-NORMED residual stream, fp32 [R, D] (rows may be strided); noise fp32 [R, dl]
+    (rows may be strided); active: R host booleans (None: all) - an inactive row's outputs are not touched.  Returns
+    (mean [R, dl], latent [R, dl], kl [R], x_next [R, D]): views of the plan's buffers, latent and kl those of slot `frame`."""
+    lib = _lib.load()
+    R, D, dl = plan["R"], plan["D"], plan["dl"]
+    desc, act = _head_call(plan, h, noise, dl, (D, dl, dl), active, frame)
     latent, kl = plan["latent"][frame], plan["kl"][frame]
     check(lib.kalle_llasa_frame_head_rows(ctypes.addressof(desc), _p(h), h.stride(0), _p(noise), noise.stride(0), float(std),
                                           plan["eps"], _p(plan["mean"]), _p(latent), _p(kl), _p(plan["x_next"]), act, R, D, dl,
@@ -958,20 +965,9 @@ def llasa_frame_head2(plan, h, noise, active=None, frame=0):
     """one frame's head, one host call.  h: the UN-NORMED residual stream, fp32 [R, D] (rows may be strided); noise fp32 [R, lat]
     (rows may be strided); active: R host booleans (None: all) - an inactive row's outputs are not touched.  Returns
     (disp [R, 2 lat], latent [R, lat], kl [R], x_next [R, D]): views of the plan's buffers, the first three those of slot `frame`."""
-    from .dit_ops import bf16_of, f32_of
     lib = _lib.load()
     R, D, lat = plan["R"], plan["D"], plan["lat"]
-    assert h.dtype == torch.float32 and tuple(h.shape) == (R, D) and h.stride(1) == 1
-    assert noise.dtype == torch.float32 and tuple(noise.shape) == (R, lat) and noise.stride(1) == 1
-    assert 0 <= frame < plan["frames"]
-    desc = plan["desc"]
-    keep = [bf16_of(p) if f[0] == "w" else f32_of(p) for f, p in zip(HEAD_FIELDS, plan["params"])]
-    for f, t in zip(HEAD_FIELDS, keep):
-        assert t.is_contiguous() and t.device == h.device
-        setattr(desc, f, t.data_ptr())
-    desc.ldw1, desc.ldw2, desc.ldwa = D, 2 * lat, lat
-    plan["keep"] = keep
-    act = None if active is None else ctypes.cast(_i32([1 if a else 0 for a in active]), ctypes.c_void_p)
+    desc, act = _head_call(plan, h, noise, lat, (D, 2 * lat, lat), active, frame)
     disp, latent, kl = plan["disp"][frame], plan["latent"][frame], plan["kl"][frame]
     check(lib.kalle_llasa_frame_head2_rows(ctypes.addressof(desc), _p(h), h.stride(0), _p(noise), noise.stride(0), plan["eps"],
                                            _p(disp), _p(latent), _p(kl), _p(plan["x_next"]), act, R, D, lat, _p(plan["ws"]),

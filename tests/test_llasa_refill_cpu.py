@@ -1,5 +1,5 @@
-"""CPU: the host side of `infer_batch(refill=True)` without a device - the row schedule (model_sigmaVAE.RowSchedule, the object
-the generation loops drive, against the closed form refill_steps), the numpy reference of kalle_kv_append_varlen that
+"""CPU: the host side of `infer_batch(refill=True)` without a device - the row schedule (generation.RowSchedule, driven by the real
+generation loop on fakes, against the closed form refill_steps), the numpy reference of kalle_kv_append_varlen that
 tests/test_kv_append_gpu.py holds the kernel to, every refusal of the real entry point (they return before any launch), and the
 argument checks of LlamaModel.prefill_rows."""
 import ctypes
@@ -13,47 +13,20 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import refill_cases as rc  # noqa: E402
+import test_generation_loop_cpu as loop  # noqa: E402
 
 ERR_ARG = -1
 
 
 # ------------------------------------------------------------------------------------------------ the schedule
 def drive(frames, R, stop_lag=0, log=None):
-    """RowSchedule driven as generate_refill drives it, the stops simulated: utterance u stops at its frame frames[u] - 1.  With
-    stop_lag=1 step s + 1 is admitted before step s is resolved.  log: receives (step, admitted pairs, live rows) per step."""
-    from kalle_audio_amd.model_sigmaVAE import RowSchedule
-    sched, live = RowSchedule(len(frames), R), {}
-
-    def enqueue(s):
-        pairs = sched.admit(s)
-        live[s] = sched.live(s)
-        if log is not None:
-            log.append((s, pairs, live[s]))
-
-    def resolve(s):
-        for r, u, f in live.pop(s):
-            if sched.rows[r] == u and f + 1 >= frames[u]:
-                sched.release(r, f + 1)
-
-    s = 0
-    if stop_lag:
-        enqueue(0)
-    while True:
-        enqueue(s + 1 if stop_lag else s)
-        resolve(s)
-        if sched.done:
-            return sched
-        s += 1
-        assert s < 100000
+    """the schedule the real loop (generation.run_frames on the fakes of tests/test_generation_loop_cpu.py) leaves for utterances
+    that run frames[u] frames each.  log: receives (step, admitted pairs, live rows) per step."""
+    return loop.drive(frames, R, stop_lag, log)[0]
 
 
-def seeded_caps(seed, n=64, lo=50, hi=250):
-    g = random.Random(seed)
-    return [g.randint(lo, hi) for _ in range(n)]
-
-
-LISTS = [(rc.CAPS, rc.ROWS), ([4, 4, 4], 16), ([5], 3), ([2, 9, 2, 2, 7, 1, 3], 3), (seeded_caps(0, 23, 2, 30), 4),
-         (seeded_caps(1), 16)]
+LISTS = loop.LISTS
+seeded_caps = loop.seeded_caps
 
 
 @pytest.mark.parametrize("lag", [0, 1])
@@ -206,7 +179,7 @@ def test_prefill_rows_argument_checks():
 
 
 def test_frame_caps_and_empty_list():
-    from kalle_audio_amd.model_sigmaVAE import _frame_caps, generate_batch
+    from kalle_audio_amd.generation import _frame_caps, generate_batch
     assert _frame_caps(7, 3) is None and _frame_caps([6, 3, 8], 3) == [6, 3, 8] and _frame_caps((2, 2), 2) == [2, 2]
     with pytest.raises(ValueError):
         _frame_caps([6, 3], 3)
