@@ -95,7 +95,10 @@ def main():
     trainer = engine.DataParallelTrainer(
         model, lr=config["lr"], optimizer="AdamW", weight_decay=config["weight_decay"],
         grad_accum_steps=config["gradient_accumulation_steps"],
-        lr_schedule=lambda s: engine.cosine_with_warmup(s + step0, warm, total))
+        lr_schedule=lambda s: engine.cosine_with_warmup(s + step0, warm, total),
+        # optional YAML keys (absent = off): accelerator.clip_grad_norm_(model.parameters(), max_grad_norm) of train_offline.py:246,
+        # and GradScaler's skipped optimizer step on a non-finite gradient (train.py:136,180-190) - both decided on the device
+        max_grad_norm=config.get("max_grad_norm"), skip_nonfinite=bool(config.get("skip_nonfinite", False)))
 
     if args.synthetic:
         B, L = args.synthetic
@@ -123,8 +126,11 @@ def main():
             continue
         step += 1
         if step % config["log_interval"] == 0 and rank == 0:               # the only host syncs: the logged scalars
+            ctl = trainer.opt_ctl()             # None unless max_grad_norm / skip_nonfinite is set
+            norm = (f"grad_norm {ctl['grad_norm']:.4f} clip_coef {ctl['clip_coef']:.4f} skipped {ctl['skipped_steps']} "
+                    if ctl else "")
             print(f"[{datetime.datetime.now():%H:%M:%S}] epoch {epoch} step {step} lr "
-                  f"{trainer.last_lr:.3e} "
+                  f"{trainer.last_lr:.3e} {norm}"
                   f"audio_loss {out['audio_loss'].item():.4f} end_loss {out['end_loss'].item():.4f}", flush=True)
         if step % int(config.get("save_interval", 10 ** 9)) == 0 and rank == 0:
             torch.save(model.state_dict(), os.path.join(config["output_dir"], f"epoch_{epoch}_step_{step}.pt"))

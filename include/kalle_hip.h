@@ -511,6 +511,55 @@ int kalle_adam_step(float* param, const float* grad, float* exp_avg, float* exp_
                     int step, float grad_scale, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Gradient-norm clipping and the non-finite skip, decided on the device (torch.nn.utils.clip_grad_norm_,
+ * train_offline.py:246; GradScaler's skipped optimizer step, train.py:136,180-190).  Three stages, every one of them
+ * readable in device memory:
+ *
+ *   kalle_grad_sumsq        one streaming pass over grad[0..n): sum of squares in double + "saw +-inf / NaN", written as
+ *                           KALLE_GRAD_NORM_PARTIALS per-workgroup partials into region `slot` of the workspace
+ *   kalle_grad_norm_finish  one workgroup: sums every region in index order, publishes norm / coef / nonfinite / skip in a
+ *                           kalle_opt_ctl and bumps its counters
+ *   kalle_adam_step_ctl     kalle_adam_step whose gradient factor is f32(grad_scale * ctl->coef) and which writes nothing
+ *                           when ctl->skip is set
+ *
+ * Workspace (kalle_grad_norm_ws_bytes(nslots) bytes, 16-byte aligned, caller-owned), region s = 0 .. nslots - 1 at byte
+ * s * KALLE_GRAD_NORM_SLOT_BYTES:
+ *     double  sumsq[KALLE_GRAD_NORM_PARTIALS]     workgroup b's sum of g^2 over the elements it read, each g widened to double
+ *                                                 first (exact, no overflow at 1e20, no underflow at 1e-30); 0 if it read none
+ *     int32_t bad[KALLE_GRAD_NORM_PARTIALS]       1 if workgroup b read an element whose fp32 exponent bits are all set
+ * A launch is always KALLE_GRAD_NORM_PARTIALS workgroups of KALLE_GRAD_NORM_BLOCK lanes; a lane reads KALLE_GRAD_NORM_UNROLL
+ * 16-byte vectors per grid sweep (one sweep = PARTIALS * BLOCK * UNROLL * 4 elements), the n % 4 tail belongs to workgroup 0.
+ * Which element a workgroup reads, and the order in which its lanes, waves and the partials are added, are functions of
+ * (n, slot) alone - no floating-point atomics, no "last arriver" - so the published norm is the same bit pattern whichever
+ * bucket or workgroup finishes first, and the same on every rank.
+ * kalle_grad_norm_finish does not clear the workspace: the caller writes every slot before every finish.
+ *
+ * KALLE_ERR_ARG before any launch (so the refusals need no device): a NULL pointer (stream excepted), n <= 0, nslots <= 0,
+ * slot outside [0, nslots), grad / ws not 16-byte aligned, ctl not 8-byte aligned, step <= 0.
+ */
+#define KALLE_GRAD_NORM_PARTIALS 1024
+#define KALLE_GRAD_NORM_BLOCK 256
+#define KALLE_GRAD_NORM_UNROLL 4
+#define KALLE_GRAD_NORM_SLOT_BYTES (KALLE_GRAD_NORM_PARTIALS * 12)
+typedef struct kalle_opt_ctl {   /* device memory; written by kalle_grad_norm_finish, read by kalle_adam_step_ctl */
+    float   norm;        /* || grad_scale * g ||_2 over every slot: (float)(sqrt(S) * (double)grad_scale) */
+    float   coef;        /* multiplies grad_scale in the Adam kernel: 1, or < 1 when clipping:
+                          * 0 < max_norm < inf ? (float)min(1.0, max_norm / (norm + 1e-6)) in double from the rounded norm : 1
+                          * (a NaN norm gives 1: such a step is either skipped or lost, as under clip_grad_norm_) */
+    int32_t nonfinite;   /* 1: some gradient element was +-inf or NaN */
+    int32_t skip;        /* 1: nonfinite && skip_nonfinite - the Adam kernel writes nothing */
+    int64_t skipped;     /* running counts, incremented by finish: steps with skip set, */
+    int64_t clipped;     /* steps with coef < 1 */
+} kalle_opt_ctl;
+int kalle_grad_norm_ws_bytes(int nslots);                 /* host query; <= 0 slots: KALLE_ERR_ARG */
+int kalle_grad_sumsq(const float* grad, int64_t n, void* ws, int slot, int nslots, void* stream);
+int kalle_grad_norm_finish(const void* ws, int nslots, float grad_scale, float max_norm, int skip_nonfinite,
+                           kalle_opt_ctl* ctl, void* stream);
+int kalle_adam_step_ctl(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* param_bf16,
+                        int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int decoupled,
+                        int step, float grad_scale, const kalle_opt_ctl* ctl, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * 1-D convolution stack of the audio VAEs (no MFMA; LDS line buffers, coalesced HBM).
  * Layout (B, C, L) fp32 or bf16 activations, fp32 weights (weight-norm already folded: w = g * v/||v||).
  */

@@ -360,13 +360,14 @@ __global__ void fourier_bwd_kernel(const float* __restrict__ dout, const float* 
 }
 
 // ---- fused Adam / AdamW ------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                   float* __restrict__ m, float* __restrict__ v,
-                                                   bf16_t* __restrict__ pb, int64_t n, float lr, float b1, float b2,
-                                                   float eps, float wd, int decoupled, float bc1, float bc2,
-                                                   float gscale) {
+// (one body for both kernels below: kalle_adam_step_ctl is bit-identical to kalle_adam_step by construction)
+__device__ __forceinline__ void adam_body(float* __restrict__ p, const float* __restrict__ g,
+                                          float* __restrict__ m, float* __restrict__ v,
+                                          bf16_t* __restrict__ pb, int64_t n, float lr, float b1, float b2,
+                                          float eps, float wd, int decoupled, float bc1, float bc2,
+                                          float gscale, const int64_t first, const int64_t stride) {
     const int64_t n4 = n >> 2;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+    for (int64_t i = first; i < n4; i += stride) {
         f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
         const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
         f32x4 mv = reinterpret_cast<f32x4*>(m)[i];
@@ -400,6 +401,126 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
         pv -= (lr / bc1) * (mv / (sqrtf(vv) / bc2 + eps));
         p[i] = pv; m[i] = mv; v[i] = vv;
         if (pb) pb[i] = f32_to_bf16(pv);
+    }
+}
+
+__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                   float* __restrict__ m, float* __restrict__ v,
+                                                   bf16_t* __restrict__ pb, int64_t n, float lr, float b1, float b2,
+                                                   float eps, float wd, int decoupled, float bc1, float bc2,
+                                                   float gscale) {
+    adam_body(p, g, m, v, pb, n, lr, b1, b2, eps, wd, decoupled, bc1, bc2, gscale,
+              (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
+}
+
+// the same step under the decision kalle_grad_norm_finish left in device memory: nothing is written on a skipped step, and the
+// clip coefficient rides on grad_scale as ONE fp32 product
+__global__ __launch_bounds__(256) void adam_ctl_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                       float* __restrict__ m, float* __restrict__ v,
+                                                       bf16_t* __restrict__ pb, int64_t n, float lr, float b1, float b2,
+                                                       float eps, float wd, int decoupled, float bc1, float bc2,
+                                                       float gscale, const kalle_opt_ctl* __restrict__ ctl) {
+    if (ctl->skip) return;
+    adam_body(p, g, m, v, pb, n, lr, b1, b2, eps, wd, decoupled, bc1, bc2, gscale * ctl->coef,
+              (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
+}
+
+// ---- gradient norm: per-workgroup partial sums of squares (double) + non-finite flag ---------------------------------
+__device__ __forceinline__ void sumsq_acc(const f32x4 x, double& acc, uint32_t& bad) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float xe = x[e];      // (a copy: __builtin_bit_cast applied to the vector element itself reads element 0)
+        const double d = (double)xe;
+        acc += d * d;
+        bad |= (uint32_t)((__builtin_bit_cast(uint32_t, xe) & 0x7f800000u) == 0x7f800000u);
+    }
+}
+
+// grid = KALLE_GRAD_NORM_PARTIALS workgroups of KALLE_GRAD_NORM_BLOCK lanes, always: workgroup b owns partial b of the slot.
+// Every address read is below g + n: the vector loops stop at n4 = n / 4 vectors, the tail reads n4 * 4 + lane < n.
+__global__ __launch_bounds__(KALLE_GRAD_NORM_BLOCK) void grad_sumsq_kernel(const float* __restrict__ g, int64_t n,
+                                                                           double* __restrict__ part,
+                                                                           int32_t* __restrict__ flag) {
+    __shared__ double red[KALLE_GRAD_NORM_BLOCK / 64];
+    __shared__ uint32_t redbad[KALLE_GRAD_NORM_BLOCK / 64];
+    const int64_t n4 = n >> 2;
+    const int64_t stride = (int64_t)gridDim.x * KALLE_GRAD_NORM_BLOCK;
+    const f32x4* __restrict__ gv = reinterpret_cast<const f32x4*>(g);
+    double acc = 0.0;
+    uint32_t bad = 0;
+    int64_t i = (int64_t)blockIdx.x * KALLE_GRAD_NORM_BLOCK + threadIdx.x;
+    static_assert(KALLE_GRAD_NORM_UNROLL == 4, "the main loop below issues four loads");
+    for (; i + 3 * stride < n4; i += 4 * stride) {      // four 16-byte loads in flight per lane
+        const f32x4 x0 = gv[i], x1 = gv[i + stride], x2 = gv[i + 2 * stride], x3 = gv[i + 3 * stride];
+        sumsq_acc(x0, acc, bad);
+        sumsq_acc(x1, acc, bad);
+        sumsq_acc(x2, acc, bad);
+        sumsq_acc(x3, acc, bad);
+    }
+    for (; i < n4; i += stride) sumsq_acc(gv[i], acc, bad);
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {     // scalar tail (n % 4)
+        const float x = g[(n4 << 2) + threadIdx.x];
+        const double d = (double)x;
+        acc += d * d;
+        bad |= (uint32_t)((__builtin_bit_cast(uint32_t, x) & 0x7f800000u) == 0x7f800000u);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {                  // per wave, a fixed butterfly
+        acc += __shfl_xor(acc, o, 64);
+        bad |= (uint32_t)__shfl_xor((int)bad, o, 64);
+    }
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0) { red[w] = acc; redbad[w] = bad; }
+    __syncthreads();
+    if (threadIdx.x == 0) {                             // per block through LDS, waves in index order
+        double t = 0.0;
+        uint32_t b = 0;
+        for (int k = 0; k < KALLE_GRAD_NORM_BLOCK / 64; ++k) { t += red[k]; b |= redbad[k]; }
+        part[blockIdx.x] = t;
+        flag[blockIdx.x] = (int32_t)(b != 0);
+    }
+}
+
+// one workgroup: lane t adds partials t, t + 256, ... of the regions laid end to end (index order), then a fixed tree over LDS
+__global__ __launch_bounds__(256) void grad_norm_finish_kernel(const char* __restrict__ ws, int nslots, float grad_scale,
+                                                               float max_norm, int skip_nonfinite,
+                                                               kalle_opt_ctl* __restrict__ ctl) {
+    __shared__ double red[256];
+    __shared__ int redbad[256];
+    double acc = 0.0;
+    int bad = 0;
+    const int total = nslots * KALLE_GRAD_NORM_PARTIALS;
+    for (int i = threadIdx.x; i < total; i += 256) {
+        const char* base = ws + (int64_t)(i / KALLE_GRAD_NORM_PARTIALS) * KALLE_GRAD_NORM_SLOT_BYTES;
+        const int j = i % KALLE_GRAD_NORM_PARTIALS;
+        acc += reinterpret_cast<const double*>(base)[j];
+        bad |= reinterpret_cast<const int32_t*>(base + KALLE_GRAD_NORM_PARTIALS * 8)[j];
+    }
+    red[threadIdx.x] = acc;
+    redbad[threadIdx.x] = bad;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            red[threadIdx.x] += red[threadIdx.x + o];
+            redbad[threadIdx.x] |= redbad[threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float norm = (float)(sqrt(red[0]) * (double)grad_scale);
+        float coef = 1.f;
+        if (max_norm > 0.f && max_norm < __builtin_inff()) {
+            const double c = (double)max_norm / ((double)norm + 1e-6);
+            coef = c < 1.0 ? (float)c : 1.f;
+        }
+        const int nonfinite = redbad[0] != 0;
+        const int skip = nonfinite && skip_nonfinite;
+        ctl->norm = norm;
+        ctl->coef = coef;
+        ctl->nonfinite = nonfinite;
+        ctl->skip = skip;
+        ctl->skipped += skip;
+        ctl->clipped += coef < 1.f;
     }
 }
 
@@ -546,6 +667,41 @@ extern "C" int kalle_adam_step(float* param, const float* grad, float* exp_avg, 
     KALLE_LAUNCH(adam_kernel, dim3(agrid), dim3(256), 0, static_cast<hipStream_t>(stream), param,
                        grad, exp_avg, exp_avg_sq, static_cast<bf16_t*>(param_bf16), n, lr, beta1, beta2, eps,
                        weight_decay, decoupled, bc1, bc2, grad_scale);
+    return kalle_check_launch();
+}
+
+extern "C" int kalle_adam_step_ctl(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* param_bf16,
+                                   int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                   int decoupled, int step, float grad_scale, const kalle_opt_ctl* ctl, void* stream) {
+    if (!param || !grad || !exp_avg || !exp_avg_sq || !ctl || n <= 0 || step <= 0) return KALLE_ERR_ARG;
+    if ((uintptr_t)ctl & 7) return KALLE_ERR_ARG;
+    const float bc1 = 1.f - powf(beta1, (float)step);       // host-computed from `step`, exactly as kalle_adam_step
+    const float bc2 = sqrtf(1.f - powf(beta2, (float)step));
+    const int agrid = (int)std::min<int64_t>(((n >> 2) + 255) / 256 + 1, 16384);
+    KALLE_LAUNCH(adam_ctl_kernel, dim3(agrid), dim3(256), 0, static_cast<hipStream_t>(stream), param,
+                       grad, exp_avg, exp_avg_sq, static_cast<bf16_t*>(param_bf16), n, lr, beta1, beta2, eps,
+                       weight_decay, decoupled, bc1, bc2, grad_scale, ctl);
+    return kalle_check_launch();
+}
+extern "C" int kalle_grad_norm_ws_bytes(int nslots) {
+    if (nslots <= 0 || nslots > (1 << 16)) return KALLE_ERR_ARG;
+    return nslots * KALLE_GRAD_NORM_SLOT_BYTES;
+}
+extern "C" int kalle_grad_sumsq(const float* grad, int64_t n, void* ws, int slot, int nslots, void* stream) {
+    if (!grad || !ws || n <= 0 || nslots <= 0 || nslots > (1 << 16) || slot < 0 || slot >= nslots) return KALLE_ERR_ARG;
+    if (((uintptr_t)grad & 15) || ((uintptr_t)ws & 15)) return KALLE_ERR_ARG;
+    char* base = static_cast<char*>(ws) + (int64_t)slot * KALLE_GRAD_NORM_SLOT_BYTES;
+    KALLE_LAUNCH(grad_sumsq_kernel, dim3(KALLE_GRAD_NORM_PARTIALS), dim3(KALLE_GRAD_NORM_BLOCK), 0,
+                 static_cast<hipStream_t>(stream), grad, n, reinterpret_cast<double*>(base),
+                 reinterpret_cast<int32_t*>(base + KALLE_GRAD_NORM_PARTIALS * 8));
+    return kalle_check_launch();
+}
+extern "C" int kalle_grad_norm_finish(const void* ws, int nslots, float grad_scale, float max_norm, int skip_nonfinite,
+                                      kalle_opt_ctl* ctl, void* stream) {
+    if (!ws || !ctl || nslots <= 0 || nslots > (1 << 16)) return KALLE_ERR_ARG;
+    if (((uintptr_t)ws & 15) || ((uintptr_t)ctl & 7)) return KALLE_ERR_ARG;
+    KALLE_LAUNCH(grad_norm_finish_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream),
+                 static_cast<const char*>(ws), nslots, grad_scale, max_norm, skip_nonfinite, ctl);
     return kalle_check_launch();
 }
 

@@ -175,8 +175,21 @@ class DataParallelTrainer:
     module tree whose repeated layers are this package's TransformerBlock / LlamaDecoderLayer: one bucket each)."""
 
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, optimizer="Adam",
-                 grad_accum_steps=1, lr_schedule=None, process_group=None, comm_dtype=torch.float32):
+                 grad_accum_steps=1, lr_schedule=None, process_group=None, comm_dtype=torch.float32,
+                 max_grad_norm=None, skip_nonfinite=False, track_grad_norm=False):
+        """max_grad_norm: clip the averaged gradient's global L2 norm (torch.nn.utils.clip_grad_norm_'s rule); skip_nonfinite:
+        an optimizer step whose gradient holds +-inf / NaN writes nothing (GradScaler.step's rule); track_grad_norm: only
+        publish the norm.  All three are decided on the device - see "Gradient norm" below; off, nothing changes."""
         from .stable_audio_tools.models.transformer import TransformerBlock
+        if max_grad_norm is not None and not float(max_grad_norm) > 0:            # (also NaN)
+            raise ValueError(f"max_grad_norm must be a positive number or None, got {max_grad_norm!r}")
+        if os.environ.get("KALLE_SHARD_OPTIMIZER", "0") == "1":
+            for arg, on in (("max_grad_norm", max_grad_norm is not None), ("skip_nonfinite", skip_nonfinite),
+                            ("track_grad_norm", track_grad_norm)):
+                if on:
+                    # a rank holds only its shard of the reduced matrix gradients there: the global norm needs one more (scalar)
+                    # all-reduce, which this trainer does not issue yet
+                    raise ValueError(f"{arg} is not supported together with KALLE_SHARD_OPTIMIZER=1")
         self.model = model
         self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(process_group) if dist.is_initialized() else 0
@@ -212,6 +225,31 @@ class DataParallelTrainer:
         self.exp_avg = torch.zeros_like(self.flat.param)
         self.exp_avg_sq = torch.zeros_like(self.flat.param)
         self._pending = []
+        # Gradient norm (max_grad_norm / skip_nonfinite / track_grad_norm; all off: none of this exists).  One workspace slot per
+        # bucket, in flat.bucket_keys order: a bucket's sum of squares is taken where its Adam slice runs today - overlapped, on
+        # the optimizer stream once its all-reduce has landed, i.e. as reads under the backward GEMMs; otherwise in
+        # optimizer_step, in bucket order - and kalle_grad_norm_finish adds the slots in index order, so the norm is the same bit
+        # pattern on every route and every rank.  It is the norm of the AVERAGED gradient (grad_scale = 1 / (world accum)), what
+        # DDP hands clip_grad_norm_.  With max_grad_norm or skip_nonfinite no Adam slice may run before the norm is final: the
+        # slices give way to ONE kalle_adam_step_ctl over the whole flat buffer behind the finish, on the same stream - that
+        # un-hidden pass is the price of the option (0.6 ms at B = 64, 2.2 ms at B = 256 on the bench shape: DESIGN.md section
+        # 5.15).  track_grad_norm alone keeps the slices.
+        # Skip rule: a skipped step leaves every bit of weights, moments and mirror; step_count, last_lr and the schedule advance
+        # (the reference calls scheduler.step() regardless), the step number is SPENT - the next applied step uses the bias
+        # corrections of step_count + 1, not torch's un-advanced state['step'] - and the EMA update runs (on unchanged weights).
+        # The host never learns of a skip without asking: opt_ctl() is the only sync.
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.track_grad_norm = bool(track_grad_norm)
+        self._norm_gate = self.max_grad_norm is not None or self.skip_nonfinite      # Adam waits for the norm
+        self._norm_on = self._norm_gate or self.track_grad_norm
+        self._norm_done = set()           # bucket keys whose slot of the current optimizer step has been queued
+        self._norm_final = False          # kalle_grad_norm_finish of the current optimizer step has been queued
+        self._ctl = self._norm_ws = None
+        if self._norm_on:
+            self._norm_slot = {k: i for i, k in enumerate(self.flat.bucket_keys)}
+            self._norm_ws = ops.grad_norm_ws(len(self._norm_slot), device)
+            self._ctl = ops.OptCtl(device)
         # Sharded optimizer (KALLE_SHARD_OPTIMIZER=1, off by default; world a power of two <= 64, fp32 buckets): a block bucket's
         # all-reduce is issued as its two halves with the optimizer in the middle - reduce-scatter of the matrix gradients, the fused Adam
         # on this rank's 1 / world of them, all-gather of the updated fp32 weights (the same bytes on the links as the all-reduce; the
@@ -298,7 +336,59 @@ class DataParallelTrainer:
                     ops.copy_rows(low, buf, 1, 1, buf.numel(), 0, buf.numel(), 0, buf.numel())
                 self._comm_events += 1
             for key in keys:
-                self._adam_bucket(key)
+                if self._norm_on:
+                    self._sumsq_bucket(key)
+                if not self._norm_gate:
+                    self._adam_bucket(key)
+
+    # -- gradient norm ------------------------------------------------------------------------------------------
+    def _sumsq_bucket(self, key):
+        a, b = self.flat.bucket_range[key]
+        ops.grad_sumsq(self.flat.grad[a:b], self._norm_ws, self._norm_slot[key], len(self._norm_slot))
+        self._norm_done.add(key)
+
+    def _norm_finish(self):
+        """the slots not written yet, in bucket order, then the one-workgroup finish (on the current stream)"""
+        for key in self.flat.bucket_keys:
+            if key not in self._norm_done:
+                self._sumsq_bucket(key)
+        ops.grad_norm_finish(self._norm_ws, len(self._norm_slot), self._ctl, grad_scale=1.0 / (self.world * self.grad_accum_steps),
+                             max_norm=self.max_grad_norm or 0.0, skip_nonfinite=self.skip_nonfinite)
+        self._norm_final = True
+
+    def _adam_ctl_all(self):
+        f = self.flat
+        ops.adam_step_ctl(f.param, f.grad, self.exp_avg, self.exp_avg_sq, f.param_bf16, self._ctl, lr=self._opt_lr,
+                          beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, weight_decay=self.weight_decay,
+                          decoupled=self.decoupled, step=self.step_count + 1,
+                          grad_scale=1.0 / (self.world * self.grad_accum_steps))
+        self._opt_done.update(f.bucket_keys)
+
+    @property
+    def grad_norm(self):
+        """device tensor [1] fp32: L2 norm of the averaged gradient of the last optimizer step (None: feature off)"""
+        return self._ctl.norm if self._ctl is not None else None
+
+    @property
+    def clip_coef(self):
+        return self._ctl.coef if self._ctl is not None else None
+
+    @property
+    def skipped_steps(self):
+        return self._ctl.skipped if self._ctl is not None else None
+
+    @property
+    def clipped_steps(self):
+        return self._ctl.clipped if self._ctl is not None else None
+
+    def opt_ctl(self):
+        """the device's record of the last optimizer step as Python numbers - the only host sync of the feature"""
+        if self._ctl is None:
+            return None
+        w = self._ctl.t.cpu()
+        f, q = w[0:2].view(torch.float32), w[4:8].view(torch.int64)
+        return {"grad_norm": f[0].item(), "clip_coef": f[1].item(), "nonfinite": bool(w[2].item()), "skip": bool(w[3].item()),
+                "skipped_steps": q[0].item(), "clipped_steps": q[1].item()}
 
     # -- sharded optimizer -------------------------------------------------------------------------------------
     def _shard_range(self, key):
@@ -396,6 +486,8 @@ class DataParallelTrainer:
         # (train_offline.py:247-248)
         self._opt_lr = self.lr * (self.lr_schedule(k - 1) if self.lr_schedule else 1.0)
         self._opt_done = set()
+        self._norm_done = set()
+        self._norm_final = False
         self._comm_events = 0
         self._shard_ev = None
 
@@ -424,7 +516,13 @@ class DataParallelTrainer:
             cur = torch.cuda.current_stream()
             ev = torch.cuda.Event()
             ev.record(cur)
-            self._queue_bucket([k for k in self.flat.bucket_keys if k not in self._opt_done], ev)
+            done = self._norm_done if self._norm_gate else self._opt_done
+            self._queue_bucket([k for k in self.flat.bucket_keys if k not in done], ev)
+            if self._norm_on:
+                with torch.cuda.stream(self._opt_stream):
+                    self._norm_finish()
+                    if self._norm_gate:
+                        self._adam_ctl_all()          # ONE pass over [0, total): no slice could run before the norm was final
             timed = self.comm_timing is not None
             if timed:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -536,7 +634,11 @@ class DataParallelTrainer:
     def optimizer_step(self):
         if self._opt_lr is None:                           # called directly (not through backward())
             self._begin_optimizer_step()
-        if not (self._overlap_now and len(self._opt_done) == len(self.flat.bucket_keys)):
+        if self._norm_on and not self._norm_final:
+            self._norm_finish()
+            if self._norm_gate:
+                self._adam_ctl_all()
+        if not (len(self._opt_done) == len(self.flat.bucket_keys) and (self._overlap_now or self._norm_gate)):
             # one fused pass over whatever has not been updated yet (everything, without the overlapped slices)
             if self._opt_done:
                 for key in self.flat.bucket_keys:
@@ -548,6 +650,8 @@ class DataParallelTrainer:
         self.last_lr = self._opt_lr                        # what this optimizer step actually used (for logging)
         self._opt_lr = None
         self._opt_done = set()
+        self._norm_done = set()
+        self._norm_final = False
         if getattr(self, "ema", None) is not None:
             self._ema_update()
 
@@ -570,6 +674,9 @@ class DataParallelTrainer:
               "layout": {n: list(v) for n, v in self.flat.slices.items()}}
         if self.micro % self.grad_accum_steps != 0:
             sd["grad"] = self.flat.grad        # a half-finished accumulation window: the micro-batches already summed
+        if self._ctl is not None:
+            c = self.opt_ctl()
+            sd["skipped_steps"], sd["clipped_steps"] = c["skipped_steps"], c["clipped_steps"]
         if getattr(self, "ema", None) is not None:
             sc = self.ema_schedule
             sd["ema"] = self.ema
@@ -598,6 +705,11 @@ class DataParallelTrainer:
                 self.flat.grad.copy_(sd["grad"])
             else:       # (older checkpoints: the partial sums are gone - restart the window rather than scale an empty buffer)
                 self.micro -= self.micro % self.grad_accum_steps
+        if self._ctl is not None:              # (their absence - a checkpoint written without the feature - leaves the counts)
+            if "skipped_steps" in sd:
+                self._ctl.skipped.fill_(int(sd["skipped_steps"]))
+            if "clipped_steps" in sd:
+                self._ctl.clipped.fill_(int(sd["clipped_steps"]))
         if "ema" in sd:
             es = dict(sd["ema_schedule"])
             step, initted = es.pop("step"), es.pop("initted")

@@ -441,6 +441,63 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, param_bf16, *, lr, beta1=0.9, be
           "kalle_adam_step")
 
 
+# gradient-norm clipping / non-finite skip, decided on the device (include/kalle_hip.h, "Gradient-norm clipping ...")
+GRAD_NORM_PARTIALS = 1024          # KALLE_GRAD_NORM_PARTIALS / _BLOCK / _UNROLL: tests/test_grad_clip_cpu.py holds them to the header
+GRAD_NORM_BLOCK = 256
+GRAD_NORM_UNROLL = 4
+
+
+class OptCtl:
+    """`kalle_opt_ctl` as a small device tensor (`t`, 8 x int32) with named views: norm, coef (fp32), nonfinite, skip (int32),
+    skipped, clipped (int64).  Reading a view is asynchronous like any tensor; `.item()` on one is a host sync."""
+
+    def __init__(self, device):
+        self.t = torch.zeros(8, device=device, dtype=torch.int32)
+        self.norm = self.t[0:1].view(torch.float32)
+        self.coef = self.t[1:2].view(torch.float32)
+        self.nonfinite = self.t[2:3]
+        self.skip = self.t[3:4]
+        self.skipped = self.t[4:6].view(torch.int64)
+        self.clipped = self.t[6:8].view(torch.int64)
+        self.coef.fill_(1.0)
+
+
+def grad_norm_ws(nslots, device):
+    """workspace of `nslots` regions for grad_sumsq / grad_norm_finish (a uint8 tensor; layout: include/kalle_hip.h)"""
+    nbytes = _lib.load().kalle_grad_norm_ws_bytes(int(nslots))
+    check(min(nbytes, 0), "kalle_grad_norm_ws_bytes")
+    return torch.zeros(nbytes, device=device, dtype=torch.uint8)
+
+
+def grad_norm_ws_views(ws, nslots):
+    """(sumsq [nslots, PARTIALS] float64, bad [nslots, PARTIALS] int32): read-only views of the workspace's stages"""
+    r = ws.view(nslots, GRAD_NORM_PARTIALS * 12)
+    return r[:, :GRAD_NORM_PARTIALS * 8].view(torch.float64), r[:, GRAD_NORM_PARTIALS * 8:].view(torch.int32)
+
+
+def grad_sumsq(grad, ws, slot, nslots):
+    """region `slot` of `ws` <- per-workgroup partial sums of grad^2 (double) and non-finite flags; grad: contiguous fp32"""
+    assert grad.dtype == torch.float32 and grad.is_contiguous()
+    check(_lib.load().kalle_grad_sumsq(_p(grad), grad.numel(), _p(ws), slot, nslots, _stream()), "kalle_grad_sumsq")
+
+
+def grad_norm_finish(ws, nslots, ctl, *, grad_scale=1.0, max_norm=0.0, skip_nonfinite=False):
+    """ctl (OptCtl) <- norm of grad_scale * (all slots), clip coefficient for max_norm (0 / inf: none), skip decision, counters"""
+    check(_lib.load().kalle_grad_norm_finish(_p(ws), nslots, grad_scale, max_norm, int(skip_nonfinite), _p(ctl.t), _stream()),
+          "kalle_grad_norm_finish")
+
+
+def adam_step_ctl(param, grad, exp_avg, exp_avg_sq, param_bf16, ctl, *, lr, beta1=0.9, beta2=0.999, eps=1e-8,
+                  weight_decay=0.0, decoupled=False, step=1, grad_scale=1.0):
+    """adam_step with the gradient factor f32(grad_scale * ctl.coef), a no-op where ctl.skip is set - both read on the device"""
+    global WEIGHTS_EPOCH
+    WEIGHTS_EPOCH += 1
+    lib = _lib.load()
+    check(lib.kalle_adam_step_ctl(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), _p(param_bf16), param.numel(), lr,
+                                  beta1, beta2, eps, weight_decay, int(decoupled), step, grad_scale, _p(ctl.t), _stream()),
+          "kalle_adam_step_ctl")
+
+
 # ------------------------------------------------------------------------------------------------ attention
 def attention_fwd(q, k, v, *, ldq, q_off, ldk, k_off, ldv, v_off, B, H, Hkv, Nq, Nk, rope=None, key_mask=None,
                   causal=False, dh=64):
