@@ -776,6 +776,29 @@ int kalle_llama_decode_ws_bytes_rows(int R, int H, int Hkv, int inner, int head_
 int kalle_llama_decode_step_rows(const kalle_llama_layer* layers, int n_layers, const float* x, float* out, int R, int H,
                                  int Hkv, int inner, int head_dim, float eps, const int32_t* t0, int cache_rows,
                                  const float* rope_cos, const float* rope_sin, void* workspace, void* stream);
+/* ---- the wide decode step: up to KALLE_DECODE_WIDE_MAX_ROWS rows share one read of the weights ---------------------------------
+ * 16 is the width of one MFMA column block, not an optimum: a batched step is a fixed cost plus very little per row.  The wide
+ * forms serve 1 <= R <= 64 rows with the arguments, the meaning and the refusals of the _rows forms above (the bound on R at
+ * 64): inactive rows (active[r] == 0 / t0[r] < 0) are neither read nor written, the second destination goes through y2_off,
+ * every refusal comes before the first HIP call, every launch is checked where it is made.  Up to 16 rows they forward to
+ * the _rows forms.  Above, the projections run in gemm_rows_wide_kernel (one weight-chunk load feeds ceil(R / 16) MFMAs, one per
+ * block of 16 batch rows; 16 weight rows per workgroup from N = 3072, 8 below) after the pre-pass, and the step runs
+ * kalle_attention_decode_rows once per chunk of 16 rows that has an active row (kalle_attn_last_plan: the last chunk launched).
+ * A ROW'S BITS ARE THOSE OF THE 16-ROW PATH: for one (weight row, batch row) pair the accumulation walks K in
+ * gemm_rows_kernel's order, so y, the caches and every workspace region of row r equal what the _rows form writes for a group
+ * of up to 16 rows that holds r, whatever R, the row's index or the other rows.
+ * Workspace: the published _rows layout at that R (kalle_llama_decode_ws_bytes_wide bytes).
+ * Not served, KALLE_ERR_ARG: e4m3 layers (there is no _wide_w8 form), R > 64, head dim 32. */
+#define KALLE_DECODE_WIDE_MAX_ROWS 64
+/* kalle_gemm_rows_fused for 1 <= R <= 64, bf16 weights: same arguments, same meaning */
+int kalle_gemm_rows_wide(const void* x, int64_t ldx, int prologue, const float* gamma, float eps, void* xhat, const void* W,
+                         int64_t ldw, void* y, int64_t ldy, int y_dtype, void* y2, int nsplit, const int64_t* y2_off,
+                         const float* residual, int64_t ldres, const int32_t* active, int R, int N, int K, void* stream);
+int kalle_llama_decode_ws_bytes_wide(int R, int H, int Hkv, int inner, int head_dim);
+/* kalle_llama_decode_step_rows for 1 <= R <= 64, bf16 layers */
+int kalle_llama_decode_step_wide(const kalle_llama_layer* layers, int n_layers, const float* x, float* out, int R, int H,
+                                 int Hkv, int inner, int head_dim, float eps, const int32_t* t0, int cache_rows,
+                                 const float* rope_cos, const float* rope_sin, void* workspace, void* stream);
 /* Packed prefill into a batch cache: after the q|k|v GEMM over the packed rows of several prompts (kalle_attention_fwd_varlen's
  * layout), the un-rotated k|v window of every sequence goes to that sequence's cache row, all sequences in ONE launch.
  *   src   bf16 [total_rows][ld_src], the k|v window at column src_off (kvw = 2*Hkv*head_dim columns)

@@ -170,10 +170,11 @@ struct RowsArgs {
     int R;
 };
 
-template <int PRO>
+// (MaskT: unsigned for the 16-row path, uint64_t for the wide one - the same expressions either way)
+template <int PRO, class MaskT = unsigned>
 __global__ __launch_bounds__(256) void rows_prologue_kernel(const void* __restrict__ xall, int64_t ldx,
                                                             const float* __restrict__ gamma, float eps,
-                                                            bf16_t* __restrict__ xhat, int64_t ldh, int K, unsigned active) {
+                                                            bf16_t* __restrict__ xhat, int64_t ldh, int K, MaskT active) {
     static_assert(PRO == PRO_RMS || PRO == PRO_SWIGLU, "PRO_BF16 has no pre-pass");
     const int r = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (!(active >> r & 1)) return;
@@ -270,6 +271,106 @@ __global__ __launch_bounds__(256) void gemm_rows_kernel(const bf16_t* __restrict
         void* yo = n < nsplit ? y : y2;
         if constexpr (YF32) static_cast<float*>(yo)[at] = s;
         else static_cast<bf16_t*>(yo)[at] = f32_to_bf16(s);
+    }
+}
+
+// ---- the wide form: 17 <= R <= 64 batch rows per weight read ------------------------------------------------------------------------
+// gemm_rows_kernel's lane layout with NCB = ceil(R / 16) column blocks: the 16-byte weight chunk a lane loaded feeds NCB MFMAs,
+// one per block of 16 batch rows, against that lane's chunk of batch rows i16, 16 + i16, ...  For one (weight row, batch row)
+// pair the accumulation is gemm_rows_kernel's, term for term: wave w takes the 256-element K blocks w, w + 4, ..., the eight
+// chunks of a block go through one accumulator in order, the four waves' partials meet as (p0 + p1) + (p2 + p3).  An MFMA
+// output element depends on its own row of A and column of B only, so a row's bits are those of the 16-row kernel whatever R,
+// TR, NCB, the row's index or the other rows.  What differs is the schedule: the pipelined unit is HALF a K block (4 chunks:
+// 16 weight + 16 NCB X registers, twice), so both operands of the next unit are in flight under the MFMAs of the current one:
+// 136 / 172 - 176 / 212 - 216 VGPRs at NCB = 2 / 3 / 4 as compiled, no scratch, where whole blocks double-buffered would need
+// about 320 by count.
+struct WideArgs {
+    int64_t y2_off[KALLE_DECODE_WIDE_MAX_ROWS];
+    uint64_t active;                         // bit r: row r takes part
+    int R;
+};
+
+template <bool YF32, int TR, int NCB>
+__global__ __launch_bounds__(256) void gemm_rows_wide_kernel(const bf16_t* __restrict__ X, int64_t ldx,
+                                                             const bf16_t* __restrict__ W, int64_t ldw, void* __restrict__ y,
+                                                             int64_t ldy, void* __restrict__ y2, int nsplit,
+                                                             const float* __restrict__ res, int64_t ldres, int N, int K,
+                                                             WideArgs a) {
+    static_assert(TR == 8 || TR == 16, "weight rows per workgroup");
+    static_assert(NCB >= 2 && NCB <= 4, "column blocks of 16 batch rows");
+    __shared__ __attribute__((aligned(16))) float part[4][NCB][64][4];
+    constexpr int CH = 8, HC = 4;                 // chunks per lane and K block (as gemm_rows_kernel) / per pipelined unit
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i16 = lane & 15, g = lane >> 4;
+    const int n0 = blockIdx.x * TR;
+    const bool wrow = TR == 16 || i16 < TR;
+    const int nc = K >> 3, NB = (nc + 4 * CH - 1) / (4 * CH);
+    const bf16_t* wr = W + (int64_t)(n0 + i16 < N ? n0 + i16 : N - 1) * ldw;
+    bool live[NCB];
+    const bf16_t* xr[NCB];
+#pragma unroll
+    for (int b = 0; b < NCB; ++b) {
+        const int r = 16 * b + i16;
+        live[b] = r < a.R && (a.active >> r & 1);
+        xr[b] = X + (live[b] ? r : 0) * ldx;                  // (not read unless live)
+    }
+    // unit u of this wave: half (u & 1) of K block wave + 4 (u >> 1)
+    auto load = [&](int u, i32x4* wq, i32x4 (*xq)[HC]) {
+        const int c0 = ((wave + 4 * (u >> 1)) * CH + (u & 1) * HC) * 4 + g;
+#pragma unroll
+        for (int j = 0; j < HC; ++j) {
+            const int c = c0 + 4 * j;
+            const bool in = c < nc;
+            const int cc = in ? c : nc - 1;
+            wq[j] = i32x4{0, 0, 0, 0};                        // past K: a zero weight chunk against a chunk of x that exists
+            if (wrow && in) wq[j] = *reinterpret_cast<const i32x4*>(wr + 8 * cc);
+#pragma unroll
+            for (int b = 0; b < NCB; ++b) {
+                xq[b][j] = i32x4{0, 0, 0, 0};
+                if (live[b]) xq[b][j] = *reinterpret_cast<const i32x4*>(xr[b] + 8 * cc);
+            }
+        }
+    };
+    f32x4 acc[NCB];
+#pragma unroll
+    for (int b = 0; b < NCB; ++b) acc[b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int NU = wave < NB ? 2 * ((NB - wave + 3) / 4) : 0;
+    i32x4 wv[HC], xv[NCB][HC];
+    if (NU) load(0, wv, xv);
+    for (int u = 0; u < NU; ++u) {
+        i32x4 wn[HC], xn[NCB][HC];
+        const bool more = u + 1 < NU;
+        if (more) load(u + 1, wn, xn);
+#pragma unroll
+        for (int j = 0; j < HC; ++j)
+#pragma unroll
+            for (int b = 0; b < NCB; ++b)
+                acc[b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wv[j]),
+                                                                 __builtin_bit_cast(bf16x8, xv[b][j]), acc[b], 0, 0, 0);
+        if (more) {
+#pragma unroll
+            for (int j = 0; j < HC; ++j) {
+                wv[j] = wn[j];
+#pragma unroll
+                for (int b = 0; b < NCB; ++b) xv[b][j] = xn[b][j];
+            }
+        }
+    }
+    // lane (i16, g) of block b holds weight rows n0 + 4 g + {0 .. 3} of batch row 16 b + i16
+#pragma unroll
+    for (int b = 0; b < NCB; ++b) *reinterpret_cast<f32x4*>(part[wave][b][lane]) = acc[b];
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < 16 * NCB * TR; idx += 256) {
+        const int r = idx / TR, j = idx % TR, n = n0 + j;
+        if (r < a.R && (a.active >> r & 1) && n < N) {
+            const int b = r >> 4, src = (j >> 2) * 16 + (r & 15), e = j & 3;
+            float s = (part[0][b][src][e] + part[1][b][src][e]) + (part[2][b][src][e] + part[3][b][src][e]);
+            if (res) s += res[r * ldres + n];
+            const int64_t at = n < nsplit ? r * ldy + n : a.y2_off[r] + (n - nsplit);
+            void* yo = n < nsplit ? y : y2;
+            if constexpr (YF32) static_cast<float*>(yo)[at] = s;
+            else static_cast<bf16_t*>(yo)[at] = f32_to_bf16(s);
+        }
     }
 }
 
@@ -566,12 +667,65 @@ inline void for_instance(bool yf32, int v, F&& f) {
     else on(std::false_type{});
 }
 
+// Weight rows per workgroup of the wide GEMM.  X never goes through LDS, so a workgroup reads all of it from
+// L2: 16 NCB x K x 2 bytes, (N / TR) times over - at TR = 8, 64 rows and the 1B down projection (N 2048, K 8192) 256 x 1 MiB
+// against 32 MiB of weights from HBM.  16 weight rows halve that and put the MFMA's upper M half to work; what they cost is
+// workgroups (N / 16).  Measured with both tiles forced at the eight decoder GEMMs of the 1B and 3B shapes, 32 and 64 rows:
+// from N = 3072 (192 workgroups of 16 rows) the 16-row tile wins everywhere, by 1.2 - 1.7 x; at N = 2048 (128 workgroups
+// on 256 CUs) the 8-row tile is 5 - 9 % ahead at either K and row count.  One threshold, no dependence on K or NCB.
+// -DKALLE_WIDE_TILE_ROWS=8 | 16 forces one tile everywhere: the builds behind that comparison
+// (python -m kalle_audio_amd.build --variant tr8 -DKALLE_WIDE_TILE_ROWS=8, run with KALLE_LIB_PATH; never set in the product build)
+inline int wide_tile_rows(int N) {
+#ifdef KALLE_WIDE_TILE_ROWS
+    static_assert(KALLE_WIDE_TILE_ROWS == 8 || KALLE_WIDE_TILE_ROWS == 16, "weight rows per workgroup");
+    (void)N;
+    return KALLE_WIDE_TILE_ROWS;
+#else
+    return N >= 3072 ? 16 : 8;
+#endif
+}
+
+// the wide R-row GEMM (bf16 weights only): proj_launch's R-row branch with the 64-bit mask and gemm_rows_wide_kernel
+inline int proj_launch_wide(const Proj& P, const void* x, int64_t ldx, int pro, const float* gamma, float eps, bf16_t* xhat,
+                            int64_t ldh, void* y, int64_t ldy, bool yf32, void* y2, int nsplit, const float* res, int64_t ldres,
+                            const WideArgs& a, int N, int K, hipStream_t st) {
+    if (P.scale) return KALLE_ERR_ARG;                       // (there is no wide e4m3 kernel)
+    const bf16_t* Wb = static_cast<const bf16_t*>(P.w);
+    const bf16_t* X = static_cast<const bf16_t*>(x);
+    if (pro != PRO_BF16) {
+        if (pro == PRO_RMS)
+            KALLE_LAUNCH((rows_prologue_kernel<PRO_RMS, uint64_t>), dim3(a.R), dim3(256), 0, st, x, ldx, gamma, eps, xhat, ldh, K,
+                         a.active);
+        else
+            KALLE_LAUNCH((rows_prologue_kernel<PRO_SWIGLU, uint64_t>), dim3(a.R), dim3(256), 0, st, x, ldx, gamma, eps, xhat, ldh,
+                         K, a.active);
+        const int rc = kalle_check_launch();
+        if (rc != KALLE_OK) return rc;
+        X = xhat;
+        ldx = ldh;
+    }
+    const int ncb = (a.R + 15) / 16, tr = wide_tile_rows(N);
+    const dim3 grid((N + tr - 1) / tr), block(256);
+    for_instance<2, 3, 4>(yf32, ncb, [&](auto yf, auto nb) {
+        constexpr bool F = decltype(yf)::value;
+        constexpr int NCB = decltype(nb)::value;
+        if (tr == 16)
+            KALLE_LAUNCH((gemm_rows_wide_kernel<F, 16, NCB>), grid, block, 0, st, X, ldx, Wb, P.ld, y, ldy, y2, nsplit, res, ldres,
+                         N, K, a);
+        else
+            KALLE_LAUNCH((gemm_rows_wide_kernel<F, 8, NCB>), grid, block, 0, st, X, ldx, Wb, P.ld, y, ldy, y2, nsplit, res, ldres,
+                         N, K, a);
+    });
+    return kalle_check_launch();
+}
+
 // y (columns n >= nsplit: y2) = W . pro(x) (+ res); returns the first failed launch.
 // rows == NULL: one row, the prologue built inside the GEMV (ldx, xhat, ldh, ldy, ldres unused).  Otherwise the R-row GEMM: the
 // prologue, if any, as a pre-pass into xhat (row stride ldh), y2 columns of row r at rows->y2_off[r].
 inline int proj_launch(const Proj& P, const void* x, int64_t ldx, int pro, const float* gamma, float eps, bf16_t* xhat,
                        int64_t ldh, void* y, int64_t ldy, bool yf32, void* y2, int nsplit, const float* res, int64_t ldres,
-                       const RowsArgs* rows, int N, int K, hipStream_t st) {
+                       const RowsArgs* rows, int N, int K, hipStream_t st, const WideArgs* wide = nullptr) {
+    if (wide) return proj_launch_wide(P, x, ldx, pro, gamma, eps, xhat, ldh, y, ldy, yf32, y2, nsplit, res, ldres, *wide, N, K, st);
     const bf16_t* Wb = static_cast<const bf16_t*>(P.w);
     const uint8_t* Wq = static_cast<const uint8_t*>(P.w);
     if (!rows) {
@@ -1087,38 +1241,52 @@ inline LayerView layer_view(const kalle_llama_layer_w8& L, int D, int inner) {
             L.kv_cache};
 }
 
-// The step behind the six exported ones.  Exactly one of lb / l8 is set.  batched: the R-row form (t0[r] < 0 = row r inactive,
-// skinny GEMMs, kalle_attention_decode_rows); otherwise R = 1, GEMVs and kalle_attention_decode_hd.  Nothing is launched unless
-// every argument and every layer passes.
+// The step behind the exported ones.  Exactly one of lb / l8 is set.  STEP_ROWS: the R-row form (t0[r] < 0 = row r inactive,
+// skinny GEMMs, kalle_attention_decode_rows); STEP_WIDE: that with 17 .. 64 rows (bf16 only) - the projections through the wide
+// GEMM, the attention once per chunk of 16 rows; STEP_ONE: R = 1, GEMVs and kalle_attention_decode_hd.  Nothing is launched
+// unless every argument and every layer passes.
+enum StepForm { STEP_ONE, STEP_ROWS, STEP_WIDE };
+
 int decode_step(const kalle_llama_layer* lb, const kalle_llama_layer_w8* l8, int n_layers, const float* x, float* out,
-                bool batched, int R, int H, int Hkv, int inner, int head_dim, float eps, const int32_t* t0, int cache_rows,
+                StepForm form, int R, int H, int Hkv, int inner, int head_dim, float eps, const int32_t* t0, int cache_rows,
                 const float* rope_cos, const float* rope_sin, void* workspace, void* stream) {
+    const bool batched = form != STEP_ONE, is_wide = form == STEP_WIDE;
     kalle_set_attn_plan(0);      // (a step refused before its first launch leaves no attention plan behind)
     if ((!lb && !l8) || n_layers <= 0 || !x || !out || !workspace || !rope_cos || !rope_sin || !t0) return KALLE_ERR_ARG;
-    if (R < 1 || R > KALLE_DECODE_MAX_ROWS) return KALLE_ERR_ARG;
+    if (R < 1 || R > (is_wide ? KALLE_DECODE_WIDE_MAX_ROWS : KALLE_DECODE_MAX_ROWS) || (is_wide && !lb)) return KALLE_ERR_ARG;
     // (a lane's unit of a weight row is 16 bytes: 8 bf16 weights, 16 e4m3 codes; D is a multiple of 64)
     if (H <= 0 || Hkv <= 0 || H % Hkv || inner <= 0 || (inner & (l8 ? 15 : 7)) || cache_rows <= 0) return KALLE_ERR_ARG;
     if (head_dim != 64 && head_dim != 128) return KALLE_ERR_ARG;
     if ((int64_t)H * head_dim > 32768 || inner > 32768) return KALLE_ERR_ARG;
     const int D = H * head_dim, kvw = 2 * Hkv * head_dim, xw = D > inner ? D : inner;
     RowsArgs a{};
-    a.R = R;
-    int32_t nk[KALLE_DECODE_MAX_ROWS];
+    WideArgs wa{};                                           // (the wide form's twin of `a`)
+    a.R = wa.R = R;
+    int32_t nk[KALLE_DECODE_WIDE_MAX_ROWS];
     for (int r = 0; r < R; ++r) {
         // (batched: the attention's LDS score array holds nk <= KALLE_ATTN_DECODE_MAX_KEYS keys; the one-row attention falls back to the tiled kernel)
         if (t0[r] >= cache_rows || (batched ? t0[r] >= KALLE_ATTN_DECODE_MAX_KEYS : t0[r] < 0)) return KALLE_ERR_ARG;
         nk[r] = t0[r] < 0 ? 0 : t0[r] + 1;
-        if (t0[r] >= 0) a.active |= 1u << r;
-        a.y2_off[r] = t0[r] < 0 ? 0 : ((int64_t)r * cache_rows + t0[r]) * kvw;
+        const int64_t off = t0[r] < 0 ? 0 : ((int64_t)r * cache_rows + t0[r]) * kvw;
+        if (t0[r] >= 0) wa.active |= (uint64_t)1 << r;
+        wa.y2_off[r] = off;
+        if (!is_wide) {
+            if (t0[r] >= 0) a.active |= 1u << r;
+            a.y2_off[r] = off;
+        }
     }
     auto layer = [&](int l) { return lb ? layer_view(lb[l], D, inner) : layer_view(l8[l], D, inner); };
     for (int l = 0; l < n_layers; ++l)
         if (!layer(l).complete(l8 != nullptr)) return KALLE_ERR_ARG;
-    if (!a.active) return KALLE_OK;
+    if (!wa.active) return KALLE_OK;
     RowsArgs plain = a;                                      // (no second destination)
-    for (int r = 0; r < R; ++r) plain.y2_off[r] = 0;
+    WideArgs wplain = wa;
+    for (int r = 0; r < R; ++r) wplain.y2_off[r] = 0;
+    for (int r = 0; r < R && !is_wide; ++r) plain.y2_off[r] = 0;
     const RowsArgs* rows_kv = batched ? &a : nullptr;
     const RowsArgs* rows = batched ? &plain : nullptr;
+    const WideArgs* wide_kv = is_wide ? &wa : nullptr;
+    const WideArgs* wide = is_wide ? &wplain : nullptr;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const DecodeWs o = decode_ws(R, H, inner, head_dim);
     char* ws = static_cast<char*>(workspace);
@@ -1139,21 +1307,40 @@ int decode_step(const kalle_llama_layer* lb, const kalle_llama_layer_w8* l8, int
         // (nsplit = D is a multiple of 64 at either head dim: a wave's rows never straddle it)
         void* kv = batched ? L.kv_cache : static_cast<bf16_t*>(L.kv_cache) + a.y2_off[0];
         int rc = proj_launch(L.qkv, xin, D, PRO_RMS, L.input_norm, eps, xn, xw, q, D, false, kv, D, nullptr, 0, rows_kv, D + kvw,
-                             D, st);
+                             D, st, wide_kv);
         if (rc != KALLE_OK) return rc;
-        rc = batched ? kalle_attention_decode_rows(q, D, 0, L.kv_cache, kvw, 0, L.kv_cache, kvw, Hkv * head_dim,
-                                                   (int64_t)cache_rows * kvw, ao, D, lse, rope_cos, rope_sin, head_dim, nk, R, H,
-                                                   Hkv, head_dim, stream)
-                     : kalle_attention_decode_hd(q, D, 0, L.kv_cache, kvw, 0, L.kv_cache, kvw, Hkv * head_dim, ao, D, lse,
-                                                 rope_cos, rope_sin, head_dim, nullptr, 1, H, Hkv, nk[0], head_dim, stream);
+        if (is_wide) {
+            // the per-row attention in chunks of 16 rows: q / ao, the cache, lse and nk offset by the chunk's first row.  A chunk
+            // with no active row launches nothing; the plan word left behind is the last launching chunk's
+            const bf16_t* cache = static_cast<const bf16_t*>(L.kv_cache);
+            const int64_t kvs = (int64_t)cache_rows * kvw;
+            int plan = 0;
+            for (int r0 = 0; r0 < R && rc == KALLE_OK; r0 += KALLE_DECODE_MAX_ROWS) {
+                const int rn = R - r0 < KALLE_DECODE_MAX_ROWS ? R - r0 : KALLE_DECODE_MAX_ROWS;
+                if (!(wa.active >> r0 & 0xFFFFu)) continue;
+                rc = kalle_attention_decode_rows(q + (int64_t)r0 * D, D, 0, cache + r0 * kvs, kvw, 0, cache + r0 * kvs, kvw,
+                                                 Hkv * head_dim, kvs, ao + (int64_t)r0 * D, D, lse + (int64_t)r0 * H, rope_cos,
+                                                 rope_sin, head_dim, nk + r0, rn, H, Hkv, head_dim, stream);
+                plan = kalle_attn_last_plan();
+            }
+            if (rc == KALLE_OK) kalle_set_attn_plan(plan);
+        } else if (batched) {
+            rc = kalle_attention_decode_rows(q, D, 0, L.kv_cache, kvw, 0, L.kv_cache, kvw, Hkv * head_dim,
+                                             (int64_t)cache_rows * kvw, ao, D, lse, rope_cos, rope_sin, head_dim, nk, R, H, Hkv,
+                                             head_dim, stream);
+        } else {
+            rc = kalle_attention_decode_hd(q, D, 0, L.kv_cache, kvw, 0, L.kv_cache, kvw, Hkv * head_dim, ao, D, lse, rope_cos,
+                                           rope_sin, head_dim, nullptr, 1, H, Hkv, nk[0], head_dim, stream);
+        }
         if (rc != KALLE_OK) return rc;
-        rc = proj_launch(L.o, ao, D, PRO_BF16, nullptr, 0.f, nullptr, 0, x2, D, true, x2, D, xin, D, rows, D, D, st);
+        rc = proj_launch(L.o, ao, D, PRO_BF16, nullptr, 0.f, nullptr, 0, x2, D, true, x2, D, xin, D, rows, D, D, st, wide);
         if (rc != KALLE_OK) return rc;
         rc = proj_launch(L.ug, x2, D, PRO_RMS, L.post_norm, eps, xn, xw, hf, 2 * inner, false, hf, 2 * inner, nullptr, 0, rows,
-                         2 * inner, D, st);
+                         2 * inner, D, st, wide);
         if (rc != KALLE_OK) return rc;
         float* xo = l + 1 == n_layers ? out : x3;
-        rc = proj_launch(L.down, hf, 2 * inner, PRO_SWIGLU, nullptr, 0.f, xn, xw, xo, D, true, xo, D, x2, D, rows, D, inner, st);
+        rc = proj_launch(L.down, hf, 2 * inner, PRO_SWIGLU, nullptr, 0.f, xn, xw, xo, D, true, xo, D, x2, D, rows, D, inner, st,
+                         wide);
         if (rc != KALLE_OK) return rc;
         xin = xo;
     }
@@ -1179,29 +1366,43 @@ extern "C" int kalle_llama_decode_step_hd(const kalle_llama_layer* layers, int n
                                           int Hkv, int inner, int head_dim, float eps, int t0, int cache_rows,
                                           const float* rope_cos, const float* rope_sin, void* workspace, void* stream) {
     const int32_t t = t0;
-    return decode_step(layers, nullptr, n_layers, x, out, false, 1, H, Hkv, inner, head_dim, eps, &t, cache_rows, rope_cos, rope_sin,
+    return decode_step(layers, nullptr, n_layers, x, out, STEP_ONE, 1, H, Hkv, inner, head_dim, eps, &t, cache_rows, rope_cos, rope_sin,
                        workspace, stream);
 }
 extern "C" int kalle_llama_decode_step_w8(const kalle_llama_layer_w8* layers, int n_layers, const float* x, float* out, int H,
                                           int Hkv, int inner, int head_dim, float eps, int t0, int cache_rows,
                                           const float* rope_cos, const float* rope_sin, void* workspace, void* stream) {
     const int32_t t = t0;
-    return decode_step(nullptr, layers, n_layers, x, out, false, 1, H, Hkv, inner, head_dim, eps, &t, cache_rows, rope_cos, rope_sin,
+    return decode_step(nullptr, layers, n_layers, x, out, STEP_ONE, 1, H, Hkv, inner, head_dim, eps, &t, cache_rows, rope_cos, rope_sin,
                        workspace, stream);
 }
 extern "C" int kalle_llama_decode_step_rows(const kalle_llama_layer* layers, int n_layers, const float* x, float* out, int R,
                                             int H, int Hkv, int inner, int head_dim, float eps, const int32_t* t0,
                                             int cache_rows, const float* rope_cos, const float* rope_sin, void* workspace,
                                             void* stream) {
-    return decode_step(layers, nullptr, n_layers, x, out, true, R, H, Hkv, inner, head_dim, eps, t0, cache_rows, rope_cos, rope_sin,
+    return decode_step(layers, nullptr, n_layers, x, out, STEP_ROWS, R, H, Hkv, inner, head_dim, eps, t0, cache_rows, rope_cos, rope_sin,
                        workspace, stream);
 }
 extern "C" int kalle_llama_decode_step_rows_w8(const kalle_llama_layer_w8* layers, int n_layers, const float* x, float* out,
                                                int R, int H, int Hkv, int inner, int head_dim, float eps, const int32_t* t0,
                                                int cache_rows, const float* rope_cos, const float* rope_sin, void* workspace,
                                                void* stream) {
-    return decode_step(nullptr, layers, n_layers, x, out, true, R, H, Hkv, inner, head_dim, eps, t0, cache_rows, rope_cos, rope_sin,
+    return decode_step(nullptr, layers, n_layers, x, out, STEP_ROWS, R, H, Hkv, inner, head_dim, eps, t0, cache_rows, rope_cos, rope_sin,
                        workspace, stream);
+}
+// the wide forms: up to 16 rows they ARE the _rows forms
+extern "C" int kalle_llama_decode_ws_bytes_wide(int R, int H, int Hkv, int inner, int head_dim) {
+    if (R < 1 || R > KALLE_DECODE_WIDE_MAX_ROWS || H <= 0 || Hkv <= 0 || inner <= 0 || (head_dim != 64 && head_dim != 128))
+        return KALLE_ERR_ARG;
+    if ((int64_t)H * head_dim > 32768 || inner > 32768) return KALLE_ERR_ARG;
+    return (int)decode_ws(R, H, inner, head_dim).end;
+}
+extern "C" int kalle_llama_decode_step_wide(const kalle_llama_layer* layers, int n_layers, const float* x, float* out, int R,
+                                            int H, int Hkv, int inner, int head_dim, float eps, const int32_t* t0,
+                                            int cache_rows, const float* rope_cos, const float* rope_sin, void* workspace,
+                                            void* stream) {
+    return decode_step(layers, nullptr, n_layers, x, out, R <= KALLE_DECODE_MAX_ROWS ? STEP_ROWS : STEP_WIDE, R, H, Hkv, inner,
+                       head_dim, eps, t0, cache_rows, rope_cos, rope_sin, workspace, stream);
 }
 // the head-dim-64 forms of the C ABI: forwarders
 extern "C" int kalle_llama_decode_ws_bytes(int H, int Hkv, int inner) { return kalle_llama_decode_ws_bytes_hd(H, Hkv, inner, 64); }
@@ -1214,18 +1415,26 @@ extern "C" int kalle_llama_decode_step(const kalle_llama_layer* layers, int n_la
 
 // ---- the R-row GEMM entry points -------------------------------------------------------------------------------------------------
 // the argument check and the RowsArgs of both weight formats, then the launch.  kalign: 8 (bf16) or 16 (e4m3) weights per 16 bytes.
-static int gemm_rows_entry(const Proj& P, int kalign, const void* x, int64_t ldx, int prologue, const float* gamma, float eps,
-                           void* xhat, void* y, int64_t ldy, int y_dtype, void* y2, int nsplit, const int64_t* y2_off,
-                           const float* residual, int64_t ldres, const int32_t* active, int R, int N, int K, void* stream) {
-    if (!x || !P.w || !y || R < 1 || R > KALLE_DECODE_MAX_ROWS || N <= 0 || K <= 0 || (K & (kalign - 1)) || (P.ld & (kalign - 1)) ||
-        K > 32768)
-        return KALLE_ERR_ARG;
+// (everything but the bound on R, which is the caller's)
+static int gemm_rows_args_ok(int kalign, const void* x, const void* w, int64_t ldw, const void* y, int64_t ldx, int prologue,
+                             const float* gamma, const void* xhat, int64_t ldy, int y_dtype, const void* y2, int nsplit,
+                             const int64_t* y2_off, int64_t ldres, int N, int K) {
+    if (!x || !w || !y || N <= 0 || K <= 0 || (K & (kalign - 1)) || (ldw & (kalign - 1)) || K > 32768) return KALLE_ERR_ARG;
     if (y_dtype != KALLE_F32 && y_dtype != KALLE_BF16) return KALLE_ERR_ARG;
     if (prologue != PRO_BF16 && prologue != PRO_RMS && prologue != PRO_SWIGLU) return KALLE_ERR_ARG;
     if (prologue == PRO_RMS ? (!gamma || (ldx & 3)) : (ldx & 7)) return KALLE_ERR_ARG;
     if (prologue != PRO_BF16 && !xhat) return KALLE_ERR_ARG;
-    if (ldx < (prologue == PRO_SWIGLU ? 2 * (int64_t)K : K) || P.ld < K || ldy < 0 || ldres < 0) return KALLE_ERR_ARG;
+    if (ldx < (prologue == PRO_SWIGLU ? 2 * (int64_t)K : K) || ldw < K || ldy < 0 || ldres < 0) return KALLE_ERR_ARG;
     if (nsplit < 0 || nsplit > N || (nsplit < N && (!y2 || !y2_off))) return KALLE_ERR_ARG;
+    return KALLE_OK;
+}
+
+static int gemm_rows_entry(const Proj& P, int kalign, const void* x, int64_t ldx, int prologue, const float* gamma, float eps,
+                           void* xhat, void* y, int64_t ldy, int y_dtype, void* y2, int nsplit, const int64_t* y2_off,
+                           const float* residual, int64_t ldres, const int32_t* active, int R, int N, int K, void* stream) {
+    if (R < 1 || R > KALLE_DECODE_MAX_ROWS) return KALLE_ERR_ARG;
+    const int ok = gemm_rows_args_ok(kalign, x, P.w, P.ld, y, ldx, prologue, gamma, xhat, ldy, y_dtype, y2, nsplit, y2_off, ldres, N, K);
+    if (ok != KALLE_OK) return ok;
     RowsArgs a{};
     a.R = R;
     for (int r = 0; r < R; ++r) {
@@ -1243,6 +1452,29 @@ extern "C" int kalle_gemm_rows_fused(const void* x, int64_t ldx, int prologue, c
                                      int N, int K, void* stream) {
     return gemm_rows_entry({W, ldw, nullptr}, 8, x, ldx, prologue, gamma, eps, xhat, y, ldy, y_dtype, y2, nsplit, y2_off, residual,
                            ldres, active, R, N, K, stream);
+}
+
+// kalle_gemm_rows_fused for up to 64 rows (bf16 weights): its argument check with the bound at 64, then the wide kernel; up to
+// 16 rows it is kalle_gemm_rows_fused
+extern "C" int kalle_gemm_rows_wide(const void* x, int64_t ldx, int prologue, const float* gamma, float eps, void* xhat,
+                                    const void* W, int64_t ldw, void* y, int64_t ldy, int y_dtype, void* y2, int nsplit,
+                                    const int64_t* y2_off, const float* residual, int64_t ldres, const int32_t* active, int R,
+                                    int N, int K, void* stream) {
+    if (R <= KALLE_DECODE_MAX_ROWS)
+        return kalle_gemm_rows_fused(x, ldx, prologue, gamma, eps, xhat, W, ldw, y, ldy, y_dtype, y2, nsplit, y2_off, residual,
+                                     ldres, active, R, N, K, stream);
+    if (R > KALLE_DECODE_WIDE_MAX_ROWS) return KALLE_ERR_ARG;
+    const int rc = gemm_rows_args_ok(8, x, W, ldw, y, ldx, prologue, gamma, xhat, ldy, y_dtype, y2, nsplit, y2_off, ldres, N, K);
+    if (rc != KALLE_OK) return rc;
+    WideArgs a{};
+    a.R = R;
+    for (int r = 0; r < R; ++r) {
+        if (!active || active[r]) a.active |= (uint64_t)1 << r;
+        a.y2_off[r] = nsplit < N ? y2_off[r] : 0;
+    }
+    if (!a.active) return KALLE_OK;
+    return proj_launch_wide({W, ldw, nullptr}, x, ldx, prologue, gamma, eps, static_cast<bf16_t*>(xhat), K, y, ldy,
+                            y_dtype == KALLE_F32, y2, nsplit, residual, ldres, a, N, K, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int kalle_gemm_rows_bf16(const void* x, int64_t ldx, const void* W, int64_t ldw, void* y, int64_t ldy, int y_dtype,

@@ -304,10 +304,28 @@ class DeviceHead:
 
 
 # ---- the callers
-def generate(owner, prompts, thres, max_length, spec=None, noise=None, stop_lag=0, refill=False):
+def batch_rows(owner, rows):
+    """the rows per decoder pass of a batched call.  rows None: min(owner.infer_batch_rows, DECODE_MAX_ROWS), as before the wide
+    step existed (a larger infer_batch_rows stays clamped); an int in 1 .. DECODE_WIDE_MAX_ROWS: that many, above DECODE_MAX_ROWS
+    through the wide step - which has no e4m3 form."""
+    if rows is not None and (isinstance(rows, bool) or not isinstance(rows, int) or not 1 <= rows <= ops.DECODE_WIDE_MAX_ROWS):
+        raise ValueError(f"rows: None or an int in 1 .. {ops.DECODE_WIDE_MAX_ROWS}, got {rows!r}")
+    if owner is None:                # (the argument check alone)
+        return rows
+    if rows is None:
+        return max(1, min(int(owner.infer_batch_rows), ops.DECODE_MAX_ROWS))
+    fmt = getattr(owner.base_model.model, "_decode_fmt", None)
+    if rows > ops.DECODE_MAX_ROWS and fmt is not None:
+        raise NotImplementedError(f"quantize_decoder({fmt!r}) together with rows={rows}: more than {ops.DECODE_MAX_ROWS} rows "
+                                  "per decoder pass run the wide step, which reads bf16 weights only")
+    return rows
+
+
+def generate(owner, prompts, thres, max_length, spec=None, noise=None, stop_lag=0, refill=False, rows=None):
     """One run of the loop.  refill=False: `infer` (one prompt: OneRow) or one group of `infer_batch` (a row per prompt, nothing
-    admitted after step 0).  refill=True: the whole list on ONE batch cache of R = min(infer_batch_rows, DECODE_MAX_ROWS,
-    len(prompts)) rows; the schedule's trace is left in owner.last_refill_trace.  max_length: an int, or one frame cap per prompt.
+    admitted after step 0).  refill=True: the whole list on ONE batch cache of R = min(batch_rows(owner, rows), len(prompts))
+    rows (rows=None: infer_batch_rows clamped to DECODE_MAX_ROWS); the schedule's trace is left in owner.last_refill_trace.
+    max_length: an int, or one frame cap per prompt.
     spec: the DeviceHeadSpec of the owner's device head (None: the host head, which takes neither noise nor stop_lag).  Returns the
     results in prompt order."""
     model = owner.base_model.model
@@ -315,15 +333,15 @@ def generate(owner, prompts, thres, max_length, spec=None, noise=None, stop_lag=
     N, dev = len(embeds), embeds[0].device
     caps = _frame_caps(max_length, N) or [max_length] * N
     top = max(caps)
-    R = max(1, min(int(owner.infer_batch_rows), ops.DECODE_MAX_ROWS, N)) if refill else N
+    R = min(batch_rows(owner, rows), N) if refill else N
     if noise is not None:
         noise = noise.to(device=dev, dtype=F32).expand(top, N, spec.lat)
     host, one, ring = spec is None, N == 1 and not refill, top + stop_lag
     room = max(e.shape[1] for e in embeds) + top
-    rows = OneRow(model, embeds, room, host) if one else BatchRows(model, embeds, R, room, host, packed=refill)
+    seats = OneRow(model, embeds, room, host) if one else BatchRows(model, embeds, R, room, host, packed=refill)
     head = HostHead(owner, R, ring) if host else DeviceHead(owner, spec, R, ring, dev, noise, all_rows=one)
     sched = RowSchedule(N, R)
-    results = run_frames(sched, rows, head, thres, caps, ring, stop_lag, horizon=None if refill else top)
+    results = run_frames(sched, seats, head, thres, caps, ring, stop_lag, horizon=None if refill else top)
     if refill:
         owner.last_refill_trace = sched.trace
     return results
@@ -357,13 +375,16 @@ def generate_one(owner, input_ids, audio_latents, thres, max_length, use_cache, 
     return generate(owner, [(input_ids, audio_latents)], thres, max_length)[0]
 
 
-def generate_batch(owner, prompts, thres, max_length, device_head, noise, stop_lag, lat, refill=False):
+def generate_batch(owner, prompts, thres, max_length, device_head, noise, stop_lag, lat, refill=False, rows=None):
     """`infer_batch` of both task models: the checks, one prompt = `owner.infer`, lists longer than `owner.infer_batch_rows` in
     groups, a group through owner._generate_device_head or through `generate` with the host head; refill=True: the whole list in
-    one run.  max_length: an int, or one frame cap per prompt."""
+    one run.  max_length: an int, or one frame cap per prompt.  rows: batch_rows' argument - the group size / the shared cache's
+    row count of this call."""
     prompts = list(prompts)
+    batch_rows(None, rows)
     if not prompts:
         return []
+    G = batch_rows(owner, rows)
     if not device_head and (noise is not None or stop_lag):
         raise ValueError("noise= and stop_lag= belong to device_head=True")
     caps = _frame_caps(max_length, len(prompts))
@@ -373,13 +394,12 @@ def generate_batch(owner, prompts, thres, max_length, device_head, noise, stop_l
     if len(prompts) == 1:
         return [owner.infer(prompts[0][0], prompts[0][1], end_disp_kl_thres=thres, max_length=top,
                             device_head=device_head, noise=noise, stop_lag=stop_lag)]
-    G = max(1, min(int(owner.infer_batch_rows), ops.DECODE_MAX_ROWS))
     if not refill and len(prompts) > G:
         part = lambda i: max_length if caps is None else caps[i:i + G]
         cut = lambda i: noise[:, i:i + G] if caps is None else noise[:max(part(i)), i:i + G]
         return [o for i in range(0, len(prompts), G)
                 for o in generate_batch(owner, prompts[i:i + G], thres, part(i), device_head,
-                                        None if noise is None else cut(i), stop_lag, lat)]
+                                        None if noise is None else cut(i), stop_lag, lat, rows=rows)]
     if device_head:
-        return owner._generate_device_head(prompts, thres, max_length, noise, stop_lag, refill=refill)
-    return generate(owner, prompts, thres, max_length, refill=refill)
+        return owner._generate_device_head(prompts, thres, max_length, noise, stop_lag, refill=refill, rows=rows)
+    return generate(owner, prompts, thres, max_length, refill=refill, rows=rows)

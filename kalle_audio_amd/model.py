@@ -127,7 +127,7 @@ class Llasa(nn.Module):
 
     @torch.no_grad()
     def infer_batch(self, prompts, end_disp_kl_thres=0.5, max_length=1000, device_head=False, noise=None, stop_lag=0,
-                    refill=False):
+                    refill=False, rows=None):
         """`infer` (KV-cached) for a list of (input_ids, audio_latents or None), as model_sigmaVAE.Llasa.infer_batch: the
         utterances of a group (up to `infer_batch_rows`) share one decoder pass per frame, a row that meets the stop rule leaves
         the batch while the others go on, longer lists run in groups, one prompt is `infer` itself.  Returns a list with what
@@ -135,13 +135,14 @@ class Llasa(nn.Module):
         [max_length, len(prompts), latent_dim] and drawn, when absent, as one torch.randn((R, 1, latent_dim)) per frame.
         max_length may be one int per prompt; refill=True (opt-in) keeps the rows full - a stopped row takes the next waiting
         prompt, prompts admitted together are prefilled in one packed pass - exactly as documented on
-        model_sigmaVAE.Llasa.infer_batch (`self.last_refill_trace` holds the schedule that ran)."""
+        model_sigmaVAE.Llasa.infer_batch (`self.last_refill_trace` holds the schedule that ran).  rows: None, or the rows per
+        decoder pass of this call, 1 .. 64 (above 16: the wide step), as documented there."""
         return generate_batch(self, prompts, end_disp_kl_thres, max_length, device_head, noise, stop_lag,
-                              self.audio_linear.weight.shape[1], refill=refill)
+                              self.audio_linear.weight.shape[1], refill=refill, rows=rows)
 
-    def _generate_device_head(self, prompts, thres, max_length, noise, stop_lag, refill=False):
+    def _generate_device_head(self, prompts, thres, max_length, noise, stop_lag, refill=False, rows=None):
         """generation.generate with the mean || log-scale head (ops.llasa_frame_head2); returns the stacked `disp` rows"""
         lat = self.audio_linear.weight.shape[1]
         device_head_limits(stop_lag, lat, ops.HEAD2_MAX_LATENT)
         spec = DeviceHeadSpec(ops.llasa_head2_plan, ops.llasa_frame_head2, (), "disp", lat)
-        return generate(self, prompts, thres, max_length, spec, noise, stop_lag, refill)
+        return generate(self, prompts, thres, max_length, spec, noise, stop_lag, refill, rows=rows)

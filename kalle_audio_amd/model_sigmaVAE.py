@@ -438,8 +438,11 @@ class LlamaModel(nn.Module):
     # ---- inference with a KV cache, R sequences of different lengths per step -------------------------------------------------
     def init_cache_batch(self, R, max_len, device):
         """one bf16 [R, max_len, 2 * kv_heads * head_dim] buffer per layer, a length per row, rope tables for max_len"""
-        if not 1 <= R <= ops.DECODE_MAX_ROWS:
-            raise ValueError(f"a batch cache holds 1 .. {ops.DECODE_MAX_ROWS} sequences, got {R}")
+        if not 1 <= R <= ops.DECODE_WIDE_MAX_ROWS:
+            raise ValueError(f"a batch cache holds 1 .. {ops.DECODE_WIDE_MAX_ROWS} sequences, got {R}")
+        if R > ops.DECODE_MAX_ROWS and self._decode_fmt is not None:
+            raise NotImplementedError(f"quantize_decoder({self._decode_fmt!r}) with more than {ops.DECODE_MAX_ROWS} rows ({R}): "
+                                      "the wide decode step reads bf16 weights only")
         w = 2 * self.cfg["num_key_value_heads"] * self.head_dim
         return {"kv": [torch.zeros((R, max_len, w), device=device, dtype=BF16) for _ in self.layers], "len": [0] * R,
                 "rope": LO.rope_tables(max_len, self._inv_freq, device)}
@@ -661,7 +664,7 @@ class Llasa(nn.Module):
 
     @torch.no_grad()
     def infer_batch(self, prompts, end_disp_kl_thres=0.5, max_length=200, device_head=False, noise=None, stop_lag=0,
-                    refill=False):
+                    refill=False, rows=None):
         """`infer` (KV-cached) for a list of (input_ids, audio_latents or None): the utterances of a group are generated together,
         one decoder pass per frame for all of them, so the decoder weights are read once per frame instead of once per frame
         and utterance.  Returns a list with what `infer` returns for each prompt.  The prompts are prefilled one by one (they
@@ -680,9 +683,14 @@ class Llasa(nn.Module):
         prefill GEMMs may pick another plan at another row count).  With noise=None one torch.randn((R, 1, latent_dim)) is
         drawn per global step, so WHICH utterance gets which draw differs from the grouped mode (and, under the host head, one
         draw per step covers all R rows as before).  stop_lag=1: a stopped row is refilled one step later (its discarded extra
-        frame has run).  The schedule that ran is left in `self.last_refill_trace`: (utterance, row, first_step, frames)."""
+        frame has run).  The schedule that ran is left in `self.last_refill_trace`: (utterance, row, first_step, frames).
+        rows (extension): None - min(infer_batch_rows, 16) rows per decoder pass, as ever; an int in 1 .. 64 - the group size
+        (refill=False) or the row count of the shared cache (refill=True) of THIS call.  Above 16 the decoder runs the wide step
+        (kalle_llama_decode_step_wide: up to 64 utterances share one read of the weights; bf16 weights only - with
+        quantize_decoder("e4m3") it is a NotImplementedError) and the device head runs once per 16 rows; an utterance's result
+        under explicit noise is, bit for bit, what groups of 16 give."""
         return generate_batch(self, prompts, end_disp_kl_thres, max_length, device_head, noise, stop_lag,
-                              self.distribution_linear[2].weight.shape[0], refill=refill)
+                              self.distribution_linear[2].weight.shape[0], refill=refill, rows=rows)
 
     def _host_frame(self, hidden):
         """the head of one frame on the host for the rows of hidden [R, 1, D]: (what `infer_batch` stacks, the sampled latent
@@ -695,7 +703,7 @@ class Llasa(nn.Module):
         kl =(torch.log(torch.tensor(e / s)) + (s * s + (mean2.float() - 1.0) ** 2) / (2 * e * e) - 0.5).sum(2)
         return audio_latent, audio_latent, kl / mean2.shape[2]
 
-    def _generate_device_head(self, prompts, thres, max_length, noise, stop_lag, refill=False):
+    def _generate_device_head(self, prompts, thres, max_length, noise, stop_lag, refill=False, rows=None):
         """generation.generate with the fixed-std head (ops.llasa_frame_head); returns the sampled latents"""
         dl = self.distribution_linear[2].weight.shape[0]
         device_head_limits(stop_lag, dl, ops.HEAD_MAX_LATENT)
@@ -704,7 +712,7 @@ class Llasa(nn.Module):
             raise NotImplementedError("device_head=True takes the fixed scalar std of init_sigmaVAE; any other std runs on the "
                                       "host path (device_head=False)")
         spec = DeviceHeadSpec(ops.llasa_head_plan, ops.llasa_frame_head, (float(std),), "latent", dl)
-        return generate(self, prompts, thres, max_length, spec, noise, stop_lag, refill)
+        return generate(self, prompts, thres, max_length, spec, noise, stop_lag, refill, rows=rows)
 
     def init_sigmaVAE(self):
         self.std = torch.tensor(0.5)

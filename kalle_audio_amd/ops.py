@@ -618,13 +618,28 @@ def attention_fwd_varlen(q, k, v, seqs, *, ldq, q_off, ldk, k_off, ldv, v_off, H
 def kv_append_varlen(src, seqs, cache, dst_rows, t0, *, src_off):
     """kalle_kv_append_varlen: the k|v window (columns src_off .. src_off + kvw of the packed bf16 buffer src [total_rows, ld]) of
     every sequence of `seqs` (a Packed) goes to cache [R, cache_rows, kvw], sequence s to cache[dst_rows[s], t0[s] + j]; dst_rows /
-    t0: host ints, one per sequence.  One launch, nothing else written.  Returns cache."""
+    t0: host ints, one per sequence.  One launch, nothing else written.  Returns cache.
+    A cache of more than DECODE_MAX_ROWS rows (the wide step's): one launch per block of 16 cache rows that receives a sequence,
+    on that block's slice of the cache with the sequences that land in it (at most 16, in their packed order)."""
     lib = _lib.load()
     assert src.dtype == cache.dtype == torch.bfloat16 and src.dim() == 2 and src.stride(1) == 1 and src.shape[0] == seqs.total_rows
     assert cache.dim() == 3 and cache.stride(2) == 1 and cache.stride(1) == cache.shape[2]
     assert len(dst_rows) == len(t0) == seqs.nseq
     R, cache_rows, kvw = cache.shape
     cast = ctypes.cast
+    if R > DECODE_MAX_ROWS and all(0 <= int(d) < R for d in dst_rows):
+        for b0 in range(0, R, DECODE_MAX_ROWS):
+            pick = [s for s, d in enumerate(dst_rows) if b0 <= int(d) < b0 + DECODE_MAX_ROWS]
+            if not pick:
+                continue
+            block = cache[b0:b0 + DECODE_MAX_ROWS]
+            check(lib.kalle_kv_append_varlen(_p(src), src.stride(0), src_off, _p(block), cache.stride(0), kvw, len(pick),
+                                             cast(_i32([seqs.row0[s] for s in pick]), ctypes.c_void_p),
+                                             cast(_i32([seqs.lens[s] for s in pick]), ctypes.c_void_p),
+                                             cast(_i32([int(dst_rows[s]) - b0 for s in pick]), ctypes.c_void_p),
+                                             cast(_i32([t0[s] for s in pick]), ctypes.c_void_p), seqs.total_rows, block.shape[0],
+                                             cache_rows, _stream()), "kalle_kv_append_varlen")
+        return cache
     check(lib.kalle_kv_append_varlen(_p(src), src.stride(0), src_off, _p(cache), cache.stride(0), kvw, seqs.nseq,
                                      cast(seqs.host[0], ctypes.c_void_p), cast(seqs.host[1], ctypes.c_void_p),
                                      cast(_i32(dst_rows), ctypes.c_void_p), cast(_i32(t0), ctypes.c_void_p), seqs.total_rows, R,
@@ -798,6 +813,7 @@ def gauss_kl_bwd(pred, label, mask_a, mask_b, sums, grad_a, grad_b, std):
 # ---- KV-cached decoding (include/kalle_hip.h): one row or R <= DECODE_MAX_ROWS sequences per step, bf16 weights or uint8 OCP
 # e4m3fn codes [N, K] + one fp32 scale per output row
 DECODE_MAX_ROWS = 16
+DECODE_WIDE_MAX_ROWS = 64        # the wide step (kalle_llama_decode_step_wide): bf16 layers only
 BF16_FIELDS = ("input_norm", "wqkv", "wo", "post_norm", "wug", "wdown", "kv_cache")
 W8_FIELDS = ("input_norm", "wqkv", "sqkv", "wo", "so", "post_norm", "wug", "sug", "wdown", "sdown", "kv_cache")
 _DECODE_STEP = {(False, False): "kalle_llama_decode_step_hd", (False, True): "kalle_llama_decode_step_w8",      # (R-row, e4m3)
@@ -829,6 +845,21 @@ def gemm_rows(x, w, *, residual=None, out_dtype=torch.float32):
     check(lib.kalle_gemm_rows_bf16(_p(x), x.stride(0), _p(w), w.stride(0), _p(y), y.stride(0), _dt(y), _p(residual),
                                    residual.stride(0) if residual is not None else 0, R, w.shape[0], K, _stream()),
           "kalle_gemm_rows_bf16")
+    return y
+
+
+def gemm_rows_wide(x, w, *, residual=None, out_dtype=torch.float32):
+    """gemm_rows for the R <= 64 rows of x: kalle_gemm_rows_wide without a prologue (up to 16 rows it is gemm_rows' kernel; a
+    row's bits are the same either way)"""
+    lib = _lib.load()
+    assert x.dim() == 2
+    R, K = x.shape
+    N = w.shape[0]
+    y = torch.empty((R, N), device=x.device, dtype=out_dtype)
+    _proj_args(x, w, torch.bfloat16, None, residual, y.shape)
+    check(lib.kalle_gemm_rows_wide(_p(x), x.stride(0), 0, None, 0.0, None, _p(w), w.stride(0), _p(y), y.stride(0), _dt(y), None, N,
+                                   None, _p(residual), residual.stride(0) if residual is not None else 0, None, R, N, K,
+                                   _stream()), "kalle_gemm_rows_wide")
     return y
 
 
@@ -890,7 +921,8 @@ def llama_decode_plan(layer_tensors, H, Hkv, inner, device, head_dim=64, rows=No
     """The host-side descriptor array + workspace of the decode step (keeps the tensors alive).  layer_tensors: per layer the
     tensors of BF16_FIELDS (input_norm fp32, wqkv bf16, wo bf16, post_norm fp32, wug bf16, wdown bf16, kv_cache bf16) or of
     W8_FIELDS (each weight uint8 and followed by its fp32 scale, the pairs as quantize_rows_e4m3 returns them); the tuple length
-    tells which.  rows = R: the R-row step, kv_cache of a layer is bf16 [R, cache_rows, 2*Hkv*head_dim]."""
+    tells which.  rows = R: the R-row step, kv_cache of a layer is bf16 [R, cache_rows, 2*Hkv*head_dim]; R above DECODE_MAX_ROWS
+    (up to DECODE_WIDE_MAX_ROWS): the wide step, bf16 layers only."""
     lib = _lib.load()
     nf = len(layer_tensors[0])
     assert nf in (len(BF16_FIELDS), len(W8_FIELDS)), f"a layer is {len(BF16_FIELDS)} (bf16) or {len(W8_FIELDS)} (e4m3) tensors"
@@ -904,14 +936,19 @@ def llama_decode_plan(layer_tensors, H, Hkv, inner, device, head_dim=64, rows=No
             setattr(d, f, t.data_ptr())
         if rows is not None:
             assert ts[-1].dim() == 3 and ts[-1].shape[0] == rows
+    wide = rows is not None and rows > DECODE_MAX_ROWS
+    if wide and w8:
+        raise NotImplementedError(f"e4m3 layers with more than {DECODE_MAX_ROWS} rows ({rows}): there is no wide e4m3 step")
     if rows is None:
         nbytes, what = lib.kalle_llama_decode_ws_bytes_hd(H, Hkv, inner, head_dim), "kalle_llama_decode_ws_bytes_hd"
+    elif wide:
+        nbytes, what = lib.kalle_llama_decode_ws_bytes_wide(rows, H, Hkv, inner, head_dim), "kalle_llama_decode_ws_bytes_wide"
     else:
         nbytes, what = lib.kalle_llama_decode_ws_bytes_rows(rows, H, Hkv, inner, head_dim), "kalle_llama_decode_ws_bytes_rows"
     check(min(nbytes, 0), what)
     plan = {"layers": arr, "n": len(layer_tensors), "keep": layer_tensors, "ws": torch.empty(nbytes, device=device, dtype=torch.uint8),
             "H": H, "Hkv": Hkv, "inner": inner, "head_dim": head_dim,
-            "step": _DECODE_STEP[rows is not None, w8]}
+            "step": "kalle_llama_decode_step_wide" if wide else _DECODE_STEP[rows is not None, w8]}
     if rows is not None:
         plan["R"] = rows
     if w8:
@@ -946,6 +983,24 @@ HEAD_FIELDS = ("norm", "w1", "b1", "w2", "b2", "wa", "ba")
 HEAD_MAX_LATENT = 512
 
 
+def _head_chunks(ws_bytes, R, what):
+    """the head entry points serve up to DECODE_MAX_ROWS rows (a workgroup per row): more rows (up to DECODE_WIDE_MAX_ROWS) run as
+    one call per chunk of up to 16 rows on row slices, so a row's bits are those of the 16-row call.  Returns ([(first row, rows,
+    workspace offset)], workspace bytes: the sum of the chunks')"""
+    if R <= DECODE_MAX_ROWS or R > DECODE_WIDE_MAX_ROWS:      # (one chunk, or too many rows: the library's own size and refusal)
+        nbytes = ws_bytes(R)
+        check(min(nbytes, 0), what)
+        return [(0, R, 0)], nbytes
+    chunks, off = [], 0
+    for r0 in range(0, R, DECODE_MAX_ROWS):
+        rn = min(DECODE_MAX_ROWS, R - r0)
+        nbytes = ws_bytes(rn)
+        check(min(nbytes, 0), what)
+        chunks.append((r0, rn, off))
+        off += (nbytes + 63) & ~63
+    return chunks, off
+
+
 def llasa_head_plan(norm, w1, b1, w2, b2, wa, ba, R, eps, device, frames=1):
     """The descriptor, workspace and output buffers of the frame head for R rows.  The seven arguments are the PARAMETERS (final
     RMSNorm weight [D], distribution_linear[0] weight [dl, D] / bias, distribution_linear[2] weight [dl, dl] / bias, audio_linear
@@ -955,11 +1010,10 @@ def llasa_head_plan(norm, w1, b1, w2, b2, wa, ba, R, eps, device, frames=1):
     lib = _lib.load()
     dl, D = w1.shape
     assert tuple(w2.shape) == (dl, dl) and tuple(wa.shape) == (D, dl) and norm.shape[0] == D
-    nbytes = lib.kalle_llasa_head_ws_bytes(R, D, dl)
-    check(min(nbytes, 0), "kalle_llasa_head_ws_bytes")
+    chunks, nbytes = _head_chunks(lambda rn: lib.kalle_llasa_head_ws_bytes(rn, D, dl), R, "kalle_llasa_head_ws_bytes")
     f32 = dict(device=device, dtype=torch.float32)
     return {"params": (norm, w1, b1, w2, b2, wa, ba), "desc": _lib.LlasaHead(), "keep": None, "R": R, "D": D, "dl": dl,
-            "eps": float(eps), "frames": frames, "ws": torch.empty(nbytes, device=device, dtype=torch.uint8),
+            "chunks": chunks, "eps": float(eps), "frames": frames, "ws": torch.empty(nbytes, device=device, dtype=torch.uint8),
             "mean": torch.zeros((R, dl), **f32), "latent": torch.zeros((frames, R, dl), **f32),
             "kl": torch.zeros((frames, R), **f32), "x_next": torch.zeros((R, D), **f32)}
 
@@ -979,7 +1033,14 @@ def _head_call(plan, h, noise, lat, lds, active, frame):
         setattr(desc, f, t.data_ptr())
     desc.ldw1, desc.ldw2, desc.ldwa = lds
     plan["keep"] = keep
-    return desc, None if active is None else ctypes.cast(_i32([1 if a else 0 for a in active]), ctypes.c_void_p)
+    # per chunk of up to 16 rows: (first row, rows, workspace, that chunk's active flags or None); of SEVERAL chunks one with no
+    # active row is left out (a single chunk is always called, as it was before there were chunks)
+    calls, single = [], len(plan["chunks"]) == 1
+    for r0, rn, off in plan["chunks"]:
+        act = None if active is None else [1 if a else 0 for a in active[r0:r0 + rn]]
+        if single or act is None or any(act):
+            calls.append((r0, rn, plan["ws"][off:], None if act is None else ctypes.cast(_i32(act), ctypes.c_void_p)))
+    return desc, calls
 
 
 def llasa_frame_head(plan, h, noise, std, active=None, frame=0):
@@ -988,11 +1049,13 @@ def llasa_frame_head(plan, h, noise, std, active=None, frame=0):
     (mean [R, dl], latent [R, dl], kl [R], x_next [R, D]): views of the plan's buffers, latent and kl those of slot `frame`."""
     lib = _lib.load()
     R, D, dl = plan["R"], plan["D"], plan["dl"]
-    desc, act = _head_call(plan, h, noise, dl, (D, dl, dl), active, frame)
+    desc, calls = _head_call(plan, h, noise, dl, (D, dl, dl), active, frame)
     latent, kl = plan["latent"][frame], plan["kl"][frame]
-    check(lib.kalle_llasa_frame_head_rows(ctypes.addressof(desc), _p(h), h.stride(0), _p(noise), noise.stride(0), float(std),
-                                          plan["eps"], _p(plan["mean"]), _p(latent), _p(kl), _p(plan["x_next"]), act, R, D, dl,
-                                          _p(plan["ws"]), _stream()), "kalle_llasa_frame_head_rows")
+    for r0, rn, ws, act in calls:
+        check(lib.kalle_llasa_frame_head_rows(ctypes.addressof(desc), _p(h[r0:]), h.stride(0), _p(noise[r0:]), noise.stride(0),
+                                              float(std), plan["eps"], _p(plan["mean"][r0:]), _p(latent[r0:]), _p(kl[r0:]),
+                                              _p(plan["x_next"][r0:]), act, rn, D, dl, _p(ws), _stream()),
+              "kalle_llasa_frame_head_rows")
     return plan["mean"], latent, kl, plan["x_next"]
 
 
@@ -1009,11 +1072,10 @@ def llasa_head2_plan(norm, w1, b1, w2, b2, wa, ba, R, eps, device, frames=1):
     d2, D = w1.shape
     lat = d2 // 2
     assert d2 == 2 * lat and tuple(w2.shape) == (d2, d2) and tuple(wa.shape) == (D, lat) and norm.shape[0] == D
-    nbytes = lib.kalle_llasa_head2_ws_bytes(R, D, lat)
-    check(min(nbytes, 0), "kalle_llasa_head2_ws_bytes")
+    chunks, nbytes = _head_chunks(lambda rn: lib.kalle_llasa_head2_ws_bytes(rn, D, lat), R, "kalle_llasa_head2_ws_bytes")
     f32 = dict(device=device, dtype=torch.float32)
     return {"params": (norm, w1, b1, w2, b2, wa, ba), "desc": _lib.LlasaHead(), "keep": None, "R": R, "D": D, "lat": lat,
-            "eps": float(eps), "frames": frames, "ws": torch.empty(nbytes, device=device, dtype=torch.uint8),
+            "chunks": chunks, "eps": float(eps), "frames": frames, "ws": torch.empty(nbytes, device=device, dtype=torch.uint8),
             "disp": torch.zeros((frames, R, d2), **f32), "latent": torch.zeros((frames, R, lat), **f32),
             "kl": torch.zeros((frames, R), **f32), "x_next": torch.zeros((R, D), **f32)}
 
@@ -1024,11 +1086,12 @@ def llasa_frame_head2(plan, h, noise, active=None, frame=0):
     (disp [R, 2 lat], latent [R, lat], kl [R], x_next [R, D]): views of the plan's buffers, the first three those of slot `frame`."""
     lib = _lib.load()
     R, D, lat = plan["R"], plan["D"], plan["lat"]
-    desc, act = _head_call(plan, h, noise, lat, (D, 2 * lat, lat), active, frame)
+    desc, calls = _head_call(plan, h, noise, lat, (D, 2 * lat, lat), active, frame)
     disp, latent, kl = plan["disp"][frame], plan["latent"][frame], plan["kl"][frame]
-    check(lib.kalle_llasa_frame_head2_rows(ctypes.addressof(desc), _p(h), h.stride(0), _p(noise), noise.stride(0), plan["eps"],
-                                           _p(disp), _p(latent), _p(kl), _p(plan["x_next"]), act, R, D, lat, _p(plan["ws"]),
-                                           _stream()), "kalle_llasa_frame_head2_rows")
+    for r0, rn, ws, act in calls:
+        check(lib.kalle_llasa_frame_head2_rows(ctypes.addressof(desc), _p(h[r0:]), h.stride(0), _p(noise[r0:]), noise.stride(0),
+                                               plan["eps"], _p(disp[r0:]), _p(latent[r0:]), _p(kl[r0:]), _p(plan["x_next"][r0:]),
+                                               act, rn, D, lat, _p(ws), _stream()), "kalle_llasa_frame_head2_rows")
     return disp, latent, kl, plan["x_next"]
 
 

@@ -8,6 +8,9 @@ Llama-3.2-3B shape  --hidden 3072 --layers 28 --heads 24 --kv-heads 8 --head-dim
 --device-head: after the host-head lines, the same KV-cached generation with device_head=True (the per-frame head as one call of
 kalle_llasa_frame_head_rows) in the same process, each line with its ratio to the host-head line; --stop-lag N (0 or 1): one more
 set of lines with stop_lag=N
+--infer-batch R accepts up to 64 rows (above 16: infer_batch(rows=R), the wide decode step).
+--wide-list [--refill] [--device-head]: INSTEAD of the lines above, 64 prompts x 200 frames through infer_batch with rows=16, 32 and
+64 in one process, three repeats each (min - max, ms per step, the acceptance comparison of DESIGN.md 5.16).
 --infer-batch R --refill [--utterances N]: INSTEAD of the lines above, N (default 64) prompts with per-prompt frame caps drawn in
 50 .. 250 (random.Random(0), printed; the stop threshold off) through infer_batch(refill=False) and infer_batch(refill=True) in one
 process, alternating, three repeats each, for every head selected: aggregate frames/s of both (min - max), the measured gain next
@@ -65,8 +68,13 @@ if "--stop-lag" in sys.argv:
 REFILL = "--refill" in sys.argv               # --infer-batch R --refill [--utterances N]: infer_batch(refill=True) against the groups
 if REFILL:
     sys.argv.remove("--refill")
-    if not INFER_BATCH:
-        sys.exit("--refill belongs to --infer-batch R")
+    if not INFER_BATCH and "--wide-list" not in sys.argv:
+        sys.exit("--refill belongs to --infer-batch R or --wide-list")
+WIDE_LIST = "--wide-list" in sys.argv         # --wide-list [--refill]: 64 prompts x 200 frames with rows=16 / 32 / 64 in ONE process
+if WIDE_LIST:
+    sys.argv.remove("--wide-list")
+    if "--infer-only" not in sys.argv and "--infer" not in sys.argv:
+        sys.argv.append("--infer-only")
 UTTERANCES = 64
 if "--utterances" in sys.argv:
     _i = sys.argv.index("--utterances")
@@ -215,6 +223,43 @@ elif not INFER_ONLY:
         f"{B*L/12.5/dt:.0f} audio-s/s (12.5 Hz frames), {fl/dt/1e12:.0f} TFLOP/s algorithmic, params {nparam/1e9:.2f} B, "
         f"loss {out['audio_loss'].item():.3f}")
 
+if WIDE_LIST:
+    # the wide step's acceptance measurement: UTTERANCES prompts of 64 / 56 / 48 / 40 tokens, 200 frames each (no early stop), the
+    # whole infer_batch call timed, rows = 16 / 32 / 64 in one process, three repeats each with the order rotating; grouped, and
+    # with --refill also refill=True.  Accepted: min of the wide repeats above max of the 16-row repeats, in aggregate frames/s.
+    m.eval()
+    nfr = 200
+    prompts = [(torch.randint(0, 128264, (64 - 8 * (r % 4),), device=dev), None) for r in range(UTTERANCES)]
+    ROWS = (16, 32, 64)
+
+    def run(rows, refill, kw, frames=nfr):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        outs = m.infer_batch(prompts, end_disp_kl_thres=-1.0, max_length=frames, refill=refill, rows=rows, **kw)
+        torch.cuda.synchronize()
+        assert len(outs) == UTTERANCES and all(o.shape[2] == frames - 1 for o in outs)
+        return time.perf_counter() - t
+
+    for label, kw in HEADS:
+        for refill in ((False, True) if REFILL else (False,)):
+            for rows in ROWS:
+                run(rows, refill, kw, frames=4)
+            dts = {rows: [] for rows in ROWS}
+            for rep in range(3):
+                for rows in ROWS[rep:] + ROWS[:rep]:
+                    dts[rows].append(run(rows, refill, kw))
+            fps = {rows: sorted(UTTERANCES * nfr / dt for dt in v) for rows, v in dts.items()}
+            steps = {rows: -(-UTTERANCES // rows) * nfr for rows in ROWS}
+            mode = "refill" if refill else "grouped"
+            for rows in ROWS:
+                print(f"wide list [{label}, {mode}] rows={rows}: {fps[rows][0]:.0f} - {fps[rows][-1]:.0f} frames/s aggregate (min - max of 3), "
+                      f"{min(dts[rows]) / steps[rows] * 1e3:.3f} - {max(dts[rows]) / steps[rows] * 1e3:.3f} ms/step incl. prefill")
+            ok = all(fps[rows][0] > fps[16][-1] for rows in (32, 64))
+            print(f"wide list [{label}, {mode}]: min(rows=32) {fps[32][0]:.0f}, min(rows=64) {fps[64][0]:.0f} against max(rows=16) "
+                  f"{fps[16][-1]:.0f} frames/s: {'ACCEPTED' if ok else 'NOT accepted'}; rows=64 / rows=16 x "
+                  f"{fps[64][0] / fps[16][-1]:.2f} - x {fps[64][-1] / fps[16][0]:.2f}")
+    sys.exit(0)
+
 if REFILL:
     # a ragged list through both modes of infer_batch in ONE process: UTTERANCES prompts of 64 / 56 / 48 / 40 tokens on R rows,
     # per-prompt frame caps from a seeded draw in 50 .. 250 (the stop threshold off, so the caps alone decide the lengths)
@@ -224,6 +269,7 @@ if REFILL:
     if DECODE_WEIGHTS:
         m.quantize_decoder(DECODE_WEIGHTS)
     R = m.infer_batch_rows = INFER_BATCH
+    ROWS_KW = dict(rows=R) if R > 16 else {}               # (above 16 rows: the wide step, asked for per call)
     rng = random.Random(0)
     caps = [rng.randint(50, 250) for _ in range(UTTERANCES)]
     prompts = [(torch.randint(0, 128264, (64 - 8 * (r % 4),), device=dev), None) for r in range(UTTERANCES)]
@@ -235,7 +281,7 @@ if REFILL:
     def run(refill, kw):
         torch.cuda.synchronize()
         t = time.perf_counter()
-        outs = m.infer_batch(prompts, end_disp_kl_thres=-1.0, max_length=caps, refill=refill, **kw)
+        outs = m.infer_batch(prompts, end_disp_kl_thres=-1.0, max_length=caps, refill=refill, **ROWS_KW, **kw)
         torch.cuda.synchronize()
         assert [o.shape[2] for o in outs] == [n - 1 for n in caps]
         return time.perf_counter() - t
@@ -311,7 +357,9 @@ if INFER_BATCH:
     m.infer_batch_rows = max(m.infer_batch_rows, INFER_BATCH)
     nfr = 200
     prompts = [(torch.randint(0, 128264, (64 - 8 * (r % 4),), device=dev), None) for r in range(INFER_BATCH)]
+    ROWS_KW = dict(rows=INFER_BATCH) if INFER_BATCH > 16 else {}       # (above 16 rows: the wide step, asked for per call)
     for label, kw in HEADS:
+        kw = dict(kw, **ROWS_KW)
         m.infer_batch(prompts, end_disp_kl_thres=-1.0, max_length=4, **kw)
         for rep in range(3):
             torch.cuda.synchronize()
@@ -320,9 +368,9 @@ if INFER_BATCH:
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
             R = len(outs)
-            tag = "" if not kw else f" [{label}: {host_dt/dt:.3f} x the host head's last repeat]"
+            tag = "" if label == "host head" else f" [{label}: {host_dt/dt:.3f} x the host head's last repeat]"
             print(f"infer_batch R={R} (repeat {rep}): {nfr} frames x {R} rows in {dt*1e3:.0f} ms = {dt/nfr*1e3:.3f} ms/step incl. prefill, "
                   f"{R*nfr/dt:.1f} frames/s aggregate, {nfr/dt:.1f} frames/s per row, "
                   f"{R*nfr/dt/one_fps:.2f} x {R} sequential infer calls ({one_fps:.1f} frames/s), out {tuple(outs[0].shape)}{tag}")
-        if not kw:
+        if label == "host head":
             host_dt = dt

@@ -3,7 +3,9 @@ over launches captured into a HIP graph: python tools/skinny_gemm_bench.py [M]
 --decode [R ...]: the eight decoder GEMMs of a KV-cached step (Llama-3.2-1B / 3B shapes) instead - gemv_kernel against
 gemv_e4m3_kernel, and gemm_rows_kernel against gemm_rows_e4m3_kernel at each R (default 1 8 16) - fp32 output, no residual, the
 weights rotating through > 600 MB of copies so that no call finds them in a cache; per kernel the median of 5 runs (min - max)
-in microseconds and the TB/s of weight bytes"""
+in microseconds and the TB/s of weight bytes
+--decode-wide: those GEMMs at 16 rows (gemm_rows_kernel), 32 and 64 rows (gemm_rows_wide_kernel) and, for comparison, ops.gemm at
+64 rows"""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from kalle_audio_amd import ops, _lib
@@ -60,6 +62,52 @@ def decode_bench(rows):
         del ws, qs
 
 
+def decode_wide_bench():
+    """--decode-wide: the same eight GEMMs through kalle_gemm_rows_fused at R = 16 and kalle_gemm_rows_wide at R = 32 and 64, and
+    - for comparison only, it is not wired into the decode step - the training GEMM's few-rows plan (ops.gemm) at 64 rows.  Per
+    kernel the median of 5 runs (min - max) in microseconds, the TB/s of weight bytes, and the time of four 16-row calls over
+    the 64-row call.  KALLE_LIB_PATH selects the build, so two tile rules can be compared on one box."""
+    shapes = [("1B q|k|v", 3072, 2048), ("1B o", 2048, 2048), ("1B up|gate", 16384, 2048), ("1B down", 2048, 8192),
+              ("3B q|k|v", 5120, 3072), ("3B o", 3072, 3072), ("3B up|gate", 16384, 3072), ("3B down", 3072, 8192)]
+    for name, n, k in shapes:
+        copies = 300 * 2 ** 20 // (n * k) + 2              # > 600 MB of bf16 copies
+        ws = [(torch.randn(n, k, device=dev) / k ** 0.5).bfloat16() for _ in range(copies)]
+        cols, med = [], {}
+        for R, fn in ((16, ops.gemm_rows), (32, ops.gemm_rows_wide), (64, ops.gemm_rows_wide), (-64, ops.gemm)):
+            xr = torch.randn(abs(R), k, device=dev).bfloat16()
+            kw = {} if R > 0 else dict(out_dtype=torch.float32)
+            med[R], lo, hi = _timed([lambda w=w: fn(xr, w, **kw) for w in ws])
+            what = f"rows R={R}" if R == 16 else f"wide R={R}" if R > 0 else "ops.gemm M=64"
+            cols.append(f"{what} {med[R]:5.1f} ({lo:.1f} - {hi:.1f}) us {n * k * 2 / med[R] / 1e6:4.1f} TB/s")
+        print(f"{name:10s} {n} x {k}: " + " | ".join(cols) + f" | 4 x rows16 / wide64 x {4 * med[16] / med[64]:.2f}", flush=True)
+        del ws
+
+
+def _timed(fns):
+    """decode_bench's `timed`: one pass through the rotating copies captured into a HIP graph, median / min / max of 5 replays"""
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        for f in fns[:2]:
+            f()
+        side.synchronize()
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr, stream=side):
+            for f in fns:
+                f()
+    gr.replay()
+    torch.cuda.synchronize()
+    runs = []
+    for _ in range(5):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        gr.replay()
+        e1.record()
+        torch.cuda.synchronize()
+        runs.append(e0.elapsed_time(e1) * 1e3 / len(fns))
+    runs.sort()
+    return runs[2], runs[0], runs[-1]
+
+
 def _gemv(x, w):
     lib = _lib.load()
     y = torch.empty(w.shape[0], device=dev)
@@ -68,6 +116,9 @@ def _gemv(x, w):
     return y
 
 
+if "--decode-wide" in sys.argv:
+    decode_wide_bench()
+    sys.exit(0)
 if "--decode" in sys.argv:
     decode_bench([int(a) for a in sys.argv[sys.argv.index("--decode") + 1:]] or [1, 8, 16])
     sys.exit(0)
