@@ -377,7 +377,7 @@ int kalle_attention_bwd_hd(const void* q, int64_t ldq, int q_off, const void* k,
  * cached keys (model_sigmaVAE.py:122-146 re-runs `self.base_model.model(inputs_embeds=...)` over the prefix for every frame; with a
  * cache only this row is new).  q: [B][ldq], out: [B][ldo], lse: [B][H] or NULL, k / v / key_mask / tables as above.
  * It is kalle_attention_fwd_hd with causal = 1 and Nq = 1, and one family more (attn_fwd_decode128 in csrc/attention.hip):
- *   head_dim 64:  exactly that call, bit for bit (attn_decode_kernel<rot>, rot in {0, 32, 64})
+ *   head_dim 64:  exactly that call, bit for bit (attn_decode_kernel<rot, AttnParams>, rot in {0, 32, 64})
  *   head_dim 128: rot = 128 only (attn_decode128_kernel: vector-ALU scoring with two lanes per key, block softmax over the scores
  *                 in LDS, P V with 16 lanes per key row; bf16 rounding of the rotated q / k and of the probabilities as in the tiled
  *                 kernel, so the two agree to the rounding of fp32 sums)
@@ -394,9 +394,9 @@ int kalle_attention_decode_hd(const void* q, int64_t ldq, int q_off, const void*
  * inside it; out: [R][ldo], lse: [R][H] or NULL.  nk is a HOST array of R ints, copied into the kernel's parameter block (as the
  * `layers` of kalle_llama_decode_step are read on the host): no device read-back, no copy.  nk[r] <= 0: row r is INACTIVE -
  * nothing of it is read (q, cache, tables) and nothing written (out, lse).  Cache rows >= nk[r] and table rows >= max(nk) are
- * never read.  The kernels are the per-row launch forms of attn_decode_kernel<rot> (head_dim 64, rot 64 or 0) and
- * attn_decode128_kernel<128> (head_dim 128, rot 128): the same statements, so the same arithmetic and rounding points; the LDS
- * score array is sized by max(nk).
+ * never read.  The kernels are attn_decode_kernel<rot, AttnRowsParams> (head_dim 64, rot 64 or 0) and
+ * attn_decode128_kernel<128, AttnRowsParams> (head_dim 128, rot 128): the templates of kalle_attention_decode_hd instantiated for
+ * per-row lengths, so the same statements, arithmetic and rounding points; the LDS score array is sized by max(nk).
  * KALLE_ERR_ARG, nothing launched: R outside 1 .. KALLE_DECODE_MAX_ROWS, max(nk) > KALLE_ATTN_DECODE_MAX_KEYS (there is no tiled
  * fallback with per-row lengths), kv_row_stride negative or not a multiple of 8, rot 32 (attn_rot_exists), and whatever
  * kalle_attention_decode_hd refuses at Nk = max(max(nk), 1).  Every row inactive: KALLE_OK, nothing launched (plan word 0) -
@@ -450,7 +450,7 @@ int kalle_attention_bwd_varlen(const void* q, int64_t ldq, int q_off, const void
  *              (attn_bwd_fused_gqa_kernel; attn_bwd_fused_gqa, asked after 4: head dim 64, not causal, rot 0, Nq <= 128,
  *              max(Nk - 128, 0) <= min(16, 128 - Nq)), 6 fwd_decode_128 (attn_decode128_kernel; attn_fwd_decode128:
  *              kalle_attention_decode_hd at head dim 128, Nk <= KALLE_ATTN_DECODE_MAX_KEYS; a forward family: bit 4 is 0),
- *              7 fwd_decode_rows (attn_decode_rows_kernel / attn_decode128_rows_kernel: kalle_attention_decode_rows; a forward
+ *              7 fwd_decode_rows (attn_decode_kernel / attn_decode128_kernel on AttnRowsParams: kalle_attention_decode_rows; a forward
  *              family, head dim and ROT in their fields), 8 fwd_varlen (attn_fwd_kernel<1, dh, VARLEN>: kalle_attention_fwd_varlen),
  *              9 bwd_varlen (attn_bwd_kernel<KV, 1, dh, VARLEN>, dQ + delta then dK / dV: kalle_attention_bwd_varlen; bit 4 is 1):
  *              words 8 | dh << 8 and 9 | 16 | dh << 8

@@ -22,6 +22,7 @@
 
 #include <cstddef>
 #include <cstring>
+#include <type_traits>
 
 namespace {
 
@@ -311,7 +312,7 @@ enum { PLAN_FWD_TILED = 1, PLAN_FWD_DECODE = 2, PLAN_BWD_TWO_PASS = 3, PLAN_BWD_
 inline bool attn_decode_fits(int Nk) { return Nk <= KALLE_ATTN_DECODE_MAX_KEYS; }
 inline bool attn_head_dim_exists(AttnEntry e, int dh) { return dh == 64 || dh == 128 || (dh == 32 && e <= ENTRY_BWD); }
 // ROT instantiations: the tile kernels and attn_decode_kernel up to the head dim; kalle_attention_decode_hd at head dim 128 asks
-// for attn_decode128_kernel<128> at every Nk; the rows kernels exist at 0 and 64 (head dim 64) and 128 (head dim 128)
+// for attn_decode128_kernel<128> at every Nk; the AttnRowsParams instantiations exist at 0 and 64 (head dim 64) and 128 (head dim 128)
 inline bool attn_rot_exists(AttnEntry e, int dh, int rot) {
     if (rot != 0 && rot != 32 && rot != 64 && rot != 128) return false;
     if (e == ENTRY_ROWS) return dh == 128 ? rot == 128 : rot == 0 || rot == 64;
@@ -1404,131 +1405,33 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_fused_gqa_kernel(AttnParams p
 // to the key from its row index), block softmax over the scores in LDS, then P.V with 8 threads per key row (16-byte
 // loads of v) and a shuffle + LDS reduction over the 32 key groups.  Operands are rounded to bf16 at the same points as
 // the tiled kernel (rotated q / k, probabilities) so both paths agree to rounding of the fp32 sums.
-// (attn_decode_body below is a copy of these statements for per-row lengths: a change here belongs there too.)
-template <int ROT>
-__global__ __launch_bounds__(256) void attn_decode_kernel(AttnParams p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* sc = reinterpret_cast<float*>(smem);  // [Nk] scores, then probabilities
-    __shared__ float qs[64];
-    __shared__ float red[8];
-    __shared__ float osum[4][64];
-    constexpr int HALF = ROT / 2;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int h = blockIdx.x, b = blockIdx.y;
-    const int hk = h / (p.H / p.Hkv);
-    const bf16_t* qsrc = p.q + (int64_t)b * p.ldq + p.q_off + h * 64;
-    const bf16_t* ksrc = p.k + (int64_t)b * p.Nk * p.ldk + p.k_off + hk * 64;
-    const bf16_t* vsrc = p.v + (int64_t)b * p.Nk * p.ldv + p.v_off + hk * 64;
-    auto rnd = [](float x) { return bf16_to_f32(f32_to_bf16(x)); };
-
-    if (tid < 64) {
-        float x = bf16_to_f32(qsrc[tid]);
-        if constexpr (ROT > 0) {
-            if (tid < ROT) {
-                const bool lo = tid < HALF;
-                const float partner = bf16_to_f32(qsrc[lo ? tid + HALF : tid - HALF]);
-                const int i = lo ? tid : tid - HALF;
-                const float c = p.cosT[(int64_t)p.qpos * HALF + i], sn = p.sinT[(int64_t)p.qpos * HALF + i];
-                x = rnd(x * c + (lo ? -partner : partner) * sn);
-            }
-        }
-        qs[tid] = x;
-    }
-    __syncthreads();
-
-    float mx = NEG_BIG;
-    for (int j = tid; j < p.Nk; j += 256) {
-        const bf16_t* kp = ksrc + (int64_t)j * p.ldk;
-        float kf[64];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            const i32x4 w = reinterpret_cast<const i32x4*>(kp)[c];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                kf[8 * c + 2 * e] = bf16lo((uint32_t)w[e]);
-                kf[8 * c + 2 * e + 1] = bf16hi((uint32_t)w[e]);
-            }
-        }
-        if constexpr (ROT > 0) {
-            const float* cp = p.cosT + (int64_t)j * HALF;
-            const float* sp = p.sinT + (int64_t)j * HALF;
-#pragma unroll
-            for (int i4 = 0; i4 < HALF / 4; ++i4) {
-                const f32x4 c = reinterpret_cast<const f32x4*>(cp)[i4], sn = reinterpret_cast<const f32x4*>(sp)[i4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int i = 4 * i4 + e;
-                    const float a = kf[i], bb = kf[i + HALF];
-                    kf[i] = rnd(a * c[e] - bb * sn[e]);
-                    kf[i + HALF] = rnd(bb * c[e] + a * sn[e]);
-                }
-            }
-        }
-        float a0 = 0.f, a1 = 0.f;
-#pragma unroll
-        for (int d = 0; d < 64; d += 2) { a0 += kf[d] * qs[d]; a1 += kf[d + 1] * qs[d + 1]; }
-        float sv = (a0 + a1) * SM_SCALE;
-        if (p.mask && !p.mask[(int64_t)b * p.Nk + j]) sv = NEG_BIG;
-        sc[j] = sv;
-        mx = fmaxf(mx, sv);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-    if (lane == 0) red[wave] = mx;
-    __syncthreads();
-    const float m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    float ls = 0.f;
-    for (int j = tid; j < p.Nk; j += 256) {
-        const float pv = __expf(sc[j] - m);
-        ls += pv;
-        sc[j] = rnd(pv);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) ls += __shfl_xor(ls, o, 64);
-    if (lane == 0) red[4 + wave] = ls;
-    __syncthreads();
-    const float l = red[4] + red[5] + red[6] + red[7];
-
-    const int kg = tid >> 3, d8 = tid & 7;
-    float acc[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc[e] = 0.f;
-#pragma unroll 4
-    for (int j = kg; j < p.Nk; j += 32) {
-        const i32x4 w = *reinterpret_cast<const i32x4*>(vsrc + (int64_t)j * p.ldv + 8 * d8);
-        const float pj = sc[j];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            acc[2 * e] += pj * bf16lo((uint32_t)w[e]);
-            acc[2 * e + 1] += pj * bf16hi((uint32_t)w[e]);
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        acc[e] += __shfl_xor(acc[e], 8, 64);
-        acc[e] += __shfl_xor(acc[e], 16, 64);
-        acc[e] += __shfl_xor(acc[e], 32, 64);
-    }
-    if (lane < 8) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) osum[wave][8 * lane + e] = acc[e];
-    }
-    __syncthreads();
-    if (tid < 64) {
-        const float o = (osum[0][tid] + osum[1][tid] + osum[2][tid] + osum[3][tid]) / l;
-        p.out[(int64_t)b * p.ldo + h * 64 + tid] = f32_to_bf16(o);
-        if (tid == 0 && p.lse) p.lse[(int64_t)b * p.H + h] = m + __logf(l);
-    }
-}
-
-// ---- the same kernel with per-row lengths (batched decoding) -------------------------------------------------------------------
-// attn_decode_kernel's statements with the key count, the query position and the cache base of batch row b = blockIdx.y as
-// arguments (Nk, qpos, kbase, vbase) instead of p.Nk, p.qpos and b * p.Nk rows; p.mask is NULL here.  A COPY, not a shared body:
-// routing attn_decode_kernel through this function changed its instruction stream (same source statements, another schedule:
-// 1144 -> 1068 lines at ROT 64), and the one-row decode path keeps the code it was measured with.  Keep the two in step.
-template <int ROT>
-__device__ __forceinline__ void attn_decode_body(const AttnParams& p, const int b, const int Nk, const int qpos,
-                                                 const bf16_t* kbase, const bf16_t* vbase) {
+//
+// The parameter type KP picks the entry point; what differs is set up once at the top of the kernel:
+//   AttnParams (kalle_attention_decode_hd / _fwd_hd): p.Nk keys for every row, the query at p.qpos, row b's keys and values at
+//     b * Nk rows of ldk / ldv elements; p.mask may be set.
+//   AttnRowsParams (kalle_attention_decode_rows, batched decoding): row b has nk[b] keys in its own cache at b * kv_row_stride
+//     elements and its query at rotary position nk[b] - 1; nk[b] <= 0: the row is inactive, its workgroups leave before the first
+//     barrier and before reading or writing anything.  nk travels in the kernel's parameter block (a host array at the C ABI): no
+//     device read-back, no copy.  p.Nk / p.qpos are not used and p.mask is NULL.
+// The statements stand in the __global__ template itself: as a __device__ function called from two kernels they compile the
+// one-row instantiations to another schedule.
+constexpr int DECODE_MAX_ROWS = KALLE_DECODE_MAX_ROWS;
+struct AttnRowsParams {
+    AttnParams p;
+    int64_t kv_row_stride;
+    int nk[DECODE_MAX_ROWS];
+};
+__device__ __forceinline__ const AttnParams& attn_params(const AttnParams& p) { return p; }
+__device__ __forceinline__ const AttnParams& attn_params(const AttnRowsParams& rp) { return rp.p; }
+template <int ROT, class KP>
+__global__ __launch_bounds__(256) void attn_decode_kernel(KP ap) {
+    constexpr bool ROWS = std::is_same_v<KP, AttnRowsParams>;
+    const AttnParams& p = attn_params(ap);
+    const int b = blockIdx.y;
+    int Nk, qpos;
+    int64_t krow0, vrow0;                         // row b's first key / value, in elements from p.k / p.v
+    if constexpr (ROWS) { Nk = ap.nk[b]; if (Nk <= 0) return; qpos = Nk - 1; krow0 = vrow0 = (int64_t)b * ap.kv_row_stride; }
+    else { Nk = ap.Nk; qpos = ap.qpos; krow0 = (int64_t)b * Nk * p.ldk; vrow0 = (int64_t)b * Nk * p.ldv; }
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* sc = reinterpret_cast<float*>(smem);  // [Nk] scores, then probabilities
     __shared__ float qs[64];
@@ -1539,8 +1442,8 @@ __device__ __forceinline__ void attn_decode_body(const AttnParams& p, const int 
     const int h = blockIdx.x;
     const int hk = h / (p.H / p.Hkv);
     const bf16_t* qsrc = p.q + (int64_t)b * p.ldq + p.q_off + h * 64;
-    const bf16_t* ksrc = kbase + p.k_off + hk * 64;
-    const bf16_t* vsrc = vbase + p.v_off + hk * 64;
+    const bf16_t* ksrc = p.k + krow0 + p.k_off + hk * 64;
+    const bf16_t* vsrc = p.v + vrow0 + p.v_off + hk * 64;
     auto rnd = [](float x) { return bf16_to_f32(f32_to_bf16(x)); };
 
     if (tid < 64) {
@@ -1642,22 +1545,6 @@ __device__ __forceinline__ void attn_decode_body(const AttnParams& p, const int 
         if (tid == 0 && p.lse) p.lse[(int64_t)b * p.H + h] = m + __logf(l);
     }
 }
-// Batched decoding: row b has nk[b] keys in its own cache at b * kv_row_stride elements and its query at rotary position
-// nk[b] - 1; nk[b] <= 0: the row is inactive, its workgroups leave before reading or writing anything.  nk travels in the
-// kernel's parameter block (a host array at the C ABI): no device read-back, no copy.  p.Nk / p.qpos / p.mask are not used.
-constexpr int DECODE_MAX_ROWS = KALLE_DECODE_MAX_ROWS;
-struct AttnRowsParams {
-    AttnParams p;
-    int64_t kv_row_stride;
-    int nk[DECODE_MAX_ROWS];
-};
-template <int ROT>
-__global__ __launch_bounds__(256) void attn_decode_rows_kernel(AttnRowsParams rp) {
-    const int b = blockIdx.y;
-    const int Nk = rp.nk[b];
-    if (Nk <= 0) return;
-    attn_decode_body<ROT>(rp.p, b, Nk, Nk - 1, rp.p.k + b * rp.kv_row_stride, rp.p.v + b * rp.kv_row_stride);
-}
 
 // ---- single-query attention at head dim 128 (Llama decoders with 128-wide heads, rotary over the whole head) ------------------
 // Same shape as attn_decode_kernel: a workgroup per (head, batch), scores on the vector ALUs, block softmax over the scores in
@@ -1676,135 +1563,18 @@ __global__ __launch_bounds__(256) void attn_decode_rows_kernel(AttnRowsParams rp
 // reduced over the 4 row groups of a wave by shuffles and over the waves through LDS.
 // What bounds it: one workgroup per head streams the head's whole K and V (512 B per key) with 8 loads per lane in flight -
 // latency, not bandwidth; at the decode shapes (24 - 32 heads on 256 CUs) the GEMVs around it own the step.
-// (attn_decode128_body below is a copy of these statements for per-row lengths: a change here belongs there too.)
+// KP as for attn_decode_kernel: one row count for all rows (AttnParams) or per-row lengths and caches (AttnRowsParams).
 constexpr int DECODE128_KB = 128, DECODE128_PV_GROUPS = 16;
-template <int ROT>
-__global__ __launch_bounds__(256) void attn_decode128_kernel(AttnParams p) {
+template <int ROT, class KP>
+__global__ __launch_bounds__(256) void attn_decode128_kernel(KP ap) {
     static_assert(ROT == 128, "rotary over the whole head: the only caller");
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* sc = reinterpret_cast<float*>(smem);  // [Nk] scores, then probabilities
-    __shared__ __attribute__((aligned(16))) float qs[128];
-    __shared__ float red[8];
-    __shared__ float osum[4][128];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int h = blockIdx.x, b = blockIdx.y;
-    const int hk = h / (p.H / p.Hkv);
-    const bf16_t* qsrc = p.q + (int64_t)b * p.ldq + p.q_off + h * 128;
-    const bf16_t* ksrc = p.k + (int64_t)b * p.Nk * p.ldk + p.k_off + hk * 128;
-    const bf16_t* vsrc = p.v + (int64_t)b * p.Nk * p.ldv + p.v_off + hk * 128;
-    auto rnd = [](float x) { return bf16_to_f32(f32_to_bf16(x)); };
-
-    if (tid < 128) {
-        const bool lo = tid < 64;
-        const float x = bf16_to_f32(qsrc[tid]), partner = bf16_to_f32(qsrc[tid ^ 64]);
-        const float c = p.cosT[(int64_t)p.qpos * 64 + (tid & 63)], sn = p.sinT[(int64_t)p.qpos * 64 + (tid & 63)];
-        qs[tid] = rnd(x * c + (lo ? -partner : partner) * sn);
-    }
-    __syncthreads();
-    const int half = tid & 1;                     // this lane's dims: [32 half, +32) and [64 + 32 half, +32)
-    float qa[32], qb[32];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        const f32x4 a = reinterpret_cast<const f32x4*>(qs + 32 * half)[c], bb = reinterpret_cast<const f32x4*>(qs + 64 + 32 * half)[c];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { qa[4 * c + e] = a[e]; qb[4 * c + e] = bb[e]; }
-    }
-
-    float mx = NEG_BIG;
-    for (int j0 = 0; j0 < p.Nk; j0 += DECODE128_KB) {
-        const int j = j0 + (tid >> 1);
-        float part = 0.f;
-        if (j < p.Nk) {
-            const bf16_t* kp = ksrc + (int64_t)j * p.ldk + 32 * half;
-            float ka[32], kb[32];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const i32x4 wa = reinterpret_cast<const i32x4*>(kp)[c], wb = reinterpret_cast<const i32x4*>(kp + 64)[c];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    ka[8 * c + 2 * e] = bf16lo((uint32_t)wa[e]);
-                    ka[8 * c + 2 * e + 1] = bf16hi((uint32_t)wa[e]);
-                    kb[8 * c + 2 * e] = bf16lo((uint32_t)wb[e]);
-                    kb[8 * c + 2 * e + 1] = bf16hi((uint32_t)wb[e]);
-                }
-            }
-            const float* cp = p.cosT + (int64_t)j * 64 + 32 * half;
-            const float* sp = p.sinT + (int64_t)j * 64 + 32 * half;
-            float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-#pragma unroll
-            for (int i4 = 0; i4 < 8; ++i4) {
-                const f32x4 c = reinterpret_cast<const f32x4*>(cp)[i4], sn = reinterpret_cast<const f32x4*>(sp)[i4];
-#pragma unroll
-                for (int e = 0; e < 4; e += 2) {
-                    const int i = 4 * i4 + e;
-                    a0 += rnd(ka[i] * c[e] - kb[i] * sn[e]) * qa[i];
-                    a1 += rnd(ka[i + 1] * c[e + 1] - kb[i + 1] * sn[e + 1]) * qa[i + 1];
-                    a2 += rnd(kb[i] * c[e] + ka[i] * sn[e]) * qb[i];
-                    a3 += rnd(kb[i + 1] * c[e + 1] + ka[i + 1] * sn[e + 1]) * qb[i + 1];
-                }
-            }
-            part = (a0 + a1) + (a2 + a3);
-        }
-        float sv = (part + __shfl_xor(part, 1, 64)) * Hd<128>::SCALE;      // (both lanes of the pair: the same sum)
-        if (j < p.Nk) {
-            if (p.mask && !p.mask[(int64_t)b * p.Nk + j]) sv = NEG_BIG;
-            if (half == 0) sc[j] = sv;
-            mx = fmaxf(mx, sv);
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-    if (lane == 0) red[wave] = mx;
-    __syncthreads();
-    const float m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    float ls = 0.f;
-    for (int j = tid; j < p.Nk; j += 256) {
-        const float pv = __expf(sc[j] - m);
-        ls += pv;
-        sc[j] = rnd(pv);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) ls += __shfl_xor(ls, o, 64);
-    if (lane == 0) red[4 + wave] = ls;
-    __syncthreads();
-    const float l = red[4] + red[5] + red[6] + red[7];
-
-    const int kg = tid >> 4, d16 = tid & 15;
-    float acc[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc[e] = 0.f;
-#pragma unroll 4
-    for (int j = kg; j < p.Nk; j += DECODE128_PV_GROUPS) {
-        const i32x4 w = *reinterpret_cast<const i32x4*>(vsrc + (int64_t)j * p.ldv + 8 * d16);
-        const float pj = sc[j];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            acc[2 * e] += pj * bf16lo((uint32_t)w[e]);
-            acc[2 * e + 1] += pj * bf16hi((uint32_t)w[e]);
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        acc[e] += __shfl_xor(acc[e], 16, 64);
-        acc[e] += __shfl_xor(acc[e], 32, 64);
-    }
-    if (lane < 16) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) osum[wave][8 * lane + e] = acc[e];
-    }
-    __syncthreads();
-    if (tid < 128) {
-        const float o = (osum[0][tid] + osum[1][tid] + osum[2][tid] + osum[3][tid]) / l;
-        p.out[(int64_t)b * p.ldo + h * 128 + tid] = f32_to_bf16(o);
-        if (tid == 0 && p.lse) p.lse[(int64_t)b * p.H + h] = m + __logf(l);
-    }
-}
-
-// (attn_decode128_kernel with per-row lengths: a copy for the same reason as attn_decode_body)
-template <int ROT>
-__device__ __forceinline__ void attn_decode128_body(const AttnParams& p, const int b, const int Nk, const int qpos,
-                                                    const bf16_t* kbase, const bf16_t* vbase) {
-    static_assert(ROT == 128, "rotary over the whole head: the only caller");
+    constexpr bool ROWS = std::is_same_v<KP, AttnRowsParams>;
+    const AttnParams& p = attn_params(ap);
+    const int b = blockIdx.y;
+    int Nk, qpos;
+    int64_t krow0, vrow0;                         // row b's first key / value, in elements from p.k / p.v
+    if constexpr (ROWS) { Nk = ap.nk[b]; if (Nk <= 0) return; qpos = Nk - 1; krow0 = vrow0 = (int64_t)b * ap.kv_row_stride; }
+    else { Nk = ap.Nk; qpos = ap.qpos; krow0 = (int64_t)b * Nk * p.ldk; vrow0 = (int64_t)b * Nk * p.ldv; }
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* sc = reinterpret_cast<float*>(smem);  // [Nk] scores, then probabilities
     __shared__ __attribute__((aligned(16))) float qs[128];
@@ -1814,8 +1584,8 @@ __device__ __forceinline__ void attn_decode128_body(const AttnParams& p, const i
     const int h = blockIdx.x;
     const int hk = h / (p.H / p.Hkv);
     const bf16_t* qsrc = p.q + (int64_t)b * p.ldq + p.q_off + h * 128;
-    const bf16_t* ksrc = kbase + p.k_off + hk * 128;
-    const bf16_t* vsrc = vbase + p.v_off + hk * 128;
+    const bf16_t* ksrc = p.k + krow0 + p.k_off + hk * 128;
+    const bf16_t* vsrc = p.v + vrow0 + p.v_off + hk * 128;
     auto rnd = [](float x) { return bf16_to_f32(f32_to_bf16(x)); };
 
     if (tid < 128) {
@@ -1922,13 +1692,6 @@ __device__ __forceinline__ void attn_decode128_body(const AttnParams& p, const i
         p.out[(int64_t)b * p.ldo + h * 128 + tid] = f32_to_bf16(o);
         if (tid == 0 && p.lse) p.lse[(int64_t)b * p.H + h] = m + __logf(l);
     }
-}
-template <int ROT>
-__global__ __launch_bounds__(256) void attn_decode128_rows_kernel(AttnRowsParams rp) {
-    const int b = blockIdx.y;
-    const int Nk = rp.nk[b];
-    if (Nk <= 0) return;
-    attn_decode128_body<ROT>(rp.p, b, Nk, Nk - 1, rp.p.k + b * rp.kv_row_stride, rp.p.v + b * rp.kv_row_stride);
 }
 
 // ================================================================================================ host: plan, launch, query
@@ -2047,7 +1810,7 @@ __forceinline__ int plan_attention(AttnEntry e, AttnArgs a, AttnRowsParams& rp, 
     case PLAN_BWD_FUSED_GQA: set_launch(g, 1, p.Hkv, p.B, 512, LDS_BWD_FUSED); break;
     default:                                                    // the single-query kernels: a workgroup per (head, row), [Nk] fp32 scores
         set_launch(g, p.H, p.B, 1, 256, a.Nk * 4);
-        if (family != PLAN_FWD_DECODE) p.stamps = nullptr;      // (as ever: attn_decode128_kernel and the rows kernels get none)
+        p.stamps = nullptr;                                     // (no single-query kernel writes stamps)
     }
     if (rows) {                                                 // the key counts travel per row: p.Nk / p.qpos / p.mask are not used
         p.Nk = p.qpos = 0;
@@ -2084,13 +1847,13 @@ int launch_attention(const AttnPlan& g, const AttnRowsParams& rp, hipStream_t st
     case ATTN_KERNEL(PLAN_FWD_TILED, 32): launch_one<attn_fwd_kernel<1, 32>>(g, 0, st, p); break;
     case ATTN_KERNEL(PLAN_FWD_TILED, 64): launch_one<attn_fwd_kernel<1, 64>>(g, 0, st, p); break;
     case ATTN_KERNEL(PLAN_FWD_TILED, 128): launch_one<attn_fwd_kernel<1, 128>>(g, 0, st, p); break;
-    case ATTN_KERNEL(PLAN_FWD_DECODE, 0): launch_one<attn_decode_kernel<0>>(g, 0, st, p); break;
-    case ATTN_KERNEL(PLAN_FWD_DECODE, 32): launch_one<attn_decode_kernel<32>>(g, 0, st, p); break;
-    case ATTN_KERNEL(PLAN_FWD_DECODE, 64): launch_one<attn_decode_kernel<64>>(g, 0, st, p); break;
-    case ATTN_KERNEL(PLAN_FWD_DECODE_128, 128): launch_one<attn_decode128_kernel<128>>(g, 0, st, p); break;
-    case ATTN_KERNEL(PLAN_FWD_DECODE_ROWS, 0): launch_one<attn_decode_rows_kernel<0>>(g, 0, st, rp); break;
-    case ATTN_KERNEL(PLAN_FWD_DECODE_ROWS, 64): launch_one<attn_decode_rows_kernel<64>>(g, 0, st, rp); break;
-    case ATTN_KERNEL(PLAN_FWD_DECODE_ROWS, 128): launch_one<attn_decode128_rows_kernel<128>>(g, 0, st, rp); break;
+    case ATTN_KERNEL(PLAN_FWD_DECODE, 0): launch_one<attn_decode_kernel<0, AttnParams>>(g, 0, st, p); break;
+    case ATTN_KERNEL(PLAN_FWD_DECODE, 32): launch_one<attn_decode_kernel<32, AttnParams>>(g, 0, st, p); break;
+    case ATTN_KERNEL(PLAN_FWD_DECODE, 64): launch_one<attn_decode_kernel<64, AttnParams>>(g, 0, st, p); break;
+    case ATTN_KERNEL(PLAN_FWD_DECODE_128, 128): launch_one<attn_decode128_kernel<128, AttnParams>>(g, 0, st, p); break;
+    case ATTN_KERNEL(PLAN_FWD_DECODE_ROWS, 0): launch_one<attn_decode_kernel<0, AttnRowsParams>>(g, 0, st, rp); break;
+    case ATTN_KERNEL(PLAN_FWD_DECODE_ROWS, 64): launch_one<attn_decode_kernel<64, AttnRowsParams>>(g, 0, st, rp); break;
+    case ATTN_KERNEL(PLAN_FWD_DECODE_ROWS, 128): launch_one<attn_decode128_kernel<128, AttnRowsParams>>(g, 0, st, rp); break;
     case ATTN_KERNEL(PLAN_BWD_TWO_PASS, 32):
         launch_one<attn_bwd_kernel<false, 1, 32>>(g, 0, st, p); launch_one<attn_bwd_kernel<true, 1, 32>>(g, 1, st, p); break;
     case ATTN_KERNEL(PLAN_BWD_TWO_PASS, 64):
