@@ -735,7 +735,7 @@ int kalle_llama_decode_step_hd(const kalle_llama_layer* layers, int n_layers, co
  * a decode step reads every decoder weight once and does one multiply-add per weight read, so R rows per step share that stream.
  *
  * Skinny GEMM: Y[r][n] = sum_k W[n][k] X[r][k] (+ residual[r][n]) for R rows; W bf16 [N][ldw] is read from HBM once for all rows
- * (gemm_rows_kernel: 8 weight rows per workgroup below N = 8192 and 16 from there - as many workgroups as kalle_gemv_bf16 has or
+ * (gemm_rows_kernel<YF32, TR, 1>: 8 weight rows per workgroup below N = 8192 and 16 from there - as many workgroups as kalle_gemv_bf16 has or
  * more - x 16 batch columns of v_mfma_f32_16x16x32_bf16, the unused columns zero, the four waves splitting K; fp32 accumulation,
  * order unspecified but fixed).  X bf16 [R][ldx], Y bf16 or fp32 [R][ldy], residual
  * fp32 [R][ldres] or NULL.  K % 8 == 0, ldx % 8 == 0, ldw % 8 == 0, K <= 32768 (as kalle_gemv_bf16), 1 <= R <= 16. */
@@ -781,11 +781,11 @@ int kalle_llama_decode_step_rows(const kalle_llama_layer* layers, int n_layers, 
  * forms serve 1 <= R <= 64 rows with the arguments, the meaning and the refusals of the _rows forms above (the bound on R at
  * 64): inactive rows (active[r] == 0 / t0[r] < 0) are neither read nor written, the second destination goes through y2_off,
  * every refusal comes before the first HIP call, every launch is checked where it is made.  Up to 16 rows they forward to
- * the _rows forms.  Above, the projections run in gemm_rows_wide_kernel (one weight-chunk load feeds ceil(R / 16) MFMAs, one per
- * block of 16 batch rows; 16 weight rows per workgroup from N = 3072, 8 below) after the pre-pass, and the step runs
+ * the _rows forms.  Above, the projections run in the same gemm_rows_kernel template at NCB = ceil(R / 16) column blocks (one
+ * weight-chunk load feeds NCB MFMAs, one per block of 16 batch rows; 16 weight rows per workgroup from N = 3072, 8 below) after the pre-pass, and the step runs
  * kalle_attention_decode_rows once per chunk of 16 rows that has an active row (kalle_attn_last_plan: the last chunk launched).
  * A ROW'S BITS ARE THOSE OF THE 16-ROW PATH: for one (weight row, batch row) pair the accumulation walks K in
- * gemm_rows_kernel's order, so y, the caches and every workspace region of row r equal what the _rows form writes for a group
+ * the order of the NCB = 1 instantiation, so y, the caches and every workspace region of row r equal what the _rows form writes for a group
  * of up to 16 rows that holds r, whatever R, the row's index or the other rows.
  * Workspace: the published _rows layout at that R (kalle_llama_decode_ws_bytes_wide bytes).
  * Not served, KALLE_ERR_ARG: e4m3 layers (there is no _wide_w8 form), R > 64, head dim 32. */

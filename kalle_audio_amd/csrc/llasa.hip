@@ -32,6 +32,55 @@ __global__ __launch_bounds__(256) void axpby_kernel(const float* __restrict__ x,
 // Rows >= nsplit go to y2 (the k | v part of the fused qkv projection lands directly in its KV-cache row).
 enum { PRO_BF16 = 0, PRO_RMS = 1, PRO_SWIGLU = 2 };
 
+// The bf16 operand row xs[K] of a projection, built by the NT threads of a workgroup from xin (PRO_BF16: a copy).  The one
+// routine behind the GEMVs (into LDS) and the R-row pre-pass (into xhat): one set of expressions, so one set of rounding points.
+// The caller puts the barrier between these stores and its reads.
+template <int PRO, int NT>
+__device__ __forceinline__ void x_prologue(const void* __restrict__ xin, const float* __restrict__ gamma, float eps, bf16_t* xs,
+                                           int K) {
+    if constexpr (PRO == PRO_BF16) {
+        const bf16_t* x = static_cast<const bf16_t*>(xin);
+        for (int i = threadIdx.x; i < (K >> 3); i += NT)
+            reinterpret_cast<i32x4*>(xs)[i] = reinterpret_cast<const i32x4*>(x)[i];
+    } else if constexpr (PRO == PRO_RMS) {
+        __shared__ float red[NT / 64];
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        const float* x = static_cast<const float*>(xin);
+        float q = 0.f;
+        for (int i = threadIdx.x; i < (K >> 2); i += NT) {
+            const f32x4 v = reinterpret_cast<const f32x4*>(x)[i];
+            q += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
+        }
+        q = wave_sum(q);
+        if (lane == 0) red[wave] = q;
+        __syncthreads();
+        float ss = red[0];
+#pragma unroll
+        for (int w = 1; w < NT / 64; ++w) ss += red[w];
+        const float rr = rsqrtf(ss / (float)K + eps);
+        for (int i = threadIdx.x; i < (K >> 2); i += NT) {
+            const f32x4 v = reinterpret_cast<const f32x4*>(x)[i];
+            const f32x4 g = reinterpret_cast<const f32x4*>(gamma)[i];
+            i32x2 o;
+            o[0] = (int)pack_bf16x2(v[0] * (g[0] * rr), v[1] * (g[1] * rr));
+            o[1] = (int)pack_bf16x2(v[2] * (g[2] * rr), v[3] * (g[3] * rr));
+            reinterpret_cast<i32x2*>(xs)[i] = o;
+        }
+    } else {
+        const bf16_t* h = static_cast<const bf16_t*>(xin);
+        for (int i = threadIdx.x; i < (K >> 3); i += NT) {
+            const i32x4 xv = reinterpret_cast<const i32x4*>(h)[i];
+            const i32x4 gv = reinterpret_cast<const i32x4*>(h + K)[i];
+            i32x4 o;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                o[j] = (int)pack_bf16x2(bf16lo((uint32_t)xv[j]) * siluf_(bf16lo((uint32_t)gv[j])),
+                                        bf16hi((uint32_t)xv[j]) * siluf_(bf16hi((uint32_t)gv[j])));
+            reinterpret_cast<i32x4*>(xs)[i] = o;
+        }
+    }
+}
+
 template <bool YF32, int PRO>
 __global__ __launch_bounds__(256) void gemv_kernel(const void* __restrict__ xin, const float* __restrict__ gamma, float eps,
                                                    const bf16_t* __restrict__ W, int64_t ldw, void* __restrict__ y,
@@ -61,43 +110,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(const void* __restrict__ xin,
     };
     i32x4 u[PF], v[PF];
     load(0, 0, u, v);
-    if constexpr (PRO == PRO_BF16) {
-        const bf16_t* x = static_cast<const bf16_t*>(xin);
-        for (int i = threadIdx.x; i < (K >> 3); i += 256)
-            reinterpret_cast<i32x4*>(xs)[i] = reinterpret_cast<const i32x4*>(x)[i];
-    } else if constexpr (PRO == PRO_RMS) {
-        __shared__ float red[4];
-        const float* x = static_cast<const float*>(xin);
-        float q = 0.f;
-        for (int i = threadIdx.x; i < (K >> 2); i += 256) {
-            const f32x4 v = reinterpret_cast<const f32x4*>(x)[i];
-            q += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
-        }
-        q = wave_sum(q);
-        if (lane == 0) red[wave] = q;
-        __syncthreads();
-        const float rr = rsqrtf((red[0] + red[1] + red[2] + red[3]) / (float)K + eps);
-        for (int i = threadIdx.x; i < (K >> 2); i += 256) {
-            const f32x4 v = reinterpret_cast<const f32x4*>(x)[i];
-            const f32x4 g = reinterpret_cast<const f32x4*>(gamma)[i];
-            i32x2 o;
-            o[0] = (int)pack_bf16x2(v[0] * (g[0] * rr), v[1] * (g[1] * rr));
-            o[1] = (int)pack_bf16x2(v[2] * (g[2] * rr), v[3] * (g[3] * rr));
-            reinterpret_cast<i32x2*>(xs)[i] = o;
-        }
-    } else {
-        const bf16_t* h = static_cast<const bf16_t*>(xin);
-        for (int i = threadIdx.x; i < (K >> 3); i += 256) {
-            const i32x4 xv = reinterpret_cast<const i32x4*>(h)[i];
-            const i32x4 gv = reinterpret_cast<const i32x4*>(h + K)[i];
-            i32x4 o;
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                o[j] = (int)pack_bf16x2(bf16lo((uint32_t)xv[j]) * siluf_(bf16lo((uint32_t)gv[j])),
-                                        bf16hi((uint32_t)xv[j]) * siluf_(bf16hi((uint32_t)gv[j])));
-            reinterpret_cast<i32x4*>(xs)[i] = o;
-        }
-    }
+    x_prologue<PRO, 256>(xin, gamma, eps, xs, K);
     __syncthreads();
     float a0 = 0.f, a1 = 0.f;
     int pr = 0, bb = 0;
@@ -147,176 +160,115 @@ __global__ __launch_bounds__(256) void gemv_kernel(const void* __restrict__ xin,
     }
 }
 
-// ---- R-row GEMM for batched decoding: Y[r][n] = sum_k W[n][k] X[r][k] (+ residual[r][n]), 1 <= R <= 16 -------------------------
+// ---- R-row GEMM for batched decoding: Y[r][n] = sum_k W[n][k] X[r][k] (+ residual[r][n]), 1 <= R <= 64 -------------------------
 // Still pure weight streaming: W is read from HBM once for all rows.  A workgroup owns TR weight rows and every row of the batch:
-// v_mfma_f32_16x16x32_bf16 with the weight rows on the M side and the batch on the 16-wide N side, rows >= R or inactive held
-// at zero.  TR = 8 for N < 8192 (the upper M half of the tile stays zero: the MFMA is idle anyway) and 16 from there, so the
-// grid is N / 8 workgroups where the one-row kernel has N / 8 (every decoder GEMM but up|gate: 256 - 640 workgroups at the 1B / 3B
-// shapes on 256 CUs) and N / 16 where it has N / 16 or N / 32.  The dot product over k does not care which k a lane supplies
-// as long as A and B agree, so lane (row i, group g) supplies the SAME 16-byte chunk of weight row i (A) and of batch row i (B)
-// to an MFMA: both operands come straight from global memory in the layout the instruction wants, and X needs no LDS at any
-// K (16 rows x 32768 x 2 B would be 1 MiB against the CU's 160 KiB).  One load instruction covers 64 contiguous bytes of each
-// weight row (the four groups side by side), eight consecutive ones a 512-byte run.  X is R x K x 2 bytes out of L2 per
-// workgroup.  The four waves take every fourth 256-element K block and their partial tiles meet in LDS (4 KiB), summed in a
-// fixed order; thread t then owns output (row t / TR, column t % TR).  Loads of the next K block are issued before the MFMAs
-// of the current one.
+// v_mfma_f32_16x16x32_bf16 with the weight rows on the M side and the batch on the 16-wide N side in NCB = ceil(R / 16) column
+// blocks, rows >= R or inactive held at zero.  The dot product over k does not care which k a lane supplies as long as A and B
+// agree, so lane (row i, group g) supplies the SAME 16-byte chunk of weight row i (A) and of batch rows i, 16 + i, ... (B, one
+// per column block): the weight chunk a lane loaded feeds NCB MFMAs, both operands come straight from global memory in the
+// layout the instruction wants, and X needs no LDS at any K (16 rows x 32768 x 2 B would be 1 MiB against the CU's 160 KiB).
+// One load instruction covers 64 contiguous bytes of each weight row (the four groups side by side), eight consecutive ones a
+// 512-byte run.  X is R x K x 2 bytes out of L2 per workgroup.
+// Accumulation, per (weight row, batch row) pair and whatever R, TR, NCB, the row's index or the other rows (an MFMA output
+// element depends on its own row of A and column of B only): wave w takes the 256-element K blocks w, w + 4, ..., the eight
+// chunks of a block go through one accumulator in order, and the four waves' partial tiles meet in LDS (4 KiB per column
+// block) as (p0 + p1) + (p2 + p3) in rows_output.  So a row's bits are the same at every R.
+// Schedule: the loads of the next unit are issued before the MFMAs of the current one.  Up to 16 rows (NCB = 1) the unit is a
+// whole K block (8 weight + 8 X chunk registers, twice: 202 VGPRs as compiled); above, HALF a block (4 weight + 4 NCB X, twice:
+// 136 / 172 - 176 / 212 - 216 VGPRs at NCB = 2 / 3 / 4), where whole blocks double-buffered would need about 320 by count.
+// Tile: up to 16 rows TR = 8 for N < 8192 (the upper M half of the tile stays zero: the MFMA is idle anyway) and 16 from there,
+// so the grid is N / 8 workgroups where the one-row kernel has N / 8 (every decoder GEMM but up|gate: 256 - 640 workgroups at
+// the 1B / 3B shapes on 256 CUs) and N / 16 where it has N / 16 or N / 32; above 16 rows wide_tile_rows below.
 // The RMSNorm / SwiGLU prologues cannot be rebuilt per workgroup here the way the one-row kernel does it: each of the N / 8
 // or N / 16 workgroups would re-read R x K fp32 from L2 (qkv at the 3B shape: 640 x 192 KiB = 120 MiB against 31 MiB of weights) and redo
-// R row norms.  rows_prologue_kernel writes the bf16 operand once per GEMM instead (R x K x 2 bytes, one short launch), with the
-// one-row kernel's expressions, so the rounding points are the same.
-struct RowsArgs {
-    int64_t y2_off[KALLE_DECODE_MAX_ROWS];   // element offset into y2 of row r's second destination
-    unsigned active;                         // bit r: row r takes part
+// R row norms.  rows_prologue_kernel writes the bf16 operand once per GEMM instead (R x K x 2 bytes, one short launch), through
+// x_prologue like the one-row kernels.
+
+// The rows of a batch as the host keeps them: one form for every R.
+struct RowSet {
+    int64_t y2_off[KALLE_DECODE_WIDE_MAX_ROWS];   // element offset into y2 of row r's second destination
+    uint64_t active;                              // bit r: row r takes part
     int R;
 };
 
-// (MaskT: unsigned for the 16-row path, uint64_t for the wide one - the same expressions either way)
-template <int PRO, class MaskT = unsigned>
+// ... and as a kernel takes them, by value: MAXR = 16 (136 bytes of kernel arguments, a 32-bit mask) or 64 (528, 64-bit)
+template <int MAXR>
+struct RowArgs {
+    static_assert(MAXR == KALLE_DECODE_MAX_ROWS || MAXR == KALLE_DECODE_WIDE_MAX_ROWS, "the two row bounds of the ABI");
+    using Mask = std::conditional_t<(MAXR > 32), uint64_t, unsigned>;
+    int64_t y2_off[MAXR];
+    Mask active;
+    int R;
+    explicit RowArgs(const RowSet& s) : active((Mask)s.active), R(s.R) {      // (s.R <= MAXR: proj_launch picks MAXR by s.R)
+        for (int r = 0; r < MAXR; ++r) y2_off[r] = s.y2_off[r];
+    }
+};
+
+template <int PRO, class MaskT>
 __global__ __launch_bounds__(256) void rows_prologue_kernel(const void* __restrict__ xall, int64_t ldx,
                                                             const float* __restrict__ gamma, float eps,
                                                             bf16_t* __restrict__ xhat, int64_t ldh, int K, MaskT active) {
     static_assert(PRO == PRO_RMS || PRO == PRO_SWIGLU, "PRO_BF16 has no pre-pass");
-    const int r = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int r = blockIdx.x;
     if (!(active >> r & 1)) return;
-    bf16_t* xs = xhat + r * ldh;
-    if constexpr (PRO == PRO_RMS) {
-        __shared__ float red[4];
-        const float* x = static_cast<const float*>(xall) + r * ldx;
-        float q = 0.f;
-        for (int i = threadIdx.x; i < (K >> 2); i += 256) {
-            const f32x4 v = reinterpret_cast<const f32x4*>(x)[i];
-            q += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
-        }
-        q = wave_sum(q);
-        if (lane == 0) red[wave] = q;
-        __syncthreads();
-        const float rr = rsqrtf((red[0] + red[1] + red[2] + red[3]) / (float)K + eps);
-        for (int i = threadIdx.x; i < (K >> 2); i += 256) {
-            const f32x4 v = reinterpret_cast<const f32x4*>(x)[i];
-            const f32x4 g = reinterpret_cast<const f32x4*>(gamma)[i];
-            i32x2 o;
-            o[0] = (int)pack_bf16x2(v[0] * (g[0] * rr), v[1] * (g[1] * rr));
-            o[1] = (int)pack_bf16x2(v[2] * (g[2] * rr), v[3] * (g[3] * rr));
-            reinterpret_cast<i32x2*>(xs)[i] = o;
-        }
-    } else {
-        const bf16_t* h = static_cast<const bf16_t*>(xall) + r * ldx;
-        for (int i = threadIdx.x; i < (K >> 3); i += 256) {
-            const i32x4 xv = reinterpret_cast<const i32x4*>(h)[i];
-            const i32x4 gv = reinterpret_cast<const i32x4*>(h + K)[i];
-            i32x4 o;
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                o[j] = (int)pack_bf16x2(bf16lo((uint32_t)xv[j]) * siluf_(bf16lo((uint32_t)gv[j])),
-                                        bf16hi((uint32_t)xv[j]) * siluf_(bf16hi((uint32_t)gv[j])));
-            reinterpret_cast<i32x4*>(xs)[i] = o;
-        }
-    }
+    if constexpr (PRO == PRO_RMS) x_prologue<PRO, 256>(static_cast<const float*>(xall) + r * ldx, gamma, eps, xhat + r * ldh, K);
+    else x_prologue<PRO, 256>(static_cast<const bf16_t*>(xall) + r * ldx, gamma, eps, xhat + r * ldh, K);
 }
 
-template <bool YF32, int TR>
+// The output stage of the R-row GEMMs, after the barrier behind the waves' partial tiles (lane (i16, g) of column block b wrote
+// weight rows n0 + 4 g + {0 .. 3} of batch row 16 b + i16): thread t owns output (row t / TR, column t % TR), then 256 further.
+// The partials summed in the fixed order, times scale[n] (SCALED: the e4m3 weights), plus the residual; columns >= nsplit go to
+// y2 at the row's y2_off.
+template <bool YF32, int TR, int NCB, bool SCALED, class MaskT>
+__device__ __forceinline__ void rows_output(const float (*part)[NCB][64][4], const float* __restrict__ scale, void* __restrict__ y,
+                                           int64_t ldy, void* __restrict__ y2, int nsplit, const float* __restrict__ res,
+                                           int64_t ldres, int n0, int N, int R, MaskT active, const int64_t* y2_off) {
+    auto store = [&](int idx) {
+        const int r = idx / TR, j = idx % TR, n = n0 + j;
+        if (r < R && (active >> r & 1) && n < N) {
+            const int b = r >> 4, src = (j >> 2) * 16 + (r & 15), e = j & 3;
+            float s = (part[0][b][src][e] + part[1][b][src][e]) + (part[2][b][src][e] + part[3][b][src][e]);
+            if constexpr (SCALED) s *= scale[n];
+            if (res) s += res[r * ldres + n];
+            const int64_t at = n < nsplit ? r * ldy + n : y2_off[r] + (n - nsplit);
+            void* yo = n < nsplit ? y : y2;
+            if constexpr (YF32) static_cast<float*>(yo)[at] = s;
+            else static_cast<bf16_t*>(yo)[at] = f32_to_bf16(s);
+        }
+    };
+    // (one pass needs no bound on idx: R <= 16 NCB rows)
+    if constexpr (16 * NCB * TR <= 256) store(threadIdx.x);
+    else
+        for (int idx = threadIdx.x; idx < 16 * NCB * TR; idx += 256) store(idx);
+}
+
+template <bool YF32, int TR, int NCB>
 __global__ __launch_bounds__(256) void gemm_rows_kernel(const bf16_t* __restrict__ X, int64_t ldx, const bf16_t* __restrict__ W,
                                                         int64_t ldw, void* __restrict__ y, int64_t ldy, void* __restrict__ y2,
                                                         int nsplit, const float* __restrict__ res, int64_t ldres, int N, int K,
-                                                        RowsArgs a) {
+                                                        RowArgs<(NCB == 1 ? KALLE_DECODE_MAX_ROWS : KALLE_DECODE_WIDE_MAX_ROWS)> a) {
     static_assert(TR == 8 || TR == 16, "weight rows per workgroup");
-    __shared__ __attribute__((aligned(16))) float part[4][64][4];
-    constexpr int CH = 8;                         // 16-byte chunks per lane and K block: a block is 8 x 4 groups x 8 = 256 elements
+    static_assert(NCB >= 1 && NCB <= 4, "column blocks of 16 batch rows");
+    __shared__ __attribute__((aligned(16))) float part[4][NCB][64][4];
+    // 16-byte chunks per lane and K block (a block is 8 x 4 groups x 8 = 256 elements) / per pipelined unit; LU = log2(units per block)
+    constexpr int CH = 8, HC = NCB == 1 ? 8 : 4, LU = NCB == 1 ? 0 : 1;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i16 = lane & 15, g = lane >> 4;
     const int n0 = blockIdx.x * TR;
     const bool wrow = TR == 16 || i16 < TR;                   // (TR = 8: M rows 8 .. 15 of the tile stay zero, nothing loaded)
     const int nc = K >> 3, NB = (nc + 4 * CH - 1) / (4 * CH);
-    const bool live = i16 < a.R && (a.active >> i16 & 1);
-    const bf16_t* wr = W + (int64_t)(n0 + i16 < N ? n0 + i16 : N - 1) * ldw;
-    const bf16_t* xr = X + (live ? i16 : 0) * ldx;            // (not read unless live)
-    auto load = [&](int kb, i32x4* wq, i32x4* xq) {
-#pragma unroll
-        for (int j = 0; j < CH; ++j) {
-            const int c = (kb * CH + j) * 4 + g;
-            const bool in = c < nc;
-            const int cc = in ? c : nc - 1;
-            wq[j] = i32x4{0, 0, 0, 0};                        // past K: a zero weight chunk against a chunk of x that exists
-            if (wrow && in) wq[j] = *reinterpret_cast<const i32x4*>(wr + 8 * cc);
-            xq[j] = i32x4{0, 0, 0, 0};
-            if (live) xq[j] = *reinterpret_cast<const i32x4*>(xr + 8 * cc);
-        }
-    };
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    i32x4 wv[CH], xv[CH];
-    int kb = wave;
-    if (kb < NB) load(kb, wv, xv);
-    for (; kb < NB; kb += 4) {
-        i32x4 wn[CH], xn[CH];
-        const bool more = kb + 4 < NB;
-        if (more) load(kb + 4, wn, xn);
-#pragma unroll
-        for (int j = 0; j < CH; ++j)
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wv[j]), __builtin_bit_cast(bf16x8, xv[j]),
-                                                          acc, 0, 0, 0);
-        if (more) {
-#pragma unroll
-            for (int j = 0; j < CH; ++j) { wv[j] = wn[j]; xv[j] = xn[j]; }
-        }
-    }
-    // lane (i16, g) holds weight rows n0 + 4 g + {0 .. 3} of batch row i16
-    *reinterpret_cast<f32x4*>(part[wave][lane]) = acc;
-    __syncthreads();
-    const int r = threadIdx.x / TR, j = threadIdx.x % TR, n = n0 + j;
-    if (r < a.R && (a.active >> r & 1) && n < N) {
-        const int src = (j >> 2) * 16 + r, e = j & 3;
-        float s = (part[0][src][e] + part[1][src][e]) + (part[2][src][e] + part[3][src][e]);
-        if (res) s += res[r * ldres + n];
-        const int64_t at = n < nsplit ? r * ldy + n : a.y2_off[r] + (n - nsplit);
-        void* yo = n < nsplit ? y : y2;
-        if constexpr (YF32) static_cast<float*>(yo)[at] = s;
-        else static_cast<bf16_t*>(yo)[at] = f32_to_bf16(s);
-    }
-}
-
-// ---- the wide form: 17 <= R <= 64 batch rows per weight read ------------------------------------------------------------------------
-// gemm_rows_kernel's lane layout with NCB = ceil(R / 16) column blocks: the 16-byte weight chunk a lane loaded feeds NCB MFMAs,
-// one per block of 16 batch rows, against that lane's chunk of batch rows i16, 16 + i16, ...  For one (weight row, batch row)
-// pair the accumulation is gemm_rows_kernel's, term for term: wave w takes the 256-element K blocks w, w + 4, ..., the eight
-// chunks of a block go through one accumulator in order, the four waves' partials meet as (p0 + p1) + (p2 + p3).  An MFMA
-// output element depends on its own row of A and column of B only, so a row's bits are those of the 16-row kernel whatever R,
-// TR, NCB, the row's index or the other rows.  What differs is the schedule: the pipelined unit is HALF a K block (4 chunks:
-// 16 weight + 16 NCB X registers, twice), so both operands of the next unit are in flight under the MFMAs of the current one:
-// 136 / 172 - 176 / 212 - 216 VGPRs at NCB = 2 / 3 / 4 as compiled, no scratch, where whole blocks double-buffered would need
-// about 320 by count.
-struct WideArgs {
-    int64_t y2_off[KALLE_DECODE_WIDE_MAX_ROWS];
-    uint64_t active;                         // bit r: row r takes part
-    int R;
-};
-
-template <bool YF32, int TR, int NCB>
-__global__ __launch_bounds__(256) void gemm_rows_wide_kernel(const bf16_t* __restrict__ X, int64_t ldx,
-                                                             const bf16_t* __restrict__ W, int64_t ldw, void* __restrict__ y,
-                                                             int64_t ldy, void* __restrict__ y2, int nsplit,
-                                                             const float* __restrict__ res, int64_t ldres, int N, int K,
-                                                             WideArgs a) {
-    static_assert(TR == 8 || TR == 16, "weight rows per workgroup");
-    static_assert(NCB >= 2 && NCB <= 4, "column blocks of 16 batch rows");
-    __shared__ __attribute__((aligned(16))) float part[4][NCB][64][4];
-    constexpr int CH = 8, HC = 4;                 // chunks per lane and K block (as gemm_rows_kernel) / per pipelined unit
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int i16 = lane & 15, g = lane >> 4;
-    const int n0 = blockIdx.x * TR;
-    const bool wrow = TR == 16 || i16 < TR;
-    const int nc = K >> 3, NB = (nc + 4 * CH - 1) / (4 * CH);
-    const bf16_t* wr = W + (int64_t)(n0 + i16 < N ? n0 + i16 : N - 1) * ldw;
+    const int R = a.R;                            // (both read once, here with the other arguments, for the loads and rows_output)
+    const auto active = a.active;
     bool live[NCB];
+#pragma unroll
+    for (int b = 0; b < NCB; ++b) live[b] = 16 * b + i16 < R && (active >> (16 * b + i16) & 1);
+    const bf16_t* wr = W + (int64_t)(n0 + i16 < N ? n0 + i16 : N - 1) * ldw;
     const bf16_t* xr[NCB];
 #pragma unroll
-    for (int b = 0; b < NCB; ++b) {
-        const int r = 16 * b + i16;
-        live[b] = r < a.R && (a.active >> r & 1);
-        xr[b] = X + (live[b] ? r : 0) * ldx;                  // (not read unless live)
-    }
-    // unit u of this wave: half (u & 1) of K block wave + 4 (u >> 1)
+    for (int b = 0; b < NCB; ++b) xr[b] = X + (live[b] ? 16 * b + i16 : 0) * ldx;      // (not read unless live)
+    // unit u of this wave: part (u & (1 << LU) - 1) of K block wave + 4 (u >> LU)
     auto load = [&](int u, i32x4* wq, i32x4 (*xq)[HC]) {
-        const int c0 = ((wave + 4 * (u >> 1)) * CH + (u & 1) * HC) * 4 + g;
+        const int c0 = ((wave + 4 * (u >> LU)) * CH + (u & ((1 << LU) - 1)) * HC) * 4 + g;
 #pragma unroll
         for (int j = 0; j < HC; ++j) {
             const int c = c0 + 4 * j;
@@ -334,7 +286,7 @@ __global__ __launch_bounds__(256) void gemm_rows_wide_kernel(const bf16_t* __res
     f32x4 acc[NCB];
 #pragma unroll
     for (int b = 0; b < NCB; ++b) acc[b] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int NU = wave < NB ? 2 * ((NB - wave + 3) / 4) : 0;
+    const int NU = wave < NB ? ((NB - wave + 3) / 4) << LU : 0;
     i32x4 wv[HC], xv[NCB][HC];
     if (NU) load(0, wv, xv);
     for (int u = 0; u < NU; ++u) {
@@ -356,22 +308,10 @@ __global__ __launch_bounds__(256) void gemm_rows_wide_kernel(const bf16_t* __res
             }
         }
     }
-    // lane (i16, g) of block b holds weight rows n0 + 4 g + {0 .. 3} of batch row 16 b + i16
 #pragma unroll
     for (int b = 0; b < NCB; ++b) *reinterpret_cast<f32x4*>(part[wave][b][lane]) = acc[b];
     __syncthreads();
-    for (int idx = threadIdx.x; idx < 16 * NCB * TR; idx += 256) {
-        const int r = idx / TR, j = idx % TR, n = n0 + j;
-        if (r < a.R && (a.active >> r & 1) && n < N) {
-            const int b = r >> 4, src = (j >> 2) * 16 + (r & 15), e = j & 3;
-            float s = (part[0][b][src][e] + part[1][b][src][e]) + (part[2][b][src][e] + part[3][b][src][e]);
-            if (res) s += res[r * ldres + n];
-            const int64_t at = n < nsplit ? r * ldy + n : a.y2_off[r] + (n - nsplit);
-            void* yo = n < nsplit ? y : y2;
-            if constexpr (YF32) static_cast<float*>(yo)[at] = s;
-            else static_cast<bf16_t*>(yo)[at] = f32_to_bf16(s);
-        }
-    }
+    rows_output<YF32, TR, NCB, false>(part, nullptr, y, ldy, y2, nsplit, res, ldres, n0, N, R, active, a.y2_off);
 }
 
 // ---- weight-only OCP e4m3 decoding: W8 uint8 [N][ldq] codes, scale fp32 [N]; weight (n, k) = scale[n] * e4m3(W8[n][k]) -----------
@@ -436,8 +376,8 @@ __global__ __launch_bounds__(256) void quantize_rows_e4m3_kernel(const bf16_t* _
     }
 }
 
-// gemv_kernel on e4m3 weights: y[n] = scale[n] * sum_k e4m3(W8[n][k]) x[k] (+ residual[n]), the three prologues with the
-// expressions of gemv_kernel (the operand stays bf16 in LDS, rounded at the same points).
+// gemv_kernel on e4m3 weights: y[n] = scale[n] * sum_k e4m3(W8[n][k]) x[k] (+ residual[n]), the three prologues through
+// x_prologue (the operand stays bf16 in LDS).
 // Byte budget: a weight row is K bytes now, so 16 bytes of it hold 16 weights and 64 lanes x 16 bytes cover 1024 of them - at
 // K = 2048 (every Llama-3.2-1B GEMV but down) a row is two loads per lane.  To keep gemv_kernel's 128 bytes per lane in flight
 // (2 rows x 4 x 16 B) a wave owns FOUR rows and issues 2 x 16 B of each per item, one item ahead; a workgroup is two such waves
@@ -473,43 +413,7 @@ __global__ __launch_bounds__(128) void gemv_e4m3_kernel(const void* __restrict__
     };
     i32x4 u[RW][PF];
     load(0, 0, u);
-    if constexpr (PRO == PRO_BF16) {
-        const bf16_t* x = static_cast<const bf16_t*>(xin);
-        for (int i = threadIdx.x; i < (K >> 3); i += 128)
-            reinterpret_cast<i32x4*>(xs)[i] = reinterpret_cast<const i32x4*>(x)[i];
-    } else if constexpr (PRO == PRO_RMS) {
-        __shared__ float red[2];
-        const float* x = static_cast<const float*>(xin);
-        float q = 0.f;
-        for (int i = threadIdx.x; i < (K >> 2); i += 128) {
-            const f32x4 v = reinterpret_cast<const f32x4*>(x)[i];
-            q += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
-        }
-        q = wave_sum(q);
-        if (lane == 0) red[wave] = q;
-        __syncthreads();
-        const float rr = rsqrtf((red[0] + red[1]) / (float)K + eps);
-        for (int i = threadIdx.x; i < (K >> 2); i += 128) {
-            const f32x4 v = reinterpret_cast<const f32x4*>(x)[i];
-            const f32x4 g = reinterpret_cast<const f32x4*>(gamma)[i];
-            i32x2 o;
-            o[0] = (int)pack_bf16x2(v[0] * (g[0] * rr), v[1] * (g[1] * rr));
-            o[1] = (int)pack_bf16x2(v[2] * (g[2] * rr), v[3] * (g[3] * rr));
-            reinterpret_cast<i32x2*>(xs)[i] = o;
-        }
-    } else {
-        const bf16_t* h = static_cast<const bf16_t*>(xin);
-        for (int i = threadIdx.x; i < (K >> 3); i += 128) {
-            const i32x4 xv = reinterpret_cast<const i32x4*>(h)[i];
-            const i32x4 gv = reinterpret_cast<const i32x4*>(h + K)[i];
-            i32x4 o;
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                o[j] = (int)pack_bf16x2(bf16lo((uint32_t)xv[j]) * siluf_(bf16lo((uint32_t)gv[j])),
-                                        bf16hi((uint32_t)xv[j]) * siluf_(bf16hi((uint32_t)gv[j])));
-            reinterpret_cast<i32x4*>(xs)[i] = o;
-        }
-    }
+    x_prologue<PRO, 128>(xin, gamma, eps, xs, K);
     __syncthreads();
     f32x2 a[RW];
 #pragma unroll
@@ -572,22 +476,24 @@ __global__ __launch_bounds__(128) void gemv_e4m3_kernel(const void* __restrict__
 // takes 16 bytes of weight row i - 16 weights, two of the MFMA's K chunks - widens them to bf16 in registers (exact: 4
 // significant bits) and feeds v_mfma_f32_16x16x32_bf16 twice, each time against the 16-byte chunk of batch row i that holds the
 // same k.  The activations stay bf16.  A K block is 256 elements as before: 4 weight loads and 8 x loads per lane.  scale[n] is
-// applied by the thread that owns output (r, n).
+// applied in rows_output by the thread that owns output (r, n).
 template <bool YF32, int TR>
 __global__ __launch_bounds__(256) void gemm_rows_e4m3_kernel(const bf16_t* __restrict__ X, int64_t ldx,
                                                              const uint8_t* __restrict__ W8, int64_t ldq,
                                                              const float* __restrict__ scale, void* __restrict__ y, int64_t ldy,
                                                              void* __restrict__ y2, int nsplit, const float* __restrict__ res,
-                                                             int64_t ldres, int N, int K, RowsArgs a) {
+                                                             int64_t ldres, int N, int K, RowArgs<KALLE_DECODE_MAX_ROWS> a) {
     static_assert(TR == 8 || TR == 16, "weight rows per workgroup");
-    __shared__ __attribute__((aligned(16))) float part[4][64][4];
+    __shared__ __attribute__((aligned(16))) float part[4][1][64][4];
     constexpr int CH = 4;                         // 16-byte weight loads per lane and K block: 4 x 4 groups x 16 = 256 elements
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i16 = lane & 15, g = lane >> 4;
     const int n0 = blockIdx.x * TR;
     const bool wrow = TR == 16 || i16 < TR;
     const int nc = K >> 4, NB = (nc + 4 * CH - 1) / (4 * CH);
-    const bool live = i16 < a.R && (a.active >> i16 & 1);
+    const int R = a.R;
+    const unsigned active = a.active;
+    const bool live = i16 < R && (active >> i16 & 1);
     const uint8_t* wr = W8 + (int64_t)(n0 + i16 < N ? n0 + i16 : N - 1) * ldq;
     const bf16_t* xr = X + (live ? i16 : 0) * ldx;            // (not read unless live)
     auto load = [&](int kb, i32x4* wq, i32x4* xq) {
@@ -638,18 +544,9 @@ __global__ __launch_bounds__(256) void gemm_rows_e4m3_kernel(const bf16_t* __res
             for (int j = 0; j < CH; ++j) { wv[j] = wn[j]; xv[2 * j] = xn[2 * j]; xv[2 * j + 1] = xn[2 * j + 1]; }
         }
     }
-    *reinterpret_cast<f32x4*>(part[wave][lane]) = acc;
+    *reinterpret_cast<f32x4*>(part[wave][0][lane]) = acc;
     __syncthreads();
-    const int r = threadIdx.x / TR, j = threadIdx.x % TR, n = n0 + j;
-    if (r < a.R && (a.active >> r & 1) && n < N) {
-        const int src = (j >> 2) * 16 + r, e = j & 3;
-        float s = scale[n] * ((part[0][src][e] + part[1][src][e]) + (part[2][src][e] + part[3][src][e]));
-        if (res) s += res[r * ldres + n];
-        const int64_t at = n < nsplit ? r * ldy + n : a.y2_off[r] + (n - nsplit);
-        void* yo = n < nsplit ? y : y2;
-        if constexpr (YF32) static_cast<float*>(yo)[at] = s;
-        else static_cast<bf16_t*>(yo)[at] = f32_to_bf16(s);
-    }
+    rows_output<YF32, TR, 1, true>(part, scale, y, ldy, y2, nsplit, res, ldres, n0, N, R, active, a.y2_off);
 }
 
 // ---- the one projection launcher: every GEMV and R-row GEMM of this file, public or inside the decode step, is launched here ---
@@ -659,11 +556,11 @@ struct Proj {
     const float* scale;     // fp32 [N] (e4m3) or NULL (bf16)
 };
 
-// f(std::bool_constant<yf32>, std::integral_constant<int, v>) for the runtime pair; v must be one of Vs
+// f(std::bool_constant<flag>, std::integral_constant<int, v>) for the runtime pair; v must be one of Vs
 template <int... Vs, class F>
-inline void for_instance(bool yf32, int v, F&& f) {
-    auto on = [&](auto yf) { ((v == Vs ? (f(yf, std::integral_constant<int, Vs>{}), 0) : 0), ...); };
-    if (yf32) on(std::true_type{});
+inline void for_instance(bool flag, int v, F&& f) {
+    auto on = [&](auto fl) { ((v == Vs ? (f(fl, std::integral_constant<int, Vs>{}), 0) : 0), ...); };
+    if (flag) on(std::true_type{});
     else on(std::false_type{});
 }
 
@@ -685,47 +582,13 @@ inline int wide_tile_rows(int N) {
 #endif
 }
 
-// the wide R-row GEMM (bf16 weights only): proj_launch's R-row branch with the 64-bit mask and gemm_rows_wide_kernel
-inline int proj_launch_wide(const Proj& P, const void* x, int64_t ldx, int pro, const float* gamma, float eps, bf16_t* xhat,
-                            int64_t ldh, void* y, int64_t ldy, bool yf32, void* y2, int nsplit, const float* res, int64_t ldres,
-                            const WideArgs& a, int N, int K, hipStream_t st) {
-    if (P.scale) return KALLE_ERR_ARG;                       // (there is no wide e4m3 kernel)
-    const bf16_t* Wb = static_cast<const bf16_t*>(P.w);
-    const bf16_t* X = static_cast<const bf16_t*>(x);
-    if (pro != PRO_BF16) {
-        if (pro == PRO_RMS)
-            KALLE_LAUNCH((rows_prologue_kernel<PRO_RMS, uint64_t>), dim3(a.R), dim3(256), 0, st, x, ldx, gamma, eps, xhat, ldh, K,
-                         a.active);
-        else
-            KALLE_LAUNCH((rows_prologue_kernel<PRO_SWIGLU, uint64_t>), dim3(a.R), dim3(256), 0, st, x, ldx, gamma, eps, xhat, ldh,
-                         K, a.active);
-        const int rc = kalle_check_launch();
-        if (rc != KALLE_OK) return rc;
-        X = xhat;
-        ldx = ldh;
-    }
-    const int ncb = (a.R + 15) / 16, tr = wide_tile_rows(N);
-    const dim3 grid((N + tr - 1) / tr), block(256);
-    for_instance<2, 3, 4>(yf32, ncb, [&](auto yf, auto nb) {
-        constexpr bool F = decltype(yf)::value;
-        constexpr int NCB = decltype(nb)::value;
-        if (tr == 16)
-            KALLE_LAUNCH((gemm_rows_wide_kernel<F, 16, NCB>), grid, block, 0, st, X, ldx, Wb, P.ld, y, ldy, y2, nsplit, res, ldres,
-                         N, K, a);
-        else
-            KALLE_LAUNCH((gemm_rows_wide_kernel<F, 8, NCB>), grid, block, 0, st, X, ldx, Wb, P.ld, y, ldy, y2, nsplit, res, ldres,
-                         N, K, a);
-    });
-    return kalle_check_launch();
-}
-
 // y (columns n >= nsplit: y2) = W . pro(x) (+ res); returns the first failed launch.
 // rows == NULL: one row, the prologue built inside the GEMV (ldx, xhat, ldh, ldy, ldres unused).  Otherwise the R-row GEMM: the
-// prologue, if any, as a pre-pass into xhat (row stride ldh), y2 columns of row r at rows->y2_off[r].
+// prologue, if any, as a pre-pass into xhat (row stride ldh), y2 columns of row r at rows->y2_off[r]; up to 16 rows the kernels
+// of either weight format at NCB = 1, above the bf16 kernel at NCB = ceil(R / 16).  The row set becomes a kernel argument here.
 inline int proj_launch(const Proj& P, const void* x, int64_t ldx, int pro, const float* gamma, float eps, bf16_t* xhat,
                        int64_t ldh, void* y, int64_t ldy, bool yf32, void* y2, int nsplit, const float* res, int64_t ldres,
-                       const RowsArgs* rows, int N, int K, hipStream_t st, const WideArgs* wide = nullptr) {
-    if (wide) return proj_launch_wide(P, x, ldx, pro, gamma, eps, xhat, ldh, y, ldy, yf32, y2, nsplit, res, ldres, *wide, N, K, st);
+                       const RowSet* rows, int N, int K, hipStream_t st) {
     const bf16_t* Wb = static_cast<const bf16_t*>(P.w);
     const uint8_t* Wq = static_cast<const uint8_t*>(P.w);
     if (!rows) {
@@ -745,30 +608,50 @@ inline int proj_launch(const Proj& P, const void* x, int64_t ldx, int pro, const
         });
         return kalle_check_launch();
     }
-    const RowsArgs& a = *rows;
+    const int R = rows->R;
+    const bool wide = R > KALLE_DECODE_MAX_ROWS;
+    if (wide && P.scale) return KALLE_ERR_ARG;               // (there is no wide e4m3 kernel)
     const bf16_t* X = static_cast<const bf16_t*>(x);
     if (pro != PRO_BF16) {
-        if (pro == PRO_RMS)
-            KALLE_LAUNCH((rows_prologue_kernel<PRO_RMS>), dim3(a.R), dim3(256), 0, st, x, ldx, gamma, eps, xhat, ldh, K, a.active);
-        else
-            KALLE_LAUNCH((rows_prologue_kernel<PRO_SWIGLU>), dim3(a.R), dim3(256), 0, st, x, ldx, gamma, eps, xhat, ldh, K, a.active);
+        for_instance<PRO_RMS, PRO_SWIGLU>(wide, pro, [&](auto w, auto p) {
+            using MaskT = std::conditional_t<decltype(w)::value, uint64_t, unsigned>;
+            KALLE_LAUNCH((rows_prologue_kernel<decltype(p)::value, MaskT>), dim3(R), dim3(256), 0, st, x, ldx, gamma, eps, xhat, ldh,
+                         K, (MaskT)rows->active);
+        });
         const int rc = kalle_check_launch();
         if (rc != KALLE_OK) return rc;
         X = xhat;
         ldx = ldh;
     }
-    // never fewer workgroups streaming weights than the one-row form has for this N: N / 8 below 8192 rows, N / 16 from there
-    const int tr = N < 8192 ? 8 : 16;
+    // up to 16 rows never fewer workgroups streaming weights than the one-row form has for this N: N / 8 below 8192 rows, N / 16
+    // from there
+    const int tr = wide ? wide_tile_rows(N) : N < 8192 ? 8 : 16;
     const dim3 grid((N + tr - 1) / tr), block(256);
-    for_instance<8, 16>(yf32, tr, [&](auto yf, auto t) {
-        constexpr bool F = decltype(yf)::value;
-        constexpr int TR = decltype(t)::value;
-        if (P.scale)
-            KALLE_LAUNCH((gemm_rows_e4m3_kernel<F, TR>), grid, block, 0, st, X, ldx, Wq, P.ld, P.scale, y, ldy, y2, nsplit, res, ldres,
-                         N, K, a);
-        else
-            KALLE_LAUNCH((gemm_rows_kernel<F, TR>), grid, block, 0, st, X, ldx, Wb, P.ld, y, ldy, y2, nsplit, res, ldres, N, K, a);
-    });
+    if (!wide) {
+        const RowArgs<KALLE_DECODE_MAX_ROWS> a(*rows);
+        for_instance<8, 16>(yf32, tr, [&](auto yf, auto t) {
+            constexpr bool F = decltype(yf)::value;
+            constexpr int TR = decltype(t)::value;
+            if (P.scale)
+                KALLE_LAUNCH((gemm_rows_e4m3_kernel<F, TR>), grid, block, 0, st, X, ldx, Wq, P.ld, P.scale, y, ldy, y2, nsplit, res,
+                             ldres, N, K, a);
+            else
+                KALLE_LAUNCH((gemm_rows_kernel<F, TR, 1>), grid, block, 0, st, X, ldx, Wb, P.ld, y, ldy, y2, nsplit, res, ldres, N, K,
+                             a);
+        });
+    } else {
+        const RowArgs<KALLE_DECODE_WIDE_MAX_ROWS> a(*rows);
+        for_instance<2, 3, 4>(yf32, (R + 15) / 16, [&](auto yf, auto nb) {
+            constexpr bool F = decltype(yf)::value;
+            constexpr int NCB = decltype(nb)::value;
+            if (tr == 16)
+                KALLE_LAUNCH((gemm_rows_kernel<F, 16, NCB>), grid, block, 0, st, X, ldx, Wb, P.ld, y, ldy, y2, nsplit, res, ldres,
+                             N, K, a);
+            else
+                KALLE_LAUNCH((gemm_rows_kernel<F, 8, NCB>), grid, block, 0, st, X, ldx, Wb, P.ld, y, ldy, y2, nsplit, res, ldres, N,
+                             K, a);
+        });
+    }
     return kalle_check_launch();
 }
 
@@ -1259,34 +1142,25 @@ int decode_step(const kalle_llama_layer* lb, const kalle_llama_layer_w8* l8, int
     if (head_dim != 64 && head_dim != 128) return KALLE_ERR_ARG;
     if ((int64_t)H * head_dim > 32768 || inner > 32768) return KALLE_ERR_ARG;
     const int D = H * head_dim, kvw = 2 * Hkv * head_dim, xw = D > inner ? D : inner;
-    RowsArgs a{};
-    WideArgs wa{};                                           // (the wide form's twin of `a`)
-    a.R = wa.R = R;
+    RowSet kvr{};                                            // (second destination: the rows' KV-cache rows)
+    kvr.R = R;
     int32_t nk[KALLE_DECODE_WIDE_MAX_ROWS];
     for (int r = 0; r < R; ++r) {
         // (batched: the attention's LDS score array holds nk <= KALLE_ATTN_DECODE_MAX_KEYS keys; the one-row attention falls back to the tiled kernel)
         if (t0[r] >= cache_rows || (batched ? t0[r] >= KALLE_ATTN_DECODE_MAX_KEYS : t0[r] < 0)) return KALLE_ERR_ARG;
         nk[r] = t0[r] < 0 ? 0 : t0[r] + 1;
-        const int64_t off = t0[r] < 0 ? 0 : ((int64_t)r * cache_rows + t0[r]) * kvw;
-        if (t0[r] >= 0) wa.active |= (uint64_t)1 << r;
-        wa.y2_off[r] = off;
-        if (!is_wide) {
-            if (t0[r] >= 0) a.active |= 1u << r;
-            a.y2_off[r] = off;
-        }
+        if (t0[r] >= 0) kvr.active |= (uint64_t)1 << r;
+        kvr.y2_off[r] = t0[r] < 0 ? 0 : ((int64_t)r * cache_rows + t0[r]) * kvw;
     }
     auto layer = [&](int l) { return lb ? layer_view(lb[l], D, inner) : layer_view(l8[l], D, inner); };
     for (int l = 0; l < n_layers; ++l)
         if (!layer(l).complete(l8 != nullptr)) return KALLE_ERR_ARG;
-    if (!wa.active) return KALLE_OK;
-    RowsArgs plain = a;                                      // (no second destination)
-    WideArgs wplain = wa;
-    for (int r = 0; r < R; ++r) wplain.y2_off[r] = 0;
-    for (int r = 0; r < R && !is_wide; ++r) plain.y2_off[r] = 0;
-    const RowsArgs* rows_kv = batched ? &a : nullptr;
-    const RowsArgs* rows = batched ? &plain : nullptr;
-    const WideArgs* wide_kv = is_wide ? &wa : nullptr;
-    const WideArgs* wide = is_wide ? &wplain : nullptr;
+    if (!kvr.active) return KALLE_OK;
+    RowSet plain{};                                          // (no second destination)
+    plain.active = kvr.active;
+    plain.R = R;
+    const RowSet* rows_kv = batched ? &kvr : nullptr;
+    const RowSet* rows = batched ? &plain : nullptr;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const DecodeWs o = decode_ws(R, H, inner, head_dim);
     char* ws = static_cast<char*>(workspace);
@@ -1305,9 +1179,9 @@ int decode_step(const kalle_llama_layer* lb, const kalle_llama_layer_w8* l8, int
         // (every launch is checked where it is made: KALLE_LAUNCH clears the error state, so a refused launch would otherwise be
         // forgotten by the next one and the step would report success over an unwritten buffer)
         // (nsplit = D is a multiple of 64 at either head dim: a wave's rows never straddle it)
-        void* kv = batched ? L.kv_cache : static_cast<bf16_t*>(L.kv_cache) + a.y2_off[0];
+        void* kv = batched ? L.kv_cache : static_cast<bf16_t*>(L.kv_cache) + kvr.y2_off[0];
         int rc = proj_launch(L.qkv, xin, D, PRO_RMS, L.input_norm, eps, xn, xw, q, D, false, kv, D, nullptr, 0, rows_kv, D + kvw,
-                             D, st, wide_kv);
+                             D, st);
         if (rc != KALLE_OK) return rc;
         if (is_wide) {
             // the per-row attention in chunks of 16 rows: q / ao, the cache, lse and nk offset by the chunk's first row.  A chunk
@@ -1317,7 +1191,7 @@ int decode_step(const kalle_llama_layer* lb, const kalle_llama_layer_w8* l8, int
             int plan = 0;
             for (int r0 = 0; r0 < R && rc == KALLE_OK; r0 += KALLE_DECODE_MAX_ROWS) {
                 const int rn = R - r0 < KALLE_DECODE_MAX_ROWS ? R - r0 : KALLE_DECODE_MAX_ROWS;
-                if (!(wa.active >> r0 & 0xFFFFu)) continue;
+                if (!(kvr.active >> r0 & 0xFFFFu)) continue;
                 rc = kalle_attention_decode_rows(q + (int64_t)r0 * D, D, 0, cache + r0 * kvs, kvw, 0, cache + r0 * kvs, kvw,
                                                  Hkv * head_dim, kvs, ao + (int64_t)r0 * D, D, lse + (int64_t)r0 * H, rope_cos,
                                                  rope_sin, head_dim, nk + r0, rn, H, Hkv, head_dim, stream);
@@ -1333,14 +1207,13 @@ int decode_step(const kalle_llama_layer* lb, const kalle_llama_layer_w8* l8, int
                                            rope_sin, head_dim, nullptr, 1, H, Hkv, nk[0], head_dim, stream);
         }
         if (rc != KALLE_OK) return rc;
-        rc = proj_launch(L.o, ao, D, PRO_BF16, nullptr, 0.f, nullptr, 0, x2, D, true, x2, D, xin, D, rows, D, D, st, wide);
+        rc = proj_launch(L.o, ao, D, PRO_BF16, nullptr, 0.f, nullptr, 0, x2, D, true, x2, D, xin, D, rows, D, D, st);
         if (rc != KALLE_OK) return rc;
         rc = proj_launch(L.ug, x2, D, PRO_RMS, L.post_norm, eps, xn, xw, hf, 2 * inner, false, hf, 2 * inner, nullptr, 0, rows,
-                         2 * inner, D, st, wide);
+                         2 * inner, D, st);
         if (rc != KALLE_OK) return rc;
         float* xo = l + 1 == n_layers ? out : x3;
-        rc = proj_launch(L.down, hf, 2 * inner, PRO_SWIGLU, nullptr, 0.f, xn, xw, xo, D, true, xo, D, x2, D, rows, D, inner, st,
-                         wide);
+        rc = proj_launch(L.down, hf, 2 * inner, PRO_SWIGLU, nullptr, 0.f, xn, xw, xo, D, true, xo, D, x2, D, rows, D, inner, st);
         if (rc != KALLE_OK) return rc;
         xin = xo;
     }
@@ -1414,7 +1287,7 @@ extern "C" int kalle_llama_decode_step(const kalle_llama_layer* layers, int n_la
 }
 
 // ---- the R-row GEMM entry points -------------------------------------------------------------------------------------------------
-// the argument check and the RowsArgs of both weight formats, then the launch.  kalign: 8 (bf16) or 16 (e4m3) weights per 16 bytes.
+// the argument check and the row set of both weight formats, then the launch.  kalign: 8 (bf16) or 16 (e4m3) weights per 16 bytes.
 // (everything but the bound on R, which is the caller's)
 static int gemm_rows_args_ok(int kalign, const void* x, const void* w, int64_t ldw, const void* y, int64_t ldx, int prologue,
                              const float* gamma, const void* xhat, int64_t ldy, int y_dtype, const void* y2, int nsplit,
@@ -1431,14 +1304,15 @@ static int gemm_rows_args_ok(int kalign, const void* x, const void* w, int64_t l
 
 static int gemm_rows_entry(const Proj& P, int kalign, const void* x, int64_t ldx, int prologue, const float* gamma, float eps,
                            void* xhat, void* y, int64_t ldy, int y_dtype, void* y2, int nsplit, const int64_t* y2_off,
-                           const float* residual, int64_t ldres, const int32_t* active, int R, int N, int K, void* stream) {
-    if (R < 1 || R > KALLE_DECODE_MAX_ROWS) return KALLE_ERR_ARG;
+                           const float* residual, int64_t ldres, const int32_t* active, int R, int max_rows, int N, int K,
+                           void* stream) {
+    if (R < 1 || R > max_rows) return KALLE_ERR_ARG;
     const int ok = gemm_rows_args_ok(kalign, x, P.w, P.ld, y, ldx, prologue, gamma, xhat, ldy, y_dtype, y2, nsplit, y2_off, ldres, N, K);
     if (ok != KALLE_OK) return ok;
-    RowsArgs a{};
+    RowSet a{};
     a.R = R;
     for (int r = 0; r < R; ++r) {
-        if (!active || active[r]) a.active |= 1u << r;
+        if (!active || active[r]) a.active |= (uint64_t)1 << r;
         a.y2_off[r] = nsplit < N ? y2_off[r] : 0;
     }
     if (!a.active) return KALLE_OK;
@@ -1451,30 +1325,16 @@ extern "C" int kalle_gemm_rows_fused(const void* x, int64_t ldx, int prologue, c
                                      const int64_t* y2_off, const float* residual, int64_t ldres, const int32_t* active, int R,
                                      int N, int K, void* stream) {
     return gemm_rows_entry({W, ldw, nullptr}, 8, x, ldx, prologue, gamma, eps, xhat, y, ldy, y_dtype, y2, nsplit, y2_off, residual,
-                           ldres, active, R, N, K, stream);
+                           ldres, active, R, KALLE_DECODE_MAX_ROWS, N, K, stream);
 }
 
-// kalle_gemm_rows_fused for up to 64 rows (bf16 weights): its argument check with the bound at 64, then the wide kernel; up to
-// 16 rows it is kalle_gemm_rows_fused
+// kalle_gemm_rows_fused with the bound at 64 rows (bf16 weights): up to 16 rows the same launch, above the NCB >= 2 kernels
 extern "C" int kalle_gemm_rows_wide(const void* x, int64_t ldx, int prologue, const float* gamma, float eps, void* xhat,
                                     const void* W, int64_t ldw, void* y, int64_t ldy, int y_dtype, void* y2, int nsplit,
                                     const int64_t* y2_off, const float* residual, int64_t ldres, const int32_t* active, int R,
                                     int N, int K, void* stream) {
-    if (R <= KALLE_DECODE_MAX_ROWS)
-        return kalle_gemm_rows_fused(x, ldx, prologue, gamma, eps, xhat, W, ldw, y, ldy, y_dtype, y2, nsplit, y2_off, residual,
-                                     ldres, active, R, N, K, stream);
-    if (R > KALLE_DECODE_WIDE_MAX_ROWS) return KALLE_ERR_ARG;
-    const int rc = gemm_rows_args_ok(8, x, W, ldw, y, ldx, prologue, gamma, xhat, ldy, y_dtype, y2, nsplit, y2_off, ldres, N, K);
-    if (rc != KALLE_OK) return rc;
-    WideArgs a{};
-    a.R = R;
-    for (int r = 0; r < R; ++r) {
-        if (!active || active[r]) a.active |= (uint64_t)1 << r;
-        a.y2_off[r] = nsplit < N ? y2_off[r] : 0;
-    }
-    if (!a.active) return KALLE_OK;
-    return proj_launch_wide({W, ldw, nullptr}, x, ldx, prologue, gamma, eps, static_cast<bf16_t*>(xhat), K, y, ldy,
-                            y_dtype == KALLE_F32, y2, nsplit, residual, ldres, a, N, K, static_cast<hipStream_t>(stream));
+    return gemm_rows_entry({W, ldw, nullptr}, 8, x, ldx, prologue, gamma, eps, xhat, y, ldy, y_dtype, y2, nsplit, y2_off, residual,
+                           ldres, active, R, KALLE_DECODE_WIDE_MAX_ROWS, N, K, stream);
 }
 
 extern "C" int kalle_gemm_rows_bf16(const void* x, int64_t ldx, const void* W, int64_t ldw, void* y, int64_t ldy, int y_dtype,
@@ -1489,7 +1349,7 @@ extern "C" int kalle_gemm_rows_fused_e4m3(const void* x, int64_t ldx, int prolog
                                           const int32_t* active, int R, int N, int K, void* stream) {
     if (!scale) return KALLE_ERR_ARG;
     return gemm_rows_entry({W8, ldq, scale}, 16, x, ldx, prologue, gamma, eps, xhat, y, ldy, y_dtype, y2, nsplit, y2_off, residual,
-                           ldres, active, R, N, K, stream);
+                           ldres, active, R, KALLE_DECODE_MAX_ROWS, N, K, stream);
 }
 
 // ---- the per-frame head of KV-cached generation: final norm, distribution_linear, sampling, stop KL, audio_linear ----------------
@@ -1533,10 +1393,10 @@ extern "C" int kalle_llasa_frame_head_rows(const kalle_llasa_head* head, const f
     if ((ldh & 3) || ldh < D || ldn < dl) return KALLE_ERR_ARG;
     if ((head->ldw1 & 7) || head->ldw1 < D || (head->ldw2 & 7) || head->ldw2 < dl || (head->ldwa & 7) || head->ldwa < dl)
         return KALLE_ERR_ARG;
-    RowsArgs a{};
+    RowSet a{};
     a.R = R;
     for (int r = 0; r < R; ++r)
-        if (!active || active[r]) a.active |= 1u << r;
+        if (!active || active[r]) a.active |= (uint64_t)1 << r;
     if (!a.active) return KALLE_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const HeadWs o = head_ws(R, D, dl);
@@ -1554,7 +1414,7 @@ extern "C" int kalle_llasa_frame_head_rows(const kalle_llasa_head* head, const f
     const float c0 = (float)(1.0 - log((double)std));        // log(e / std)
     const float c1 = (float)(0.5 / (M_E * M_E));             // 1 / (2 e^2)
     KALLE_LAUNCH(llasa_head_kernel, dim3(R), dim3(256), 0, st, h1, static_cast<const bf16_t*>(head->w2), head->ldw2, head->b2, noise,
-                 ldn, std, c0, c1, ga, mean, latent, lat, kl, dl, lg, a.active);
+                 ldn, std, c0, c1, ga, mean, latent, lat, kl, dl, lg, (unsigned)a.active);
     rc = kalle_check_launch();
     if (rc != KALLE_OK) return rc;
     return proj_launch({head->wa, head->ldwa, nullptr}, lat, dl, PRO_BF16, nullptr, 0.f, nullptr, 0, x_next, D, true, x_next, D,
@@ -1603,10 +1463,10 @@ extern "C" int kalle_llasa_frame_head2_rows(const kalle_llasa_head* head, const 
     if ((ldh & 3) || ldh < D || ldn < lat) return KALLE_ERR_ARG;
     if ((head->ldw1 & 7) || head->ldw1 < D || (head->ldw2 & 7) || head->ldw2 < d2 || (head->ldwa & 7) || head->ldwa < lat)
         return KALLE_ERR_ARG;
-    RowsArgs a{};
+    RowSet a{};
     a.R = R;
     for (int r = 0; r < R; ++r)
-        if (!active || active[r]) a.active |= 1u << r;
+        if (!active || active[r]) a.active |= (uint64_t)1 << r;
     if (!a.active) return KALLE_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const Head2Ws o = head2_ws(R, D, lat);
@@ -1623,7 +1483,7 @@ extern "C" int kalle_llasa_frame_head2_rows(const kalle_llasa_head* head, const 
     while ((8 << lg) < d2) ++lg;                             // G = 1 << lg lanes per weight row, the power of two >= d2 / 8
     const float c1 = (float)(0.5 / (M_E * M_E));             // 1 / (2 e^2)
     KALLE_LAUNCH(llasa_head2_kernel, dim3(R), dim3(256), 0, st, h1, static_cast<const bf16_t*>(head->w2), head->ldw2, head->b2, noise,
-                 ldn, c1, ga, disp, sc, latent, lb, kl, lat, lg, a.active);
+                 ldn, c1, ga, disp, sc, latent, lb, kl, lat, lg, (unsigned)a.active);
     rc = kalle_check_launch();
     if (rc != KALLE_OK) return rc;
     return proj_launch({head->wa, head->ldwa, nullptr}, lb, lat, PRO_BF16, nullptr, 0.f, nullptr, 0, x_next, D, true, x_next, D,

@@ -1,4 +1,4 @@
-"""-m gpu: the batched decode path - gemm_rows_kernel / rows_prologue_kernel (kalle_gemm_rows_bf16, kalle_gemm_rows_fused),
+"""-m gpu: the batched decode path - gemm_rows_kernel at NCB = 1 / rows_prologue_kernel (kalle_gemm_rows_bf16, kalle_gemm_rows_fused),
 the per-row single-query attention (kalle_attention_decode_rows) and kalle_llama_decode_step_rows - element by element against
 the fp64 references of tests/kernel_refs.py, by the method of tests/test_decode_gpu.py: each stage from its own inputs as the
 kernel produced them, NaN-guarded buffers and a fenced workspace, untouched memory compared bit for bit, wrong references caught.

@@ -1,4 +1,4 @@
-"""-m gpu: the wide decode path - gemm_rows_wide_kernel behind kalle_gemm_rows_wide and kalle_llama_decode_step_wide, 17 .. 64
+"""-m gpu: the wide decode path - gemm_rows_kernel at NCB = 2 .. 4 behind kalle_gemm_rows_wide and kalle_llama_decode_step_wide, 17 .. 64
 rows per read of the weights - by the method, helpers and bounds of tests/test_decode_rows_gpu.py (nothing new is measured): every
 element of the GEMM against the fp64 reference under NaN-guarded buffers, and, the property the wide path promises, every row BIT
 FOR BIT what the 16-row entry points give for the chunk of up to 16 rows that holds it - outputs, second destination, xhat,

@@ -1,10 +1,10 @@
 """the forward GEMMs of one DiT block at generation batch sizes (M = 252 rows for B = 1 with CFG), each timed alone with HIP events
 over launches captured into a HIP graph: python tools/skinny_gemm_bench.py [M]
 --decode [R ...]: the eight decoder GEMMs of a KV-cached step (Llama-3.2-1B / 3B shapes) instead - gemv_kernel against
-gemv_e4m3_kernel, and gemm_rows_kernel against gemm_rows_e4m3_kernel at each R (default 1 8 16) - fp32 output, no residual, the
+gemv_e4m3_kernel, and gemm_rows_kernel<YF32, TR, 1> against gemm_rows_e4m3_kernel at each R (default 1 8 16) - fp32 output, no residual, the
 weights rotating through > 600 MB of copies so that no call finds them in a cache; per kernel the median of 5 runs (min - max)
 in microseconds and the TB/s of weight bytes
---decode-wide: those GEMMs at 16 rows (gemm_rows_kernel), 32 and 64 rows (gemm_rows_wide_kernel) and, for comparison, ops.gemm at
+--decode-wide: those GEMMs at 16 rows (gemm_rows_kernel at NCB = 1), 32 and 64 rows (NCB = 2 and 4) and, for comparison, ops.gemm at
 64 rows"""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
