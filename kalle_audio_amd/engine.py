@@ -12,11 +12,15 @@ bucketed NCCL all-reduce] -> optimizer.step -> scheduler.step -> barrier) around
     straight into the bucket, and the bucket's all-reduce is issued the moment the block's backward has been queued -
     RCCL runs it on its own stream behind an event, overlapping the remaining backward;
   * one fused Adam/AdamW launch over the flat buffers updates master weights, moments and the bf16 mirror and folds
-    the 1/world_size gradient averaging in (no separate scale pass, no per-step host sync, no barrier).
+    the 1/world_size gradient averaging in (no separate scale pass, no per-step host sync, no barrier);
+  * WHERE that Adam runs - one pass at the end, slices beside the backward pass, sharded between reduce-scatter and all-gather,
+    or one norm-gated pass - and what a micro-batch clears is decided by ONE pure function, plan_step(); the trainer's methods
+    branch on its StepPlan (step_plan() is the host-only query) and keep what an optimizer step has done so far in one _Step.
 """
 import math
 import contextlib
 import os
+from typing import NamedTuple
 
 import torch
 import torch.distributed as dist
@@ -170,6 +174,59 @@ class FlatBuckets:
         return self.grad[a:b]
 
 
+class StepPlan(NamedTuple):
+    """what ONE micro-batch does around its backward pass, and the optimizer step behind it if it ends a window (plan_step)"""
+    accumulate: bool         # blk._kalle_grad_accumulate: the blocks' gradient kernels add into their sinks
+    wgrad_overwrite: bool    # blk._kalle_wgrad_overwrite: the grouped weight-gradient launch writes the matrices whole
+    clear: str               # cleared before the backward: "none" | "all" of flat.grad | "tail" (`_rest` / `_vae`) | "small+tail"
+    boundary: bool          # last micro-batch of its window: an optimizer step begins before its backward and ends after it
+    sharded: bool            # block buckets go reduce-scatter / Adam on the own chunk / all-gather
+    overlap: bool            # buckets are queued on the side streams while the backward pass still runs
+    hook: str                # a block's backward hook: "none" | "shard" | "allreduce" (deferred) | "queue" (_queue_bucket)
+    reduce_tail: bool        # _finish_comm, not overlapped: deferred all-reduce of `_rest` / `_vae`
+    wait_side: bool          # _finish_comm, not overlapped: the compute stream waits for the side streams (sharded buckets ran there)
+    norm: bool               # the gradient norm is taken (one slot per bucket, then the finish)
+    gate: bool               # ... and Adam waits for it: no slices, ONE kalle_adam_step_ctl behind the finish
+
+
+def plan_step(*, rows, first, boundary, group_wgrad, overlap_adam, overlap_min_rows, sharded, comm, norm_on, norm_gate, blocks, cuda):
+    """Pure: plain values in, StepPlan out.  rows: rows per block of this micro-batch (None: no backward() ran it - hooks or
+    optimizer_step() driven by hand: nothing runs on the side); first / boundary: its place in the accumulation window;
+    group_wgrad: dit_ops.GROUP_WGRAD; sharded / comm: the sharded optimizer / the gradient all-reduce are ACTIVE (the
+    constructor refuses the norm options next to the former); blocks: the model has bucket units; cuda: flat buffers on a GPU."""
+    assert (comm or not sharded) and (norm_on or not norm_gate) and not (sharded and norm_on)
+    r = rows or 0
+    # With the grouped weight-gradient launch (every block's matrices in one kernel) the first micro-batch WRITES the matrix
+    # gradients - no clear of the 4.2 GB they occupy, no read-add-store - and only the vectors at the head of every bucket are
+    # cleared, one small memset each.  Without it ONE clear of the flat gradient per optimizer step, every gradient kernel
+    # then accumulating, pays only where the weight gradients are split-K GEMMs (K = rows >= ~8 k: clearing in front of each
+    # of them and of each column sum is ~300 launches and twice the time); a weight gradient that writes its output whole
+    # would have to read the cleared buffer back (B = 16: -5 %), so smaller micro-batches overwrite on the first micro-batch.
+    grouped = bool(group_wgrad) and r > 0 and r % 8 == 0
+    clear_once = r >= 8192 and not grouped
+    # Overlap: a block's bucket is final as soon as its backward kernels are queued (and its all-reduce has landed), so its slice
+    # of the fused Adam runs right then on a side stream - an HBM-bound pass under the MFMA-bound GEMMs of the blocks still to
+    # come - instead of one 5.4 ms pass over all 1.05 B parameters at the end.  At small batches (B = 16: 2016 rows) those GEMMs
+    # are short, latency-bound launches that the optimizer's 31.5 GB of traffic slows down by as much as it hides (33.6 -> 33.8
+    # ms); from B = 64 on it pays (73.3 -> 72.6 ms)
+    overlap = bool(boundary and rows is not None and overlap_adam and (r >= overlap_min_rows or not blocks))
+    hook = "none" if not boundary else "shard" if sharded else "queue" if overlap else "allreduce" if comm else "none"
+    clear = "none" if not first else "all" if clear_once else "small+tail" if grouped else "tail"
+    return StepPlan(accumulate=True if (clear_once or grouped) else not first, wgrad_overwrite=grouped and first, clear=clear,
+                    boundary=bool(boundary), sharded=bool(sharded), overlap=overlap, hook=hook,
+                    reduce_tail=bool(boundary and comm and not overlap), wait_side=bool(boundary and sharded and cuda and not overlap),
+                    norm=bool(norm_on), gate=bool(norm_gate))
+
+
+class _Step:
+    """what ONE optimizer step has done so far: made by _begin_optimizer_step, dropped at the end of optimizer_step"""
+    def __init__(self, k, lr, plan, adam_kw=None):
+        self.k, self.lr, self.plan, self.adam_kw = k, lr, plan, adam_kw     # step number (1, 2, ...), its lr, its plan, Adam's keywords
+        self.adam_done, self.norm_done = set(), set()   # bucket keys whose Adam slice / slot of the norm workspace has been queued
+        self.norm_final, self.comm_events = False, 0    # the norm's finish has been queued; reductions the side streams waited for
+        self.shard_ev = None                            # behind the last sharded bucket's Adam: it has read the shared chunk buffer
+
+
 class DataParallelTrainer:
     """Owns flat buffers, bucketed gradient all-reduce and the fused optimizer for a DiT or the Llasa task model (any
     module tree whose repeated layers are this package's TransformerBlock / LlamaDecoderLayer: one bucket each)."""
@@ -183,13 +240,12 @@ class DataParallelTrainer:
         from .stable_audio_tools.models.transformer import TransformerBlock
         if max_grad_norm is not None and not float(max_grad_norm) > 0:            # (also NaN)
             raise ValueError(f"max_grad_norm must be a positive number or None, got {max_grad_norm!r}")
-        if os.environ.get("KALLE_SHARD_OPTIMIZER", "0") == "1":
-            for arg, on in (("max_grad_norm", max_grad_norm is not None), ("skip_nonfinite", skip_nonfinite),
-                            ("track_grad_norm", track_grad_norm)):
-                if on:
-                    # a rank holds only its shard of the reduced matrix gradients there: the global norm needs one more (scalar)
-                    # all-reduce, which this trainer does not issue yet
-                    raise ValueError(f"{arg} is not supported together with KALLE_SHARD_OPTIMIZER=1")
+        want_shard = os.environ.get("KALLE_SHARD_OPTIMIZER", "0") == "1"
+        for arg, on in (("max_grad_norm", max_grad_norm is not None), ("skip_nonfinite", skip_nonfinite), ("track_grad_norm", track_grad_norm)):
+            if on and want_shard:
+                # a rank holds only its shard of the reduced matrix gradients there: the global norm needs one more (scalar)
+                # all-reduce, which this trainer does not issue yet
+                raise ValueError(f"{arg} is not supported together with KALLE_SHARD_OPTIMIZER=1")
         self.model = model
         self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(process_group) if dist.is_initialized() else 0
@@ -226,14 +282,12 @@ class DataParallelTrainer:
         self.exp_avg_sq = torch.zeros_like(self.flat.param)
         self._pending = []
         # Gradient norm (max_grad_norm / skip_nonfinite / track_grad_norm; all off: none of this exists).  One workspace slot per
-        # bucket, in flat.bucket_keys order: a bucket's sum of squares is taken where its Adam slice runs today - overlapped, on
-        # the optimizer stream once its all-reduce has landed, i.e. as reads under the backward GEMMs; otherwise in
-        # optimizer_step, in bucket order - and kalle_grad_norm_finish adds the slots in index order, so the norm is the same bit
-        # pattern on every route and every rank.  It is the norm of the AVERAGED gradient (grad_scale = 1 / (world accum)), what
-        # DDP hands clip_grad_norm_.  With max_grad_norm or skip_nonfinite no Adam slice may run before the norm is final: the
-        # slices give way to ONE kalle_adam_step_ctl over the whole flat buffer behind the finish, on the same stream - that
-        # un-hidden pass is the price of the option (0.6 ms at B = 64, 2.2 ms at B = 256 on the bench shape: DESIGN.md section
-        # 5.15).  track_grad_norm alone keeps the slices.
+        # bucket, in flat.bucket_keys order: a bucket's sum of squares is taken where its Adam slice runs - overlapped, on the
+        # optimizer stream once its all-reduce has landed, i.e. as reads under the backward GEMMs; otherwise in optimizer_step,
+        # in bucket order - and kalle_grad_norm_finish adds the slots in index order, so the norm is the same bit pattern on
+        # every route and every rank.  It is the norm of the AVERAGED gradient (grad_scale), what DDP hands clip_grad_norm_.
+        # With max_grad_norm or skip_nonfinite the slices give way to ONE un-hidden pass behind the finish (StepPlan.gate): the
+        # price of the option, 0.6 ms at B = 64, 2.2 ms at B = 256 on the bench shape.
         # Skip rule: a skipped step leaves every bit of weights, moments and mirror; step_count, last_lr and the schedule advance
         # (the reference calls scheduler.step() regardless), the step number is SPENT - the next applied step uses the bias
         # corrections of step_count + 1, not torch's un-advanced state['step'] - and the EMA update runs (on unchanged weights).
@@ -243,8 +297,6 @@ class DataParallelTrainer:
         self.track_grad_norm = bool(track_grad_norm)
         self._norm_gate = self.max_grad_norm is not None or self.skip_nonfinite      # Adam waits for the norm
         self._norm_on = self._norm_gate or self.track_grad_norm
-        self._norm_done = set()           # bucket keys whose slot of the current optimizer step has been queued
-        self._norm_final = False          # kalle_grad_norm_finish of the current optimizer step has been queued
         self._ctl = self._norm_ws = None
         if self._norm_on:
             self._norm_slot = {k: i for i, k in enumerate(self.flat.bucket_keys)}
@@ -256,23 +308,22 @@ class DataParallelTrainer:
         # Adam pass shrinks from 31.5 GB to 31.5 / world GB per rank and step, the bf16 mirror is re-cast from the gathered weights).
         # The vectors at the head of a bucket (norm scales, biases) stay all-reduced and are updated on every rank; so do the buckets
         # outside the blocks.  Moments exist on their owner only: state_dict() gathers them (a collective - call it on every rank).
-        self.shard_opt = (os.environ.get("KALLE_SHARD_OPTIMIZER", "0") == "1" and comm_dtype == torch.float32
-                          and self.world & (self.world - 1) == 0 and self.world <= 64)
+        self.shard_opt = want_shard and comm_dtype == torch.float32 and self.world & (self.world - 1) == 0 and self.world <= 64
         self._shard_bufs = {}
-        # Optimizer overlapped with the backward pass: a block's bucket is final as soon as its backward kernels are queued (and
-        # its all-reduce has landed), so its slice of the fused Adam runs right then on a side stream - an HBM-bound pass under
-        # the MFMA-bound GEMMs of the blocks still to come - instead of one 5.4 ms pass over all 1.05 B parameters at the end.
-        # (KALLE_OVERLAP_ADAM=0: the single pass at the end of the step.)
+        # Optimizer overlapped with the backward pass (KALLE_OVERLAP_ADAM=0: the single pass at the end of the step): see plan_step
         self.overlap_adam = device.type == "cuda" and os.environ.get("KALLE_OVERLAP_ADAM", "1") != "0"
         side = self.overlap_adam or (device.type == "cuda" and self.shard_opt)
-        self._opt_stream = torch.cuda.Stream(device=device) if side else None
-        self._comm_stream = torch.cuda.Stream(device=device) if side else None
-        self._comm_events = 0
-        self._shard_ev = None
-        self._opt_done = set()            # bucket keys whose Adam slice of the current optimizer step has been queued
-        self._opt_lr = None               # learning rate of the optimizer step in progress (set when its backward starts)
-        self._overlap_now = False         # decided per optimizer step: only where the backward GEMMs are long enough to hide it
+        self._opt_stream, self._comm_stream = (torch.cuda.Stream(device=device), torch.cuda.Stream(device=device)) if side else (None, None)
         self.overlap_min_rows = int(os.environ.get("KALLE_OVERLAP_ADAM_MIN_ROWS", "4096"))
+        self.ema = self.ema_schedule = None     # (enable_ema)
+        self._tail_keys = [k for k in ("_rest", "_vae") if k in self.flat.bucket_range]    # the buckets outside the blocks
+        # StepPlan.clear -> ranges of flat.grad: autograd accumulates (+=) into the tail buckets' views, the blocks' kernels add
+        # into the vectors at the head of their buckets (a block whose parameters are all frozen has none)
+        tail = [self.flat.bucket_range[k] for k in self._tail_keys]
+        small = [r for r in (self.flat.small_range.get(pre, (0, 0)) for pre in prefixes) if r[1] > r[0]]
+        self._clear = {"none": [], "all": [(0, self.flat.total)], "tail": tail, "small+tail": small + tail}
+        self._plan = self._step = None    # StepPlan of the micro-batch backward() is running; _Step of the optimizer step in progress
+        self._last = _Step(0, None, self.step_plan(None))      # ... of the one before: what _overlap_now / _comm_events report
         for n, blk in self.blocks:
             pre = n + "."
             blk._kalle_grad_sinks = {k[len(pre):]: self.flat.grad_view(k) for k in self.flat.names if k.startswith(pre)}
@@ -291,9 +342,40 @@ class DataParallelTrainer:
             if getattr(p, "_kalle_wants_sink", False) and bucket_of(n) == "_rest":
                 p._kalle_grad_sink = self.flat.grad_view(n)
 
+    # -- the plan and the state of the optimizer step in progress -----------------------------------------
+    def step_plan(self, rows, micro=None):
+        """Host-only query (the trainer's gemm_plan): the StepPlan of micro-batch number `micro` (default: the next) at `rows` rows
+        per block (None: driven by hand, without backward()).  The one place that reads the switches plan_step takes, per call."""
+        from . import dit_ops
+        micro = self.micro if micro is None else micro
+        comm = self._comm_active()
+        return plan_step(rows=rows, first=micro % self.grad_accum_steps == 0, boundary=(micro + 1) % self.grad_accum_steps == 0,
+                         group_wgrad=dit_ops.GROUP_WGRAD, overlap_adam=self.overlap_adam, overlap_min_rows=self.overlap_min_rows,
+                         sharded=self.shard_opt and comm, comm=comm, norm_on=self._norm_on, norm_gate=self._norm_gate,
+                         blocks=bool(self.blocks), cuda=self.flat.grad.is_cuda)
+
+    _opt_lr = property(lambda self: self._step.lr if self._step is not None else None)      # None between optimizer steps
+    _overlap_now = property(lambda self: (self._step or self._last).plan.overlap)           # of the step in progress, else the last
+    _comm_events = property(lambda self: (self._step or self._last).comm_events)
+    # the averaging the optimizer folds in: the flat gradient holds the window's SUM over micro-batches and ranks
+    grad_scale = property(lambda self: 1.0 / (self.world * self.grad_accum_steps))
+
+    def _begin_optimizer_step(self, plan=None):
+        """fixes the step number and learning rate of the optimizer step whose last micro-batch is about to run backward"""
+        k = self.step_count + 1
+        # lr_schedule(s): multiplier for the optimizer step taken after `s` completed ones - torch LambdaLR's convention, so the
+        # k-th step (k = 1, 2, ...) uses lr_lambda(k - 1) exactly as optimizer.step(); scheduler.step() does (train_offline.py:247-248)
+        lr = self.lr * (self.lr_schedule(k - 1) if self.lr_schedule else 1.0)
+        kw = dict(lr=lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, weight_decay=self.weight_decay,
+                  decoupled=self.decoupled, step=k, grad_scale=self.grad_scale)
+        self._step = _Step(k, lr, plan or self.step_plan(None), kw)
+
     # -- gradient communication ---------------------------------------------------------------------------
     def _comm_active(self):
         return self.world > 1 or (dist.is_initialized() and bool(os.environ.get("KALLE_FORCE_COMM")))
+
+    def _sharded_active(self):
+        return self.step_plan(None).sharded
 
     def _allreduce(self, buf, defer=True):
         """starts the all-reduce of one bucket; returns (work handle | None, low-precision staging tensor | None).  defer: the
@@ -301,15 +383,10 @@ class DataParallelTrainer:
         otherwise the caller waits where it needs the result"""
         if not self._comm_active():
             return None, None
-        if self.comm_dtype == torch.float32 or not buf.is_cuda:
-            work = dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=self.pg, async_op=True)
-            if defer:
-                self._pending.append((work, None, None))
-            return work, None
-        low = ops.cast(buf, self.comm_dtype)
-        work = dist.all_reduce(low, op=dist.ReduceOp.SUM, group=self.pg, async_op=True)
+        low = None if self.comm_dtype == torch.float32 or not buf.is_cuda else ops.cast(buf, self.comm_dtype)
+        work = dist.all_reduce(buf if low is None else low, op=dist.ReduceOp.SUM, group=self.pg, async_op=True)
         if defer:
-            self._pending.append((work, low, buf))
+            self._pending.append((work, low, None if low is None else buf))
         return work, low
 
     def _queue_bucket(self, keys, ev):
@@ -319,7 +396,7 @@ class DataParallelTrainer:
         optimizer.  OPTIMIZER stream: waits for the all-reduce's completion (work.wait() blocks that stream, not the host),
         copies a low-precision result back into the fp32 bucket and runs the bucket's slice of the fused Adam - under the
         backward kernels of the blocks still to come and under the next buckets' all-reduces."""
-        works = []
+        works, st = [], self._step
         if self._comm_active():
             with torch.cuda.stream(self._comm_stream):
                 self._comm_stream.wait_event(ev)
@@ -334,52 +411,38 @@ class DataParallelTrainer:
                 if low is not None:
                     low.record_stream(self._opt_stream)          # (allocated on the comm stream, read here)
                     ops.copy_rows(low, buf, 1, 1, buf.numel(), 0, buf.numel(), 0, buf.numel())
-                self._comm_events += 1
+                st.comm_events += 1
             for key in keys:
-                if self._norm_on:
+                if st.plan.norm:
                     self._sumsq_bucket(key)
-                if not self._norm_gate:
+                if not st.plan.gate:
                     self._adam_bucket(key)
 
     # -- gradient norm ------------------------------------------------------------------------------------------
     def _sumsq_bucket(self, key):
         a, b = self.flat.bucket_range[key]
         ops.grad_sumsq(self.flat.grad[a:b], self._norm_ws, self._norm_slot[key], len(self._norm_slot))
-        self._norm_done.add(key)
+        self._step.norm_done.add(key)
 
     def _norm_finish(self):
-        """the slots not written yet, in bucket order, then the one-workgroup finish (on the current stream)"""
-        for key in self.flat.bucket_keys:
-            if key not in self._norm_done:
+        """on the current stream: the slots not written yet, in bucket order, then the one-workgroup finish - and, when Adam
+        waits for the norm, ONE pass over [0, total) behind it: no slice could run before the norm was final"""
+        st, f = self._step, self.flat
+        for key in f.bucket_keys:
+            if key not in st.norm_done:
                 self._sumsq_bucket(key)
-        ops.grad_norm_finish(self._norm_ws, len(self._norm_slot), self._ctl, grad_scale=1.0 / (self.world * self.grad_accum_steps),
+        ops.grad_norm_finish(self._norm_ws, len(self._norm_slot), self._ctl, grad_scale=self.grad_scale,
                              max_norm=self.max_grad_norm or 0.0, skip_nonfinite=self.skip_nonfinite)
-        self._norm_final = True
+        st.norm_final = True
+        if st.plan.gate:
+            ops.adam_step_ctl(f.param, f.grad, self.exp_avg, self.exp_avg_sq, f.param_bf16, self._ctl, **st.adam_kw)
+            st.adam_done.update(f.bucket_keys)
 
-    def _adam_ctl_all(self):
-        f = self.flat
-        ops.adam_step_ctl(f.param, f.grad, self.exp_avg, self.exp_avg_sq, f.param_bf16, self._ctl, lr=self._opt_lr,
-                          beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, weight_decay=self.weight_decay,
-                          decoupled=self.decoupled, step=self.step_count + 1,
-                          grad_scale=1.0 / (self.world * self.grad_accum_steps))
-        self._opt_done.update(f.bucket_keys)
-
-    @property
-    def grad_norm(self):
-        """device tensor [1] fp32: L2 norm of the averaged gradient of the last optimizer step (None: feature off)"""
-        return self._ctl.norm if self._ctl is not None else None
-
-    @property
-    def clip_coef(self):
-        return self._ctl.coef if self._ctl is not None else None
-
-    @property
-    def skipped_steps(self):
-        return self._ctl.skipped if self._ctl is not None else None
-
-    @property
-    def clipped_steps(self):
-        return self._ctl.clipped if self._ctl is not None else None
+    # device tensors [1] of the last optimizer step's record (None: feature off); grad_norm: fp32 L2 norm of the averaged gradient
+    grad_norm = property(lambda self: self._ctl.norm if self._ctl is not None else None)
+    clip_coef = property(lambda self: self._ctl.coef if self._ctl is not None else None)
+    skipped_steps = property(lambda self: self._ctl.skipped if self._ctl is not None else None)
+    clipped_steps = property(lambda self: self._ctl.clipped if self._ctl is not None else None)
 
     def opt_ctl(self):
         """the device's record of the last optimizer step as Python numbers - the only host sync of the feature"""
@@ -398,14 +461,11 @@ class DataParallelTrainer:
         c = (b1 - s1) // self.world              # (parameters are laid out on 64-element boundaries: any power of two <= 64 divides)
         return s0, s1, b1, c, s1 + self.rank * c
 
-    def _sharded_active(self):
-        return self.shard_opt and self._comm_active()
-
     def _sharded_bucket(self, key, ev):
         """reduce-scatter -> Adam on the own chunk (and on the all-reduced vectors) -> all-gather of the fp32 weights -> bf16 mirror.
         On the GPU: collectives on the comm stream, Adam on the optimizer stream, both behind the backward pass's event; on the CPU
         (gloo tests) the same calls in order."""
-        f = self.flat
+        f, st = self.flat, self._step
         s0, s1, b1, c, o0 = self._shard_range(key)
         cuda = f.grad.is_cuda
         comm = torch.cuda.stream(self._comm_stream) if cuda else contextlib.nullcontext()
@@ -416,8 +476,8 @@ class DataParallelTrainer:
         with comm:
             if cuda:
                 self._comm_stream.wait_event(ev)
-                if self._shard_ev is not None:
-                    self._comm_stream.wait_event(self._shard_ev)      # the previous bucket's Adam has read the shared chunk buffer
+                if st.shard_ev is not None:
+                    self._comm_stream.wait_event(st.shard_ev)      # the previous bucket's Adam has read the shared chunk buffer
             w_vec = dist.all_reduce(f.grad[s0:s1], op=dist.ReduceOp.SUM, group=self.pg, async_op=True) if s1 > s0 else None
             w_rs = dist.reduce_scatter_tensor(shard, f.grad[s1:b1], op=dist.ReduceOp.SUM, group=self.pg, async_op=True) if c else None
         with opt:
@@ -432,7 +492,7 @@ class DataParallelTrainer:
             if cuda:
                 ev2 = torch.cuda.Event()
                 ev2.record(self._opt_stream)
-                self._shard_ev = ev2
+                st.shard_ev = ev2
         with comm:
             if cuda:
                 self._comm_stream.wait_event(ev2)
@@ -444,8 +504,8 @@ class DataParallelTrainer:
                         ops.copy_rows(f.param[s1:b1], f.param_bf16[s1:b1], 1, 1, b1 - s1, 0, b1 - s1, 0, b1 - s1)
                     else:
                         f.param_bf16[s1:b1].copy_(f.param[s1:b1])
-        self._comm_events += 1
-        self._opt_done.add(key)
+        st.comm_events += 1
+        st.adam_done.add(key)
 
     def gather_moments(self):
         """sharded optimizer: every rank receives the Adam moments of the chunks it does not own (a collective; state_dict() calls it)"""
@@ -460,155 +520,101 @@ class DataParallelTrainer:
                     dist.all_gather_into_tensor(buf[s1:b1], buf[o0:o0 + c].clone(), group=self.pg)
 
     def _on_block_done(self, blk):
-        """called (from autograd's backward) right after a block's backward kernels were queued"""
-        key = blk._kalle_bucket_key
-        if key is None or not self._boundary():
+        """called (from autograd's backward) right after a block's backward kernels were queued; outside backward() it plans for itself"""
+        key, hook = blk._kalle_bucket_key, (self._plan or self.step_plan(None)).hook
+        if key is None or hook == "none":       # (a frozen block owns no bucket; off a window's boundary nothing is final yet)
             return
-        if self._sharded_active():
-            ev = None
-            if self.flat.grad.is_cuda:
-                ev = torch.cuda.Event()
-                ev.record(torch.cuda.current_stream())
-            self._sharded_bucket(key, ev)
-            return
-        if not self._overlap_now:
+        if hook == "allreduce":
             self._allreduce(self.flat.bucket_grad(key))
             return
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream())
-        self._queue_bucket([key], ev)
-
-    def _begin_optimizer_step(self):
-        """fixes the step number and learning rate of the optimizer step whose last micro-batch is about to run backward"""
-        k = self.step_count + 1
-        # lr_schedule(s): multiplier for the optimizer step taken after `s` completed ones - torch LambdaLR's convention,
-        # so the k-th step (k = 1, 2, ...) uses lr_lambda(k - 1) exactly as optimizer.step(); scheduler.step() does
-        # (train_offline.py:247-248)
-        self._opt_lr = self.lr * (self.lr_schedule(k - 1) if self.lr_schedule else 1.0)
-        self._opt_done = set()
-        self._norm_done = set()
-        self._norm_final = False
-        self._comm_events = 0
-        self._shard_ev = None
+        ev = torch.cuda.current_stream().record_event() if self.flat.grad.is_cuda else None
+        if hook == "shard":
+            self._sharded_bucket(key, ev)
+        else:
+            self._queue_bucket([key], ev)
 
     def _adam_bucket(self, key):
         a, b = self.flat.bucket_range[key]
         self._adam_range(a, b)
-        self._opt_done.add(key)
+        self._step.adam_done.add(key)
 
     def _adam_range(self, a, b, grad=None):
         if b <= a:
             return
         f = self.flat
         ops.adam_step(f.param[a:b], f.grad[a:b] if grad is None else grad, self.exp_avg[a:b], self.exp_avg_sq[a:b],
-                      f.param_bf16[a:b] if f.param_bf16 is not None else None, lr=self._opt_lr, beta1=self.betas[0],
-                      beta2=self.betas[1], eps=self.eps, weight_decay=self.weight_decay, decoupled=self.decoupled,
-                      step=self.step_count + 1, grad_scale=1.0 / (self.world * self.grad_accum_steps))
+                      f.param_bf16[a:b] if f.param_bf16 is not None else None, **self._step.adam_kw)
 
     def _boundary(self):
         return (self.micro + 1) % self.grad_accum_steps == 0
 
+    @contextlib.contextmanager
+    def _timed(self, count, on=True):
+        """with comm_timing a list: two events around the waits of the compute stream in the body.  Exposed (not overlapped)
+        time = how long the stream sits in them - nothing is launched on it between the two; kept with `count` buckets"""
+        timed = self.comm_timing is not None and on
+        if timed:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+        yield
+        if timed:
+            e1.record()
+            self.comm_timing.append((e0, e1, count))
+
     def _finish_comm(self):
-        if self._overlap_now and self._boundary():
+        plan = self._plan or self.step_plan(None)
+        if plan.overlap:
             # what the bucket hooks did not cover (embedders, in / out projections, a trained VAE) goes the same way; the compute
             # stream then waits for the optimizer stream ONCE - the time it sits there is what neither the all-reduces nor the
             # optimizer slices managed to hide behind the backward pass
-            cur = torch.cuda.current_stream()
-            ev = torch.cuda.Event()
-            ev.record(cur)
-            done = self._norm_done if self._norm_gate else self._opt_done
-            self._queue_bucket([k for k in self.flat.bucket_keys if k not in done], ev)
-            if self._norm_on:
+            st, cur = self._step, torch.cuda.current_stream()
+            done = st.norm_done if plan.gate else st.adam_done
+            self._queue_bucket([k for k in self.flat.bucket_keys if k not in done], cur.record_event())
+            if plan.norm:
                 with torch.cuda.stream(self._opt_stream):
                     self._norm_finish()
-                    if self._norm_gate:
-                        self._adam_ctl_all()          # ONE pass over [0, total): no slice could run before the norm was final
-            timed = self.comm_timing is not None
-            if timed:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            cur.wait_stream(self._opt_stream)
-            if self._sharded_active():
-                cur.wait_stream(self._comm_stream)          # the all-gathers of the updated weights and their bf16 re-cast
-            if timed:
-                e1.record()
-                self.comm_timing.append((e0, e1, self._comm_events))
-            return
-        if self._boundary():
-            for key in ("_rest", "_vae"):
-                if key in self.flat.bucket_range:
-                    self._allreduce(self.flat.bucket_grad(key))
-            if self._sharded_active() and self.flat.grad.is_cuda and self._opt_stream is not None:
-                # (small micro-batches keep the single optimizer pass for what is left; the sharded buckets ran on the side streams)
-                cur = torch.cuda.current_stream()
+            with self._timed(st.comm_events):
                 cur.wait_stream(self._opt_stream)
-                cur.wait_stream(self._comm_stream)
-        timed = self.comm_timing is not None and self._pending and self.flat.grad.is_cuda
-        if timed:
-            # exposed (not overlapped) all-reduce time = how long the compute stream sits in the waits below: nothing is
-            # launched on it between the two events
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        for work, low, dst in self._pending:
-            work.wait()
-            if low is not None:
-                ops.copy_rows(low, dst, 1, 1, dst.numel(), 0, dst.numel(), 0, dst.numel())
-        if timed:
-            e1.record()
-            self.comm_timing.append((e0, e1, len(self._pending)))
+                if plan.sharded:
+                    cur.wait_stream(self._comm_stream)          # the all-gathers of the updated weights and their bf16 re-cast
+            return
+        if plan.reduce_tail:
+            for key in self._tail_keys:
+                self._allreduce(self.flat.bucket_grad(key))
+        if plan.wait_side:      # (small micro-batches keep the single optimizer pass for what is left; the sharded buckets ran on the side)
+            cur = torch.cuda.current_stream()
+            cur.wait_stream(self._opt_stream)
+            cur.wait_stream(self._comm_stream)
+        with self._timed(len(self._pending), on=self._pending and self.flat.grad.is_cuda):
+            for work, low, dst in self._pending:
+                work.wait()
+                if low is not None:
+                    ops.copy_rows(low, dst, 1, 1, dst.numel(), 0, dst.numel(), 0, dst.numel())
         self._pending = []
 
     def comm_summary(self):
         """after a device sync: {"ranks", "backend", "buckets_per_step", "exposed_ms_per_step"} from the events collected while
         `comm_timing` was a list (bench.py switches it on for the timed steps)"""
         ev = self.comm_timing or []
-        active = dist.is_initialized() and (self.world > 1 or bool(os.environ.get("KALLE_FORCE_COMM")))
-        out = {"ranks": self.world, "backend": dist.get_backend(self.pg) if dist.is_initialized() else None,
-               "allreduce_active": bool(active), "sharded_optimizer": bool(active and self.shard_opt),
-               "comm_dtype": str(self.comm_dtype).replace("torch.", ""),
-               "buckets_per_step": ev[0][2] if ev else 0,
-               "exposed_ms_per_step": (sum(a.elapsed_time(b) for a, b, _ in ev) / len(ev)) if ev else 0.0}
-        return out
+        return {"ranks": self.world, "backend": dist.get_backend(self.pg) if dist.is_initialized() else None,
+                "allreduce_active": self._comm_active(), "sharded_optimizer": self._sharded_active(),
+                "comm_dtype": str(self.comm_dtype).replace("torch.", ""), "buckets_per_step": ev[0][2] if ev else 0,
+                "exposed_ms_per_step": (sum(a.elapsed_time(b) for a, b, _ in ev) / len(ev)) if ev else 0.0}
 
     # -- one micro-batch ------------------------------------------------------------------------------------
     def backward(self, loss):
-        first = self.micro % self.grad_accum_steps == 0
-        # ONE clear of the flat gradient per optimizer step; every gradient kernel then accumulates into its sink.  (Letting
-        # the first micro-batch overwrite instead costs a separate small clear in front of each split-K weight gradient and
-        # column sum: ~300 launches and twice the time of this single pass.)
-        # That only pays when the weight gradients are split-K GEMMs (K = tokens of the micro-batch >= ~8 k): a weight gradient
-        # that writes its output whole would have to read the cleared buffer back instead (B = 16: -5 %), so small
-        # micro-batches keep the overwrite-on-first-micro-batch rule.
         rows = max((getattr(blk, "_kalle_last_rows", 0) for _, blk in self.blocks), default=0)
-        from . import dit_ops
-        # With the grouped weight-gradient launch (every block's matrices in one kernel) the first micro-batch WRITES the matrix
-        # gradients - no clear of the 4.2 GB they occupy and no read-add-store - and only the vectors at the head of every bucket
-        # (norm scales, biases: sinks the kernels add into atomically) are cleared, one small memset per bucket.
-        grouped = dit_ops.GROUP_WGRAD and rows > 0 and rows % 8 == 0
-        clear_once = rows >= 8192 and not grouped
+        plan = self._plan = self.step_plan(rows)
         for _, blk in self.blocks:
-            blk._kalle_grad_accumulate = True if (clear_once or grouped) else not first
-            blk._kalle_wgrad_overwrite = grouped and first
-        if first:
-            if clear_once:
-                self.flat.grad.zero_()
-            else:
-                if grouped:
-                    for _, blk in self.blocks:
-                        a, b = self.flat.small_range.get(blk._kalle_bucket_key, (0, 0))
-                        if b > a:
-                            self.flat.grad[a:b].zero_()
-                for key in ("_rest", "_vae"):
-                    if key in self.flat.bucket_range:
-                        self.flat.bucket_grad(key).zero_()     # autograd accumulates (+=) into these views
-        if self._boundary():
-            self._begin_optimizer_step()
-            # at small batches (B = 16: 2016 rows) the backward GEMMs are short, latency-bound launches that the optimizer's
-            # 31.5 GB of traffic slows down by as much as it hides (33.6 -> 33.8 ms); from B = 64 on it pays (73.3 -> 72.6 ms)
-            self._overlap_now = self.overlap_adam and (rows >= self.overlap_min_rows or not self.blocks)
+            blk._kalle_grad_accumulate, blk._kalle_wgrad_overwrite = plan.accumulate, plan.wgrad_overwrite
+        for a, b in self._clear[plan.clear]:
+            self.flat.grad[a:b].zero_()
+        if plan.boundary:
+            self._begin_optimizer_step(plan)
         loss.backward()
         self._finish_comm()
-        if self._boundary():
+        self._plan = None
+        if plan.boundary:
             self.optimizer_step()
         self.micro += 1
 
@@ -632,27 +638,22 @@ class DataParallelTrainer:
         return {n: self.ema[s:s + ne].view(self.flat.params[n].shape) for n, (s, ne) in self.flat.slices.items()}
 
     def optimizer_step(self):
-        if self._opt_lr is None:                           # called directly (not through backward())
+        if self._step is None:                             # called directly (not through backward())
             self._begin_optimizer_step()
-        if self._norm_on and not self._norm_final:
+        st = self._step
+        if st.plan.norm and not st.norm_final:
             self._norm_finish()
-            if self._norm_gate:
-                self._adam_ctl_all()
-        if not (len(self._opt_done) == len(self.flat.bucket_keys) and (self._overlap_now or self._norm_gate)):
-            # one fused pass over whatever has not been updated yet (everything, without the overlapped slices)
-            if self._opt_done:
-                for key in self.flat.bucket_keys:
-                    if key not in self._opt_done:
-                        self._adam_bucket(key)
-            else:
-                self._adam_range(0, self.flat.total)
+        # Adam for what is left: nothing after overlapped slices or the gated pass, the rest after sharded buckets, else ONE pass
+        if not st.adam_done:
+            self._adam_range(0, self.flat.total)
+        else:
+            for key in self.flat.bucket_keys:
+                if key not in st.adam_done:
+                    self._adam_bucket(key)
         self.step_count += 1
-        self.last_lr = self._opt_lr                        # what this optimizer step actually used (for logging)
-        self._opt_lr = None
-        self._opt_done = set()
-        self._norm_done = set()
-        self._norm_final = False
-        if getattr(self, "ema", None) is not None:
+        self.last_lr = st.lr                               # what this optimizer step actually used (for logging)
+        self._last, self._step = st, None
+        if self.ema is not None:
             self._ema_update()
 
     def train_step(self, diffusion, latents, t, noise, cond, objective="v", padding_mask=None):
@@ -677,12 +678,11 @@ class DataParallelTrainer:
         if self._ctl is not None:
             c = self.opt_ctl()
             sd["skipped_steps"], sd["clipped_steps"] = c["skipped_steps"], c["clipped_steps"]
-        if getattr(self, "ema", None) is not None:
+        if self.ema is not None:
             sc = self.ema_schedule
             sd["ema"] = self.ema
-            sd["ema_schedule"] = {"step": sc.step, "initted": sc.initted, "beta": sc.beta, "power": sc.power,
-                                  "update_every": sc.update_every, "update_after_step": sc.update_after_step,
-                                  "inv_gamma": sc.inv_gamma, "min_value": sc.min_value}
+            sd["ema_schedule"] = {k: getattr(sc, k) for k in ("step", "initted", "beta", "power", "update_every", "update_after_step",
+                                                              "inv_gamma", "min_value")}
         return sd
 
     def load_state_dict(self, sd):
