@@ -635,6 +635,44 @@ int kalle_conv_transpose1d_cfirst_fwd(const float* x_padded, const float* w_pack
 int kalle_conv_transpose1d_fwd(const void* x, int x_dtype, const float* w_packed, const float* bias, void* y,
                                int y_dtype, int B, int Cin, int Lin, int Cout, int Lout, int ksize, int stride,
                                int padding, const kalle_act* in_act, const kalle_conv_epilogue* epi, void* stream);
+/* Ragged batches: the five forward entry points above with per-row valid lengths.  Row b of x [B][C][Lin] is a tensor of
+ * lens_in[b] positions and row b of y [B][Cout][Lout] one of lens_out[b]; the row strides stay Lin and Lout.
+ *   - inputs at positions >= lens_in[b] read as ZERO, whatever the memory holds (what zero padding supplies when the row runs
+ *     alone); the mask acts on the load, before the input activation, and every input activation maps 0 to 0;
+ *   - outputs (y and y_raw) at positions >= lens_out[b] are NOT WRITTEN (the buffers keep their contents there);
+ *   - lens_in[b] == 0 makes row b inactive: lens_out[b] must be 0 and nothing of the row is read or written; a workgroup whose
+ *     position tile lies at or past lens_out[b] leaves before it stages anything, so the cost follows the live samples;
+ *   - every row inactive: KALLE_OK, nothing launched.
+ * Each array (int32 [B]) is passed twice, as row0 / len of kalle_attention_fwd_varlen are: ..._host is checked here and read by
+ * nobody else, ..._dev is what the kernels read; that the two agree is the caller's contract.  All arrays NULL = the dense
+ * entry point (which is that call).  Refused with KALLE_ERR_ARG before any launch: some but not all arrays NULL; a length < 0;
+ * lens_in[b] > Lin; lens_out[b] > Lout; lens_out[b] beyond what lens_in[b] inputs yield - conv: (lens_in[b] - 1 + padding) /
+ * stride + 1, transposed: (lens_in[b] - 1) * stride - padding + ksize (the bounds the dense calls put on Lout against Lin).
+ * The plan does not depend on the lengths: kalle_conv_plan / kalle_conv_transpose_plan answer for (B, Lin, Lout) as for the
+ * dense call, and kalle_conv_last_plan after a _lens call that passed its checks is the dense call's word (also when every row
+ * was inactive).  Channels-per-lane families: kalle_conv_pad_act_lens applies lens_in (zeros from lens_in[b] on; an inactive
+ * row's copy is not made), kalle_conv1d_cfirst_fwd_lens checks lens_out against lens_in (it cannot know Lin) and obeys lens_out,
+ * kalle_conv_transpose1d_cfirst_fwd_lens takes lens_out only.  Forward only: no backward kernel takes lengths. */
+int kalle_conv1d_fwd_lens(const void* x, int x_dtype, const float* w_packed, const float* bias, void* y, int y_dtype, int B,
+                          int Cin, int Lin, int Cout, int Lout, int ksize, int stride, int padding, int dilation,
+                          const kalle_act* in_act, const kalle_conv_epilogue* epi, const int32_t* lens_in_host,
+                          const int32_t* lens_in_dev, const int32_t* lens_out_host, const int32_t* lens_out_dev, void* stream);
+int kalle_conv_transpose1d_fwd_lens(const void* x, int x_dtype, const float* w_packed, const float* bias, void* y,
+                                    int y_dtype, int B, int Cin, int Lin, int Cout, int Lout, int ksize, int stride,
+                                    int padding, const kalle_act* in_act, const kalle_conv_epilogue* epi,
+                                    const int32_t* lens_in_host, const int32_t* lens_in_dev, const int32_t* lens_out_host,
+                                    const int32_t* lens_out_dev, void* stream);
+int kalle_conv_pad_act_lens(const float* x, float* x_padded, int B, int C, int Lin, int Lp, int padding, const kalle_act* act,
+                            int phases, const int32_t* lens_in_host, const int32_t* lens_in_dev, void* stream);
+int kalle_conv1d_cfirst_fwd_lens(const float* x_padded, const float* w_packed, const float* bias, float* y, int B, int Cin,
+                                 int Lp, int Cout, int Lout, int ksize, int stride, int padding, int dilation,
+                                 const kalle_conv_epilogue* epi, float* workspace, const int32_t* lens_in_host,
+                                 const int32_t* lens_in_dev, const int32_t* lens_out_host, const int32_t* lens_out_dev,
+                                 void* stream);
+int kalle_conv_transpose1d_cfirst_fwd_lens(const float* x_padded, const float* w_packed, const float* bias, float* y, int B,
+                                           int Cin, int Lp, int Cout, int Lout, int ksize, int stride, int padding,
+                                           const kalle_conv_epilogue* epi, const int32_t* lens_out_host,
+                                           const int32_t* lens_out_dev, void* stream);
 /* which kernel the calling thread's most recent kalle_conv1d_fwd / kalle_conv_transpose1d_fwd / kalle_conv1d_cfirst_fwd /
  * kalle_conv_transpose1d_cfirst_fwd / kalle_conv_wgrad launched; 0 when that call returned before launching anything.
  *   bits 0-3 family: 1 conv1d_kernel (fallback), 2 conv1d_v2_kernel, 3 convT1d_kernel (fallback), 4 convT1d_v2_kernel,

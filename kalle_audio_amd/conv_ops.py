@@ -89,23 +89,110 @@ def conv_transpose_plan(B, Cin, Lin, Cout, Lout, K, *, stride, padding, act=0, a
                  x_f32, y_f32)
 
 
+def conv_len(L, K, stride=1, padding=0, pad_right=None, dilation=1):
+    """outputs a conv makes of L inputs (torch's formula; left pad `padding`, right pad `pad_right`, default the same)"""
+    pr = padding if pad_right is None else pad_right
+    return (L + padding + pr - dilation * (K - 1) - 1) // stride + 1
+
+
+def conv_transpose_len(L, K, stride, padding, trim=0):
+    """outputs a transposed conv makes of L inputs, less `trim`"""
+    return (L - 1) * stride - 2 * padding + K - trim
+
+
+class RaggedLengths:
+    """The per-row lengths of a ragged batch at every resolution a conv stack takes it through: `levels[i]` is a tuple of B
+    ints, level 0 the stack's input.  All levels sit in ONE host int32 array and ONE device int32 tensor [levels][B],
+    uploaded here, once per encode / decode call; a layer gets its two rows of it as a `Lens`.  The stack plans the
+    levels before it runs (each from the layer's own output-length formula, row by row); a layer recomputes its own from its
+    input level and must find it (`Lens.to`), so a stack that plans one thing and runs another fails loudly."""
+
+    def __init__(self, levels, device):
+        self.levels = [tuple(int(v) for v in lv) for lv in levels]
+        self.B = len(self.levels[0])
+        if any(len(lv) != self.B for lv in self.levels) or any(v < 0 for lv in self.levels for v in lv):
+            raise ValueError("RaggedLengths: every level holds one non-negative length per row")
+        flat = [v for lv in self.levels for v in lv]
+        self._host = (ctypes.c_int32 * len(flat))(*flat)
+        self._dev = torch.tensor(flat, dtype=torch.int32).to(device)         # the one upload
+
+    def at(self, i=0):
+        return Lens(self, i)
+
+
+class Lens:
+    """the row lengths of one level of a RaggedLengths: `host` (tuple), and the host / device addresses the C ABI takes"""
+    __slots__ = ("owner", "i")
+
+    def __init__(self, owner, i):
+        self.owner, self.i = owner, i
+
+    @property
+    def host(self):
+        return self.owner.levels[self.i]
+
+    def host_ptr(self):
+        return ctypes.c_void_p(ctypes.addressof(self.owner._host) + 4 * self.owner.B * self.i)
+
+    def dev_ptr(self):
+        return ctypes.c_void_p(self.owner._dev.data_ptr() + 4 * self.owner.B * self.i)
+
+    def to(self, lengths):
+        """the level that holds `lengths`: this one or the nearest later one"""
+        lengths = tuple(lengths)
+        for j in range(self.i, len(self.owner.levels)):
+            if self.owner.levels[j] == lengths:
+                return Lens(self.owner, j)
+        raise ValueError(f"lengths {lengths} are not a planned level of this ragged batch (from level {self.i}: "
+                         f"{self.owner.levels[self.i:]})")
+
+    def map(self, fn):
+        """fn applied to every live row (an inactive row, length 0, stays inactive; a result below 0 counts as 0)"""
+        return self.to(max(0, fn(v)) if v > 0 else 0 for v in self.host)
+
+
+def plan_levels(lengths, maps):
+    """levels for RaggedLengths: `lengths`, then one level per length map of the stack, applied row by row as Lens.map does"""
+    levels = [tuple(int(v) for v in lengths)]
+    for fn in maps:
+        levels.append(tuple(max(0, fn(v)) if v > 0 else 0 for v in levels[-1]))
+    return levels
+
+
+def _check_lens(lens, x, B, L, *others):
+    if not isinstance(lens, Lens):
+        raise TypeError("lens: a conv_ops.Lens (RaggedLengths(...).at(level))")
+    if lens.owner.B != B or lens.owner._dev.device != x.device:
+        raise ValueError(f"lens holds {lens.owner.B} rows on {lens.owner._dev.device}, x {B} on {x.device}")
+    if max(lens.host) > L:
+        raise ValueError(f"a length of {lens.host} exceeds the tensor's {L}")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x,) + others):
+        raise NotImplementedError("ragged lengths are inference only: no backward kernel takes them")
+
+
 def conv1d(x, w_packed, bias, *, Cout, K, stride=1, padding=0, dilation=1, act=0, alpha=None, beta=None,
            logscale=True, residual=None, post=0, out_dtype=None, pad_right=None, act_param=0.0, out_scale=1.0,
-           accumulate_into=None, post_act=None, want_raw=False):
+           accumulate_into=None, post_act=None, want_raw=False, lens=None, zero_tail=False):
     """padding = left pad; pad_right defaults to the same (symmetric). act: 0 none, 1 snake(-beta), 2 ELU, 3 LeakyReLU,
-    4 WaveNet gate.  Store: (conv + bias + residual) * out_scale (+= accumulate_into) -> post_act -> tanh (post=1)."""
+    4 WaveNet gate.  Store: (conv + bias + residual) * out_scale (+= accumulate_into) -> post_act -> tanh (post=1).
+    lens: a Lens over x's rows - row b is a tensor of lens.host[b] positions (include/kalle_hip.h, ragged batches); the output's
+    lengths are this layer's own formula per row.  Outputs past a row's length are not written: zero_tail starts y from zeros
+    (the last layer of a stack), otherwise they hold whatever the allocator left and the next layer's lens masks them."""
     lib = _lib.load()
     x = x.contiguous()
     B, Cin, Lin = x.shape
     if act == 4:
         Cin //= 2
-    pr = padding if pad_right is None else pad_right
-    Lout = (Lin + padding + pr - dilation * (K - 1) - 1) // stride + 1
+    Lout = conv_len(Lin, K, stride, padding, pad_right, dilation)
+    lens_out = None
+    if lens is not None:
+        _check_lens(lens, x, B, Lin, residual, accumulate_into)
+        lens_out = lens.map(lambda v: conv_len(v, K, stride, padding, pad_right, dilation))
     if accumulate_into is not None:
         y = accumulate_into
         assert y.is_contiguous() and tuple(y.shape) == (B, Cout, Lout)
     else:
-        y = torch.empty((B, Cout, Lout), device=x.device, dtype=out_dtype or x.dtype)
+        y = (torch.zeros if lens is not None and zero_tail else torch.empty)((B, Cout, Lout), device=x.device, dtype=out_dtype or x.dtype)
     if residual is not None:
         residual = residual.contiguous()
         assert residual.dtype == x.dtype and residual.shape == y.shape
@@ -115,6 +202,22 @@ def conv1d(x, w_packed, bias, *, Cout, K, stride=1, padding=0, dilation=1, act=0
     # the library picks the kernel family (kalle_conv_plan); families 5 / 6 run over a padded, pre-activated copy of x
     family, _, Lp, lead, phases, nws = _query(lib.kalle_conv_plan, "kalle_conv_plan", ia, ep, _dt(x), _dt(y), B, Cin, Lin, Cout, Lout, K,
                                               stride, padding, dilation)
+    if lens is not None:      # the same plan, the ..._lens entry points
+        li = (lens.host_ptr(), lens.dev_ptr())
+        lo = (lens_out.host_ptr(), lens_out.dev_ptr())
+        if family >= 5:
+            xp = torch.empty((B, Cin, Lp), device=x.device, dtype=torch.float32)
+            check(lib.kalle_conv_pad_act_lens(_p(x), _p(xp), B, Cin, Lin, Lp, lead, ctypes.addressof(ia), phases, *li, _stream()),
+                  "kalle_conv_pad_act_lens")
+            ws = torch.empty(nws, device=x.device, dtype=torch.float32) if nws > 0 else None
+            check(lib.kalle_conv1d_cfirst_fwd_lens(_p(xp), _p(w_packed), _p(bias), _p(y), B, Cin, Lp, Cout, Lout, K, stride, padding,
+                                                   dilation, ctypes.addressof(ep), _p(ws), *li, *lo, _stream()),
+                  "kalle_conv1d_cfirst_fwd_lens")
+        else:
+            check(lib.kalle_conv1d_fwd_lens(_p(x), _dt(x), _p(w_packed), _p(bias), _p(y), _dt(y), B, Cin, Lin, Cout, Lout, K, stride,
+                                            padding, dilation, ctypes.addressof(ia), ctypes.addressof(ep), *li, *lo, _stream()),
+                  "kalle_conv1d_fwd_lens")
+        return (y, y_raw) if want_raw else y
     if family >= 5:
         xp = torch.empty((B, Cin, Lp), device=x.device, dtype=torch.float32)
         check(lib.kalle_conv_pad_act(_p(x), _p(xp), B, Cin, Lin, Lp, lead, ctypes.addressof(ia), phases, _stream()),
@@ -130,19 +233,38 @@ def conv1d(x, w_packed, bias, *, Cout, K, stride=1, padding=0, dilation=1, act=0
 
 
 def conv_transpose1d(x, w_packed, bias, *, Cout, K, stride, padding, act=0, alpha=None, beta=None, logscale=True,
-                     out_dtype=None, trim=0, act_param=0.0, post_act=None, want_raw=False):
+                     out_dtype=None, trim=0, act_param=0.0, post_act=None, want_raw=False, lens=None, zero_tail=False):
     """trim: drop the last `trim` outputs (causal transposed conv); negative: keep up to `padding` outputs beyond the symmetric
-    right trim (data gradient of a strided conv)"""
+    right trim (data gradient of a strided conv).  lens / zero_tail: as in conv1d"""
     lib = _lib.load()
     x = x.contiguous()
     B, Cin, Lin = x.shape
-    Lout = (Lin - 1) * stride - 2 * padding + K - trim
-    y = torch.empty((B, Cout, Lout), device=x.device, dtype=out_dtype or x.dtype)
+    Lout = conv_transpose_len(Lin, K, stride, padding, trim)
+    lens_out = None
+    if lens is not None:
+        _check_lens(lens, x, B, Lin)
+        lens_out = lens.map(lambda v: conv_transpose_len(v, K, stride, padding, trim))
+    y = (torch.zeros if lens is not None and zero_tail else torch.empty)((B, Cout, Lout), device=x.device, dtype=out_dtype or x.dtype)
     ia = _act_struct(act, alpha, beta, logscale, act_param)
     y_raw = torch.empty_like(y) if want_raw else None
     ep = _epilogue(None, 1.0, False, False, post_act, y_raw)
     family, _, Lp, lead, phases, _ = _query(lib.kalle_conv_transpose_plan, "kalle_conv_transpose_plan", ia, ep, _dt(x), _dt(y), B, Cin,
                                             Lin, Cout, Lout, K, stride, padding)
+    if lens is not None:
+        li = (lens.host_ptr(), lens.dev_ptr())
+        lo = (lens_out.host_ptr(), lens_out.dev_ptr())
+        if family == 7:
+            xp = torch.empty((B, Cin, Lp), device=x.device, dtype=torch.float32)
+            check(lib.kalle_conv_pad_act_lens(_p(x), _p(xp), B, Cin, Lin, Lp, lead, ctypes.addressof(ia), phases, *li, _stream()),
+                  "kalle_conv_pad_act_lens")
+            check(lib.kalle_conv_transpose1d_cfirst_fwd_lens(_p(xp), _p(w_packed), _p(bias), _p(y), B, Cin, Lp, Cout, Lout, K, stride,
+                                                             padding, ctypes.addressof(ep), *lo, _stream()),
+                  "kalle_conv_transpose1d_cfirst_fwd_lens")
+        else:
+            check(lib.kalle_conv_transpose1d_fwd_lens(_p(x), _dt(x), _p(w_packed), _p(bias), _p(y), _dt(y), B, Cin, Lin, Cout, Lout, K,
+                                                      stride, padding, ctypes.addressof(ia), ctypes.addressof(ep), *li, *lo, _stream()),
+                  "kalle_conv_transpose1d_fwd_lens")
+        return (y, y_raw) if want_raw else y
     if family == 7:
         xp = torch.empty((B, Cin, Lp), device=x.device, dtype=torch.float32)
         check(lib.kalle_conv_pad_act(_p(x), _p(xp), B, Cin, Lin, Lp, lead, ctypes.addressof(ia), phases, _stream()),

@@ -19,6 +19,8 @@
 // ceil(K/S)-tap convolutions (one per output phase) run back to back by the same workgroup.
 // Fallback kernels ("v1": strided conv, gated input, mixed dtypes): 64 co x 64 positions per workgroup, 4x4 per thread.
 #include <cstdlib>
+#include <initializer_list>
+#include <type_traits>
 #include "common.h"
 #include "../../include/kalle_hip.h"
 
@@ -66,6 +68,12 @@ struct ConvParams {
     void* y_raw;               // dual output: the un-activated value also goes here (same shape / dtype as y)
     int nco, ntile, co_fast;   // v2 grid: blockIdx.x enumerates (position tile, channel tile), channel tile fastest if co_fast
 };
+// Ragged batch: row b is a tensor of lens_in[b] inputs and lens_out[b] outputs inside its [Lin] / [Lout] row - inputs at or past
+// lens_in[b] read as zero, outputs at or past lens_out[b] are not stored.  Every kernel is a template on LENS: the dense
+// instantiation takes ConvParams and its code knows nothing of lengths (the same instruction stream as before lengths existed),
+// the LENS one takes ConvParamsL.  (host side: lens_out == NULL means dense)
+struct ConvParamsL : ConvParams { const int* lens_in; const int* lens_out; };
+template <bool LENS> using ConvArgs = std::conditional_t<LENS, ConvParamsL, ConvParams>;
 
 // (conv + bias + residual) * out_scale (+= y) -> post activation -> tanh -> store
 template <bool XF32, bool YF32, bool RES = true>
@@ -91,13 +99,18 @@ __device__ __forceinline__ void post_act_params(const ConvParams& p, int co, flo
     }
 }
 
-template <bool XF32, bool YF32>
-__global__ __launch_bounds__(256) void conv1d_kernel(ConvParams p) {
+template <bool XF32, bool YF32, bool LENS = false>
+__global__ __launch_bounds__(256) void conv1d_kernel(ConvArgs<LENS> p) {
     __shared__ float Xs[CI_T][MAX_SPAN];
     __shared__ __attribute__((aligned(16))) float Ws[CI_T][MAX_K][CO_T];
     const int tid = threadIdx.x;
     const int tc = tid & 15, tl = tid >> 4;           // 16 channel groups x 16 position groups
     const int b = blockIdx.z, co0 = blockIdx.y * CO_T, l0 = blockIdx.x * L_T;
+    int lin_b = 0, lout_b = 0;                        // this row's lengths (LENS only)
+    if constexpr (LENS) {
+        lin_b = p.lens_in[b]; lout_b = p.lens_out[b];
+        if (l0 >= lout_b) return;                     // nothing to store: leave before staging anything
+    }
     const int span = (L_T - 1) * p.stride + (p.K - 1) * p.dil + 1;
     const int in0 = l0 * p.stride - p.pad;            // input position of span element 0
 
@@ -114,7 +127,7 @@ __global__ __launch_bounds__(256) void conv1d_kernel(ConvParams p) {
             const int c = idx / span, sp = idx - c * span;
             const int ci = ci0 + c, li = in0 + sp;
             float v = 0.f;
-            if (ci < p.Cin && li >= 0 && li < p.Lin) {
+            if (ci < p.Cin && li >= 0 && li < (LENS ? lin_b : p.Lin)) {
                 const int64_t xi = ((int64_t)b * p.xC + ci) * p.Lin + li;
                 v = ld1<XF32>(p.x, xi);
                 if (p.act == 1) {
@@ -166,20 +179,25 @@ __global__ __launch_bounds__(256) void conv1d_kernel(ConvParams p) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int l = l0 + 4 * tl + j;
-            if (l >= p.Lout) continue;
+            if (l >= (LENS ? lout_b : p.Lout)) continue;
             conv_store<XF32, YF32>(p, co, ((int64_t)b * p.Cout + co) * p.Lout + l, acc[i][j], bv, pa, pinv_b);
         }
     }
 }
 
 // transposed conv: y[b,co,lo] = bias + sum_ci sum_k act(x)[b,ci,li] w[ci,k,co],  lo = li*stride - pad + k
-template <bool XF32, bool YF32>
-__global__ __launch_bounds__(256) void convT1d_kernel(ConvParams p) {
+template <bool XF32, bool YF32, bool LENS = false>
+__global__ __launch_bounds__(256) void convT1d_kernel(ConvArgs<LENS> p) {
     __shared__ float Xs[CI_T][L_T + 8];
     __shared__ __attribute__((aligned(16))) float Ws[CI_T][MAX_K + 2][CO_T];
     const int tid = threadIdx.x;
     const int tc = tid & 15, tl = tid >> 4;
     const int b = blockIdx.z, co0 = blockIdx.y * CO_T, l0 = blockIdx.x * L_T;
+    int lin_b = 0, lout_b = 0;
+    if constexpr (LENS) {
+        lin_b = p.lens_in[b]; lout_b = p.lens_out[b];
+        if (l0 >= lout_b) return;
+    }
     // input positions that can reach outputs [l0, l0+L_T): li in [floor((l0+pad-K+1)/s), floor((l0+L_T-1+pad)/s)]
     int li_lo = l0 + p.pad - p.K + 1;
     li_lo = li_lo >= 0 ? li_lo / p.stride : -((-li_lo + p.stride - 1) / p.stride);
@@ -198,7 +216,7 @@ __global__ __launch_bounds__(256) void convT1d_kernel(ConvParams p) {
             const int c = idx / nli, sp = idx - c * nli;
             const int ci = ci0 + c, li = li_lo + sp;
             float v = 0.f;
-            if (ci < p.Cin && li >= 0 && li < p.Lin) {
+            if (ci < p.Cin && li >= 0 && li < (LENS ? lin_b : p.Lin)) {
                 v = ld1<XF32>(p.x, ((int64_t)b * p.Cin + ci) * p.Lin + li);
                 if (p.act == 1) {
                     float a = p.aa[ci], bb = p.ab[ci];
@@ -249,7 +267,7 @@ __global__ __launch_bounds__(256) void convT1d_kernel(ConvParams p) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int l = l0 + 4 * tl + j;
-            if (l >= p.Lout) continue;
+            if (l >= (LENS ? lout_b : p.Lout)) continue;
             conv_store<XF32, YF32>(p, co, ((int64_t)b * p.Cout + co) * p.Lout + l, acc[i][j], bv, pa, pinv_b);
         }
     }
@@ -281,9 +299,9 @@ struct ConvPass {        // one pass of the core = one output phase
 // NW/WCO over positions (tiny-Cout layers: WCO = 1); CI input channels per staged chunk; SPAN = LDS row length.
 // NW = 8 (512 threads) stages x once for 128 output channels: half the x traffic and half the staging instructions per
 // FMA of the 4-wave tiling - what the HBM-side pointwise (k = 1) convs need.
-template <int COW, int LPT, int WCO, int CI, int SPAN, bool XF32, bool YF32, int NW = 4>
+template <int COW, int LPT, int WCO, int CI, int SPAN, bool XF32, bool YF32, int NW = 4, bool LENS = false>
 __device__ __forceinline__ void conv_core(const ConvParams& p, const ConvPass& g, float (*Xs)[SPAN], int b, int co_w,
-                                          int lane, int wave, int wave_l) {
+                                          int lane, int wave, int wave_l, int lin_b = 0, int lout_b = 0) {   // row b's lengths (LENS)
     constexpr int LW = 64 * LPT;
     constexpr int NS = SPAN / 64;                     // span slots per lane
     constexpr int NH = CI / NW;                       // channels of a chunk staged by one wave
@@ -327,7 +345,7 @@ __device__ __forceinline__ void conv_core(const ConvParams& p, const ConvPass& g
             for (int s = 0; s < NS; ++s) {
                 const int sp = lane + 64 * s, li = g.in0 + sp;
                 float v = 0.f;
-                if (sp < g.span && ci < p.Cin && li >= 0 && li < p.Lin)
+                if (sp < g.span && ci < p.Cin && li >= 0 && li < (LENS ? lin_b : p.Lin))
                     v = ld1<XF32>(p.x, ((int64_t)b * p.xC + ci) * p.Lin + li);
                 stg[h][s] = v;
             }
@@ -349,7 +367,7 @@ __device__ __forceinline__ void conv_core(const ConvParams& p, const ConvPass& g
                 const int sp = lane + 64 * s, li = g.in0 + sp;
                 if (sp < g.span) {
                     float v = stg[h][s];
-                    if (p.act && ci < p.Cin && li >= 0 && li < p.Lin) v = act_apply(v, p.act, a, inv_b);
+                    if (p.act && ci < p.Cin && li >= 0 && li < (LENS ? lin_b : p.Lin)) v = act_apply(v, p.act, a, inv_b);
                     const int slot = g.S == 1 ? sp : (sp & (g.S - 1)) * g.pspan + (sp >> g.lgS);
                     Xs[buf * CI + c][slot] = v;
                 }
@@ -472,15 +490,15 @@ __device__ __forceinline__ void conv_core(const ConvParams& p, const ConvPass& g
 #pragma unroll
         for (int j = 0; j < LPT; ++j) {
             const int64_t l = g.o0 + (int64_t)(wave_l * LW + lane + 64 * j) * g.ostride;
-            if (l < 0 || l >= p.Lout) continue;
+            if (l < 0 || l >= (LENS ? lout_b : p.Lout)) continue;
             conv_store<XF32, YF32, false>(p, co, ((int64_t)b * p.Cout + co) * p.Lout + l, acc[i][j >> 1][j & 1], bv, pa,
                                           pinv_b);
         }
     }
 }
 
-template <int COW, int LPT, int WCO, int CI, int SPAN, bool XF32, bool YF32, int NW = 4>
-__global__ __launch_bounds__(64 * NW) void conv1d_v2_kernel(ConvParams p) {
+template <int COW, int LPT, int WCO, int CI, int SPAN, bool XF32, bool YF32, int NW = 4, bool LENS = false>
+__global__ __launch_bounds__(64 * NW) void conv1d_v2_kernel(ConvArgs<LENS> p) {
     constexpr int LT = 64 * LPT * (NW / WCO);
     __shared__ float Xs[2 * CI + 1][SPAN];           // two buffers + one pad row for the one-step-ahead prefetch
     const int lane = threadIdx.x & 63;
@@ -488,6 +506,11 @@ __global__ __launch_bounds__(64 * NW) void conv1d_v2_kernel(ConvParams p) {
     const int bt = p.co_fast ? blockIdx.x / p.nco : blockIdx.x % p.ntile;
     const int bc = p.co_fast ? blockIdx.x % p.nco : blockIdx.x / p.ntile;
     const int l0 = bt * LT;
+    int lin_b = 0, lout_b = 0;
+    if constexpr (LENS) {
+        lin_b = p.lens_in[blockIdx.z]; lout_b = p.lens_out[blockIdx.z];
+        if (l0 >= lout_b) return;                     // the whole position tile is past the row's end (or the row inactive)
+    }
     ConvPass g;
     g.ntaps = p.K;
     g.w0 = 0;
@@ -515,8 +538,12 @@ __global__ __launch_bounds__(64 * NW) void conv1d_v2_kernel(ConvParams p) {
         g.xtap = g.pspan;
         g.xtap_wrap = 1 - (S - 1) * g.pspan;
     }
-    conv_core<COW, LPT, WCO, CI, SPAN, XF32, YF32, NW>(p, g, Xs, blockIdx.z, bc * (WCO * COW) + (wave % WCO) * COW, lane,
-                                                            wave, wave / WCO);
+    if constexpr (LENS)
+        conv_core<COW, LPT, WCO, CI, SPAN, XF32, YF32, NW, true>(p, g, Xs, blockIdx.z, bc * (WCO * COW) + (wave % WCO) * COW, lane,
+                                                                      wave, wave / WCO, lin_b, lout_b);
+    else
+        conv_core<COW, LPT, WCO, CI, SPAN, XF32, YF32, NW>(p, g, Xs, blockIdx.z, bc * (WCO * COW) + (wave % WCO) * COW, lane,
+                                                                wave, wave / WCO);
 }
 
 // transposed conv: output lo = q*S + r - pad (phase r < S, input position q):
@@ -525,8 +552,8 @@ __global__ __launch_bounds__(64 * NW) void conv1d_v2_kernel(ConvParams p) {
 // (64*LPT*(4/WCO) input positions q) x (channel tile).  Workgroup ids are laid out so that the S phases of a tile differ
 // by multiples of 8: the hardware deals consecutive ids round-robin to the 8 XCDs, so all phases of a tile run on the
 // SAME XCD within a few ids of each other and their interleaved 4-byte stores merge in that XCD's L2 before write-back.
-template <int COW, int LPT, int WCO, int CI, int SPAN, bool XF32, bool YF32>
-__global__ __launch_bounds__(256) void convT1d_v2_kernel(ConvParams p) {
+template <int COW, int LPT, int WCO, int CI, int SPAN, bool XF32, bool YF32, bool LENS = false>
+__global__ __launch_bounds__(256) void convT1d_v2_kernel(ConvArgs<LENS> p) {
     constexpr int LT = 64 * LPT * (4 / WCO);
     __shared__ float Xs[2 * CI + 1][SPAN];
     const int lane = threadIdx.x & 63;
@@ -552,8 +579,15 @@ __global__ __launch_bounds__(256) void convT1d_v2_kernel(ConvParams p) {
     g.wchan = p.K - (int64_t)(g.ntaps - 1) * S;
     g.o0 = (int64_t)q0 * S + r - p.pad;
     g.ostride = S;
-    conv_core<COW, LPT, WCO, CI, SPAN, XF32, YF32>(p, g, Xs, blockIdx.z, bc * (WCO * COW) + (wave % WCO) * COW, lane,
-                                                        wave, wave / WCO);
+    if constexpr (LENS) {
+        const int lin_b = p.lens_in[blockIdx.z], lout_b = p.lens_out[blockIdx.z];
+        if (g.o0 >= lout_b) return;                   // o0 is the lowest output of this (tile, phase)
+        conv_core<COW, LPT, WCO, CI, SPAN, XF32, YF32, 4, true>(p, g, Xs, blockIdx.z, bc * (WCO * COW) + (wave % WCO) * COW, lane,
+                                                                     wave, wave / WCO, lin_b, lout_b);
+    } else {
+        conv_core<COW, LPT, WCO, CI, SPAN, XF32, YF32>(p, g, Xs, blockIdx.z, bc * (WCO * COW) + (wave % WCO) * COW, lane,
+                                                            wave, wave / WCO);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ few positions, many channels
@@ -565,13 +599,19 @@ __global__ __launch_bounds__(256) void convT1d_v2_kernel(ConvParams p) {
 // activated copy of x (kalle_conv_pad_act), fed to v_pk_fma_f32 as SGPR pairs.  No LDS, no barriers, waves independent.
 // phases > 1 (strided conv): padded index j is stored at (j % phases) * (Lp / phases) + j / phases, so the inputs of a tap
 // for consecutive outputs are consecutive
-__global__ __launch_bounds__(256) void pad_act_kernel(const float* __restrict__ x, float* __restrict__ xp, int C, int Lin,
-                                                      int Lp, int pad, int act, const float* __restrict__ aa,
-                                                      const float* __restrict__ ab, int logscale, float act_param,
-                                                      int phases, int gx) {
+template <bool LENS>
+__device__ __forceinline__ void pad_act_body(const float* __restrict__ x, float* __restrict__ xp, int C, int Lin,
+                                             int Lp, int pad, int act, const float* __restrict__ aa,
+                                             const float* __restrict__ ab, int logscale, float act_param,
+                                             int phases, int gx, const int* __restrict__ lens) {
     const int row = blockIdx.x / gx;                // b * C + c (rows on grid x: B * C exceeds grid y's 65535 at 1024 channels x 64 chunks)
     const int bx = blockIdx.x - row * gx;
     const int c = row % C;
+    int lin_b = 0;                                  // ragged batch: zeros from lens[b] on; an inactive row's copy is not made
+    if constexpr (LENS) {
+        lin_b = lens[row / C];
+        if (lin_b == 0) return;
+    }
     float a = act_param, inv_b = 0.f;
     if (act == 1) {
         a = aa[c];
@@ -582,13 +622,25 @@ __global__ __launch_bounds__(256) void pad_act_kernel(const float* __restrict__ 
     for (int j = bx * 256 + threadIdx.x; j < Lp; j += gx * 256) {
         const int li = j - pad;
         float v = 0.f;
-        if (li >= 0 && li < Lin) {
+        if (li >= 0 && li < (LENS ? lin_b : Lin)) {
             v = x[(int64_t)row * Lin + li];
             if (act) v = act_apply(v, act, a, inv_b);
         }
         const int slot = phases == 1 ? j : (j % phases) * (Lp / phases) + j / phases;
         xp[(int64_t)row * Lp + slot] = v;
     }
+}
+__global__ __launch_bounds__(256) void pad_act_kernel(const float* __restrict__ x, float* __restrict__ xp, int C, int Lin,
+                                                      int Lp, int pad, int act, const float* __restrict__ aa,
+                                                      const float* __restrict__ ab, int logscale, float act_param,
+                                                      int phases, int gx) {
+    pad_act_body<false>(x, xp, C, Lin, Lp, pad, act, aa, ab, logscale, act_param, phases, gx, nullptr);
+}
+__global__ __launch_bounds__(256) void pad_act_lens_kernel(const float* __restrict__ x, float* __restrict__ xp, int C, int Lin,
+                                                           int Lp, int pad, int act, const float* __restrict__ aa,
+                                                           const float* __restrict__ ab, int logscale, float act_param,
+                                                           int phases, int gx, const int* __restrict__ lens) {
+    pad_act_body<true>(x, xp, C, Lin, Lp, pad, act, aa, ab, logscale, act_param, phases, gx, lens);
 }
 
 struct ConvCParams {
@@ -604,8 +656,11 @@ struct ConvCParams {
     float out_scale;
     int pact; const float* paa; const float* pab; int plogscale; float pparam;
 };
+struct ConvCParamsL : ConvCParams { const int* lens_out; };   // ragged batch: row b stores its first lens_out[b] outputs only
+template <bool LENS> using ConvCArgs = std::conditional_t<LENS, ConvCParamsL, ConvCParams>;
 
-__global__ __launch_bounds__(256) void conv1d_cfirst_kernel(ConvCParams p) {
+template <bool LENS = false>
+__global__ __launch_bounds__(256) void conv1d_cfirst_kernel(ConvCArgs<LENS> p) {
     constexpr int P = 16, D = 4;                    // positions per wave, weight prefetch depth
     __shared__ float red[3 * 64 * 64];              // partial accumulators of the input-channel splits (48 KiB)
     const int lane = threadIdx.x & 63;
@@ -615,7 +670,15 @@ __global__ __launch_bounds__(256) void conv1d_cfirst_kernel(ConvCParams p) {
     const int sp = wave % S;                        // this wave's input-channel slice (within the workgroup's)
     const int ph = blockIdx.x % p.nphase;           // output phase (transposed conv), 0 otherwise
     const int l0 = ((blockIdx.x / p.nphase) * (4 / S) + wave / S) * P;   // first (input-side) position of the tile
-    const bool live = l0 < p.npos;                  // (whole tile groups stay together: sp-waves of a tile share `live`)
+    bool live_b = l0 < p.npos;                      // (whole tile groups stay together: sp-waves of a tile share `live`)
+    int lout_b = 0;
+    if constexpr (LENS) {                           // outputs of position q: q * ostride + ph - opad, rising with q
+        lout_b = p.lens_out[b];
+        const int64_t shift = p.nphase == 1 ? 0 : ph - p.opad;
+        if ((int64_t)(blockIdx.x / p.nphase) * (4 / S) * P * p.ostride + shift >= lout_b) return;   // the workgroup's first tile is past the end
+        live_b = live_b && (int64_t)l0 * p.ostride + shift < lout_b;
+    }
+    const bool live = live_b;
     const int co = blockIdx.y * 256 + 4 * lane;
     const int cw = min(co, p.CoutP - 4);            // clamped weight column (lanes past Cout are never stored)
     const int cper = (p.Cin + S * p.ks - 1) / (S * p.ks);
@@ -739,7 +802,7 @@ __global__ __launch_bounds__(256) void conv1d_cfirst_kernel(ConvCParams p) {
 #pragma unroll
             for (int j = 0; j < P; ++j) {
                 const int64_t l = (int64_t)(l0 + j) * p.ostride + oo;
-                if (l >= 0 && l < p.Lout) pp[l] = acc[c][j >> 1][j & 1];
+                if (l >= 0 && l < (LENS ? lout_b : p.Lout)) pp[l] = acc[c][j >> 1][j & 1];
             }
         }
         return;
@@ -761,7 +824,7 @@ __global__ __launch_bounds__(256) void conv1d_cfirst_kernel(ConvCParams p) {
 #pragma unroll
         for (int j = 0; j < P; ++j) {
             const int64_t l = (int64_t)(l0 + j) * p.ostride + oo;
-            if (l < 0 || l >= p.Lout) continue;
+            if (l < 0 || l >= (LENS ? lout_b : p.Lout)) continue;
             float v = (acc[c][j >> 1][j & 1] + bv) * p.out_scale;   // (residual already inside acc)
             if (p.post & 2) v += yp[l];
             if (p.y_raw) p.y_raw[((int64_t)b * p.Cout + cc) * p.Lout + l] = v;
@@ -773,10 +836,14 @@ __global__ __launch_bounds__(256) void conv1d_cfirst_kernel(ConvCParams p) {
 }
 
 // sums the input-channel slices of a split conv1d_cfirst launch and applies the conv epilogue (same order as above)
-__global__ __launch_bounds__(256) void cfirst_finish_kernel(ConvCParams p) {
+template <bool LENS = false>
+__global__ __launch_bounds__(256) void cfirst_finish_kernel(ConvCArgs<LENS> p) {
     const int64_t n = (int64_t)p.B * p.Cout * p.Lout;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const int cc = (int)((i / p.Lout) % p.Cout);
+        if constexpr (LENS) {
+            if ((int)(i % p.Lout) >= p.lens_out[i / ((int64_t)p.Cout * p.Lout)]) continue;   // (its partial sums were not written)
+        }
         float v = p.res ? p.res[i] : 0.f;
         for (int s = 0; s < p.ks; ++s) v += p.part[(int64_t)s * n + i];
         v = (v + (p.bias ? p.bias[cc] : 0.f)) * p.out_scale;
@@ -1142,23 +1209,44 @@ constexpr int64_t form_key(int cow, int lpt, int wco, int ci, int span, int nw) 
 }
 int64_t form_key(const TileForm& f) { return form_key(f.cow, f.lpt, f.wco, f.ci, f.span, f.nw); }
 
+// (every kernel exists twice: the dense instantiation, whose code does not know of lengths, and the LENS one a ragged call gets)
 template <int COW, int LPT, int WCO, int CI, int SPAN, int NW>
-void launch_v2(const ConvPlan& pl, const ConvParams& p, bool f32, hipStream_t st) {
-    if (f32) KALLE_LAUNCH((conv1d_v2_kernel<COW, LPT, WCO, CI, SPAN, true, true, NW>), pl.grid, pl.block, 0, st, p);
-    else KALLE_LAUNCH((conv1d_v2_kernel<COW, LPT, WCO, CI, SPAN, false, false, NW>), pl.grid, pl.block, 0, st, p);
+void launch_v2(const ConvPlan& pl, const ConvParamsL& p, bool f32, hipStream_t st) {
+    const ConvParams& d = p;
+    if (p.lens_out) {
+        if (f32) KALLE_LAUNCH((conv1d_v2_kernel<COW, LPT, WCO, CI, SPAN, true, true, NW, true>), pl.grid, pl.block, 0, st, p);
+        else KALLE_LAUNCH((conv1d_v2_kernel<COW, LPT, WCO, CI, SPAN, false, false, NW, true>), pl.grid, pl.block, 0, st, p);
+    } else if (f32) KALLE_LAUNCH((conv1d_v2_kernel<COW, LPT, WCO, CI, SPAN, true, true, NW>), pl.grid, pl.block, 0, st, d);
+    else KALLE_LAUNCH((conv1d_v2_kernel<COW, LPT, WCO, CI, SPAN, false, false, NW>), pl.grid, pl.block, 0, st, d);
 }
 template <int COW, int LPT, int WCO>
-void launch_tv2(const ConvPlan& pl, const ConvParams& p, bool f32, hipStream_t st) {
-    if (f32) KALLE_LAUNCH((convT1d_v2_kernel<COW, LPT, WCO, 8, 640, true, true>), pl.grid, pl.block, 0, st, p);
-    else KALLE_LAUNCH((convT1d_v2_kernel<COW, LPT, WCO, 8, 640, false, false>), pl.grid, pl.block, 0, st, p);
+void launch_tv2(const ConvPlan& pl, const ConvParamsL& p, bool f32, hipStream_t st) {
+    const ConvParams& d = p;
+    if (p.lens_out) {
+        if (f32) KALLE_LAUNCH((convT1d_v2_kernel<COW, LPT, WCO, 8, 640, true, true, true>), pl.grid, pl.block, 0, st, p);
+        else KALLE_LAUNCH((convT1d_v2_kernel<COW, LPT, WCO, 8, 640, false, false, true>), pl.grid, pl.block, 0, st, p);
+    } else if (f32) KALLE_LAUNCH((convT1d_v2_kernel<COW, LPT, WCO, 8, 640, true, true>), pl.grid, pl.block, 0, st, d);
+    else KALLE_LAUNCH((convT1d_v2_kernel<COW, LPT, WCO, 8, 640, false, false>), pl.grid, pl.block, 0, st, d);
+}
+template <bool LENS>
+void launch_v1(const ConvPlan& pl, const ConvArgs<LENS>& p, bool xf, bool yf, hipStream_t st) {
+    if (xf && yf) KALLE_LAUNCH((conv1d_kernel<true, true, LENS>), pl.grid, pl.block, 0, st, p);
+    else if (xf) KALLE_LAUNCH((conv1d_kernel<true, false, LENS>), pl.grid, pl.block, 0, st, p);
+    else if (yf) KALLE_LAUNCH((conv1d_kernel<false, true, LENS>), pl.grid, pl.block, 0, st, p);
+    else KALLE_LAUNCH((conv1d_kernel<false, false, LENS>), pl.grid, pl.block, 0, st, p);
+}
+template <bool LENS>
+void launch_tv1(const ConvPlan& pl, const ConvArgs<LENS>& p, bool xf, bool yf, hipStream_t st) {
+    if (xf && yf) KALLE_LAUNCH((convT1d_kernel<true, true, LENS>), pl.grid, pl.block, 0, st, p);
+    else if (xf) KALLE_LAUNCH((convT1d_kernel<true, false, LENS>), pl.grid, pl.block, 0, st, p);
+    else if (yf) KALLE_LAUNCH((convT1d_kernel<false, true, LENS>), pl.grid, pl.block, 0, st, p);
+    else KALLE_LAUNCH((convT1d_kernel<false, false, LENS>), pl.grid, pl.block, 0, st, p);
 }
 // false: the plan names a form that was never compiled (a planner bug; nothing is launched)
-bool launch_conv1d(const ConvPlan& pl, const ConvParams& p, bool xf, bool yf, hipStream_t st) {
+bool launch_conv1d(const ConvPlan& pl, const ConvParamsL& p, bool xf, bool yf, hipStream_t st) {
     if (pl.family == 1) {
-        if (xf && yf) KALLE_LAUNCH((conv1d_kernel<true, true>), pl.grid, pl.block, 0, st, p);
-        else if (xf) KALLE_LAUNCH((conv1d_kernel<true, false>), pl.grid, pl.block, 0, st, p);
-        else if (yf) KALLE_LAUNCH((conv1d_kernel<false, true>), pl.grid, pl.block, 0, st, p);
-        else KALLE_LAUNCH((conv1d_kernel<false, false>), pl.grid, pl.block, 0, st, p);
+        if (p.lens_out) launch_v1<true>(pl, p, xf, yf, st);
+        else launch_v1<false>(pl, p, xf, yf, st);
         return true;
     }
     switch (form_key(pl.form)) {
@@ -1180,12 +1268,10 @@ bool launch_conv1d(const ConvPlan& pl, const ConvParams& p, bool xf, bool yf, hi
     }
     return true;
 }
-bool launch_convT(const ConvPlan& pl, const ConvParams& p, bool xf, bool yf, hipStream_t st) {
+bool launch_convT(const ConvPlan& pl, const ConvParamsL& p, bool xf, bool yf, hipStream_t st) {
     if (pl.family == 3) {
-        if (xf && yf) KALLE_LAUNCH((convT1d_kernel<true, true>), pl.grid, pl.block, 0, st, p);
-        else if (xf) KALLE_LAUNCH((convT1d_kernel<true, false>), pl.grid, pl.block, 0, st, p);
-        else if (yf) KALLE_LAUNCH((convT1d_kernel<false, true>), pl.grid, pl.block, 0, st, p);
-        else KALLE_LAUNCH((convT1d_kernel<false, false>), pl.grid, pl.block, 0, st, p);
+        if (p.lens_out) launch_tv1<true>(pl, p, xf, yf, st);
+        else launch_tv1<false>(pl, p, xf, yf, st);
         return true;
     }
     switch (form_key(pl.form)) {
@@ -1298,12 +1384,41 @@ int plan_cfirst_T(bool tensors, int B, int Cin, int Lp, int Cout, int Lout, int 
     return KALLE_OK;
 }
 
-void launch_cfirst(const ConvPlan& pl, const ConvCParams& p, hipStream_t st) {
-    KALLE_LAUNCH(conv1d_cfirst_kernel, pl.grid, pl.block, 0, st, p);
+void launch_cfirst(const ConvPlan& pl, const ConvCParamsL& p, hipStream_t st) {
+    const ConvCParams& d = p;
+    if (p.lens_out) KALLE_LAUNCH(conv1d_cfirst_kernel<true>, pl.grid, pl.block, 0, st, p);
+    else KALLE_LAUNCH(conv1d_cfirst_kernel<false>, pl.grid, pl.block, 0, st, d);
     if (pl.ks > 1) {
         const int64_t n = (int64_t)p.B * p.Cout * p.Lout;
-        KALLE_LAUNCH(cfirst_finish_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 2048)), dim3(256), 0, st, p);
+        const dim3 grid((unsigned)std::min<int64_t>((n + 255) / 256, 2048));
+        if (p.lens_out) KALLE_LAUNCH(cfirst_finish_kernel<true>, grid, dim3(256), 0, st, p);
+        else KALLE_LAUNCH(cfirst_finish_kernel<false>, grid, dim3(256), 0, st, d);
     }
+}
+
+// ---- ragged batches: the per-row lengths of the ..._lens entry points (contract: include/kalle_hip.h)
+// Each array comes as a host copy (checked here, read by nobody else) and a device copy (read by the kernels).
+enum { LENS_DENSE, LENS_LIVE, LENS_IDLE, LENS_BAD };
+// h_in may be absent (an entry point that takes output lengths only) and so may h_out; Lin / Lout < 0: that bound is not known
+// to the entry point.  max_out(len_in): the most outputs the layer makes of len_in inputs (0 of 0: an inactive row).
+template <class F>
+int read_lens(int n_given, int n_taken, const int32_t* h_in, const int32_t* h_out, int B, int Lin, int Lout, F max_out) {
+    if (n_given == 0) return LENS_DENSE;
+    if (n_given != n_taken) return LENS_BAD;        // a host copy without its device copy, lens_in without lens_out, ...
+    bool any = false;
+    for (int b = 0; b < B; ++b) {
+        const int64_t li = h_in ? h_in[b] : -1, lo = h_out ? h_out[b] : -1;
+        if (h_in && (li < 0 || (Lin >= 0 && li > Lin))) return LENS_BAD;
+        if (h_out && (lo < 0 || (Lout >= 0 && lo > Lout))) return LENS_BAD;
+        if (h_in && h_out && lo > (li == 0 ? 0 : max_out(li))) return LENS_BAD;
+        any = any || (h_out ? lo > 0 : li > 0);
+    }
+    return any ? LENS_LIVE : LENS_IDLE;
+}
+int count_given(std::initializer_list<const void*> ps) {
+    int n = 0;
+    for (const void* q : ps) n += q != nullptr;
+    return n;
 }
 
 // ---- which family a call gets (kalle_conv_plan / kalle_conv_transpose_plan; kalle_audio_amd/conv_ops.py asks them)
@@ -1342,38 +1457,71 @@ extern "C" int kalle_conv_last_plan(void) { return g_conv_plan; }
 // library-internal (conv1d_bwd.hip records its launches through it): not part of the ABI, not exported
 extern "C" __attribute__((visibility("hidden"))) void kalle_set_conv_plan(int plan) { g_conv_plan = plan; }
 
-extern "C" int kalle_conv1d_fwd(const void* x, int x_dtype, const float* w_packed, const float* bias, void* y,
-                                int y_dtype, int B, int Cin, int Lin, int Cout, int Lout, int ksize, int stride,
-                                int padding, int dilation, const kalle_act* in_act, const kalle_conv_epilogue* epi,
-                                void* stream) {
+extern "C" int kalle_conv1d_fwd_lens(const void* x, int x_dtype, const float* w_packed, const float* bias, void* y,
+                                     int y_dtype, int B, int Cin, int Lin, int Cout, int Lout, int ksize, int stride,
+                                     int padding, int dilation, const kalle_act* in_act, const kalle_conv_epilogue* epi,
+                                     const int32_t* lens_in_host, const int32_t* lens_in_dev, const int32_t* lens_out_host,
+                                     const int32_t* lens_out_dev, void* stream) {
     g_conv_plan = 0;
-    ConvParams p{};
+    ConvParamsL p{};
     ConvPlan pl;
     p.x = x; p.w = w_packed; p.bias = bias; p.y = y;
     const int rc = plan_conv1d(x && w_packed && y, x_dtype, y_dtype, B, Cin, Lin, Cout, Lout, ksize, stride, padding, dilation,
                                in_act, epi, p, pl);
     if (rc != KALLE_OK) return rc;
+    const int lens = read_lens(count_given({lens_in_host, lens_in_dev, lens_out_host, lens_out_dev}), 4, lens_in_host, lens_out_host,
+                               B, Lin, Lout, [&](int64_t li) { return (li - 1 + padding) / stride + 1; });
+    if (lens == LENS_BAD) return KALLE_ERR_ARG;
+    p.lens_in = lens_in_dev; p.lens_out = lens_out_dev;
+    if (lens == LENS_IDLE) {                        // every row inactive: nothing to launch; the plan is the dense call's
+        g_conv_plan = pl.word;
+        return KALLE_OK;
+    }
     if (!launch_conv1d(pl, p, x_dtype == KALLE_F32, y_dtype == KALLE_F32, static_cast<hipStream_t>(stream)))
         return KALLE_ERR_UNSUPPORTED;
     g_conv_plan = pl.word;
     return kalle_check_launch();
 }
+extern "C" int kalle_conv1d_fwd(const void* x, int x_dtype, const float* w_packed, const float* bias, void* y,
+                                int y_dtype, int B, int Cin, int Lin, int Cout, int Lout, int ksize, int stride,
+                                int padding, int dilation, const kalle_act* in_act, const kalle_conv_epilogue* epi,
+                                void* stream) {
+    return kalle_conv1d_fwd_lens(x, x_dtype, w_packed, bias, y, y_dtype, B, Cin, Lin, Cout, Lout, ksize, stride, padding, dilation,
+                                 in_act, epi, nullptr, nullptr, nullptr, nullptr, stream);
+}
 
-extern "C" int kalle_conv_transpose1d_fwd(const void* x, int x_dtype, const float* w_packed, const float* bias, void* y,
-                                          int y_dtype, int B, int Cin, int Lin, int Cout, int Lout, int ksize,
-                                          int stride, int padding, const kalle_act* in_act,
-                                          const kalle_conv_epilogue* epi, void* stream) {
+extern "C" int kalle_conv_transpose1d_fwd_lens(const void* x, int x_dtype, const float* w_packed, const float* bias, void* y,
+                                               int y_dtype, int B, int Cin, int Lin, int Cout, int Lout, int ksize,
+                                               int stride, int padding, const kalle_act* in_act,
+                                               const kalle_conv_epilogue* epi, const int32_t* lens_in_host,
+                                               const int32_t* lens_in_dev, const int32_t* lens_out_host,
+                                               const int32_t* lens_out_dev, void* stream) {
     g_conv_plan = 0;
-    ConvParams p{};
+    ConvParamsL p{};
     ConvPlan pl;
     p.x = x; p.w = w_packed; p.bias = bias; p.y = y;
     const int rc = plan_convT(x && w_packed && y, x_dtype, y_dtype, B, Cin, Lin, Cout, Lout, ksize, stride, padding, in_act, epi,
                               p, pl);
     if (rc != KALLE_OK) return rc;
+    const int lens = read_lens(count_given({lens_in_host, lens_in_dev, lens_out_host, lens_out_dev}), 4, lens_in_host, lens_out_host,
+                               B, Lin, Lout, [&](int64_t li) { return (li - 1) * stride - padding + ksize; });
+    if (lens == LENS_BAD) return KALLE_ERR_ARG;
+    p.lens_in = lens_in_dev; p.lens_out = lens_out_dev;
+    if (lens == LENS_IDLE) {
+        g_conv_plan = pl.word;
+        return KALLE_OK;
+    }
     if (!launch_convT(pl, p, x_dtype == KALLE_F32, y_dtype == KALLE_F32, static_cast<hipStream_t>(stream)))
         return KALLE_ERR_UNSUPPORTED;
     g_conv_plan = pl.word;
     return kalle_check_launch();
+}
+extern "C" int kalle_conv_transpose1d_fwd(const void* x, int x_dtype, const float* w_packed, const float* bias, void* y,
+                                          int y_dtype, int B, int Cin, int Lin, int Cout, int Lout, int ksize,
+                                          int stride, int padding, const kalle_act* in_act,
+                                          const kalle_conv_epilogue* epi, void* stream) {
+    return kalle_conv_transpose1d_fwd_lens(x, x_dtype, w_packed, bias, y, y_dtype, B, Cin, Lin, Cout, Lout, ksize, stride, padding,
+                                           in_act, epi, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int kalle_conv_pad_len(int Lout, int ksize, int stride, int padding, int dilation) {
@@ -1383,18 +1531,31 @@ extern "C" int kalle_convT_pad_len(int Lout, int ksize, int stride, int padding)
     return convT_pad_geom(Lout, ksize, stride, padding).Lp;
 }
 
-extern "C" int kalle_conv_pad_act(const float* x, float* x_padded, int B, int C, int Lin, int Lp, int padding,
-                                  const kalle_act* act, int phases, void* stream) {
+extern "C" int kalle_conv_pad_act_lens(const float* x, float* x_padded, int B, int C, int Lin, int Lp, int padding,
+                                       const kalle_act* act, int phases, const int32_t* lens_in_host, const int32_t* lens_in_dev,
+                                       void* stream) {
     if (!x || !x_padded || B <= 0 || C <= 0 || Lin <= 0 || Lp <= 0 || padding < 0 || phases <= 0 || Lp % phases)
         return KALLE_ERR_ARG;
     const int gx = (Lp + 255) / 256 > 64 ? 64 : (Lp + 255) / 256;
     if ((int64_t)B * C * gx > 0x7fffffff) return KALLE_ERR_ARG;
     ActArgs a;
     if (!read_act(act, a, false)) return KALLE_ERR_ARG;
-    KALLE_LAUNCH(pad_act_kernel, dim3((unsigned)(B * C * gx)), dim3(256), 0,
-                 static_cast<hipStream_t>(stream), x, x_padded, C, Lin, Lp, padding, a.code, a.alpha, a.beta, a.logscale, a.param,
-                 phases, gx);
+    const int lens = read_lens(count_given({lens_in_host, lens_in_dev}), 2, lens_in_host, nullptr, B, Lin, -1, [](int64_t) { return 0; });
+    if (lens == LENS_BAD) return KALLE_ERR_ARG;
+    if (lens == LENS_IDLE) return KALLE_OK;
+    const dim3 grid((unsigned)(B * C * gx));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (lens == LENS_LIVE)
+        KALLE_LAUNCH(pad_act_lens_kernel, grid, dim3(256), 0, st, x, x_padded, C, Lin, Lp, padding, a.code, a.alpha, a.beta, a.logscale,
+                     a.param, phases, gx, lens_in_dev);
+    else
+        KALLE_LAUNCH(pad_act_kernel, grid, dim3(256), 0, st, x, x_padded, C, Lin, Lp, padding, a.code, a.alpha, a.beta, a.logscale,
+                     a.param, phases, gx);
     return kalle_check_launch();
+}
+extern "C" int kalle_conv_pad_act(const float* x, float* x_padded, int B, int C, int Lin, int Lp, int padding,
+                                  const kalle_act* act, int phases, void* stream) {
+    return kalle_conv_pad_act_lens(x, x_padded, B, C, Lin, Lp, padding, act, phases, nullptr, nullptr, stream);
 }
 
 extern "C" int kalle_conv_cfirst_ws_floats(int B, int Cin, int Cout, int Lout, int ksize) {
@@ -1402,33 +1563,56 @@ extern "C" int kalle_conv_cfirst_ws_floats(int B, int Cin, int Cout, int Lout, i
     return cfirst_ws_floats(B, Cin, Cout, Lout, ksize);
 }
 
-extern "C" int kalle_conv1d_cfirst_fwd(const float* x_padded, const float* w_packed, const float* bias, float* y, int B,
-                                       int Cin, int Lp, int Cout, int Lout, int ksize, int stride, int padding,
-                                       int dilation, const kalle_conv_epilogue* epi, float* workspace, void* stream) {
+extern "C" int kalle_conv1d_cfirst_fwd_lens(const float* x_padded, const float* w_packed, const float* bias, float* y, int B,
+                                            int Cin, int Lp, int Cout, int Lout, int ksize, int stride, int padding,
+                                            int dilation, const kalle_conv_epilogue* epi, float* workspace,
+                                            const int32_t* lens_in_host, const int32_t* lens_in_dev, const int32_t* lens_out_host,
+                                            const int32_t* lens_out_dev, void* stream) {
     g_conv_plan = 0;
-    ConvCParams p{};
+    ConvCParamsL p{};
     ConvPlan pl;
     p.xp = x_padded; p.w = w_packed; p.bias = bias; p.y = y; p.part = workspace;
     const int rc = plan_cfirst(x_padded && w_packed && y, B, Cin, Lp, Cout, Lout, ksize, stride, padding, dilation, epi,
                                workspace != nullptr, p, pl);
     if (rc != KALLE_OK) return rc;
-    launch_cfirst(pl, p, static_cast<hipStream_t>(stream));
+    // (the padded copy hides Lin: kalle_conv_pad_act_lens holds the input lengths to it)
+    const int lens = read_lens(count_given({lens_in_host, lens_in_dev, lens_out_host, lens_out_dev}), 4, lens_in_host, lens_out_host,
+                               B, -1, Lout, [&](int64_t li) { return (li - 1 + padding) / stride + 1; });
+    if (lens == LENS_BAD) return KALLE_ERR_ARG;
+    p.lens_out = lens_out_dev;                      // (the input lengths acted in kalle_conv_pad_act_lens)
+    if (lens != LENS_IDLE) launch_cfirst(pl, p, static_cast<hipStream_t>(stream));
     g_conv_plan = pl.word;
-    return kalle_check_launch();
+    return lens == LENS_IDLE ? KALLE_OK : kalle_check_launch();
+}
+extern "C" int kalle_conv1d_cfirst_fwd(const float* x_padded, const float* w_packed, const float* bias, float* y, int B,
+                                       int Cin, int Lp, int Cout, int Lout, int ksize, int stride, int padding,
+                                       int dilation, const kalle_conv_epilogue* epi, float* workspace, void* stream) {
+    return kalle_conv1d_cfirst_fwd_lens(x_padded, w_packed, bias, y, B, Cin, Lp, Cout, Lout, ksize, stride, padding, dilation, epi,
+                                        workspace, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
-extern "C" int kalle_conv_transpose1d_cfirst_fwd(const float* x_padded, const float* w_packed, const float* bias, float* y,
-                                                 int B, int Cin, int Lp, int Cout, int Lout, int ksize, int stride,
-                                                 int padding, const kalle_conv_epilogue* epi, void* stream) {
+extern "C" int kalle_conv_transpose1d_cfirst_fwd_lens(const float* x_padded, const float* w_packed, const float* bias, float* y,
+                                                      int B, int Cin, int Lp, int Cout, int Lout, int ksize, int stride,
+                                                      int padding, const kalle_conv_epilogue* epi, const int32_t* lens_out_host,
+                                                      const int32_t* lens_out_dev, void* stream) {
     g_conv_plan = 0;
-    ConvCParams p{};
+    ConvCParamsL p{};
     ConvPlan pl;
     p.xp = x_padded; p.w = w_packed; p.bias = bias; p.y = y;
     const int rc = plan_cfirst_T(x_padded && w_packed && y, B, Cin, Lp, Cout, Lout, ksize, stride, padding, epi, p, pl);
     if (rc != KALLE_OK) return rc;
-    launch_cfirst(pl, p, static_cast<hipStream_t>(stream));
+    const int lens = read_lens(count_given({lens_out_host, lens_out_dev}), 2, nullptr, lens_out_host, B, -1, Lout, [](int64_t) { return 0; });
+    if (lens == LENS_BAD) return KALLE_ERR_ARG;
+    p.lens_out = lens_out_dev;
+    if (lens != LENS_IDLE) launch_cfirst(pl, p, static_cast<hipStream_t>(stream));
     g_conv_plan = pl.word;
-    return kalle_check_launch();
+    return lens == LENS_IDLE ? KALLE_OK : kalle_check_launch();
+}
+extern "C" int kalle_conv_transpose1d_cfirst_fwd(const float* x_padded, const float* w_packed, const float* bias, float* y,
+                                                 int B, int Cin, int Lp, int Cout, int Lout, int ksize, int stride,
+                                                 int padding, const kalle_conv_epilogue* epi, void* stream) {
+    return kalle_conv_transpose1d_cfirst_fwd_lens(x_padded, w_packed, bias, y, B, Cin, Lp, Cout, Lout, ksize, stride, padding, epi,
+                                                  nullptr, nullptr, stream);
 }
 
 // The two queries: the dispatch of conv_ops.conv1d / conv_transpose1d for any caller, without a device.  The channels-per-lane

@@ -524,7 +524,14 @@ class BigVGANFlowVAE(nn.Module):
         eps = torch.randn_like(m_q) if noise is None else noise
         return (m_q + eps * torch.exp(logs_q)).contiguous(), logs_q
 
-    def forward(self, x, noise=None):
+    @staticmethod
+    def _no_lengths(lengths):
+        if lengths is not None:
+            raise NotImplementedError("ragged lengths on the mel-VAE: its anti-aliased activations and flow read neighbouring "
+                                      "positions, and its kernels take no lengths (the Oobleck VAE does: autoencoders.py)")
+
+    def forward(self, x, noise=None, lengths=None):
+        self._no_lengths(lengths)
         x = self.audio_encoder(x)
         assert self.use_vae
         z, logs_q = self._sample(x, noise)
@@ -532,10 +539,12 @@ class BigVGANFlowVAE(nn.Module):
         x = self._decode(z)
         return x, (z_p, logs_q, None, None)
 
-    def extract_latents(self, x):
+    def extract_latents(self, x, lengths=None):
+        self._no_lengths(lengths)
         return self.audio_encoder(x)
 
-    def inference_from_latents(self, x, do_sample=True, noise=None):
+    def inference_from_latents(self, x, do_sample=True, noise=None, lengths=None):
+        self._no_lengths(lengths)
         x = _prep(x)
         if self.use_vae and do_sample:
             assert x.size(1) == self.latent_dim * 2, "Input must be like [B, D, H]"

@@ -31,6 +31,12 @@ def _wants_grad(module, x):
     return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in module.parameters()))
 
 
+def _no_grad_with_lens(module, x, lens, act=None):
+    """ragged lengths are an inference feature: no backward kernel takes them"""
+    if lens is not None and (_wants_grad(module, x) or (act is not None and _wants_grad(act, x))):
+        raise NotImplementedError("ragged lengths with gradients: the backward kernels take no lengths (run under torch.no_grad())")
+
+
 def _act_args(act):
     """(code, alpha, beta, logscale) for the conv kernels' fused input activation."""
     if act is None or isinstance(act, nn.Identity):
@@ -85,9 +91,15 @@ class WNConv1d(_WNBase):
         self.weight_g = nn.Parameter(ref.weight.detach().flatten(1).norm(dim=1).view(-1, 1, 1).clone())
         self.bias = nn.Parameter(ref.bias.detach().clone()) if bias else None
 
-    def forward(self, x, act=None, residual=None, post=0, post_act=None, want_raw=False):
-        """want_raw: also return the value before `post_act` -> (activated, raw)"""
+    def out_len(self, L):
+        """outputs of L inputs (this layer's own formula: what a ragged batch applies per row)"""
+        return conv_ops.conv_len(L, self.kernel_size, self.stride, self.padding, self.pad_right, self.dilation)
+
+    def forward(self, x, act=None, residual=None, post=0, post_act=None, want_raw=False, lens=None, zero_tail=False):
+        """want_raw: also return the value before `post_act` -> (activated, raw); lens: a conv_ops.Lens, row b of x is a
+        tensor of lens.host[b] positions (zero_tail: the output is zero past each row's length, not left unwritten)"""
         x = _prep(x)
+        _no_grad_with_lens(self, x, lens, act)
         if _wants_grad(self, x) or (act is not None and _wants_grad(act, x)):
             assert post_act is None and not want_raw, "fused output activations belong to the inference path"
             from ... import conv_train
@@ -96,7 +108,7 @@ class WNConv1d(_WNBase):
         return conv_ops.conv1d(x, self._packed(), self._bias(), Cout=self.out_channels, K=self.kernel_size,
                                stride=self.stride, padding=self.padding, dilation=self.dilation, act=code, alpha=a,
                                beta=b, logscale=ls, residual=residual, post=post, post_act=_post_act(post_act),
-                               want_raw=want_raw, pad_right=self.pad_right)
+                               want_raw=want_raw, pad_right=self.pad_right, lens=lens, zero_tail=zero_tail)
 
 
 class WNConvTranspose1d(_WNBase):
@@ -112,8 +124,12 @@ class WNConvTranspose1d(_WNBase):
         self.weight_g = nn.Parameter(ref.weight.detach().flatten(1).norm(dim=1).view(-1, 1, 1).clone())
         self.bias = nn.Parameter(ref.bias.detach().clone()) if bias else None
 
-    def forward(self, x, act=None, post_act=None, want_raw=False):
+    def out_len(self, L):
+        return conv_ops.conv_transpose_len(L, self.kernel_size, self.stride, self.padding)
+
+    def forward(self, x, act=None, post_act=None, want_raw=False, lens=None):
         x = _prep(x)
+        _no_grad_with_lens(self, x, lens, act)
         if _wants_grad(self, x) or (act is not None and _wants_grad(act, x)):
             assert post_act is None and not want_raw, "fused output activations belong to the inference path"
             from ... import conv_train
@@ -121,7 +137,8 @@ class WNConvTranspose1d(_WNBase):
         code, a, b, ls = _act_args(act)
         return conv_ops.conv_transpose1d(x, self._packed(), self._bias(), Cout=self.out_channels,
                                          K=self.kernel_size, stride=self.stride, padding=self.padding, act=code,
-                                         alpha=a, beta=b, logscale=ls, post_act=_post_act(post_act), want_raw=want_raw)
+                                         alpha=a, beta=b, logscale=ls, post_act=_post_act(post_act), want_raw=want_raw,
+                                         lens=lens)
 
 
 class Activation1d(nn.Module):
@@ -195,21 +212,24 @@ class ResidualUnit(nn.Module):
             get_activation("snake" if use_snake else "elu", antialias=antialias_activation, channels=out_channels),
             WNConv1d(in_channels=out_channels, out_channels=out_channels, kernel_size=1))
 
-    def forward(self, x, post_act=None, x_act=None, dual=False):
+    def forward(self, x, post_act=None, x_act=None, dual=False, lens=None):
         """x_act: layers[0](x) if the producer already stored it (then the k=7 conv stages its input without any activation
-        work); dual: return (post_act(y), y) - the pair the next unit wants"""
+        work); dual: return (post_act(y), y) - the pair the next unit wants; lens: the rows' lengths (both convs keep them)"""
         x = _prep(x)
+        _no_grad_with_lens(self, x, lens)
         if self.antialias:              # plain composition (the producer-side activation fusion needs pointwise activations)
+            if lens is not None:
+                raise NotImplementedError("ragged lengths with antialias_activation: its FIRs read neighbouring positions")
             assert post_act is None and x_act is None and not dual
             return _ac(self.layers[3], _ac(self.layers[1], x, self.layers[0]), self.layers[2], residual=x)
         if _wants_grad(self, x):        # training: two autograd units, raw tensors in between
             h = self.layers[1](x, act=self.layers[0])
             return self.layers[3](h, act=self.layers[2], residual=x)
         if x_act is not None:
-            h = self.layers[1](x_act, post_act=self.layers[2])
+            h = self.layers[1](x_act, post_act=self.layers[2], lens=lens)
         else:
-            h = self.layers[1](x, act=self.layers[0], post_act=self.layers[2])
-        return self.layers[3](h, residual=x, post_act=post_act, want_raw=dual)
+            h = self.layers[1](x, act=self.layers[0], post_act=self.layers[2], lens=lens)
+        return self.layers[3](h, residual=x, post_act=post_act, want_raw=dual, lens=lens)
 
 
 class EncoderBlock(nn.Module):
@@ -226,18 +246,26 @@ class EncoderBlock(nn.Module):
             WNConv1d(in_channels=in_channels, out_channels=out_channels, kernel_size=2 * stride, stride=stride,
                      padding=math.ceil(stride / 2)))
 
-    def forward(self, x, post_act=None, x_act=None, dual=False):
-        """x_act = layers[0].layers[0](x) if the producer stored it; dual: the strided conv returns (post_act(y), y)"""
+    def length_maps(self):
+        """the block's length-changing layers, as functions of a row's length"""
+        return [self.layers[4].out_len]
+
+    def forward(self, x, post_act=None, x_act=None, dual=False, lens=None):
+        """x_act = layers[0].layers[0](x) if the producer stored it; dual: the strided conv returns (post_act(y), y);
+        lens: the rows' lengths at the block's input (the units keep them, the strided conv maps them)"""
         ru = self.layers
+        _no_grad_with_lens(self, x, lens)
         if self.antialias:
+            if lens is not None:
+                raise NotImplementedError("ragged lengths with antialias_activation: its FIRs read neighbouring positions")
             assert post_act is None and x_act is None and not dual
             return _ac(ru[4], ru[2](ru[1](ru[0](x))), ru[3])
         if _wants_grad(self, x):
             return ru[4](ru[2](ru[1](ru[0](x))), act=ru[3])
-        xa, x = ru[0](x, post_act=ru[1].layers[0], x_act=x_act, dual=True)
-        xa, x = ru[1](x, post_act=ru[2].layers[0], x_act=xa, dual=True)
-        x = ru[2](x, post_act=self.layers[3], x_act=xa)
-        return self.layers[4](x, post_act=post_act, want_raw=dual)
+        xa, x = ru[0](x, post_act=ru[1].layers[0], x_act=x_act, dual=True, lens=lens)
+        xa, x = ru[1](x, post_act=ru[2].layers[0], x_act=xa, dual=True, lens=lens)
+        x = ru[2](x, post_act=self.layers[3], x_act=xa, lens=lens)
+        return self.layers[4](x, post_act=post_act, want_raw=dual, lens=lens)
 
 
 class DecoderBlock(nn.Module):
@@ -264,12 +292,22 @@ class DecoderBlock(nn.Module):
             ResidualUnit(in_channels=out_channels, out_channels=out_channels, dilation=3, use_snake=use_snake),
             ResidualUnit(in_channels=out_channels, out_channels=out_channels, dilation=9, use_snake=use_snake))
 
-    def forward(self, x, pre_activated=False, post_act=None):
+    def length_maps(self):
+        """the block's length-changing layers, as functions of a row's length: sample repetition, or the transposed conv (the
+        'same' conv behind the repetition keeps the length)"""
+        if self.nearest:
+            return [lambda L: L * self.nearest]
+        return [self.layers[1].out_len]
+
+    def forward(self, x, pre_activated=False, post_act=None, lens=None):
         # every unit's output is needed raw (skip path of the next unit) and activated (its first conv): the producers store
         # both, so no k=7 conv spends VALU time re-activating its input tile once per output-channel tile
         ru = self.layers
         up = ru[1]
+        _no_grad_with_lens(self, x, lens)
         if self.antialias:              # act -> up-sample -> units, one pass each (low-pass filtering does not commute with repetition)
+            if lens is not None:
+                raise NotImplementedError("ragged lengths with antialias_activation: its FIRs read neighbouring positions")
             assert not pre_activated and post_act is None
             x = ru[0](x)
             if self.nearest:
@@ -280,13 +318,17 @@ class DecoderBlock(nn.Module):
             # a pointwise activation commutes with sample repetition: repeat x, then the conv activates while it stages
             from ... import conv_train
             x, up = conv_train.UpsampleNearestFn.apply(_prep(x).float(), self.nearest), ru[1][1]
+            if lens is not None:        # a row of n positions repeats to n * stride; past that the repeated tail is masked
+                lens = lens.map(lambda L: L * self.nearest)
         if _wants_grad(self, x):
             assert not pre_activated
             return ru[4](ru[3](ru[2](up(x, act=ru[0]))))
-        xa, x = up(x, act=None if pre_activated else ru[0], post_act=ru[2].layers[0], want_raw=True)
-        xa, x = ru[2](x, post_act=ru[3].layers[0], x_act=xa, dual=True)
-        xa, x = ru[3](x, post_act=ru[4].layers[0], x_act=xa, dual=True)
-        return ru[4](x, post_act=post_act, x_act=xa)
+        xa, x = up(x, act=None if pre_activated else ru[0], post_act=ru[2].layers[0], want_raw=True, lens=lens)
+        if lens is not None:
+            lens = lens.map(up.out_len)
+        xa, x = ru[2](x, post_act=ru[3].layers[0], x_act=xa, dual=True, lens=lens)
+        xa, x = ru[3](x, post_act=ru[4].layers[0], x_act=xa, dual=True, lens=lens)
+        return ru[4](x, post_act=post_act, x_act=xa, lens=lens)
 
 
 class OobleckEncoder(nn.Module):
@@ -307,7 +349,16 @@ class OobleckEncoder(nn.Module):
                    WNConv1d(in_channels=c_mults[-1] * channels, out_channels=latent_dim, kernel_size=3, padding=1)]
         self.layers = nn.Sequential(*layers)
 
-    def forward(self, x):
+    def length_maps(self):
+        """every layer that changes a row's length, in order (the first and last convs and the units keep it)"""
+        n = len(self.layers)
+        return [self.layers[0].out_len] + [f for i in range(1, n - 2) for f in self.layers[i].length_maps()] + [self.layers[n - 1].out_len]
+
+    def forward(self, x, lengths=None):
+        """lengths: B ints, the valid samples of each row of x [B, C, Lmax] - every layer then treats row b as a tensor of its
+        own length (exactly the row encoded alone), the result is zero past each row's latent length.  None: dense"""
+        if lengths is not None:
+            return self._forward_ragged(x, lengths)
         n = len(self.layers)
         if n == 3:
             return _ac(self.layers[2], self.layers[0](x), self.layers[1])
@@ -329,6 +380,44 @@ class OobleckEncoder(nn.Module):
             else:
                 xa, x = self.layers[i](x, post_act=first_act(i + 1), x_act=xa, dual=True)
         return self.layers[n - 1](x)
+
+    def _forward_ragged(self, x, lengths):
+        """the fused inference path above, every layer with its rows' lengths (one upload for the whole stack)"""
+        n = len(self.layers)
+        lengths = _checked_lengths(lengths, x)
+        if self.antialias:
+            raise NotImplementedError("ragged lengths with antialias_activation: its FIRs read neighbouring positions")
+        if _wants_grad(self, x):
+            raise NotImplementedError("ragged lengths with gradients: the backward kernels take no lengths (run under torch.no_grad())")
+        levels = conv_ops.plan_levels(lengths, self.length_maps())
+        if min(levels[-1]) < 1:
+            raise ValueError(f"a clip of {lengths} samples is too short for one latent frame")
+        x = _prep(x)
+        lens = conv_ops.RaggedLengths(levels, x.device).at(0)
+        if n == 3:
+            h = self.layers[0](x, lens=lens)
+            return self.layers[2](h, act=self.layers[1], lens=lens.map(self.layers[0].out_len), zero_tail=True)
+        first_act = lambda i: self.layers[i].layers[0].layers[0]      # noqa: E731
+        xa, x = self.layers[0](x, post_act=first_act(1), want_raw=True, lens=lens)
+        lens = lens.map(self.layers[0].out_len)
+        for i in range(1, n - 2):
+            if i == n - 3:
+                x = self.layers[i](x, post_act=self.layers[n - 2], x_act=xa, lens=lens)
+            else:
+                xa, x = self.layers[i](x, post_act=first_act(i + 1), x_act=xa, dual=True, lens=lens)
+            for f in self.layers[i].length_maps():
+                lens = lens.map(f)
+        return self.layers[n - 1](x, lens=lens, zero_tail=True)
+
+
+def _checked_lengths(lengths, x):
+    """B ints in 1 .. x.shape[2], or ValueError"""
+    lengths = [int(v) for v in lengths]
+    if len(lengths) != x.shape[0]:
+        raise ValueError(f"{len(lengths)} lengths for a batch of {x.shape[0]}")
+    if min(lengths) < 1 or max(lengths) > x.shape[2]:
+        raise ValueError(f"lengths {lengths}: each must lie in 1 .. {x.shape[2]}")
+    return lengths
 
 
 class OobleckDecoder(nn.Module):
@@ -353,7 +442,15 @@ class OobleckDecoder(nn.Module):
                    nn.Tanh() if final_tanh else nn.Identity()]
         self.layers = nn.Sequential(*layers)
 
-    def forward(self, x):
+    def length_maps(self):
+        n = len(self.layers)
+        return [self.layers[0].out_len] + [f for i in range(1, n - 3) for f in self.layers[i].length_maps()] + [self.layers[n - 2].out_len]
+
+    def forward(self, x, lengths=None):
+        """lengths: B ints, the valid frames of each row of x [B, latent, Tmax]: every layer treats row b as a tensor of its
+        own length (exactly the row decoded alone), the waveform is zero past each row's length.  None: dense"""
+        if lengths is not None:
+            return self._forward_ragged(x, lengths)
         n = len(self.layers)
         if self.antialias:
             x = self.layers[0](x)
@@ -373,6 +470,25 @@ class OobleckDecoder(nn.Module):
             x = self.layers[i](x, pre_activated=True, post_act=nxt(i))
         post = 1 if isinstance(self.layers[n - 1], nn.Tanh) else 0
         return self.layers[n - 2](x, post=post)   # tanh fused into the store
+
+    def _forward_ragged(self, x, lengths):
+        n = len(self.layers)
+        lengths = _checked_lengths(lengths, x)
+        if self.antialias:
+            raise NotImplementedError("ragged lengths with antialias_activation: its FIRs read neighbouring positions")
+        if _wants_grad(self, x):
+            raise NotImplementedError("ragged lengths with gradients: the backward kernels take no lengths (run under torch.no_grad())")
+        x = _prep(x)
+        lens = conv_ops.RaggedLengths(conv_ops.plan_levels(lengths, self.length_maps()), x.device).at(0)
+        nxt = lambda i: self.layers[i + 1].layers[0] if i + 1 < n - 3 else self.layers[n - 3]      # noqa: E731
+        x = self.layers[0](x, post_act=nxt(0), lens=lens)
+        lens = lens.map(self.layers[0].out_len)
+        for i in range(1, n - 3):
+            x = self.layers[i](x, pre_activated=True, post_act=nxt(i), lens=lens)
+            for f in self.layers[i].length_maps():
+                lens = lens.map(f)
+        post = 1 if isinstance(self.layers[n - 1], nn.Tanh) else 0
+        return self.layers[n - 2](x, post=post, lens=lens, zero_tail=True)
 
 
 class AudioAutoencoder(nn.Module):
@@ -398,9 +514,15 @@ class AudioAutoencoder(nn.Module):
         self.soft_clip = soft_clip
         self.is_discrete = self.bottleneck is not None and self.bottleneck.is_discrete
 
-    def encode(self, audio, return_info=False, skip_pretransform=False, iterate_batch=False, **kwargs):
+    def encode(self, audio, return_info=False, skip_pretransform=False, iterate_batch=False, lengths=None, **kwargs):
+        """lengths: B ints, the valid samples of each row of audio [B, C, Lmax] (a ragged batch): row b's latents are those
+        of audio[b, :, :lengths[b]] encoded alone, and zero past its latent length (both bottlenecks map 0 to 0)"""
         info = {}
-        if self.encoder is not None:
+        if lengths is not None:
+            if self.encoder is None or iterate_batch:
+                raise NotImplementedError("lengths= needs the encoder, in one batched pass")
+            latents = self.encoder(audio, lengths=lengths)
+        elif self.encoder is not None:
             if iterate_batch:
                 latents = torch.cat([self.encoder(audio[i:i + 1]) for i in range(audio.shape[0])], dim=0)
             else:
@@ -414,10 +536,16 @@ class AudioAutoencoder(nn.Module):
             return latents, info
         return latents
 
-    def decode(self, latents, iterate_batch=False, **kwargs):
+    def decode(self, latents, iterate_batch=False, lengths=None, **kwargs):
+        """lengths: B ints, the valid frames of each row of latents [B, C, Tmax] (a ragged batch): row b's waveform is that of
+        latents[b, :, :lengths[b]] decoded alone, and zero past its length"""
         if self.bottleneck is not None:
             latents = self.bottleneck.decode(latents)
-        if iterate_batch:
+        if lengths is not None:
+            if iterate_batch:
+                raise NotImplementedError("lengths= is the batched alternative to iterate_batch")
+            decoded = self.decoder(latents, lengths=lengths, **kwargs)
+        elif iterate_batch:
             decoded = torch.cat([self.decoder(latents[i:i + 1]) for i in range(latents.shape[0])], dim=0)
         else:
             decoded = self.decoder(latents, **kwargs)
@@ -492,8 +620,76 @@ class AudioAutoencoder(nn.Module):
                              src_strides=(B * Cy * Ly, Cy * Ly, Ly), dst_strides=(0, y_final.stride(0), y_final.stride(1)))
         return y_final
 
+    # ---- ragged lists --------------------------------------------------------------------------------------------------
+    # Utterances of different length cannot share a dense batch: zero padding is not zero after the first bias, and it bleeds
+    # back through the receptive field (DESIGN 5.20).  The list forms sort by length, cut groups whose padded size stays under
+    # a cap, run each group as ONE ragged pass (lengths=) and hand the rows back in input order.
+    def _ragged_groups(self, sizes, out_per_in, cap):
+        """[[index, ...], ...]: indices sorted by size, consecutive runs whose B x Lmax_out stays under cap (a group holds at
+        least one item, at most chunk_batch)"""
+        order = sorted(range(len(sizes)), key=lambda i: sizes[i])
+        groups, cur = [], []
+        for i in order:
+            if cur and ((len(cur) + 1) * out_per_in(sizes[i]) > cap or len(cur) >= self.chunk_batch):
+                groups.append(cur)
+                cur = []
+            cur.append(i)
+        if cur:
+            groups.append(cur)
+        return groups
+
+    def _default_cap(self):
+        return self.chunk_batch * 128 * self.downsampling_ratio      # chunk_batch rows of the default chunk (128 latents)
+
+    @staticmethod
+    def _stack(items, C):
+        """[1, C, L_i] (or [C, L_i]) tensors -> ([B, C, Lmax] zero-padded, lengths)"""
+        items = [t[0] if t.dim() == 3 else t for t in items]
+        if any(t.dim() != 2 or t.shape[0] != C or t.shape[1] < 1 for t in items):
+            raise ValueError(f"every item must be [1, {C}, L] or [{C}, L] with L >= 1")
+        lengths = [int(t.shape[1]) for t in items]
+        x = items[0].new_zeros((len(items), C, max(lengths)))
+        for b, t in enumerate(items):
+            x[b, :, :lengths[b]] = t
+        return x, lengths
+
+    def decode_list(self, latents_list, max_batch_samples=None, **kwargs):
+        """latents_list: tensors [1, C, T_i] (what Llasa.infer_batch returns) -> list of waveforms [1, C_out, T_i * ratio], in
+        input order; max_batch_samples caps B x Lmax_out of a group (default: chunk_batch default chunks)"""
+        if not latents_list:
+            return []
+        cap = self._default_cap() if max_batch_samples is None else int(max_batch_samples)
+        C = latents_list[0].shape[-2]
+        out = [None] * len(latents_list)
+        sizes = [int(t.shape[-1]) for t in latents_list]
+        maps = self.decoder.length_maps()
+        for grp in self._ragged_groups(sizes, lambda T: T * self.downsampling_ratio, cap):
+            z, lengths = self._stack([latents_list[i] for i in grp], C)
+            y = self.decode(z, lengths=lengths, **kwargs)
+            for b, i in enumerate(grp):
+                out[i] = y[b:b + 1, :, :conv_ops.plan_levels([lengths[b]], maps)[-1][0]].clone()
+        return out
+
+    def encode_list(self, audio_list, max_batch_samples=None, **kwargs):
+        """audio_list: tensors [1, C, L_i] -> list of latents [1, latent, L_i's latent length], in input order"""
+        if not audio_list:
+            return []
+        cap = self._default_cap() if max_batch_samples is None else int(max_batch_samples)
+        C = audio_list[0].shape[-2]
+        out = [None] * len(audio_list)
+        sizes = [int(t.shape[-1]) for t in audio_list]
+        maps = self.encoder.length_maps()
+        for grp in self._ragged_groups(sizes, lambda L: L, cap):
+            x, lengths = self._stack([audio_list[i] for i in grp], C)
+            z = self.encode(x, lengths=lengths, **kwargs)
+            for b, i in enumerate(grp):
+                out[i] = z[b:b + 1, :, :conv_ops.plan_levels([lengths[b]], maps)[-1][0]].clone()
+        return out
+
     def encode_audio(self, audio, chunked=False, overlap=32, chunk_size=128, **kwargs):
         """autoencoders.py:429-497; chunk_size / overlap in latents"""
+        if chunked and kwargs.get("lengths") is not None:
+            raise NotImplementedError("lengths= with chunked=True: chunks of a ragged batch are not planned")
         if not chunked:
             return self.encode(audio, **kwargs)
         r = self.downsampling_ratio
@@ -504,6 +700,8 @@ class AudioAutoencoder(nn.Module):
 
     def decode_audio(self, latents, chunked=False, overlap=32, chunk_size=128, **kwargs):
         """autoencoders.py:499-560"""
+        if chunked and kwargs.get("lengths") is not None:
+            raise NotImplementedError("lengths= with chunked=True: chunks of a ragged batch are not planned")
         if not chunked:
             return self.decode(latents, **kwargs)
         r = self.downsampling_ratio

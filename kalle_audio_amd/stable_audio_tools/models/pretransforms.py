@@ -55,5 +55,19 @@ class AutoencoderPretransform(Pretransform):
         decoded = self.model.decode_audio(z, chunked=self.chunked, iterate_batch=self.iterate_batch, **kwargs)
         return decoded.float()
 
+    # ragged batches: encode(x, lengths=[...]) / decode(z, lengths=[...]) pass `lengths` on (samples / frames per row; the
+    # result is zero past each row's length); the list forms take what Llasa.infer_batch returns
+    def decode_list(self, latents_list, max_batch_samples=None):
+        if self.chunked or self.iterate_batch:
+            raise NotImplementedError("decode_list is the batched, unchunked path")
+        zs = [(z * self.scale).to(torch.bfloat16) if self.model_half else z * self.scale for z in latents_list]
+        return [y.float() for y in self.model.decode_list(zs, max_batch_samples=max_batch_samples)]
+
+    def encode_list(self, audio_list, max_batch_samples=None):
+        if self.chunked or self.iterate_batch:
+            raise NotImplementedError("encode_list is the batched, unchunked path")
+        xs = [x.to(torch.bfloat16) if self.model_half else x for x in audio_list]
+        return [z.float() / self.scale for z in self.model.encode_list(xs, max_batch_samples=max_batch_samples)]
+
     def load_state_dict(self, state_dict, strict=True):
         self.model.load_state_dict(state_dict, strict=strict)
