@@ -10,6 +10,13 @@ import sys
 __version__ = "0.1.0"
 
 
+def weights_changed():
+    """Call after writing weights in a way neither torch nor this package records - `p.data.copy_`, `p.data.lerp_` (ema_pytorch),
+    a collective on `p.data`: every copy derived from weights is re-made at its next use (ops.weights_changed)."""
+    from . import ops
+    ops.weights_changed()
+
+
 def install():
     """Make `import stable_audio_tools` resolve to this package's drop-in (for the reference's entry scripts)."""
     import importlib

@@ -20,14 +20,18 @@ import os as _os
 GROUP_WGRAD = _os.environ.get("KALLE_GROUP_WGRAD", "1") != "0"     # all weight gradients of a block in one launch
 
 
+_key_is = ops.weights_key_is       # (a module global: one lookup less in front of every GEMM)
+
+
 def bf16_of(p):
-    """bf16 compute copy of an fp32 parameter, re-cast only when the parameter changed (or pinned by the engine)."""
+    """bf16 compute copy of an fp32 parameter, re-cast only when the parameter changed (ops.weights_key; or pinned by the engine).
+    The entry is (key, copy, pin of the storage the copy was cast from)."""
     pinned = getattr(p, "_kalle_bf16_pinned", None)
     if pinned is not None:
         return pinned
     c = getattr(p, "_kalle_bf16", None)
-    if c is None or c[0] != p._version or c[1].device != p.device:
-        c = (p._version, ops.cast(p.detach().float(), BF16))
+    if c is None or not _key_is(c[0], p):
+        c = (ops.weights_key(p), ops.cast(p.detach().float(), BF16), ops.weights_pin(p))
         p._kalle_bf16 = c
     return c[1]
 

@@ -38,6 +38,12 @@ class FusedAdam(torch.optim.Optimizer):
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
+        # The kernel writes the weights through the raw pointer: every launch moves the write epoch (ops.weights_key), which
+        # invalidates every derived copy.  The bf16 compute copies (dit_ops.bf16_of) of THIS optimizer's parameters need no
+        # re-cast: a copy that is current now is updated by the same launch (param_bf16) - or belongs to a parameter this step
+        # does not write - and is stamped with the new key at the end; one that is not current is dropped.
+        mine = [p for g in self.param_groups for p in g["params"]]
+        current = {id(p) for p in mine if getattr(p, "_kalle_bf16", None) is not None and p._kalle_bf16[0] == ops.weights_key(p)}
         for g in self.param_groups:
             for p in g["params"]:
                 if p.grad is None:
@@ -49,17 +55,18 @@ class FusedAdam(torch.optim.Optimizer):
                     st["exp_avg_sq"] = torch.zeros_like(p, dtype=torch.float32)
                 st["step"] += 1
                 grad = p.grad if p.grad.dtype == torch.float32 else p.grad.float()
-                # The kernel writes the weights through the raw pointer, so p._version does not move and the bf16 compute
-                # copy that dit_ops.bf16_of caches per parameter version would go stale: a live copy is updated by the same
-                # launch (param_bf16), anything else is dropped so the next forward re-casts.
                 c = getattr(p, "_kalle_bf16", None)
-                live = (c is not None and getattr(p, "_kalle_bf16_pinned", None) is None and c[0] == p._version
-                        and c[1].device == p.device and c[1].is_contiguous() and p.is_contiguous())
+                live = (id(p) in current and getattr(p, "_kalle_bf16_pinned", None) is None
+                        and c[1].is_contiguous() and p.is_contiguous())
                 ops.adam_step(p.data, grad.contiguous(), st["exp_avg"], st["exp_avg_sq"], c[1] if live else None,
                               lr=g["lr"], beta1=g["betas"][0], beta2=g["betas"][1], eps=g["eps"],
                               weight_decay=g["weight_decay"], decoupled=g["adam_w_mode"], step=st["step"])
                 if c is not None and not live:
                     del p._kalle_bf16
+        for p in mine:
+            c = getattr(p, "_kalle_bf16", None)
+            if c is not None and id(p) in current:
+                p._kalle_bf16 = (ops.weights_key(p),) + c[1:]
         return loss
 
 
@@ -160,9 +167,12 @@ class FlatBuckets:
                 self.param[s:s + ne].copy_(p.detach().reshape(-1).to(device=device, dtype=torch.float32))
                 p.data = self.param[s:s + ne].view(p.shape)
                 p.grad = self.grad[s:s + ne].view(p.shape)
+                for stale in ("_kalle_bf16", "_kalle_e4m3"):    # (copies an earlier forward left: they pin the old storage, and
+                    p.__dict__.pop(stale, None)                 # the mirror hides the first for good)
                 if with_bf16:
                     self.param_bf16[s:s + ne].copy_(self.param[s:s + ne])
                     p._kalle_bf16_pinned = self.param_bf16[s:s + ne].view(p.shape)
+        ops.weights_changed()       # every parameter was re-pointed: whatever an earlier forward derived from them is void
         self.params = dict(named_params)
 
     def grad_view(self, name):
@@ -277,6 +287,7 @@ class DataParallelTrainer:
         if self.world > 1:
             for _, p in named:
                 dist.broadcast(p.data, src=0, group=self.pg)
+            ops.weights_changed()       # (a collective on .data: torch's version counters have not moved)
         self.flat = FlatBuckets(named, bucket_of, device)
         self.exp_avg = torch.zeros_like(self.flat.param)
         self.exp_avg_sq = torch.zeros_like(self.flat.param)

@@ -15,7 +15,7 @@ import torch
 from torch import nn
 from torch.nn import Parameter
 
-from . import conv_ops
+from . import conv_ops, ops
 
 
 def _prep(x):
@@ -122,10 +122,11 @@ class _ConvBase(nn.Module):
 
     def _packed(self):
         ps = (self.weight_g, self.weight_v) if self._wn else (self.weight,)
-        key = tuple(p._version for p in ps) + (ps[-1].device, self._wn)
+        key = ops.weights_key(*ps)
         c = getattr(self, "_kalle_packed", None)
         if c is None or c[0] != key:
-            c = (key, conv_ops.weight_norm_fold(ps[-1], ps[0] if self._wn else None, transposed=self.transposed))
+            c = (key, conv_ops.weight_norm_fold(ps[-1], ps[0] if self._wn else None, transposed=self.transposed),
+                 ops.weights_pin(*ps))
             self._kalle_packed = c
         return c[1]
 

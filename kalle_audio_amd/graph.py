@@ -6,6 +6,8 @@ needs to issue them (`stable_audio_tools/inference/sampling.py:24-86` calls `mod
 `CUDAGraph` on ROCm records the hipLaunchKernelGGL calls the C-ABI issues on the capturing stream - and replays it with
 the inputs copied into static buffers.  Inference only (no autograd, no RNG inside the captured region).
 """
+import gc
+
 import torch
 
 
@@ -37,9 +39,20 @@ class GraphedForward:
                 for _ in range(self.warmup):
                     self.fn(*s_args, **s_kw)
             torch.cuda.current_stream().wait_stream(side)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                out = self.fn(*s_args, **s_kw)
+            # Python's cyclic collector must not run inside the capture: a dead cycle that owns another captured graph (a model and
+            # the trainer hooked into its blocks refer to each other) would be destroyed there, which the runtime refuses
+            # while a stream is capturing - the process aborts.  torch.cuda.graph collected before a capture until 2.9 and
+            # no longer does: collect here, and keep the collector off until the capture has ended.
+            gc.collect()
+            gc_was_on = gc.isenabled()
+            gc.disable()
+            try:
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    out = self.fn(*s_args, **s_kw)
+            finally:
+                if gc_was_on:
+                    gc.enable()
             ent = self._cache[key] = (g, s_args, s_kw, out)
         g, s_args, s_kw, out = ent
         for dst, src in zip(s_args, args):

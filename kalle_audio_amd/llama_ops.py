@@ -77,12 +77,11 @@ def layer_params(layer):
 
 def e4m3_of(p):
     """(codes uint8 [N, K], scale fp32 [N]) of a projection weight: ops.quantize_rows_e4m3 of its bf16 compute copy, re-made only
-    when the parameter changed - its `_version`, or ops.WEIGHTS_EPOCH for writes through a raw pointer (the rule of the sampler's
-    graph cache)"""
-    key = (p._version, ops.WEIGHTS_EPOCH, p.device)
+    when the parameter changed (ops.weights_key, the rule of every weight-derived copy)"""
+    key = ops.weights_key(p)
     c = getattr(p, "_kalle_e4m3", None)
     if c is None or c[0] != key:
-        c = (key,) + ops.quantize_rows_e4m3(bf16_of(p))
+        c = (key,) + ops.quantize_rows_e4m3(bf16_of(p)) + (ops.weights_pin(p),)
         p._kalle_e4m3 = c
     return c[1], c[2]
 

@@ -334,11 +334,13 @@ class LlamaModel(nn.Module):
         return self
 
     def _decode_plan(self, cache, device, rows=None):
-        """the cache's plan for the current decode weight format; rebuilt when the format changed or (quantised) a weight did"""
+        """the cache's plan for the current decode weight format; rebuilt when the format changed or a weight did - in EITHER
+        format: a bf16 plan holds the addresses of the bf16 compute copies and of the norm scales, a quantised one those of the
+        codes and scales, and both go stale with the parameters they were made from (ops.weights_key)"""
         fmt = self._decode_fmt
         plan = cache.get("plan")
-        # (bf16 plans hold the weights themselves: nothing to key)
-        key = None if fmt is None else (ops.WEIGHTS_EPOCH,) + tuple(p._version for p in self._decode_weights(plan is None))
+        ws = self._decode_weights()
+        key = ops.weights_key(*ws)
         if plan is None or plan.get("fmt") != fmt or plan["wkey"] != key:
             if fmt is None:
                 ps = [LO.layer_params(layer) for layer in self.layers]
@@ -348,17 +350,21 @@ class LlamaModel(nn.Module):
                 ts = [q + (kv,) for q, kv in zip(qs, cache["kv"])]
             p0 = ps[0]
             plan = ops.llama_decode_plan(ts, p0.H, p0.Hkv, p0.wug.shape[0] // 2, device, head_dim=p0.hd, rows=rows)
-            plan["eps"], plan["wkey"] = p0.eps, key
+            plan["eps"], plan["wkey"], plan["wpin"] = p0.eps, key, ops.weights_pin(*ws)
             cache["plan"] = plan
         return plan
 
-    def _decode_weights(self, refresh):
-        """the projection weights whose versions key a quantised plan; collected once per cache (module attribute lookups are
-        too slow to repeat for every frame), the versions themselves are read at every step"""
-        ws = self.__dict__.get("_decode_weight_list")
-        if ws is None or refresh:
-            ws = self.__dict__["_decode_weight_list"] = [w for layer in self.layers for w in self._layer_weights(layer)]
-        return ws
+    def _decode_weights(self):
+        """the parameters a decode plan reads (per layer: two norm scales, four projections), looked up at every step: module
+        attribute lookups are too slow to repeat for every frame, so what is collected once is the `_parameters` dict of each
+        owning module - a replaced Parameter object (load_state_dict(assign=True)) is found there, a remembered one would not be"""
+        slots = self.__dict__.get("_decode_weight_list")
+        if slots is None:
+            slots = self.__dict__["_decode_weight_list"] = [
+                m._parameters for layer in self.layers
+                for m in (layer.input_layernorm, layer.self_attn.qkv_proj, layer.self_attn.o_proj, layer.post_attention_layernorm,
+                          layer.mlp.up_gate_proj, layer.mlp.down_proj)]
+        return [d["weight"] for d in slots]
 
     @staticmethod
     def _layer_weights(layer):

@@ -427,8 +427,40 @@ def grad_cast(g, nbatch, rows_per_batch, gate=None, x_out=None, x_in=None, row_m
     return gb, dgate
 
 
-WEIGHTS_EPOCH = 0      # bumped by every launch that writes weights through a raw pointer (torch's `_version` does not see it):
-                       # part of the key of every cache derived from weights (stacked k | v weights, captured graphs)
+WEIGHTS_EPOCH = 0      # bumped by every write to weights that torch does not record (raw-pointer launches, re-pointed storage,
+                       # collectives on .data, weights_changed()): the last field of weights_key()
+
+
+def weights_changed():
+    """Tell every cache derived from weights that some weight was written in a way neither torch nor this package can see
+    (`p.data.copy_`, `p.data.lerp_` - ema_pytorch's writes -, a collective on `p.data`): all of them are re-made at their next use.
+    The package's own raw-pointer writers (adam_step, the trainer's construction) call it themselves."""
+    global WEIGHTS_EPOCH
+    WEIGHTS_EPOCH += 1
+
+
+def weights_key(*params):
+    """THE key of every copy derived from parameters ("Weight-derived caches"): per parameter its identity,
+    torch's version counter, the address, device and dtype of its storage, then the write epoch.  Pure: reads, never writes.
+    `_version` follows in-place ops, load_state_dict and torch.optim steps; the address a re-pointed `p.data` (only while the
+    cache also holds weights_pin() of the same parameters - a freed block may be handed out again at the same address); the
+    identity a replaced Parameter (load_state_dict(assign=True)); the epoch everything torch does not record."""
+    return tuple([(id(p), p._version, p.data_ptr(), p.device, p.dtype) for p in params]) + (WEIGHTS_EPOCH,)
+
+
+def weights_key_is(key, p):
+    """key == weights_key(p) for a cache entry that hangs ON the parameter `p` and holds weights_pin(p), without building the
+    key: dit_ops.bf16_of asks this in front of every GEMM, so it reads what can move on its own - epoch, version, address.
+    The identity is the entry's place; device and dtype belong to the storage, and while the old storage is pinned another
+    one has another address (tests/test_weight_caches_cpu.py holds this to the full comparison on every route)."""
+    k = key[0]
+    return key[1] == WEIGHTS_EPOCH and k[1] == p._version and k[2] == p.data_ptr()
+
+
+def weights_pin(*params):
+    """aliases of the parameters' CURRENT storage, kept next to a weights_key(): while they live, that storage is not freed, so
+    a tensor `p.data` is re-pointed to (module.half().float() allocates the same size again) cannot land on the keyed address"""
+    return tuple([p.detach() for p in params])
 
 
 def adam_step(param, grad, exp_avg, exp_avg_sq, param_bf16, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0,

@@ -14,7 +14,7 @@ from typing import Any, Dict, Literal
 import torch
 from torch import nn
 
-from ... import conv_ops
+from ... import conv_ops, ops
 from .blocks import SnakeBeta
 from .bottleneck import Bottleneck
 
@@ -59,10 +59,11 @@ class _WNBase(nn.Module):
     transposed = False
 
     def _packed(self):
-        key = (self.weight_g._version, self.weight_v._version, self.weight_v.device)
+        key = ops.weights_key(self.weight_g, self.weight_v)
         c = getattr(self, "_kalle_packed", None)
         if c is None or c[0] != key:
-            c = (key, conv_ops.weight_norm_fold(self.weight_v, self.weight_g, transposed=self.transposed))
+            c = (key, conv_ops.weight_norm_fold(self.weight_v, self.weight_g, transposed=self.transposed),
+                 ops.weights_pin(self.weight_g, self.weight_v))
             self._kalle_packed = c
         return c[1]
 

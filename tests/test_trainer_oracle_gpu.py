@@ -248,6 +248,7 @@ def test_t7_fused_adam_front_end(dev, adam_w_mode):
     p.grad and the optimizer's own state; a live bf16 compute copy is bit-equal to bf16(p) after the step, a stale one is gone,
     a parameter with grad None is untouched and has no state"""
     import test_round2_gpu as r2
+    from kalle_audio_amd import ops
     from kalle_audio_amd.engine import FusedAdam
     from kalle_audio_amd.stable_audio_tools.training.diffusion import diffusion_train_step
     m = r2._small_dit(dev)
@@ -260,7 +261,7 @@ def test_t7_fused_adam_front_end(dev, adam_w_mode):
         opt.zero_grad(set_to_none=True)
         loss, _ = diffusion_train_step(m, lat, t, noise, cond)
         loss.backward()
-        live = [n for n, p in named if getattr(p, "_kalle_bf16", None) is not None and p._kalle_bf16[0] == p._version]
+        live = [n for n, p in named if getattr(p, "_kalle_bf16", None) is not None and p._kalle_bf16[0] == ops.weights_key(p)]
         assert len(live) >= 8, live
         frozen_n, frozen_p = next((n, p) for n, p in named if p.dim() == 1 and p.grad is not None)
         stale_n, stale_p = next((n, p) for n, p in named if n in live)
@@ -270,7 +271,7 @@ def test_t7_fused_adam_front_end(dev, adam_w_mode):
         if k == 2:
             with torch.no_grad():
                 stale_p.add_(0.0)                      # moves the version: the cached bf16 copy no longer belongs to these weights
-            assert stale_p._kalle_bf16[0] != stale_p._version
+            assert stale_p._kalle_bf16[0] != ops.weights_key(stale_p)
         act = [(n, p) for n, p in named if p.grad is not None]
         zero = lambda p: torch.zeros_like(p, dtype=torch.float32)
         cat = lambda ts: torch.cat([x.detach().float().reshape(-1) for x in ts]).cpu()
@@ -292,7 +293,7 @@ def test_t7_fused_adam_front_end(dev, adam_w_mode):
         assert all(opt.state[p]["step"] == k for n, p in act) and (k < 3 or frozen_n not in dict(act))
         for n, p in named:
             if n in live and not (k == 2 and n == stale_n):
-                assert p._kalle_bf16[0] == p._version and to._bits_equal(p._kalle_bf16[1], p.detach().bfloat16()), n
+                assert p._kalle_bf16[0] == ops.weights_key(p) and to._bits_equal(p._kalle_bf16[1], p.detach().bfloat16()), n
         if k == 2:
             assert not hasattr(stale_p, "_kalle_bf16")
         if k == 3:
